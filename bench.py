@@ -31,7 +31,8 @@ weak scaling); per frame the ranks all_gather one small record of per-block sums
 resampled particles over RCCL (all_to_all of the rows each rank needs, resolved by the owners of the sources).
 `value` = frames processed by all ranks / wall time = gpus x steps / t.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes the arrays the K-th timed step left (DUMP_NAMES) to DIR: the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -89,6 +90,37 @@ def algorithmic_bytes(N, K, D, B=1):
     update = K * 24 + B * N * PER_PARTICLE_UPDATE
     tail = B * N * PER_PARTICLE_TAIL
     return {"score_codebook": score, "particle_update": update, "tail": tail, "step": score + update + tail}
+
+
+# --dump-outputs: what a caller of the timed path holds after its last step (the engines' names; the sharded engine: this rank's slice)
+DUMP_NAMES = ("poses", "poses_prop", "weights", "weights_res", "nn_idx", "ridx", "rmse")
+DUMP_BUDGET = 64 << 20  # bytes over all files of all ranks
+
+
+def dump_outputs(path, arrays, n_rows, rank=0, world=1, budget=DUMP_BUDGET):
+    """Writes `arrays` (name -> tensor) as `path`/<name>.npy (<name>_rank<r>.npy with several ranks): float32 and float64 as they
+    are, integers as float64 (exact).  When the files would exceed this rank's share of `budget`, the per-particle arrays (first
+    dimension `n_rows`) keep a fixed seeded sample of rows, the same rows in each, listed in sample_rows.npy.  Returns name -> shape."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    share = budget // world - 4096  # (room for the .npy headers)
+    per_row = [k for k, a in host.items() if a.ndim and a.shape[0] == n_rows]
+    total = sum(a.nbytes for a in host.values())
+    if total > share:
+        row_bytes = sum(host[k].nbytes // n_rows for k in per_row) + 8  # (+ the row's entry in sample_rows)
+        m = (share - (total - sum(host[k].nbytes for k in per_row))) // row_bytes
+        if m < 1:
+            raise SystemExit("bench.py --dump-outputs: the outputs do not fit in %d bytes" % share)
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, size=m, replace=False))
+        for k in per_row:
+            host[k] = host[k][rows]
+        host["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
 
 
 def cpu_baseline(cb, traj, N, budget_s=12.0, max_steps=40):
@@ -509,7 +541,11 @@ def main():
     ap.add_argument("--eager", action="store_true", help="materialise the resampled particles every frame (three launches per frame)")
     ap.add_argument("--resample", default="weighted_random", choices=["weighted_random", "low_var"],
                     help="resampler mode (particle_filter.py:230-307): the reference's default multinomial draws, or systematic")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (poses, weights, "
+                                                          "resample and NN indices, rmse) to DIR/<name>.npy, float32 / float64, 64 MB at most")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     def guarded(fn, *a, **kw):
         """the figures beside the headline must not cost the line: a failure is reported in their place"""
@@ -693,6 +729,8 @@ def main():
     gc.enable()
     if run_log is not None:
         run_log = run_log.clone()
+    # device copies now: the passes below step the same engine on
+    last_step = {name: getattr(eng, name).clone() for name in DUMP_NAMES} if args.dump_outputs else None
     rows_timed = None
     if tele_before is not None:  # codebook rows the timed frames scored (sparse scoring): claimed by particle waves + off the list
         td = eng.telemetry.cpu().numpy()[:4].astype(np.int64) - tele_before[:4].astype(np.int64)
@@ -930,6 +968,8 @@ def main():
         out["cpu_baseline"] = cpu_baseline(cb, traj, N)
         if not sharded and not args.eager and args.resample == "weighted_random":
             out["cpu_baseline"]["parity_probe"] = guarded(parity_probe, eng, N, 4000)
+    if last_step is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, last_step, N, rank, world)}
     if rank == 0:
         try:  # anything native libraries left in the C stdio buffer goes out first: the JSON line is the last line
             import ctypes

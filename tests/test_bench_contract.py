@@ -36,3 +36,76 @@ def test_bench_refuses_to_run_without_a_gpu(monkeypatch):
     with pytest.raises(SystemExit) as e:
         b.main()
     assert "MI355X" in str(e.value)  # loud failure, no CPU fallback
+
+
+def test_bench_rejects_zero_steps(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        b.main()
+    assert e.value.code == 2  # argparse's usage error, before any device work
+
+
+def test_dump_outputs_dtypes_budget_and_sample(tmp_path):
+    """--dump-outputs' writer: float32 / float64 files, integers exact as float64; over the budget the per-particle arrays keep the
+    same fixed rows (sample_rows.npy), run after run, and the files stay inside the budget."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    N = 1000
+    arrays = {"poses": torch.arange(N * 16, dtype=torch.float32).reshape(N, 4, 4), "weights": torch.linspace(0, 1, N, dtype=torch.float64),
+              "ridx": torch.arange(N, dtype=torch.int32).flip(0), "rmse": torch.tensor([1.5, 2.5], dtype=torch.float64)}
+    assert b.dump_outputs(str(tmp_path / "whole"), arrays, N) == {"poses": [N, 4, 4], "weights": [N], "ridx": [N], "rmse": [2]}
+    ridx = np.load(tmp_path / "whole" / "ridx.npy")
+    assert ridx.dtype == np.float64 and np.array_equal(ridx, np.arange(N)[::-1])
+    assert np.load(tmp_path / "whole" / "poses.npy").dtype == np.float32
+
+    budget = 48_000
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), arrays, N, budget=budget)
+    names = sorted(os.listdir(tmp_path / "s1"))
+    assert names == ["poses.npy", "ridx.npy", "rmse.npy", "sample_rows.npy", "weights.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in names) <= budget
+    rows = np.load(tmp_path / "s1" / "sample_rows.npy").astype(np.int64)
+    assert 0 < rows.size < N and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "poses.npy"), arrays["poses"].numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "ridx.npy"), N - 1 - rows)
+    assert np.array_equal(np.load(tmp_path / "s1" / "rmse.npy"), [1.5, 2.5])
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)), f
+
+    b.dump_outputs(str(tmp_path / "r"), arrays, N, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / "r")) == ["poses_rank1.npy", "ridx_rank1.npy", "rmse_rank1.npy", "weights_rank1.npy"]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """bench.py --dump-outputs twice with the same arguments: the same arrays, bit for bit, beside a line with steps and ms_per_step."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    N = 4096
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "3", "--particles", str(N),
+           "--codebook", "4096", "--dim", "256", "--no-cpu-baseline", "--no-profile", "--no-loop", "--no-diffuse", "--no-extras"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-2000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+    for line in lines:
+        assert line["steps"] == 5 and line["ms_per_step"] > 0
+        assert line["dump_outputs"]["arrays"] == lines[0]["dump_outputs"]["arrays"]
+    shapes = lines[0]["dump_outputs"]["arrays"]
+    assert shapes["poses"] == [N, 4, 4] and shapes["ridx"] == [N] and shapes["rmse"] == [2]
+    for name in shapes:
+        a, b_ = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)), name
+        assert np.array_equal(a, b_), name
+    ridx = np.load(tmp_path / "a" / "ridx.npy")
+    assert ridx.min() >= 0 and ridx.max() < N
