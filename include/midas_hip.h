@@ -86,6 +86,21 @@ int midas_score(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const doubl
 int midas_score_batch(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes_dev,
                       double* scores_dev);
 
+/* Batched float64 form: one pass over the codebook on the matrix cores (v_mfma_f64_16x16x4_f64), the codes kept in float64.
+ * scores[b*K + k] is BIT-IDENTICAL to midas_score's for every code and row: the dot product is formed as the 16 partial fma
+ * chains of the summation spec (oracle/midas_oracle.c MO_SCORE_BODY) - elements 64 j + 4 s + c for D in {128, 256, 512, 1024}
+ * with 16-byte-aligned embeddings and codes, elements s + 16 t otherwise - joined by the 16-lane xor tree and divided by
+ * max(|e_b|, 1e-8) * norms[k].  Any K, D, B >= 1; float32 embeddings (widened exactly) or float64. */
+int midas_score_batch_f64(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes_dev,
+                          double* scores_dev);
+/* Precision of the dense batch scoring pass inside midas_filter_step_batch (a property of the codebook handle).
+ * MIDAS_F32 (default): midas_score_batch where it applies (float32 embeddings, D % 16 == 0), the float64 GEMV loop otherwise.
+ * MIDAS_F64: midas_score_batch_f64 for every embedding dtype and D - the scores of midas_score, bit for bit - in the serial form
+ * and in the side-stream overlap form alike.  Batches scored sparsely (score stamps) are float64 GEMV arithmetic either way.
+ * A host-side setting read when a step is enqueued: it applies from the next midas_filter_step_batch call on, enqueues nothing, and
+ * is not synchronised with other threads using the same codebook handle. */
+int midas_codebook_set_batch_precision(midas_codebook* cb, int32_t dtype);
+
 /* ---- SE(3) feature and exact nearest neighbour  (K3, K4) ------------------------------------- */
 /* feat6 = [ (1-w) t , w log(R) ]  - R3_SE3 (tactile_tree/tactile_tree.py:73-77, modules/pose.py:19-23) */
 int midas_se3_feature(midas_ctx* ctx, int64_t N, const float* poses_dev, float w, float* feat6_dev);

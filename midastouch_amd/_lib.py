@@ -211,6 +211,8 @@ SIGNATURES = {
     "midas_codebook_destroy": (C.c_int, [_P]),
     "midas_score": (C.c_int, [_P, _P, _I32, _P, _P]),
     "midas_score_batch": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "midas_score_batch_f64": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "midas_codebook_set_batch_precision": (C.c_int, [_P, _I32]),
     "midas_se3_feature": (C.c_int, [_P, _I64, _P, _F, _P]),
     "midas_tree_build": (C.c_int, [_P, _I32, _I64, _P, C.POINTER(_P)]),
     "midas_tree_destroy": (C.c_int, [_P]),

@@ -133,7 +133,7 @@ MIDAS_EXPORT int midas_ctx_create(int device, void* hip_stream, midas_ctx** out)
     const char* lazy = getenv("MIDAS_LAZY_MODULES");
     if (!(lazy && lazy[0] == '1')) {
         int (*const warm[])() = {warm_score, warm_particles, warm_resample, warm_cluster, warm_topn, warm_selfsim, warm_loop,
-                                 warm_dbscan, warm_dbscan_nd, warm_index_build, warm_mt19937, warm_topk_aten};
+                                 warm_dbscan, warm_dbscan_nd, warm_index_build, warm_mt19937, warm_topk_aten, warm_score_f64};
         for (auto w : warm)
             if (w() != 0) { (void)hipGetLastError(); }  // not fatal: the unit then loads at its first launch, as before
     }
@@ -256,6 +256,21 @@ MIDAS_EXPORT int midas_score_batch(midas_ctx* ctx, const midas_codebook* cb, int
     MIDAS_ENTER(ctx);
     MIDAS_REQUIRE(ctx, cb && B >= 1 && codes_dev && scores_dev);
     return launch_score_batch(ctx, cb, B, codes_dev, scores_dev);
+}
+
+MIDAS_EXPORT int midas_score_batch_f64(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes_dev,
+                                       double* scores_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, cb && B >= 1 && codes_dev && scores_dev);
+    return launch_score_batch_f64(ctx, cb, B, codes_dev, scores_dev);
+}
+
+MIDAS_EXPORT int midas_codebook_set_batch_precision(midas_codebook* cb, int32_t dtype) {
+    if (!cb) return MIDAS_ERR_INVALID;
+    midas_ctx* ctx = cb->ctx;
+    MIDAS_REQUIRE(ctx, dtype == MIDAS_F32 || dtype == MIDAS_F64);
+    cb->batch_precision = dtype;
+    return MIDAS_OK;
 }
 
 // ---- features / trees ----------------------------------------------------------------------------
@@ -540,7 +555,9 @@ static int filter_step_impl(midas_ctx* ctx, const midas_codebook* cb, const mida
     // tail then gathers the scores.  Other layouts / batches: scoring, then the particle update with the scores.
     void* lp_raw = nullptr;
     // a batch scores all its codes in one pass over the codebook on the matrix cores when the layout allows it
-    const bool mfma = B > 1 && cb->dtype == MIDAS_F32 && cb->D % 16 == 0 && (uintptr_t)cb->emb % 16 == 0;
+    // (float64 batch precision: k_score_mfma_f64, which takes every embedding dtype and D)
+    const bool mfma = B > 1 && (cb->batch_precision == MIDAS_F64 ||
+                                (cb->dtype == MIDAS_F32 && cb->D % 16 == 0 && (uintptr_t)cb->emb % 16 == 0));
     // Batch: that pass (a separate kernel shape: 1024-thread workgroups, 132 KB of LDS) runs on a side stream
     // concurrently with the particle update, which does not need the scores; the fork / join events cost ~8 us,
     // the overlap saves the ~60 us of the scoring.
@@ -612,7 +629,7 @@ static int filter_step_impl(midas_ctx* ctx, const midas_codebook* cb, const mida
         MIDAS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_fork, main_stream));  // the codes, and last frame's readers of `scores`
         MIDAS_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
         ctx->stream = ctx->side;
-        rc = launch_score_batch(ctx, cb, B, s.code_dev, (double*)scores);
+        rc = launch_score_dense_batch(ctx, cb, B, s.code_dev, (double*)scores);
         ctx->stream = main_stream;
         if (rc) return rc;
         MIDAS_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join, ctx->side));
@@ -623,7 +640,7 @@ static int filter_step_impl(midas_ctx* ctx, const midas_codebook* cb, const mida
         defer = true;
     } else if (!defer) {
         prof_mark(ctx, 0);
-        if ((rc = mfma ? launch_score_batch(ctx, cb, B, s.code_dev, (double*)scores)
+        if ((rc = mfma ? launch_score_dense_batch(ctx, cb, B, s.code_dev, (double*)scores)
                        : launch_score(ctx, cb, B, s.code_dev, (double*)scores)))
             return rc;
         prof_mark(ctx, 1);

@@ -119,6 +119,7 @@ struct midas_codebook {
     int32_t dtype;
     const void* emb;  // caller-owned
     double* norms;    // [K] max(|C_k|, 1e-8), library-owned
+    int32_t batch_precision = MIDAS_F32;  // the dense batch pass of midas_filter_step_batch: MIDAS_F32 k_score_mfma, MIDAS_F64 k_score_mfma_f64
 };
 
 struct midas_tree {
@@ -166,7 +167,7 @@ int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* deta
 namespace midas {
 MIDAS_WARM_DECL(score) MIDAS_WARM_DECL(particles) MIDAS_WARM_DECL(resample) MIDAS_WARM_DECL(cluster) MIDAS_WARM_DECL(topn)
 MIDAS_WARM_DECL(selfsim) MIDAS_WARM_DECL(loop) MIDAS_WARM_DECL(dbscan) MIDAS_WARM_DECL(dbscan_nd) MIDAS_WARM_DECL(index_build)
-MIDAS_WARM_DECL(mt19937) MIDAS_WARM_DECL(topk_aten)
+MIDAS_WARM_DECL(mt19937) MIDAS_WARM_DECL(topk_aten) MIDAS_WARM_DECL(score_f64)
 }  // namespace midas
 
 // scratch carve-out (stream-ordered reuse; one stream per context)
@@ -222,6 +223,8 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 int launch_row_norms(midas_ctx* ctx, int64_t K, int32_t D, const void* emb, int32_t dtype, double* norms);
 int launch_score(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes, double* scores);
 int launch_score_batch(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes, double* scores);
+int launch_score_batch_f64(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes, double* scores);
+int launch_score_dense_batch(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes, double* scores);
 
 // particles.hip
 int launch_se3_feature(midas_ctx* ctx, int64_t N, const float* poses, float w, float* feat6);

@@ -480,14 +480,23 @@ class BatchFilterEngine:
     """B independent trajectories against one codebook, one C-ABI call per frame of the whole batch
     (BASELINE config 5, "throughput mode": SURVEY.md 8(e) batch mode).
 
-    State tensors carry a leading batch dimension.  The B tactile codes of a frame are scored in one pass
-    over the codebook on the matrix cores (float32 fma chains, `midas_score_batch`), so a trajectory's
-    scores differ from the single-trajectory engine's float64 GEMV in the 7th digit; everything else is the
-    same kernels with the trajectory as grid.y.  Device-mode Philox streams are keyed by b*N + n.
+    State tensors carry a leading batch dimension; everything but the scoring is the same kernels as the single-trajectory
+    engine with the trajectory as grid.y.  Device-mode Philox streams are keyed by b*N + n.
+
+    `scores` chooses how the B tactile codes of a frame are scored:
+    - "auto" (default): sparse per trajectory (score stamps: the particle waves score the rows they need with the float64
+      arithmetic of the single-trajectory step - exact to `oracle.score_codebook`) for a float32 codebook with D in
+      {128, 256, 512, 1024}, unless MIDAS_DENSE_SCORES=1; otherwise one dense pass over the codebook - on the matrix cores in
+      float32 (`midas_score_batch`, exact to `oracle.score_codebook_batch`, ~1e-7 from the float64 scores) where it applies,
+      the float64 GEMV loop otherwise.
+    - "dense_f64": one dense pass on the matrix cores in float64 (`midas_score_batch_f64`) for any codebook - bit-identical
+      to `oracle.score_codebook` and to the single-trajectory engine's scores.
     """
 
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, batch: int, num_particles: int, *, sig_t=1e-4, sig_r=0.5,
-                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None):
+                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None, scores="auto"):
+        if scores not in ("auto", "dense_f64"):
+            raise MidasError(f"scores must be 'auto' or 'dense_f64', got {scores!r}")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.ctx = _lib.context(dev)
         self.device = self.ctx.device
@@ -522,6 +531,9 @@ class BatchFilterEngine:
         _os = os
         self.sparse_scores = self.codebook.emb.dtype == torch.float32 and self.codebook.D in (128, 256, 512, 1024) and \
             _os.environ.get("MIDAS_DENSE_SCORES", "0") != "1"
+        if scores == "dense_f64":  # no stamps: every frame is one float64 pass over all rows on the matrix cores
+            self.sparse_scores = False
+            self.codebook.set_batch_precision("f64")
         self._stamps = torch.zeros((B, self.codebook.K), dtype=torch.int32, device=d) if self.sparse_scores else None
         self._epoch = 0
 

@@ -58,14 +58,29 @@ class Codebook:
         self.ctx.call("midas_score", self.h, codes.shape[0], _ptr(codes), _ptr(out))
         return out
 
-    def score_batch(self, codes: torch.Tensor) -> torch.Tensor:
-        """(B, K) scores of B codes in one pass over the codebook on the matrix cores (float32 fma chains)."""
+    def score_batch(self, codes: torch.Tensor, precision: str = "f32") -> torch.Tensor:
+        """(B, K) scores of B codes in one pass over the codebook on the matrix cores.
+
+        precision "f32" (`midas_score_batch`): the codes rounded to float32, float32 fma chains - within ~1e-7 of `score`, equal to
+        `oracle.score_codebook_batch`; float32 embeddings with D % 16 == 0 only.  "f64" (`midas_score_batch_f64`): float64 codes and
+        arithmetic in the summation spec's order - bit-identical to `score` and `oracle.score_codebook`; any embeddings and D."""
+        entry = {"f32": "midas_score_batch", "f64": "midas_score_batch_f64"}.get(precision)
+        if entry is None:
+            raise MidasError(f"precision must be 'f32' or 'f64', got {precision!r}")
         codes = torch.atleast_2d(codes).to(self.emb.device, torch.float64).contiguous()
         if codes.shape[1] != self.D:
             raise MidasError(f"tactile code has {codes.shape[1]} dims, codebook has {self.D}")
         out = torch.empty((codes.shape[0], self.K), dtype=torch.float64, device=self.emb.device)
-        self.ctx.call("midas_score_batch", self.h, codes.shape[0], _ptr(codes), _ptr(out))
+        self.ctx.call(entry, self.h, codes.shape[0], _ptr(codes), _ptr(out))
         return out
+
+    def set_batch_precision(self, precision: str) -> None:
+        """Precision of the dense batch scoring pass inside `midas_filter_step_batch` ("f32": today's default, "f64": the
+        float64 kernel of `score_batch(..., "f64")`, bit-identical to `score`)."""
+        dtype = {"f32": _lib.MIDAS_F32, "f64": _lib.MIDAS_F64}.get(precision)
+        if dtype is None:
+            raise MidasError(f"precision must be 'f32' or 'f64', got {precision!r}")
+        self.ctx.check(self.ctx.lib.midas_codebook_set_batch_precision(self.h, dtype))
 
     def __del__(self, _finalizing=sys.is_finalizing):  # pragma: no cover  # (bound at import: module globals are gone by then)
         if _finalizing():  # the process is going away: the HIP runtime may be gone already (its calls would abort, not raise)
