@@ -274,6 +274,16 @@ int midas_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses_dev, con
 int midas_selfsim_panel(midas_ctx* ctx, const midas_codebook* cb, int64_t i0, int64_t R, float* panel_dev, int64_t ldo);
 int midas_selfsim_topn(midas_ctx* ctx, const midas_codebook* cb, int32_t n, const double* feat_dev, int32_t d,
                        int64_t rows_per_panel, double* err_dev, int32_t* idx_dev);
+/* The float64 forms, exact: panel_dev[(i - i0) * ldo + j] = cos(E_i, E_j) as float64 for i in [i0, i0 + R), all j, ldo >= K -
+ * every value BIT-IDENTICAL to midas_score's for code E_i (widened to float64) against row j (the 16 spec chains on
+ * v_mfma_f64_16x16x4_f64, as midas_score_batch_f64).  Any embedding dtype, K, D >= 1. */
+int midas_selfsim_panel_f64(midas_ctx* ctx, const midas_codebook* cb, int64_t i0, int64_t R, double* panel_dev, int64_t ldo);
+/* midas_selfsim_topn on those panels, each consumed by midas_topn_pose_error's selection: err_dev / idx_dev equal, bit for bit,
+ * what midas_score + midas_topn_pose_error give row by row.  Any embedding dtype and D; 1 <= n <= 256, 1 <= d <= 16.  Scratch:
+ * two panels of rows_per_panel x K float64 (rows_per_panel <= 0: MIDAS_SELFSIM_F64_ROWS = 2048 - 1.6 GB at K = 50k). */
+#define MIDAS_SELFSIM_F64_ROWS 2048
+int midas_selfsim_topn_f64(midas_ctx* ctx, const midas_codebook* cb, int32_t n, const double* feat_dev, int32_t d,
+                           int64_t rows_per_panel, double* err_dev, int32_t* idx_dev);
 int midas_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores_dev, int64_t row0, int32_t n,
                           const double* feat_dev, int32_t d, double* err_dev, int32_t* idx_dev);
 

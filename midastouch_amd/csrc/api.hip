@@ -133,7 +133,8 @@ MIDAS_EXPORT int midas_ctx_create(int device, void* hip_stream, midas_ctx** out)
     const char* lazy = getenv("MIDAS_LAZY_MODULES");
     if (!(lazy && lazy[0] == '1')) {
         int (*const warm[])() = {warm_score, warm_particles, warm_resample, warm_cluster, warm_topn, warm_selfsim, warm_loop,
-                                 warm_dbscan, warm_dbscan_nd, warm_index_build, warm_mt19937, warm_topk_aten, warm_score_f64};
+                                 warm_dbscan, warm_dbscan_nd, warm_index_build, warm_mt19937, warm_topk_aten, warm_score_f64,
+                                 warm_selfsim_f64};
         for (auto w : warm)
             if (w() != 0) { (void)hipGetLastError(); }  // not fatal: the unit then loads at its first launch, as before
     }
@@ -1438,6 +1439,75 @@ MIDAS_EXPORT int midas_selfsim_topn(midas_ctx* ctx, const midas_codebook* cb, in
         ctx->stream = ctx->side;  // the launcher enqueues on ctx->stream
         rc = launch_topn_pose_error_dots(ctx, (int32_t)rows, K, pan, ldo, cb->norms, rinv, i0, n, feat_dev, d, err_dev + i0,
                                          idx_dev ? idx_dev + i0 * n : nullptr);
+        ctx->stream = main_stream;
+        if (rc) return finish(rc);
+        TOPN_CHECK(hipEventRecord(ev_sel[k], ctx->side));
+    }
+#undef TOPN_CHECK
+    return finish(MIDAS_OK);  // the results are ordered behind the main stream again
+}
+
+MIDAS_EXPORT int midas_selfsim_panel_f64(midas_ctx* ctx, const midas_codebook* cb, int64_t i0, int64_t R, double* panel_dev, int64_t ldo) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, cb && panel_dev && i0 >= 0 && R >= 1 && i0 + R <= cb->K && ldo >= cb->K);
+    return launch_selfsim_panel_f64(ctx, cb, i0, R, panel_dev, ldo);
+}
+
+// midas_selfsim_topn's pipeline on float64 panels of final cosines (k_selfsim_mfma_f64, bit-identical to midas_score) and the
+// streaming selection of midas_topn_pose_error: the errors and indices of the default exact path, for any embedding dtype and D.
+// Scratch: two panels of rows_per_panel x K doubles (rows_per_panel <= 0: MIDAS_SELFSIM_F64_ROWS).
+MIDAS_EXPORT int midas_selfsim_topn_f64(midas_ctx* ctx, const midas_codebook* cb, int32_t n, const double* feat_dev, int32_t d,
+                                        int64_t rows_per_panel, double* err_dev, int32_t* idx_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, cb && feat_dev && err_dev && n >= 1 && n <= 256 && d >= 1 && d <= 16);
+    const int64_t K = cb->K, ldo = K;
+    const int64_t want = rows_per_panel > 0 ? rows_per_panel : MIDAS_SELFSIM_F64_ROWS;
+    const int64_t R = want < K ? want : K;
+    const int64_t npanels = ceil_div(K, R);
+    // two panels: the selection of panel p runs on the side stream beside the GEMM of panel p + 1, events hand them over
+    const int nbuf = npanels > 1 ? 2 : 1;
+    void* panel;
+    int rc = midas_scratch(ctx, (size_t)nbuf * R * ldo * sizeof(double), &panel);
+    if (rc) return rc;
+    if (!ctx->side) MIDAS_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+    hipEvent_t ev_gemm[2] = {nullptr, nullptr}, ev_sel[2] = {nullptr, nullptr};
+    hipStream_t main_stream = ctx->stream;
+    // every exit goes through `finish` (as midas_selfsim_topn): the side stream joined behind the main stream, the events destroyed
+    auto finish = [&](int code) {
+        ctx->stream = main_stream;
+        hipEvent_t join = nullptr;
+        if (hipEventCreateWithFlags(&join, hipEventDisableTiming) == hipSuccess) {
+            if (hipEventRecord(join, ctx->side) == hipSuccess) (void)hipStreamWaitEvent(main_stream, join, 0);
+            (void)hipEventDestroy(join);
+        }
+        for (int k = 0; k < 2; ++k) {
+            if (ev_gemm[k]) (void)hipEventDestroy(ev_gemm[k]);
+            if (ev_sel[k]) (void)hipEventDestroy(ev_sel[k]);
+        }
+        return code;
+    };
+#define TOPN_CHECK(expr)                                                                                              \
+    do {                                                                                                              \
+        hipError_t _e = (expr);                                                                                       \
+        if (_e != hipSuccess) return finish(midas_set_error(ctx, MIDAS_ERR_HIP, #expr, hipGetErrorString(_e)));       \
+    } while (0)
+    for (int k = 0; k < nbuf; ++k) {
+        TOPN_CHECK(hipEventCreateWithFlags(&ev_gemm[k], hipEventDisableTiming));
+        TOPN_CHECK(hipEventCreateWithFlags(&ev_sel[k], hipEventDisableTiming));
+    }
+    TOPN_CHECK(hipEventRecord(ev_sel[0], main_stream));  // the side stream starts behind the caller's inputs
+    TOPN_CHECK(hipStreamWaitEvent(ctx->side, ev_sel[0], 0));
+    for (int64_t p = 0; p < npanels; ++p) {
+        const int k = (int)(p % nbuf);
+        const int64_t i0 = p * R, rows = K - i0 < R ? K - i0 : R;
+        double* pan = (double*)panel + (size_t)k * R * ldo;
+        if (p >= nbuf) TOPN_CHECK(hipStreamWaitEvent(main_stream, ev_sel[k], 0));  // the panel's previous tenant has been consumed
+        rc = launch_selfsim_panel_f64(ctx, cb, i0, rows, pan, ldo);
+        if (rc) return finish(rc);
+        TOPN_CHECK(hipEventRecord(ev_gemm[k], main_stream));
+        TOPN_CHECK(hipStreamWaitEvent(ctx->side, ev_gemm[k], 0));
+        ctx->stream = ctx->side;  // the launcher enqueues on ctx->stream
+        rc = launch_topn_pose_error(ctx, (int32_t)rows, K, pan, ldo, i0, n, feat_dev, d, err_dev + i0, idx_dev ? idx_dev + i0 * n : nullptr);
         ctx->stream = main_stream;
         if (rc) return finish(rc);
         TOPN_CHECK(hipEventRecord(ev_sel[k], ctx->side));

@@ -167,7 +167,7 @@ int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* deta
 namespace midas {
 MIDAS_WARM_DECL(score) MIDAS_WARM_DECL(particles) MIDAS_WARM_DECL(resample) MIDAS_WARM_DECL(cluster) MIDAS_WARM_DECL(topn)
 MIDAS_WARM_DECL(selfsim) MIDAS_WARM_DECL(loop) MIDAS_WARM_DECL(dbscan) MIDAS_WARM_DECL(dbscan_nd) MIDAS_WARM_DECL(index_build)
-MIDAS_WARM_DECL(mt19937) MIDAS_WARM_DECL(topk_aten) MIDAS_WARM_DECL(score_f64)
+MIDAS_WARM_DECL(mt19937) MIDAS_WARM_DECL(topk_aten) MIDAS_WARM_DECL(score_f64) MIDAS_WARM_DECL(selfsim_f64)
 }  // namespace midas
 
 // scratch carve-out (stream-ordered reuse; one stream per context)
@@ -492,12 +492,16 @@ int launch_mt_normal32(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int6
 // topn.hip
 int launch_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores, int64_t row0, int32_t n,
                            const double* feat, int32_t d, double* err_out, int32_t* idx_out);
+int launch_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores, int64_t ld, int64_t row0, int32_t n,
+                           const double* feat, int32_t d, double* err_out, int32_t* idx_out);
 
 int launch_topn_rinv(midas_ctx* ctx, int64_t K, int64_t ld, const double* norms, float* rinv);
 int launch_topn_pose_error_dots(midas_ctx* ctx, int32_t B, int64_t K, const float* panel, int64_t ld, const double* norms, const float* rinv,
                                 int64_t row0, int32_t n, const double* feat, int32_t d, double* err_out, int32_t* idx_out);
 // selfsim.hip
 int launch_selfsim_panel(midas_ctx* ctx, const midas_codebook* cb, int64_t i0, int64_t R, float* panel, int64_t ldo);
+// selfsim_f64.hip
+int launch_selfsim_panel_f64(midas_ctx* ctx, const midas_codebook* cb, int64_t i0, int64_t R, double* panel, int64_t ldo);
 
 // profiling hook used by the step: record event `slot` on the stream when profiling is on
 void prof_mark(midas_ctx* ctx, int slot);

@@ -255,7 +255,13 @@ __global__ __launch_bounds__(256) void k_topn_rinv(int64_t K, int64_t ld, const 
 
 int launch_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores, int64_t row0, int32_t n,
                            const double* feat, int32_t d, double* err_out, int32_t* idx_out) {
-    hipLaunchKernelGGL(k_topn_pose_error<false>, dim3((unsigned)B), dim3(256), 0, ctx->stream, K, (const void*)scores, K, (const double*)nullptr, row0, (int)n,
+    return launch_topn_pose_error(ctx, B, K, scores, K, row0, n, feat, d, err_out, idx_out);
+}
+
+// rows of stride ld (>= K): the float64 panels of midas_selfsim_topn_f64
+int launch_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores, int64_t ld, int64_t row0, int32_t n,
+                           const double* feat, int32_t d, double* err_out, int32_t* idx_out) {
+    hipLaunchKernelGGL(k_topn_pose_error<false>, dim3((unsigned)B), dim3(256), 0, ctx->stream, K, (const void*)scores, ld, (const double*)nullptr, row0, (int)n,
                        feat, (int)d, err_out, idx_out);
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;

@@ -74,6 +74,17 @@ class Codebook:
         self.ctx.call(entry, self.h, codes.shape[0], _ptr(codes), _ptr(out))
         return out
 
+    def self_similarity(self, i0: int = 0, rows: int | None = None) -> torch.Tensor:
+        """(rows, K) float64: cos(E_i, E_j) for the entries i in [i0, i0 + rows) against all K entries (`midas_selfsim_panel_f64`,
+        float64 chains on the matrix cores) - bit-identical to `score(self.emb[i0:i0 + rows].double())`.  rows None: to the end."""
+        i0 = int(i0)
+        rows = self.K - i0 if rows is None else int(rows)
+        if i0 < 0 or rows < 1 or i0 + rows > self.K:
+            raise MidasError(f"self_similarity rows [{i0}, {i0 + rows}) outside the codebook's {self.K} entries")
+        out = torch.empty((rows, self.K), dtype=torch.float64, device=self.emb.device)
+        self.ctx.call("midas_selfsim_panel_f64", self.h, i0, rows, _ptr(out), self.K)
+        return out
+
     def set_batch_precision(self, precision: str) -> None:
         """Precision of the dense batch scoring pass inside `midas_filter_step_batch` ("f32": today's default, "f64": the
         float64 kernel of `score_batch(..., "f64")`, bit-identical to `score`)."""
