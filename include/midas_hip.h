@@ -284,6 +284,35 @@ int midas_selfsim_panel_f64(midas_ctx* ctx, const midas_codebook* cb, int64_t i0
 #define MIDAS_SELFSIM_F64_ROWS 2048
 int midas_selfsim_topn_f64(midas_ctx* ctx, const midas_codebook* cb, int32_t n, const double* feat_dev, int32_t d,
                            int64_t rows_per_panel, double* err_dev, int32_t* idx_dev);
+/* ---- one-dimensional t-SNE: modules/misc.py:111-129 color_tsne, sklearn TSNE(n_components=1, perplexity=40) as
+ * eval/viz_codebook.py:34-40 calls it, with the exact O(K^2) gradient in place of Barnes-Hut ---- */
+/* sklearn NearestNeighbors(n_neighbors=k).kneighbors_graph(mode="distance") squared (TSNE._fit's kNN, sklearn/manifold/_t_sne.py):
+ * for every row i of X (K x F, dtype MIDAS_F32 | MIDAS_F64, row stride ld elements) the k nearest other rows by squared euclidean
+ * distance |x_i|^2 + |x_j|^2 - 2 x_i.x_j in float64 (dot products on v_mfma_f64_16x16x4_f64), clamped at 0, self excluded by
+ * index, ties by (d2, index); idx_dev (K x k int32) and d2_dev (K x k float64) in ascending order.  nan_to_num != 0: np.nan_to_num
+ * applied to every element as it is read (X is not written).  1 <= k <= min(256, K - 1).  Scratch: (1 + rows_per_panel) x K
+ * float64 (rows_per_panel <= 0: MIDAS_TSNE_KNN_ROWS - 0.8 GB at K = 50k). */
+#define MIDAS_TSNE_KNN_ROWS 2048
+int midas_tsne_knn(midas_ctx* ctx, const void* X_dev, int32_t dtype, int64_t K, int64_t F, int64_t ld, int32_t nan_to_num,
+                   int32_t k, int64_t rows_per_panel, int32_t* idx_dev, double* d2_dev);
+/* sklearn/manifold/_utils.pyx _binary_search_perplexity: conditional P (K x k float64) from the float32 squared distances
+ * (K x k, in the column order of _joint_probabilities_nn's sorted CSR), float64 arithmetic, beta bisection from 1, 100 steps. */
+int midas_tsne_perplexity(midas_ctx* ctx, const float* d2_dev, int64_t K, int32_t k, float perplexity, double* P_dev);
+/* _t_sne._kl_divergence_bh at angle 0 (the exact gradient, one degree of freedom): grad_dev (K float32) =
+ * 4 [sum_{j in P_i} p_ij q_ij (y_i - y_j) - sum_{j != i} q_ij^2 (y_i - y_j) / Z], q_ij = 1 / (1 + (y_i - y_j)^2), Z = sum q_ij,
+ * P a K x K CSR (crow int64, col int32, val float32 as _kl_divergence_bh reads it).  kl_dev: NULL or 1 float64 out,
+ * sum p_ij log(max(p_ij, FLT_MIN) / max(q_ij / Z, FLT_MIN)) (compute_gradient_positive).  Bit-reproducible. */
+int midas_tsne_gradient(midas_ctx* ctx, int64_t K, const float* y_dev, const int64_t* crow_dev, const int32_t* col_dev,
+                        const float* val_dev, float* grad_dev, double* kl_dev);
+/* One call of _t_sne._gradient_descent on that objective, in place on y_dev: iterations it .. max_iter - 1, gains +0.2 / x0.8
+ * clipped at 0.01, the momentum, the learning rate (lr_float32 = 0: a numpy float64 scalar - learning_rate="auto" - so the update is
+ * float64; 1: a Python float, all float32), the stopping rule every n_iter_check iterations (best error, n_iter_without_progress,
+ * min_grad_norm).  The host reads one record at each check.  result (HOST, 2 float64): {final error, last iteration}. */
+int midas_tsne_optimize(midas_ctx* ctx, int64_t K, float* y_dev, const int64_t* crow_dev, const int32_t* col_dev,
+                        const float* val_dev, int32_t it, int32_t max_iter, double momentum, double learning_rate,
+                        int32_t lr_float32, int32_t n_iter_check, int32_t n_iter_without_progress, double min_grad_norm,
+                        double* result);
+
 int midas_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores_dev, int64_t row0, int32_t n,
                           const double* feat_dev, int32_t d, double* err_dev, int32_t* idx_dev);
 

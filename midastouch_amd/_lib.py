@@ -242,6 +242,10 @@ SIGNATURES = {
     "midas_selfsim_panel": (C.c_int, [_P, _P, _I64, _I64, _P, _I64]),
     "midas_selfsim_topn_f64": (C.c_int, [_P, _P, _I32, _P, _I32, _I64, _P, _P]),
     "midas_selfsim_panel_f64": (C.c_int, [_P, _P, _I64, _I64, _P, _I64]),
+    "midas_tsne_knn": (C.c_int, [_P, _P, _I32, _I64, _I64, _I64, _I32, _I32, _I64, _P, _P]),
+    "midas_tsne_perplexity": (C.c_int, [_P, _P, _I64, _I32, _F, _P]),
+    "midas_tsne_gradient": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P]),
+    "midas_tsne_optimize": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _D, _D, _I32, _I32, _I32, _D, _P]),
     "midas_cluster_centers": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "midas_filter_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(StepArgs)]),
     "midas_filter_step_batch": (C.c_int, [_P, _P, _P, _P, C.POINTER(StepArgs), _I32]),

@@ -1,4 +1,5 @@
 // api.hip - context, scratch, profiling and the extern "C" surface of libmidas_hip.so.
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -134,7 +135,7 @@ MIDAS_EXPORT int midas_ctx_create(int device, void* hip_stream, midas_ctx** out)
     if (!(lazy && lazy[0] == '1')) {
         int (*const warm[])() = {warm_score, warm_particles, warm_resample, warm_cluster, warm_topn, warm_selfsim, warm_loop,
                                  warm_dbscan, warm_dbscan_nd, warm_index_build, warm_mt19937, warm_topk_aten, warm_score_f64,
-                                 warm_selfsim_f64};
+                                 warm_selfsim_f64, warm_tsne};
         for (auto w : warm)
             if (w() != 0) { (void)hipGetLastError(); }  // not fatal: the unit then loads at its first launch, as before
     }
@@ -1514,6 +1515,99 @@ MIDAS_EXPORT int midas_selfsim_topn_f64(midas_ctx* ctx, const midas_codebook* cb
     }
 #undef TOPN_CHECK
     return finish(MIDAS_OK);  // the results are ordered behind the main stream again
+}
+
+// ---- one-dimensional t-SNE (tsne.hip) ----
+
+MIDAS_EXPORT int midas_tsne_knn(midas_ctx* ctx, const void* X_dev, int32_t dtype, int64_t K, int64_t F, int64_t ld, int32_t nan_to_num,
+                                int32_t k, int64_t rows_per_panel, int32_t* idx_dev, double* d2_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, X_dev && idx_dev && d2_dev && (dtype == MIDAS_F32 || dtype == MIDAS_F64) && K >= 2 && F >= 1 && ld >= F);
+    MIDAS_REQUIRE(ctx, k >= 1 && k <= 256 && k <= K - 1 && K < INT32_MAX);
+    const int64_t want = rows_per_panel > 0 ? rows_per_panel : MIDAS_TSNE_KNN_ROWS;
+    const int64_t rows = want < K ? want : K;
+    void* scratch;
+    const int rc = midas_scratch(ctx, (size_t)(K + rows * K) * sizeof(double), &scratch);
+    if (rc) return rc;
+    return launch_tsne_knn(ctx, X_dev, dtype, K, F, ld, nan_to_num, k, rows, (double*)scratch, idx_dev, d2_dev);
+}
+
+MIDAS_EXPORT int midas_tsne_perplexity(midas_ctx* ctx, const float* d2_dev, int64_t K, int32_t k, float perplexity, double* P_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, d2_dev && P_dev && K >= 1 && k >= 1 && k <= 256 && perplexity > 0.0f);
+    return launch_tsne_perplexity(ctx, d2_dev, K, k, log((double)perplexity), P_dev);
+}
+
+MIDAS_EXPORT int midas_tsne_gradient(midas_ctx* ctx, int64_t K, const float* y_dev, const int64_t* crow_dev, const int32_t* col_dev,
+                                     const float* val_dev, float* grad_dev, double* kl_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, K >= 2 && y_dev && crow_dev && col_dev && val_dev && grad_dev);
+    void* work;
+    const int rc = midas_scratch(ctx, tsne_grad_scratch_doubles(K) * sizeof(double), &work);
+    if (rc) return rc;
+    const int r1 = launch_tsne_objective(ctx, K, y_dev, crow_dev, col_dev, val_dev, (double*)work, kl_dev);
+    if (r1) return r1;
+    return launch_tsne_update(ctx, K, nullptr, (double*)work, 0, grad_dev, nullptr, nullptr, 0.0, 0.0, 0.0f, nullptr);
+}
+
+MIDAS_EXPORT int midas_tsne_optimize(midas_ctx* ctx, int64_t K, float* y_dev, const int64_t* crow_dev, const int32_t* col_dev,
+                                     const float* val_dev, int32_t it, int32_t max_iter, double momentum, double learning_rate,
+                                     int32_t lr_float32, int32_t n_iter_check, int32_t n_iter_without_progress, double min_grad_norm,
+                                     double* result) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, K >= 2 && y_dev && crow_dev && col_dev && val_dev && result && it >= 0 && n_iter_check >= 1);
+    const size_t nw = tsne_grad_scratch_doubles(K);
+    void* scratch;
+    const int rc = midas_scratch(ctx, (nw + 2 * (size_t)K + 8) * sizeof(double) + (size_t)K * sizeof(float), &scratch);
+    if (rc) return rc;
+    double* work = (double*)scratch;
+    double* update = work + nw;
+    double* gsq = update + K;
+    double* rec = gsq + K;  // {KL, sum grad^2}
+    float* gains = (float*)(rec + 8);
+    int r = launch_tsne_reset(ctx, K, gains, update);
+    if (r) return r;
+    const int mode = lr_float32 ? 2 : 1;
+    const float min_gain = 0.01f;
+    double error = DBL_MAX, best_error = DBL_MAX, hrec[2];
+    int64_t best_iter = it, i = it;
+    bool broke = false, last_err = false;
+    for (i = it; i < max_iter; ++i) {
+        const bool check = (i + 1) % n_iter_check == 0, want_err = check || i == max_iter - 1;
+        if ((r = launch_tsne_objective(ctx, K, y_dev, crow_dev, col_dev, val_dev, work, want_err ? rec : nullptr))) return r;
+        if ((r = launch_tsne_update(ctx, K, y_dev, work, mode, nullptr, gains, update, momentum, learning_rate, min_gain, gsq))) return r;
+        last_err = want_err;
+        if (!want_err) error = 0.0;  // the objective reports no error on these iterations
+        if (check) {
+            if ((r = launch_tsne_sum(ctx, gsq, K, rec + 1))) return r;
+            MIDAS_HIP_CHECK(ctx, hipMemcpyAsync(hrec, rec, sizeof(hrec), hipMemcpyDeviceToHost, ctx->stream));
+            MIDAS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            error = hrec[0];
+            const double grad_norm = sqrt(hrec[1]);
+            if (error < best_error) {
+                best_error = error;
+                best_iter = i;
+            } else if (i - best_iter > n_iter_without_progress) {
+                broke = true;
+                break;
+            }
+            if (grad_norm <= min_grad_norm) {
+                broke = true;
+                break;
+            }
+        }
+    }
+    if (!broke && i > it) {
+        i -= 1;  // the last iteration run (Python's loop variable)
+        if (last_err && (i + 1) % n_iter_check != 0) {
+            MIDAS_HIP_CHECK(ctx, hipMemcpyAsync(hrec, rec, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            MIDAS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+            error = hrec[0];
+        }
+    }
+    result[0] = error;
+    result[1] = (double)i;
+    return MIDAS_OK;
 }
 
 MIDAS_EXPORT int midas_selftest_wave_sums(midas_ctx* ctx, const double* in64_dev, double* out256_dev) {

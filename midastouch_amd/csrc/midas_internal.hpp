@@ -168,6 +168,7 @@ namespace midas {
 MIDAS_WARM_DECL(score) MIDAS_WARM_DECL(particles) MIDAS_WARM_DECL(resample) MIDAS_WARM_DECL(cluster) MIDAS_WARM_DECL(topn)
 MIDAS_WARM_DECL(selfsim) MIDAS_WARM_DECL(loop) MIDAS_WARM_DECL(dbscan) MIDAS_WARM_DECL(dbscan_nd) MIDAS_WARM_DECL(index_build)
 MIDAS_WARM_DECL(mt19937) MIDAS_WARM_DECL(topk_aten) MIDAS_WARM_DECL(score_f64) MIDAS_WARM_DECL(selfsim_f64)
+MIDAS_WARM_DECL(tsne)
 }  // namespace midas
 
 // scratch carve-out (stream-ordered reuse; one stream per context)
@@ -502,6 +503,17 @@ int launch_topn_pose_error_dots(midas_ctx* ctx, int32_t B, int64_t K, const floa
 int launch_selfsim_panel(midas_ctx* ctx, const midas_codebook* cb, int64_t i0, int64_t R, float* panel, int64_t ldo);
 // selfsim_f64.hip
 int launch_selfsim_panel_f64(midas_ctx* ctx, const midas_codebook* cb, int64_t i0, int64_t R, double* panel, int64_t ldo);
+// tsne.hip
+int launch_tsne_knn(midas_ctx* ctx, const void* X, int32_t dtype, int64_t K, int64_t F, int64_t ld, int32_t ntn, int32_t k,
+                    int64_t rows, double* scratch, int32_t* idx_out, double* d2_out);
+int launch_tsne_perplexity(midas_ctx* ctx, const float* d2, int64_t K, int32_t k, double desired_entropy, double* P);
+size_t tsne_grad_scratch_doubles(int64_t K);
+int launch_tsne_objective(midas_ctx* ctx, int64_t K, const float* y, const int64_t* crow, const int32_t* col, const float* val,
+                          double* work, double* kl_out);
+int launch_tsne_update(midas_ctx* ctx, int64_t K, float* y, double* work, int mode, float* grad_out, float* gains, double* update,
+                       double momentum, double lr, float min_gain, double* gsq);
+int launch_tsne_reset(midas_ctx* ctx, int64_t K, float* gains, double* update);
+int launch_tsne_sum(midas_ctx* ctx, const double* x, int64_t n, double* out);
 
 // profiling hook used by the step: record event `slot` on the stream when profiling is on
 void prof_mark(midas_ctx* ctx, int slot);

@@ -7,6 +7,8 @@ queries against all K entries; `fast=True, precision="f64"`: the same panels in 
 `midas_selfsim_topn_f64` - the default path's values bit for bit, any embedding dtype and D) and the selection kernel
 (`midas_topn_pose_error`) consumes each tile in one pass - the K x K matrix (20 GB at K = 50 k) never exists.
 `confusion_matrix` is `modules/misc.py:78-108` (`eval/viz_codebook.py:37`): the same float64 panels, this time materialised.
+`color_tsne` is `modules/misc.py:111-129` (sklearn's one-dimensional t-SNE of the nan_to_num'd matrix, min-max scaled, through
+`plt.cm.Spectral`) on the device (`tsne.tsne_1d`); `codebook_colors` is the compute of `eval/viz_codebook.py:34-40`.
 The heat-map of `filter/filter.py:213-215` is `particle_filter.get_similarity(code, codebook.get_embeddings(), softmax=False)`.
 """
 from __future__ import annotations
@@ -83,6 +85,31 @@ def confusion_matrix(embeddings: torch.Tensor, sz: int | None = None, batch_size
     cb.ctx.call("midas_selfsim_panel_f64", cb.h, 0, sz, ops._ptr(C), sz)
     lo, hi = C.min(), C.max()
     return (C - lo) / (hi - lo)
+
+
+def color_tsne(C: torch.Tensor, TSNE_init: str = "pca") -> torch.Tensor:
+    """`modules/misc.py:111-129` on the device: TSNE(n_components=1, perplexity=40, init=TSNE_init, random_state=0) of
+    np.nan_to_num(C) (applied as C is read - C is not modified), min-max scaled, `plt.cm.Spectral(...)[:, :3]`: (K, 3) float64.
+    The t-SNE uses the exact gradient (tsne.tsne_1d)."""
+    from . import tsne
+
+    X = C if isinstance(C, torch.Tensor) else torch.as_tensor(C)
+    if not X.is_cuda:
+        raise ops.MidasError("color_tsne needs C on a HIP device; there is no CPU fallback")
+    y = tsne.tsne_1d(X, perplexity=40.0, init=TSNE_init, random_state=0, nan_to_num=True)
+    return tsne.spectral_colors(y)
+
+
+def codebook_colors(embeddings: torch.Tensor, sz: int | None = None) -> torch.Tensor:
+    """The compute of `eval/viz_codebook.py:34-40`: (sz, 3) float64 colours of the codebook entries.  D > 256:
+    color_tsne(confusion_matrix(embeddings, sz), "pca") - the sz x sz matrix is materialised, 8 sz^2 bytes; otherwise
+    color_tsne on the embeddings."""
+    emb = embeddings if isinstance(embeddings, torch.Tensor) else torch.as_tensor(embeddings)
+    if not emb.is_cuda:
+        raise ops.MidasError("codebook_colors needs the embeddings on a HIP device; there is no CPU fallback")
+    if emb.shape[1] > 256:
+        return color_tsne(confusion_matrix(emb, sz), "pca")
+    return color_tsne(emb, "pca")
 
 
 def get_random_error(poses, n: int = NUM_NEIGHBORS, rng=None) -> float:
