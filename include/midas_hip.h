@@ -223,6 +223,20 @@ typedef struct midas_mt_segment {
 int midas_mt19937_draws(midas_ctx* ctx, uint32_t* state_dev, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs,
                         const float* radius_dev, const float* cos_dev, const float* sin_dev, uint32_t* hist_dev,
                         const uint32_t* polys_dev, int32_t pieces);
+/* midas_mt19937_draws for B streams by one call - B seeded runs of the reference, one trajectory each (a sweep over trials:
+ * torch.manual_seed(s_b) per process, modules/particle_filter.py:326-335, :245), drawn for a batch engine in one go.
+ *   states_dev (in/out) B rows of 626 uint32, each a state as midas_mt19937_seed / from_host leave it; rows may stand at different
+ *              positions inside their blocks.  Row b is left as midas_mt19937_draws leaves that state.
+ *   segs       as midas_mt19937_draws; segs[i].out_dev holds B x count values, stream b's from b x count on.
+ *   hist_dev   (in/out) B rows of MIDAS_MT19937_HIST_WORDS.
+ *   polys_dev  ONE table of pieces x 624 words for all streams: J_c is a distance from the history's first word, the same for every
+ *              stream (all draw the same sizes), whatever position the states stand at.
+ * skip_words (the same for every stream), pieces, NULL polys_dev (the sequential walk) and the history rules are those of
+ * midas_mt19937_draws; row b of every output is, number for number, that call's on state row b; B = 1 is that call.  Scratch:
+ * B x (words + 1872) x 4 bytes sequentially, B x (ceil(words / 624) + 1 + pieces) x 624 x 4 bytes in pieces. */
+int midas_mt19937_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* states_dev, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs,
+                              const float* radius_dev, const float* cos_dev, const float* sin_dev, uint32_t* hist_dev,
+                              const uint32_t* polys_dev, int32_t pieces);
 
 /* ---- resample  (K6, K7, K8) ------------------------------------------------------------------ */
 /* cdf = blocked_prefix(w) / total, cdf[N-1] = 1 (float64, fixed summation order - DESIGN.md).

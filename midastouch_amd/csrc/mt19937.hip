@@ -61,11 +61,15 @@ __device__ __forceinline__ uint32_t mt_twist(uint32_t a, uint32_t b) {
 // state: [0, 624) the current block (already twisted), [624] = words of it consumed so far (624: a new block is due).
 // Relative stream index r: word r % 624 of block r / 624, block 0 = the stored one.  The call consumes [pos, pos + skip + nwords)
 // and hands out the last nwords of them: raw[(b - b0) * 624 + k] for the blocks b >= b0 = (pos + skip) / 624, meta[0] = the
-// offset of the first wanted word in raw.
+// offset of the first wanted word in raw.  Several streams (midas_mt19937_draws_batch): workgroup b walks state row b (MT_N + 2 words)
+// into raw + b raw_stride, meta[b].
 __global__ __launch_bounds__(MT_THREADS) void k_mt_blocks(uint32_t* __restrict__ state, long long skip, long long nwords,
-                                                          uint32_t* __restrict__ raw, int32_t* __restrict__ meta) {
+                                                          uint32_t* __restrict__ raw, int32_t* __restrict__ meta, long long raw_stride = 0) {
     __shared__ uint32_t s_mt[2][MT_N];
     const int c = threadIdx.x;
+    state += (size_t)blockIdx.x * (MT_N + 2);
+    if (raw) raw += (size_t)blockIdx.x * raw_stride;
+    if (meta) meta += blockIdx.x;
     for (int k = c; k < MT_N; k += MT_THREADS) s_mt[0][k] = state[k];
     const long long pos = (long long)state[MT_N];
     const long long w0 = pos + skip, e = w0 + nwords;
@@ -127,10 +131,15 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_blocks(uint32_t* __restrict__
 constexpr int MT_DEG = 19937;
 constexpr int MT_HIST = MT_DEG + MT_N - 1;  // x[k + i], k < 624, i < 19937
 static_assert(MT_HIST == MIDAS_MT19937_HIST_WORDS, "include/midas_hip.h");
+// grid.y = stream b: raw + b raw_stride, meta[b], out + b N, hist + b MT_HIST.
 __global__ __launch_bounds__(256) void k_mt_emit(const uint32_t* __restrict__ raw, const int32_t* __restrict__ meta, long long N,
-                                                 double* __restrict__ out, uint32_t* __restrict__ hist, long long off = 0) {
+                                                 double* __restrict__ out, uint32_t* __restrict__ hist, long long off = 0, long long raw_stride = 0) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
+    raw += (size_t)blockIdx.y * raw_stride;
+    if (meta) meta += blockIdx.y;
+    out += (size_t)blockIdx.y * N;
+    if (hist) hist += (size_t)blockIdx.y * MT_HIST;
     const uint32_t* w = raw + (meta ? meta[0] : 0) + off + 2 * i;  // off: the segment's first word (midas_mt19937_draws)
     const uint32_t w0 = w[0], w1 = w[1];
     const unsigned long long r = (((unsigned long long)mt_temper(w0) << 32) | mt_temper(w1)) & ((1ull << 53) - 1ull);
@@ -156,10 +165,14 @@ static_assert(MT_N % MT_JW == 0 && MT_JQ % 4 == 0, "whole workgroups per piece, 
 // window words i + m, m = 0 .. 15, one m at a time - bank (L + m) mod 64, all different: no LDS conflicts (a thread per term with
 // its sixteen consecutive words collided four to five deep, and the kernel took 40 us where this takes 7 for eight pieces).
 // The four waves share the q range; a lane's 78 polynomial words are in registers before the window has arrived.
+// grid.z = stream b: its history hist + b MT_HIST, its starts + b G MT_N; the polynomials are the same for every stream (a distance
+// from the history's first word).
 __global__ __launch_bounds__(256) void k_mt_jump(const uint32_t* __restrict__ hist, const uint32_t* __restrict__ polys,
                                                  uint32_t* __restrict__ starts) {
     extern __shared__ uint32_t s_win[];  // MT_JWIN words (the first 4 x MT_JW reused for the cross-wave step)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, k0 = blockIdx.x * MT_JW, c = blockIdx.y;
+    hist += (size_t)blockIdx.z * MT_HIST;
+    starts += (size_t)blockIdx.z * gridDim.y * MT_N;
     const uint32_t* P = polys + (size_t)c * MT_N + (lane >> 5);
     uint32_t pw[MT_JQ / 4];
 #pragma unroll
@@ -213,10 +226,14 @@ __global__ __launch_bounds__(256) void k_mt_jump(const uint32_t* __restrict__ hi
 // Piece c = blocks [c bpc, (c + 1) bpc) of the call's nblocks blocks of 624 words (block 0 starts at the call's first word): its first
 // block is starts[c], the others follow by the block recurrence of k_mt_blocks (same column walk, one barrier a block).  The piece
 // that holds the call's last word leaves the generator's state: that block and the words consumed of it.
+// grid.y = stream b: starts + b G MT_N, raw + b raw_stride, state row b.
 __global__ __launch_bounds__(MT_THREADS) void k_mt_chunks(const uint32_t* __restrict__ starts, long long nwords, int bpc, uint32_t* __restrict__ raw,
-                                                          uint32_t* __restrict__ state) {
+                                                          uint32_t* __restrict__ state, long long raw_stride = 0) {
     __shared__ uint32_t s_mt[2][MT_N];
     const int c = threadIdx.x;
+    starts += (size_t)blockIdx.y * gridDim.x * MT_N;
+    raw += (size_t)blockIdx.y * raw_stride;
+    state += (size_t)blockIdx.y * (MT_N + 2);
     const long long nblocks = (nwords + MT_N - 1) / MT_N;
     const long long fb = (long long)blockIdx.x * bpc;
     if (fb >= nblocks) return;
@@ -277,9 +294,13 @@ int launch_mt_seed(midas_ctx* ctx, uint64_t seed, uint32_t* state) {
 constexpr uint32_t MT_U24 = (1u << 24) - 1u;
 __global__ __launch_bounds__(256) void k_mt_normal(const uint32_t* __restrict__ raw, const int32_t* __restrict__ meta, long long numel, long long nwords,
                                                    const float* __restrict__ R, const float* __restrict__ C, const float* __restrict__ S,
-                                                   float mean, float std, float* __restrict__ out, uint32_t* __restrict__ hist, long long off = 0) {
+                                                   float mean, float std, float* __restrict__ out, uint32_t* __restrict__ hist, long long off = 0,
+                                                   long long raw_stride = 0) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const uint32_t* w = raw + (meta ? meta[0] : 0) + off;
+    if (meta) meta += blockIdx.y;  // grid.y = stream b (as k_mt_emit)
+    out += (size_t)blockIdx.y * numel;
+    if (hist) hist += (size_t)blockIdx.y * MT_HIST;
+    const uint32_t* w = raw + (size_t)blockIdx.y * raw_stride + (meta ? meta[0] : 0) + off;
     if (hist && i < MT_HIST && i < nwords) hist[i] = w[i];
     if (i >= numel) return;
     const bool tail = (numel & 15) && i >= numel - 16;        // redrawn from the sixteen words behind the first numel
@@ -293,18 +314,22 @@ __global__ __launch_bounds__(256) void k_mt_normal(const uint32_t* __restrict__ 
 // The words of a call: sequential walk (k_mt_blocks; raw + meta offset) or in pieces (k_mt_jump + k_mt_chunks; offset 0, meta null).
 // `polys` = G polynomials of 624 words (t^J_c mod phi, J_c = distance from the first word in `hist` to the first word of piece c - the
 // host knows both); skip_words is part of J_c already: in pieces the state is replaced, not advanced.
-static int mt_words(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int64_t nwords, const uint32_t* hist, const uint32_t* polys, int32_t G,
-                    uint32_t** raw_out, int32_t** meta_out) {
+// B streams (state: B rows of MT_N + 2 words, hist: B rows of MT_HIST, the same polys for all): stream b's words start at
+// *raw_out + b *stride_out (meta: B offsets).
+static int mt_words(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t skip_words, int64_t nwords, const uint32_t* hist, const uint32_t* polys,
+                    int32_t G, uint32_t** raw_out, int32_t** meta_out, int64_t* stride_out) {
     void* p;
     int rc;
     *raw_out = nullptr;
     *meta_out = nullptr;
+    *stride_out = 0;
     if (polys && G > 0) {
         const int64_t nblocks = ceil_div(nwords, MT_N);
         const int bpc = (int)ceil_div(nblocks, G);
-        if ((rc = midas_scratch(ctx, ((size_t)nblocks + 1) * MT_N * sizeof(uint32_t), &p))) return rc;
+        const int64_t stride = (nblocks + 1) * MT_N;
+        if ((rc = midas_scratch(ctx, (size_t)B * stride * sizeof(uint32_t), &p))) return rc;
         uint32_t* raw = (uint32_t*)p;
-        if ((rc = midas_scratch(ctx, (size_t)G * MT_N * sizeof(uint32_t), &p))) return rc;
+        if ((rc = midas_scratch(ctx, (size_t)B * G * MT_N * sizeof(uint32_t), &p))) return rc;
         uint32_t* starts = (uint32_t*)p;
         static bool attr_set[64] = {};
         const int di = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
@@ -313,26 +338,33 @@ static int mt_words(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int64_t
             MIDAS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_mt_jump, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             attr_set[di] = true;
         }
-        hipLaunchKernelGGL(k_mt_jump, dim3(MT_N / MT_JW, (unsigned)G), dim3(256), lds, ctx->stream, hist, polys, starts);
-        hipLaunchKernelGGL(k_mt_chunks, dim3((unsigned)G), dim3(MT_THREADS), 0, ctx->stream, (const uint32_t*)starts, (long long)nwords, bpc, raw, state);
+        hipLaunchKernelGGL(k_mt_jump, dim3(MT_N / MT_JW, (unsigned)G, (unsigned)B), dim3(256), lds, ctx->stream, hist, polys, starts);
+        hipLaunchKernelGGL(k_mt_chunks, dim3((unsigned)G, (unsigned)B), dim3(MT_THREADS), 0, ctx->stream, (const uint32_t*)starts, (long long)nwords, bpc,
+                           raw, state, (long long)stride);
         *raw_out = raw;
+        *stride_out = stride;
         return MIDAS_OK;
     }
+    int64_t stride = 0;
     if (nwords > 0) {
         // blocks b0 .. bl: at most the words, the rest of the block they start in and of the one they end in
-        if ((rc = midas_scratch(ctx, ((size_t)nwords + 3 * MT_N) * sizeof(uint32_t), &p))) return rc;
+        stride = nwords + 3 * MT_N;
+        if ((rc = midas_scratch(ctx, (size_t)B * stride * sizeof(uint32_t), &p))) return rc;
         *raw_out = (uint32_t*)p;
-        if ((rc = midas_scratch(ctx, 64, &p))) return rc;
+        if ((rc = midas_scratch(ctx, (size_t)(B > 16 ? B : 16) * sizeof(int32_t), &p))) return rc;
         *meta_out = (int32_t*)p;
     }
-    hipLaunchKernelGGL(k_mt_blocks, dim3(1), dim3(MT_THREADS), 0, ctx->stream, state, (long long)skip_words, (long long)nwords, *raw_out, *meta_out);
+    hipLaunchKernelGGL(k_mt_blocks, dim3((unsigned)B), dim3(MT_THREADS), 0, ctx->stream, state, (long long)skip_words, (long long)nwords, *raw_out,
+                       *meta_out, (long long)stride);
+    *stride_out = stride;
     return MIDAS_OK;
 }
 
 int launch_mt_rand64_chunked(midas_ctx* ctx, uint32_t* state, int64_t N, double* out, uint32_t* hist, const uint32_t* polys, int32_t G) {
     uint32_t* raw;
     int32_t* meta;
-    int rc = mt_words(ctx, state, 0, 2 * N, hist, polys, G, &raw, &meta);
+    int64_t stride;
+    int rc = mt_words(ctx, 1, state, 0, 2 * N, hist, polys, G, &raw, &meta, &stride);
     if (rc) return rc;
     hipLaunchKernelGGL(k_mt_emit, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw, (const int32_t*)meta,
                        (long long)N, out, hist);
@@ -344,7 +376,8 @@ int launch_mt_rand64(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int64_
     if (N == 0 && skip_words == 0) return MIDAS_OK;
     uint32_t* raw;
     int32_t* meta;
-    int rc = mt_words(ctx, state, skip_words, 2 * N, nullptr, nullptr, 0, &raw, &meta);
+    int64_t stride;
+    int rc = mt_words(ctx, 1, state, skip_words, 2 * N, nullptr, nullptr, 0, &raw, &meta, &stride);
     if (rc) return rc;
     if (N > 0)
         hipLaunchKernelGGL(k_mt_emit, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw, (const int32_t*)meta, (long long)N,
@@ -359,7 +392,8 @@ int launch_mt_normal32(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int6
     const int64_t nwords = numel + ((numel & 15) ? 16 : 0);
     uint32_t* raw;
     int32_t* meta;
-    int rc = mt_words(ctx, state, skip_words, nwords, hist, polys, G, &raw, &meta);
+    int64_t stride;
+    int rc = mt_words(ctx, 1, state, skip_words, nwords, hist, polys, G, &raw, &meta, &stride);
     if (rc) return rc;
     const int64_t threads = numel > MT_HIST ? numel : (nwords < MT_HIST ? nwords : MT_HIST);  // (the history's words have a thread each)
     hipLaunchKernelGGL(k_mt_normal, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw, (const int32_t*)meta,
@@ -373,41 +407,52 @@ int launch_mt_normal32(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int6
 // three calls that is three jumps, three walks, three launches' worth of Python.  Here the segments' words are generated together
 // (one jump + one set of pieces over the sum of their words), each segment is then transformed from its place in the raw words; the
 // history the next call's jump reads is copied once.
-__global__ __launch_bounds__(256) void k_mt_hist(const uint32_t* __restrict__ raw, const int32_t* __restrict__ meta, uint32_t* __restrict__ hist) {
+__global__ __launch_bounds__(256) void k_mt_hist(const uint32_t* __restrict__ raw, const int32_t* __restrict__ meta, uint32_t* __restrict__ hist,
+                                                 long long raw_stride = 0) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < MT_HIST) hist[i] = raw[(meta ? meta[0] : 0) + i];
+    const int b = blockIdx.y;  // stream (as k_mt_emit)
+    if (i < MT_HIST) hist[(size_t)b * MT_HIST + i] = raw[(size_t)b * raw_stride + (meta ? meta[b] : 0) + i];
 }
 
-int launch_mt_draws(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs, const float* R,
-                    const float* C, const float* S, uint32_t* hist, const uint32_t* polys, int32_t G) {
+// B streams (midas_mt19937_draws_batch): every kernel takes the stream on a grid dimension - k_mt_blocks one workgroup per stream,
+// k_mt_jump / k_mt_chunks (pieces x B), the transforms and the history copy grid.y = B - with the per-stream strides of mt_words;
+// segment i of stream b lands at out_dev + b count.  B = 1 is the single-stream call, launch for launch.
+int launch_mt_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs,
+                          const float* R, const float* C, const float* S, uint32_t* hist, const uint32_t* polys, int32_t G) {
     int64_t total = 0;
     for (int i = 0; i < nseg; ++i)
         total += segs[i].kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * segs[i].count : segs[i].count + ((segs[i].count & 15) ? 16 : 0);
     uint32_t* raw;
     int32_t* meta;
-    int rc = mt_words(ctx, state, skip_words, total, hist, polys, G, &raw, &meta);
+    int64_t stride;
+    int rc = mt_words(ctx, B, state, skip_words, total, hist, polys, G, &raw, &meta, &stride);
     if (rc) return rc;
     int64_t off = 0;
     for (int i = 0; i < nseg; ++i) {
         const int64_t n = segs[i].count;
         if (segs[i].kind == MIDAS_MT_SEGMENT_RAND64) {
             if (n > 0)
-                hipLaunchKernelGGL(k_mt_emit, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw, (const int32_t*)meta,
-                                   (long long)n, (double*)segs[i].out_dev, (uint32_t*)nullptr, (long long)off);
+                hipLaunchKernelGGL(k_mt_emit, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
+                                   (const int32_t*)meta, (long long)n, (double*)segs[i].out_dev, (uint32_t*)nullptr, (long long)off, (long long)stride);
             off += 2 * n;
         } else {
             const int64_t nw = n + ((n & 15) ? 16 : 0);
-            hipLaunchKernelGGL(k_mt_normal, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw, (const int32_t*)meta,
-                               (long long)n, (long long)nw, R, C, S, segs[i].mean, segs[i].std, (float*)segs[i].out_dev, (uint32_t*)nullptr,
-                               (long long)off);
+            hipLaunchKernelGGL(k_mt_normal, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
+                               (const int32_t*)meta, (long long)n, (long long)nw, R, C, S, segs[i].mean, segs[i].std, (float*)segs[i].out_dev,
+                               (uint32_t*)nullptr, (long long)off, (long long)stride);
             off += nw;
         }
     }
     if (hist && total >= MT_HIST)
-        hipLaunchKernelGGL(k_mt_hist, dim3((unsigned)ceil_div((int64_t)MT_HIST, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
-                           (const int32_t*)meta, hist);
+        hipLaunchKernelGGL(k_mt_hist, dim3((unsigned)ceil_div((int64_t)MT_HIST, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
+                           (const int32_t*)meta, hist, (long long)stride);
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
+}
+
+int launch_mt_draws(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs, const float* R,
+                    const float* C, const float* S, uint32_t* hist, const uint32_t* polys, int32_t G) {
+    return launch_mt_draws_batch(ctx, 1, state, skip_words, nseg, segs, R, C, S, hist, polys, G);
 }
 
 MIDAS_WARM_TU(mt19937, k_mt_seed)

@@ -550,11 +550,70 @@ class BatchFilterEngine:
         self.poses.copy_(ops.gather_rows(self.cb_poses, idx).view_as(self.poses))
         self.hint.copy_(idx.view_as(self.hint))
 
+    def seed_torch_streams(self, seeds, motion: bool = False, pieces: int = 0):
+        """Trajectory b draws from the device replica of torch's CPU generator under torch.manual_seed(seeds[b]) - B seeded runs of
+        the reference, one process each (TorchCpuStreams; PipelinedFilterEngine.seed_torch_stream for one trajectory).  `seeds`: B
+        ints, or B torch.Generators continued where they stand (from_host), or None: back to Philox.
+        motion=False: every step() without `u` resamples trajectory b with the uniforms torch.multinomial(w_b.double(), N, True)
+        would consume on stream b (modules/particle_filter.py:245); with host tn / rot the streams first step over the words of the
+        two torch.normal((N, 3)) calls.  motion=True: tn, rot and u all come from the streams in the reference's order
+        (torch.normal(0, sig_t, (N, 3)), torch.normal(0, sig_r, (N, 3)), N float64 uniforms: :326-335, :245) - unit normals, scaled
+        by sig_t / sig_r where they are used (fl(n x std): ATen's fused multiply-add with mean 0) - and explicit tn / rot / u are an
+        error.  One walk of the generators per frame; the context's scratch for it is reserved here.  `pieces` (TorchCpuStreams'):
+        0 by default - the jump costs B x pieces x 39 workgroups of 78 KB LDS, and at c5 (B = 64) it takes 0.42 ms where the 64
+        sequential walks, side by side, take 37 us (the mt19937 paragraph).
+        After a run, `torch_streams.to_host(b, g)` hands stream b back to a host generator."""
+        self._unit_noise = None  # (tn, rot, event): unit normals of the NEXT frame (the pipelined engine draws them a frame ahead)
+        if seeds is None:
+            self.torch_streams, self.torch_motion = None, False
+            return None
+        seeds = list(seeds)
+        if len(seeds) != self.B:
+            raise MidasError(f"seed_torch_streams: {len(seeds)} seeds for {self.B} trajectories")
+        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
+            raise MidasError("seeded torch streams reproduce torch.multinomial's draws: resample='weighted_random' only")
+        from .torch_rng import TorchCpuStreams
+        st = TorchCpuStreams(seeds, self.device, pieces=pieces)
+        N = self.N
+        frame = [("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3)), ("rand64", N)] if motion else [("rand64", N)]
+        st.reserve(frame)
+        self.torch_streams, self.torch_motion = st, bool(motion)
+        return st
+
+    def _stream_draws(self, tn, rot, u):
+        """This frame's draws from the seeded streams (seed_torch_streams): (tn, rot, u, event of u or None)."""
+        st = getattr(self, "torch_streams", None)
+        if st is None:
+            return tn, rot, u, None
+        B, N = self.B, self.N
+        if self.torch_motion:
+            if tn is not None or rot is not None or u is not None:
+                raise MidasError("seed_torch_streams(motion=True): the streams draw tn, rot and u - passing them would desynchronise "
+                                 "the streams from the reference's")
+            return self._seeded_frame()
+        if u is not None:
+            return tn, rot, u, None  # (the caller's uniforms: the streams are not used this frame)
+        if tn is not None:
+            st.skip_normal(3 * N).skip_normal(3 * N)
+        (u,), ev = st.draws_async([("rand64", N)])
+        return tn, rot, u, ev
+
+    def _seeded_frame(self):
+        """motion=True: the frame's normals and uniforms by one walk (the eager step reads all three at once)."""
+        N = self.N
+        (a, b, u), ev = self.torch_streams.draws_async([("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3)), ("rand64", N)])
+        if ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(ev)
+        return a * self.sig_t, b * self.sig_r, u, None
+
     def step(self, odoms, codes, gts=None, tn=None, rot=None, u=None, u32=-1.0):
         """odoms (B,4,4) f32, codes (B,D) f64, gts (B,4,4) f32 or None; optional host draws tn/rot (B,N,3), u (B,N)."""
         d, B, N = self.device, self.B, self.N
         if (tn is None) != (rot is None):
             raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
+        tn, rot, u, ev = self._stream_draws(tn, rot, u)
+        if ev is not None:
+            torch.cuda.current_stream(d).wait_event(ev)
         odoms, gts = operand(odoms, "odoms", torch.float32, (B, 4, 4), d), operand(gts, "gt poses", torch.float32, (B, 4, 4), d)
         codes = operand(codes, "tactile codes", torch.float64, (B, self.codebook.D), d)
         tn, rot = operand(tn, "tn", torch.float32, (B, N, 3), d), operand(rot, "rot", torch.float32, (B, N, 3), d)
@@ -662,10 +721,37 @@ class PipelinedBatchFilterEngine(BatchFilterEngine):
         self._poses.copy_(ops.gather_rows(self.cb_poses, idx).view_as(self._poses))
         self._hint.copy_(idx.view_as(self._hint))
 
+    def _seeded_frame(self):
+        """motion=True: this frame's normals were drawn a frame ahead, behind the previous frame's uniforms; this frame's uniforms
+        (consumed by the NEXT launch's folded resample or by flush()) and the next frame's normals follow them in one walk, beside
+        this frame's kernels on the generators' own stream."""
+        N, st = self.N, self.torch_streams
+        if self._unit_noise is None:
+            (a, b), ev = st.draws_async([("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3))])
+            self._unit_noise = (a, b, ev)
+        a, b, ev = self._unit_noise
+        if ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(ev)
+        tn, rot = a * self.sig_t, b * self.sig_r
+        (u, a, b), ev = st.draws_async([("rand64", N), ("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3))])
+        self._unit_noise = (a, b, ev)
+        return tn, rot, u, ev
+
+    def _wait_draws(self):
+        """The pending frame's uniforms may still be in flight on the generators' stream: order this stream behind them."""
+        ev = getattr(self, "_draw_event", None)
+        if ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(ev)
+            self._draw_event = None
+
     def step(self, odoms, codes, gts=None, tn=None, rot=None, u=None, u32=-1.0):
         d, B, N = self.device, self.B, self.N
         if (tn is None) != (rot is None):
             raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
+        own_u = u is None
+        tn, rot, u, u_event = self._stream_draws(tn, rot, u)
+        own_u = own_u and u is not None  # generated here (a tensor nobody else holds): kept for the folded resample without a copy
+        self._wait_draws()
         odoms, gts = operand(odoms, "odoms", torch.float32, (B, 4, 4), d), operand(gts, "gt poses", torch.float32, (B, 4, 4), d)
         codes = operand(codes, "tactile codes", torch.float64, (B, self.codebook.D), d)
         tn, rot = operand(tn, "tn", torch.float32, (B, N, 3), d), operand(rot, "rot", torch.float32, (B, N, 3), d)
@@ -693,7 +779,8 @@ class PipelinedBatchFilterEngine(BatchFilterEngine):
         self._keep = (odoms, codes, gts, tn, rot, pu)
         self.ctx.bind_current_stream()
         self.ctx.check(self.ctx.lib.midas_lazy_step_batch(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), B))
-        self._draw = (None if u is None else u.clone(), float(u32), self.step_count)
+        self._draw = (None if u is None else (u if own_u else u.clone()), float(u32), self.step_count)
+        self._draw_event = u_event
         self._had_gt = gts is not None
         self._pending, self._flushed, self._cur = True, False, nxt
         self.step_count += 1
@@ -702,6 +789,7 @@ class PipelinedBatchFilterEngine(BatchFilterEngine):
         """Materialise the latest frame's resample of every trajectory."""
         if not self._pending or self._flushed:
             return
+        self._wait_draws()
         cur = self._cur
         u, u32, stp = self._draw
         a = LazyFlushArgs()

@@ -6,6 +6,9 @@ CPU generator (modules/particle_filter.py:245): under `torch.manual_seed(s)` the
 same uniforms without a host generator or a per-frame upload; `skip_normal(numel)` steps over the outputs a
 `torch.normal(..., size)` of float32 values would have taken (add_noise_to_odom, :326-335), so a caller that still draws
 its motion noise on the host generator stays aligned with the reference's stream.
+
+`TorchCpuStreams(seeds)` holds B such streams - B seeded runs of the reference, one trajectory each, as a batch engine runs
+them - and draws a frame of all of them by one call (midas_mt19937_draws_batch).
 """
 from __future__ import annotations
 
@@ -31,7 +34,152 @@ def normal_words(numel: int) -> int:
     return numel + (16 if numel % 16 else 0)
 
 
-class TorchCpuStream:
+# ---- torch's host generator state <-> a device state row ----------------------------------------------------------------
+# Layout of the host state (CPUGeneratorImpl's legacy pod, 5056 bytes): uint64 seed | int32 left | int32 seeded | uint64 next |
+# uint64 state[624] | ..; a device row is the 624 words of the current block and the number of them consumed (csrc/mt19937.hip).
+def _host_state_row(generator: torch.Generator | None):
+    """The device state row (626 int32, host) that continues `generator` (None: torch's default CPU generator) where it stands."""
+    import numpy as np
+    b = (torch.get_rng_state() if generator is None else generator.get_state()).numpy()
+    if b.size != 5056:
+        raise _lib.MidasError("unexpected layout of torch's CPU generator state")
+    left = int(np.frombuffer(b[8:12].tobytes(), dtype=np.int32)[0])
+    nxt = int(np.frombuffer(b[16:24].tobytes(), dtype=np.uint64)[0])
+    words = np.frombuffer(b[24:24 + 624 * 8].tobytes(), dtype=np.uint64).astype(np.uint32)
+    # at::mt19937 twists when --left reaches 0: left == 1 means "a new block is due" whatever next says (fresh seeds: left 1, next 0)
+    pos = 624 if left == 1 else nxt
+    return np.concatenate([words, np.array([pos, 0], dtype=np.uint32)]).view(np.int32)
+
+
+def _set_host_state(st, generator: torch.Generator | None):
+    """Make `generator` (None: torch's default CPU generator) continue where the device state row `st` (626 uint32, host) stands."""
+    import numpy as np
+    pos = int(st[624])
+    g = torch.default_generator if generator is None else generator
+    b = g.get_state().numpy().copy()
+    if b.size != 5056:
+        raise _lib.MidasError("unexpected layout of torch's CPU generator state")
+    # pos words of the stored block are consumed: next = pos, left = 624 - pos + 1 (the twist happens when --left hits 0)
+    b[8:12] = np.frombuffer(np.int32(624 - pos + 1).tobytes(), dtype=np.uint8)
+    b[12:16] = np.frombuffer(np.int32(1).tobytes(), dtype=np.uint8)
+    b[16:24] = np.frombuffer(np.uint64(pos if pos < 624 else 0).tobytes(), dtype=np.uint8)
+    b[24:24 + 624 * 8] = np.frombuffer(st[:624].astype(np.uint64).tobytes(), dtype=np.uint8)
+    g.set_state(torch.from_numpy(b))
+
+
+class _GeneratorSide:
+    """What TorchCpuStream and TorchCpuStreams share: the generator's stream and context, the jump-polynomial cache with its
+    chaining policy (`chain_after`, `pieces_for`) and the torch.normal tables."""
+
+    def _setup(self, device, overlap: bool, pieces: int):
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = _lib.context(dev).device
+        self.overlap = bool(overlap)
+        if self.overlap:
+            self.side = torch.cuda.Stream(self.device)
+            with torch.cuda.stream(self.side):
+                self.ctx = _lib.Context(self.device)  # bound to the side stream for good (never re-bound)
+        else:
+            self.side = None
+            self.ctx = _lib.context(dev)
+        self.pending_skip = 0
+        self.pieces = int(pieces)
+        self.chain_after = 2  # occurrences of a (previous size, skip, size) pattern before its jump polynomials are computed (1: at once)
+        self._hist_words = 0   # words the call that wrote _hist handed out (0: no history)
+        self._polys = {}       # (previous words, skip, words) -> device table of the pieces' polynomials
+
+    def _enter(self):
+        """Orders the generator's stream behind the caller's current stream (state, buffers and seeds are shared with it)."""
+        if self.side is None:
+            self.ctx.bind_current_stream()
+            return
+        self.side.wait_stream(torch.cuda.current_stream(self.device))
+
+    def _call(self, name, *args):
+        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx.h, *args))
+
+    def skip_words(self, n: int):
+        """Step over n 32-bit outputs (applied with the next draw)."""
+        self.pending_skip += int(n)
+        return self
+
+    def skip_normal(self, numel: int):
+        """Step over what torch.normal(mean, std, size) with `numel` float32 values takes."""
+        return self.skip_words(normal_words(numel))
+
+    def _chain_polys(self, words: int, pieces: int | None = None):
+        """The jump polynomials of a call of `words` words, or None (no history / too short: the sequential walk)."""
+        pieces = self.pieces if pieces is None else pieces
+        if pieces > 0 and self._hist_words and words >= _lib.MT19937_HIST_WORDS:
+            # the polynomials cost the host ~10 ms each: worth it for a pattern of sizes that REPEATS (a fixed-N engine: the same
+            # three calls every frame), not for a particle count that changes every frame (the annealing loop: 100 ms a frame of
+            # host arithmetic when every call asked for its own set) - a (previous size, skip, size) is served in pieces from its
+            # second occurrence on
+            key = (self._hist_words, self.pending_skip, words, pieces)
+            if key in self._polys:
+                return self._polys[key]
+            seen = self.__dict__.setdefault("_seen", {})
+            if len(seen) > 256:
+                seen.clear()
+            seen[key] = seen.get(key, 0) + 1
+            if seen[key] >= self.chain_after:
+                return self._piece_polys(self._hist_words, self.pending_skip, words, pieces)
+        return None
+
+    def _drawn(self, words: int, out):
+        # (a call too short to leave a history, or a pure skip, breaks the chain: the next call walks sequentially)
+        self._hist_words = words if words >= _lib.MT19937_HIST_WORDS else 0
+        self.pending_skip = 0
+        if self.side is None:
+            return out, None
+        ev = torch.cuda.Event()
+        ev.record(self.side)
+        return out, ev
+
+    def _normal_tables(self):
+        """The three 2^24-entry tables of torch.normal's float32 path on this machine (torch_normal.py), on the device."""
+        tabs = getattr(self, "_ntab", None)
+        if tabs is None:
+            from . import torch_normal
+            with torch.cuda.stream(self.side) if self.side is not None else _null():
+                tabs = tuple(torch.from_numpy(a).to(self.device) for a in torch_normal.host_tables())
+            self._ntab = tabs
+        return tabs
+
+    def pieces_for(self, words: int) -> int:
+        """Pieces a call of `words` words is cut into: `pieces` for a draw of 2 x 10^5 words (N = 10^5 uniforms), more for longer calls
+        so that a piece stays ~54 blocks of 624 words (the walk of a piece is the sequential part; a jump costs ~2 us a piece)."""
+        if self.pieces <= 0:
+            return 0
+        return max(self.pieces, min(48, -(-words // (54 * 624))))
+
+    def _piece_polys(self, prev_words: int, skip: int, words: int, pieces: int | None = None):
+        pieces = self.pieces if pieces is None else pieces
+        key = (prev_words, skip, words, pieces)
+        tab = self._polys.get(key)
+        if tab is None:
+            import numpy as np
+
+            from . import mt_jump
+            nblocks = -(-words // 624)
+            bpc = -(-nblocks // pieces)
+            rows = []
+            for c in range(pieces):
+                J = prev_words + skip + c * bpc * 624
+                if not mt_jump.check(J):
+                    raise _lib.MidasError(f"mt19937 jump polynomial for distance {J} failed its check against the reference generator")
+                rows.append(mt_jump.jump_words(J))
+            host = torch.from_numpy(np.stack(rows).view(np.int32))
+            if len(self._polys) >= 16:
+                self._polys.clear()
+            # uploaded on the generator's stream (the caller is inside _enter() .. the launch)
+            with torch.cuda.stream(self.side) if self.side is not None else _null():
+                tab = host.to(self.device)
+            self._polys[key] = tab
+        return tab
+
+
+class TorchCpuStream(_GeneratorSide):
     """`overlap=True` (default): the generator runs on a stream and a library context of its own - its single-workgroup block
     recurrence (one CU, ~100 us for a frame's 2 N words at N = 100k: 321 blocks of 624 words at 310 ns) then runs BESIDE the frame kernels of the caller's stream
     instead of in front of them.  `rand64()` orders the result behind the caller's stream as before; `rand64_async()` returns
@@ -47,35 +195,11 @@ class TorchCpuStream:
     step at c2 goes from 10.8k to 22.7k frames/s (4 / 6 / 8 / 12 pieces: 21.7 / 22.7 / 21.7 / 21.8k; tools/bench_parity_mode.py)."""
 
     def __init__(self, seed: int, device=None, overlap: bool = True, pieces: int = 6):
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.device = _lib.context(dev).device
-        self.overlap = bool(overlap)
-        if self.overlap:
-            self.side = torch.cuda.Stream(self.device)
-            with torch.cuda.stream(self.side):
-                self.ctx = _lib.Context(self.device)  # bound to the side stream for good (never re-bound)
-        else:
-            self.side = None
-            self.ctx = _lib.context(dev)
+        self._setup(device, overlap, pieces)
         self.state = torch.zeros(626, dtype=torch.int32, device=self.device)
-        self.pending_skip = 0
-        self.pieces = int(pieces)
-        self.chain_after = 2  # occurrences of a (previous size, skip, size) pattern before its jump polynomials are computed (1: at once)
         self._hist = torch.zeros(_lib.MT19937_HIST_WORDS, dtype=torch.int32, device=self.device)
-        self._hist_words = 0   # words the call that wrote _hist handed out (0: no history)
-        self._polys = {}       # (previous words, skip, words) -> device table of the pieces' polynomials
         self._bufs, self._turn = [None, None, None], 0
         self.manual_seed(seed)
-
-    def _enter(self):
-        """Orders the generator's stream behind the caller's current stream (state, buffers and seeds are shared with it)."""
-        if self.side is None:
-            self.ctx.bind_current_stream()
-            return
-        self.side.wait_stream(torch.cuda.current_stream(self.device))
-
-    def _call(self, name, *args):
-        self.ctx.check(getattr(self.ctx.lib, name)(self.ctx.h, *args))
 
     def manual_seed(self, seed: int):
         """torch.manual_seed(seed) for this stream."""
@@ -88,21 +212,12 @@ class TorchCpuStream:
 
     # ---- hand-over between torch's host generator and this stream --------------------------------------------------
     # A caller that draws some numbers on the host (init_filter, particle_filter.py:129-145) and the per-frame ones here keeps
-    # ONE stream: from_host() continues the host generator where it stands, to_host() gives it back.  Layout of the host
-    # state (CPUGeneratorImpl's legacy pod, 5056 bytes): uint64 seed | int32 left | int32 seeded | uint64 next | uint64 state[624] | ..
+    # ONE stream: from_host() continues the host generator where it stands, to_host() gives it back (_host_state_row /
+    # _set_host_state: the layout of the host state).
     def from_host(self, generator: torch.Generator | None = None):
         """Continue `generator` (default: torch's default CPU generator) on the device: the next draw here is the number the host
         generator would have produced next."""
-        import numpy as np
-        b = (torch.get_rng_state() if generator is None else generator.get_state()).numpy()
-        if b.size != 5056:
-            raise _lib.MidasError("unexpected layout of torch's CPU generator state")
-        left = int(np.frombuffer(b[8:12].tobytes(), dtype=np.int32)[0])
-        nxt = int(np.frombuffer(b[16:24].tobytes(), dtype=np.uint64)[0])
-        words = np.frombuffer(b[24:24 + 624 * 8].tobytes(), dtype=np.uint64).astype(np.uint32)
-        # at::mt19937 twists when --left reaches 0: left == 1 means "a new block is due" whatever next says (fresh seeds: left 1, next 0)
-        pos = 624 if left == 1 else nxt
-        host = np.concatenate([words, np.array([pos, 0], dtype=np.uint32)]).view(np.int32)
+        host = _host_state_row(generator)
         self._enter()
         with torch.cuda.stream(self.side) if self.side is not None else _null():
             self.state.copy_(torch.from_numpy(host.copy()), non_blocking=False)
@@ -124,28 +239,8 @@ class TorchCpuStream:
             self.side.synchronize()
         else:
             torch.cuda.current_stream(self.device).synchronize()
-        st = self.state.cpu().numpy().view(np.uint32)
-        pos = int(st[624])
-        g = torch.default_generator if generator is None else generator
-        b = g.get_state().numpy().copy()
-        if b.size != 5056:
-            raise _lib.MidasError("unexpected layout of torch's CPU generator state")
-        # pos words of the stored block are consumed: next = pos, left = 624 - pos + 1 (the twist happens when --left hits 0)
-        b[8:12] = np.frombuffer(np.int32(624 - pos + 1).tobytes(), dtype=np.uint8)
-        b[12:16] = np.frombuffer(np.int32(1).tobytes(), dtype=np.uint8)
-        b[16:24] = np.frombuffer(np.uint64(pos if pos < 624 else 0).tobytes(), dtype=np.uint8)
-        b[24:24 + 624 * 8] = np.frombuffer(st[:624].astype(np.uint64).tobytes(), dtype=np.uint8)
-        g.set_state(torch.from_numpy(b))
+        _set_host_state(self.state.cpu().numpy().view(np.uint32), generator)
         return self
-
-    def skip_words(self, n: int):
-        """Step over n 32-bit outputs (applied with the next draw)."""
-        self.pending_skip += int(n)
-        return self
-
-    def skip_normal(self, numel: int):
-        """Step over what torch.normal(mean, std, size) with `numel` float32 values takes."""
-        return self.skip_words(normal_words(numel))
 
     def rand64_async(self, N: int, out: torch.Tensor | None = None):
         """The next N values of torch.rand(N, dtype=torch.float64), enqueued on the generator's stream: (tensor, event or None).
@@ -188,45 +283,6 @@ class TorchCpuStream:
         self._call("midas_mt19937_rand64_chunked", _ptr(self.state), self.pending_skip, N, _ptr(out), _ptr(self._hist), _ptr(polys),
                    self.pieces if polys is not None else 0)
         return self._drawn(words, out)
-
-    def _chain_polys(self, words: int, pieces: int | None = None):
-        """The jump polynomials of a call of `words` words, or None (no history / too short: the sequential walk)."""
-        pieces = self.pieces if pieces is None else pieces
-        if pieces > 0 and self._hist_words and words >= _lib.MT19937_HIST_WORDS:
-            # the polynomials cost the host ~10 ms each: worth it for a pattern of sizes that REPEATS (a fixed-N engine: the same
-            # three calls every frame), not for a particle count that changes every frame (the annealing loop: 100 ms a frame of
-            # host arithmetic when every call asked for its own set) - a (previous size, skip, size) is served in pieces from its
-            # second occurrence on
-            key = (self._hist_words, self.pending_skip, words, pieces)
-            if key in self._polys:
-                return self._polys[key]
-            seen = self.__dict__.setdefault("_seen", {})
-            if len(seen) > 256:
-                seen.clear()
-            seen[key] = seen.get(key, 0) + 1
-            if seen[key] >= self.chain_after:
-                return self._piece_polys(self._hist_words, self.pending_skip, words, pieces)
-        return None
-
-    def _drawn(self, words: int, out):
-        # (a call too short to leave a history, or a pure skip, breaks the chain: the next call walks sequentially)
-        self._hist_words = words if words >= _lib.MT19937_HIST_WORDS else 0
-        self.pending_skip = 0
-        if self.side is None:
-            return out, None
-        ev = torch.cuda.Event()
-        ev.record(self.side)
-        return out, ev
-
-    def _normal_tables(self):
-        """The three 2^24-entry tables of torch.normal's float32 path on this machine (torch_normal.py), on the device."""
-        tabs = getattr(self, "_ntab", None)
-        if tabs is None:
-            from . import torch_normal
-            with torch.cuda.stream(self.side) if self.side is not None else _null():
-                tabs = tuple(torch.from_numpy(a).to(self.device) for a in torch_normal.host_tables())
-            self._ntab = tabs
-        return tabs
 
     def normal_async(self, mean: float, std: float, size, out: torch.Tensor | None = None):
         """torch.normal(mean, std, size=size) of float32 values - the reference's motion-noise draws (particle_filter.py:326-335) -
@@ -300,38 +356,6 @@ class TorchCpuStream:
         _, ev = self._drawn(words, None)
         return outs, ev
 
-    def pieces_for(self, words: int) -> int:
-        """Pieces a call of `words` words is cut into: `pieces` for a draw of 2 x 10^5 words (N = 10^5 uniforms), more for longer calls
-        so that a piece stays ~54 blocks of 624 words (the walk of a piece is the sequential part; a jump costs ~2 us a piece)."""
-        if self.pieces <= 0:
-            return 0
-        return max(self.pieces, min(48, -(-words // (54 * 624))))
-
-    def _piece_polys(self, prev_words: int, skip: int, words: int, pieces: int | None = None):
-        pieces = self.pieces if pieces is None else pieces
-        key = (prev_words, skip, words, pieces)
-        tab = self._polys.get(key)
-        if tab is None:
-            import numpy as np
-
-            from . import mt_jump
-            nblocks = -(-words // 624)
-            bpc = -(-nblocks // pieces)
-            rows = []
-            for c in range(pieces):
-                J = prev_words + skip + c * bpc * 624
-                if not mt_jump.check(J):
-                    raise _lib.MidasError(f"mt19937 jump polynomial for distance {J} failed its check against the reference generator")
-                rows.append(mt_jump.jump_words(J))
-            host = torch.from_numpy(np.stack(rows).view(np.int32))
-            if len(self._polys) >= 16:
-                self._polys.clear()
-            # uploaded on the generator's stream (the caller is inside _enter() .. the launch)
-            with torch.cuda.stream(self.side) if self.side is not None else _null():
-                tab = host.to(self.device)
-            self._polys[key] = tab
-        return tab
-
     def rand64(self, N: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """The next N values of torch.rand(N, dtype=torch.float64) (== the draws of torch.multinomial(w64, N, True)), ordered
         behind the caller's current stream; a fresh tensor unless `out` is given."""
@@ -343,3 +367,143 @@ class TorchCpuStream:
         if ev is not None:
             torch.cuda.current_stream(self.device).wait_event(ev)
         return u
+
+
+class TorchCpuStreams(_GeneratorSide):
+    """B of torch's CPU streams, drawn together: stream b is a process of the reference under torch.manual_seed(seeds[b]) (or a
+    host generator continued by from_host), and one call (midas_mt19937_draws_batch) hands out the same draws of every stream -
+    a batch engine's frame of B seeded trajectories (BatchFilterEngine.seed_torch_streams).
+
+    `device`, `overlap`, `pieces`, `chain_after` and `pieces_for` are TorchCpuStream's; the jump polynomials are shared by all
+    streams (a distance from the first word of the previous call's history, the same for every stream).  draws_async returns
+    fresh (B, ...) tensors written on the generator's stream and an event every read orders behind - no rotating buffers."""
+
+    def __init__(self, seeds, device=None, overlap: bool = True, pieces: int = 6):
+        seeds = list(seeds)
+        if not seeds:
+            raise _lib.MidasError("TorchCpuStreams needs at least one stream")
+        self.B = len(seeds)
+        self._setup(device, overlap, pieces)
+        self.state = torch.zeros((self.B, 626), dtype=torch.int32, device=self.device)
+        self._hist = torch.zeros((self.B, _lib.MT19937_HIST_WORDS), dtype=torch.int32, device=self.device)
+        if all(isinstance(s, torch.Generator) for s in seeds):
+            self.from_host(seeds)
+        else:
+            self.manual_seed(seeds)
+
+    def _count(self, items, what):
+        items = list(items)
+        if len(items) != self.B:
+            raise _lib.MidasError(f"{what}: expected {self.B} (one per stream), got {len(items)}")
+        return items
+
+    def _restart(self):
+        self.pending_skip = 0
+        self._hist_words = 0
+
+    def manual_seed(self, seeds):
+        """torch.manual_seed(seeds[b]) for stream b."""
+        seeds = self._count(seeds, "seeds")
+        self._enter()
+        for b, s in enumerate(seeds):
+            self._call("midas_mt19937_seed", int(s) & 0xFFFFFFFFFFFFFFFF, _ptr(self.state[b]))
+        self._restart()
+        return self
+
+    def from_host(self, generators):
+        """Stream b continues the host generator generators[b] where it stands."""
+        import numpy as np
+        rows = np.stack([_host_state_row(g) for g in self._count(generators, "generators")])
+        self._enter()
+        with torch.cuda.stream(self.side) if self.side is not None else _null():
+            self.state.copy_(torch.from_numpy(rows), non_blocking=False)
+        self._restart()
+        return self
+
+    def to_host(self, b: int, generator: torch.Generator | None = None):
+        """Give stream b back: `generator` (default: torch's default CPU generator) continues where stream b stands (pending skips
+        applied to every stream).  Synchronises with the generator's stream."""
+        import numpy as np
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise _lib.MidasError(f"stream {b} of {self.B}")
+        if self.pending_skip:
+            self._enter()
+            self._batch_call([(_lib.MT_SEGMENT_RAND64, 0, 0.0, 1.0, None)], None)
+            self._restart()
+        if self.side is not None:
+            self.side.synchronize()
+        else:
+            torch.cuda.current_stream(self.device).synchronize()
+        _set_host_state(self.state[b].cpu().numpy().view(np.uint32), generator)
+        return self
+
+    def _batch_call(self, segs, polys, pieces: int = 0, tables=(None, None, None)):
+        import ctypes as C
+        arr = (_lib.MtSegment * len(segs))()
+        for a, (kind, count, mean, std, out) in zip(arr, segs):
+            a.kind, a.count, a.mean, a.std, a.out_dev = kind, count, mean, std, None if out is None else out.data_ptr()
+        R, Ct, S = tables
+        self._call("midas_mt19937_draws_batch", self.B, _ptr(self.state), self.pending_skip, len(segs), C.cast(arr, C.c_void_p), _ptr(R),
+                   _ptr(Ct), _ptr(S), _ptr(self._hist), _ptr(polys), pieces if polys is not None else 0)
+
+    def _segments(self, spec):
+        """spec -> ([(kind, count, mean, std, shape)], words per stream)."""
+        segs, words = [], 0
+        for item in spec:
+            if item[0] == "rand64":
+                n = int(item[1])
+                segs.append((_lib.MT_SEGMENT_RAND64, n, 0.0, 1.0, (n,)))
+                words += 2 * n
+            elif item[0] == "normal":
+                _, mean, std, size = item
+                shape = tuple(int(d) for d in size) if hasattr(size, "__len__") else (int(size),)
+                numel = 1
+                for d in shape:
+                    numel *= d
+                if numel < 16:
+                    raise _lib.MidasError("torch.normal of fewer than 16 values uses another code path of ATen: not modelled")
+                segs.append((_lib.MT_SEGMENT_NORMAL32, numel, float(mean), float(std), shape))
+                words += normal_words(numel)
+            else:
+                raise ValueError(f"unknown draw {item[0]!r}")
+        return segs, words
+
+    def draws_async(self, spec):
+        """The draws of `spec` (TorchCpuStream.draws_async's format: ("rand64", N), ("normal", mean, std, size), in the stream's order)
+        from every stream by ONE call: ([tensors of shape (B, ...)], event or None) - row b of each is what TorchCpuStream.draws_async
+        gives on stream b.  Fresh tensors, written on the generator's stream behind the caller's current stream: the consumer waits
+        for the event before it reads them (None: the same stream, already ordered)."""
+        segs, words = self._segments(spec)
+        outs, call = [], []
+        for kind, count, mean, std, shape in segs:
+            dt = torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32
+            out = torch.empty((self.B,) + shape, dtype=dt, device=self.device)
+            if self.side is not None:
+                out.record_stream(self.side)
+            outs.append(out)
+            call.append((kind, count, mean, std, out))
+        tables = self._normal_tables() if any(k == _lib.MT_SEGMENT_NORMAL32 for k, *_ in segs) else (None, None, None)
+        self._enter()
+        pieces = self.pieces_for(words)
+        polys = self._chain_polys(words, pieces)
+        self._batch_call(call, polys, pieces, tables)
+        _, ev = self._drawn(words, None)
+        return outs, ev
+
+    def scratch_bytes(self, spec) -> int:
+        """Scratch one draws_async(spec) call takes of the generator's context, sequential or in pieces (the larger)."""
+        _, words = self._segments(spec)
+        r = lambda b: (b + 255) // 256 * 256  # noqa: E731  (the allocator's rounding)
+        seq = r(self.B * (words + 3 * 624) * 4) + r(max(self.B, 16) * 4)
+        pieces = self.pieces_for(words)
+        nblocks = -(-words // 624)
+        chunked = r(self.B * (nblocks + 1) * 624 * 4) + r(self.B * pieces * 624 * 4) if pieces > 0 else 0
+        return max(seq, chunked)
+
+    def reserve(self, *specs):
+        """Reserve the generator context's scratch for the largest of these per-frame calls up front, so that no frame allocates
+        device memory (synchronises the generator's stream)."""
+        need = max(self.scratch_bytes(s) for s in specs)
+        self.ctx.check(self.ctx.lib.midas_scratch_reserve(self.ctx.h, need))
+        return self
