@@ -14,17 +14,23 @@ on-device Philox streams (real work inside the timed region).
 Protocol: particles start from `init_filter(gt_0, N)` (sigma_t = mesh scale / 3, sigma_r = 60 deg,
 particle_filter.py:124-145) projected onto the codebook (filter.py:159-160); the first 20 frames after that wide start are
 timed on their own (`config.diffuse_regime`: stale hints, tree-search fallbacks), then W warm-up steps, then exactly K
-timed steps enqueued by ONE C-ABI call (midas_lazy_run) between barrier + synchronize; a second pass of K steps with one
-HIP event per step gives `config.ms_per_step_median / _p95`.
+timed steps enqueued by ONE C-ABI call (midas_lazy_run) between barrier + synchronize; with `--full` a second pass of K steps
+with one HIP event per step gives `config.per_step.ms_per_step_median / _p95`.
 
 Single GPU: the pipelined engine - the resample + gather of frame t runs as a prologue of frame t+1's front kernel
 (a per-slot dependence), so every timed step performs one resample (the previous frame's), one propagate / NN /
 prune, one codebook scoring and one softmax / CDF pass and leaves its rmse: the same work per step, two launches instead
 of three, the resampled poses never written to HBM.  The K-th frame's resample (nobody's prologue yet) is materialised
-by `eng.flush()` INSIDE the timed region: `value` contains K complete resamples.  Beside the headline (the fixed-N step of SURVEY.md 8(d)) `config` carries the rates a caller sees who
-wants more per frame: `steps_per_sec_materialised_every_frame` (the particle set read after every frame, three launches)
-and `reference_loop_frames_per_sec` (midastouch_amd.filter.filter: the reference's loop with DBSCAN every 50th frame,
-cluster centres and annealing every frame on the device-side particle count, N0 = N).
+by `eng.flush()` INSIDE the timed region: `value` contains K complete resamples.
+
+A plain run does what the headline needs and nothing more: set-up (the first-touch and diffuse-regime frames included: they
+fix the trajectory position and the Philox step the timed frames start from), warm-up, the K timed steps, `--dump-outputs`,
+the line.  `--full` adds every figure that takes runs of its own: beside the headline (the fixed-N step of SURVEY.md 8(d))
+`config` then carries the rates a caller sees who wants more per frame: `steps_per_sec_materialised_every_frame` (the
+particle set read after every frame, three launches) and `reference_loop_frames_per_sec` (midastouch_amd.filter.filter: the
+reference's loop with DBSCAN every 50th frame, cluster centres and annealing every frame on the device-side particle count,
+N0 = N), the per-step HIP-event pass, the per-kernel timing and roofline, the seeded mode, c1 / c3 / c4 / c5, the sharded frame
+on one GPU and the CPU baseline.  The `--no-*` options switch parts of that off again; figures a run did not take are null.
 
 Multi-GPU (N>1): one filter whose particles are sharded across the ranks (N_total = gpus x 100k,
 weak scaling); per frame the ranks all_gather one small record of per-block sums / extrema and exchange the
@@ -529,6 +535,9 @@ def main():
     ap.add_argument("--particles", type=int, default=100_000, help="particles per GPU")
     ap.add_argument("--codebook", type=int, default=50_000)
     ap.add_argument("--dim", type=int, default=512)
+    ap.add_argument("--full", action="store_true", help="also take every figure beside the headline that needs runs of its own (CPU baseline, "
+                                                        "per-step and per-kernel passes, roofline, reference-named loop, seeded mode, c1 / c3 / "
+                                                        "c4 / c5, sharded frame on one GPU); the --no-* options below thin it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-loop", action="store_true", help="skip the reference-named loop (filter() with clustering + annealing)")
@@ -546,6 +555,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    full = args.full
 
     def guarded(fn, *a, **kw):
         """the figures beside the headline must not cost the line: a failure is reported in their place"""
@@ -671,6 +681,7 @@ def main():
             torch.cuda.synchronize()
     diffuse = None
     if not sharded and not args.no_diffuse:  # the first frames after a wide start: hints are stale, the cloud covers the whole object
+        # (also in a plain run: these frames advance the engine's step count, i.e. the Philox draws of the timed frames)
         wide_init(200 + rank)
         tele0 = eng.telemetry.cpu().numpy().copy()
         ND = 20
@@ -742,7 +753,7 @@ def main():
     status = eng.status.cpu().numpy().tolist()
     # the same engine with the resampled particle set materialised (read) after every frame: three launches per frame
     eager_rate = None
-    if not sharded and not args.eager:
+    if full and not sharded and not args.eager:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for i in range(args.steps):
@@ -760,7 +771,7 @@ def main():
                      "note": "device wall clock at the end of each frame of the timed midas_lazy_run call"}
     # per-step distribution: the same K steps again, one HIP event after each (one step per call)
     step_stats = None
-    if not sharded:
+    if full and not sharded:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         evs[0].record()
         for i in range(args.steps):
@@ -772,7 +783,7 @@ def main():
                       "ms_per_step_min": float(per_step.min()), "ms_per_step_max": float(per_step.max())}
     # the reference-named loop (clustering + annealing every frame, device-side particle count) on the same workload
     loop_rate = None
-    if not sharded and not args.no_loop:
+    if full and not sharded and not args.no_loop:
         loop_rate = reference_loop_rate(cb, traj, N, dev, tree, eng.tree3)
         loop_rate["note"] = ("the reference's annealing floor (1000) lets the set shrink to N_final within about ten frames, so this is "
                              "mostly a small-N figure; floor_N holds all N particles (the rate a caller sees who never lets the set anneal): "
@@ -813,6 +824,7 @@ def main():
                    "init": "init_filter(gt_0, N) (sigma_t = mesh scale / 3, sigma_r = 60 deg) projected onto the codebook",
                    "timed_region": ("K steps by one midas_shard_run call (library-owned RCCL communicator)" if sharded and eng.exchange == "peer_c" and eng._ccomm is not None
                                     else "K steps by one midas_lazy_run call" if hasattr(eng, "run") and not sharded and not args.eager else "K step() calls"),
+                   "full": full,  # False: the figures that take runs of their own (below and beside) were not taken - null or absent
                    "steps_per_sec_materialised_every_frame": eager_rate,
                    "steps_per_sec_last_resample_pending": lazy_rate,
                    "reference_loop_frames_per_sec": loop_rate,
@@ -822,7 +834,7 @@ def main():
     }
 
     # per-kernel HIP-event timing (separate pass so the events do not perturb the headline)
-    if not sharded and not args.no_profile:
+    if full and not sharded and not args.no_profile:
         # one kernel bracketed at a time (two events per frame) so the others run back to back
         names = ["score_codebook", "particle_update", "tail_a", "tail_b"]
         fi = args.warmup + 3 * args.steps
@@ -955,7 +967,7 @@ def main():
                            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                            "algorithmic_bytes_per_launch": ab["step"], "kernel_ms": ms_per_step, "step_bytes": ab["step"],
                            "step_frac": achieved / HBM_PEAK_GBS}
-    if not sharded and not args.no_extras:
+    if full and not sharded and not args.no_extras:
         out["config"]["parity_mode"] = guarded(parity_mode_rate, cb, traj, N, dev, tree, eng.tree3)
         out["config"]["parity_mode_all_draws"] = guarded(parity_mode_rate, cb, traj, N, dev, tree, eng.tree3, 100, True)
         if N == 100_000 and K == 50_000 and D == 512:  # beside the headline workload only
@@ -964,7 +976,7 @@ def main():
             out["config"]["c3_single_gpu"] = guarded(big_config_rates, dev, "c3")
             out["config"]["c4_single_gpu"] = guarded(big_config_rates, dev, "c4")
             out["config"]["sharded_one_gpu"] = guarded(sharded_one_gpu)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cb, traj, N)
         if not sharded and not args.eager and args.resample == "weighted_random":
             out["cpu_baseline"]["parity_probe"] = guarded(parity_probe, eng, N, 4000)

@@ -109,3 +109,34 @@ def test_dump_outputs_repeat_bit_for_bit(tmp_path):
         assert np.array_equal(a, b_), name
     ridx = np.load(tmp_path / "a" / "ridx.npy")
     assert ridx.min() >= 0 and ridx.max() < N
+
+
+@pytest.mark.gpu
+def test_full_adds_side_figures_and_leaves_the_timed_steps(tmp_path):
+    """A plain line carries the headline only; --full adds the passes of its own (here: the materialised-every-frame and per-step
+    passes) after the timed steps, which leave what the timed steps computed as it was: the same dumped arrays, bit for bit."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "3", "--particles", "4096",
+           "--codebook", "4096", "--dim", "256"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-profile", "--no-loop", "--no-extras"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-2000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines[tag] = json.loads(js[0])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["metric"] == "filter_steps_per_sec" and line["steps"] == 5 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert plain["config"]["full"] is False and full["config"]["full"] is True
+    assert plain["config"]["per_step"] is None and plain["config"]["steps_per_sec_materialised_every_frame"] is None
+    assert "roofline" not in plain and "cpu_baseline" not in plain and plain["config"]["reference_loop_frames_per_sec"] is None
+    assert full["config"]["per_step"]["ms_per_step_median"] > 0 and full["config"]["steps_per_sec_materialised_every_frame"] > 0
+    assert plain["dump_outputs"]["arrays"] == full["dump_outputs"]["arrays"]
+    for name in plain["dump_outputs"]["arrays"]:
+        assert np.array_equal(np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))), name

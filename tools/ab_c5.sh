@@ -8,7 +8,7 @@ one() { # name, lib or ""
   echo "== $name"
   env ${lib:+MIDAS_HIP_LIB=$lib} timeout 300 python tools/bench_c5.py 2>&1 | grep "^c5" | tee -a $OUT/$name.c5.log
   if [ -z "$NOC2" ]; then
-  env ${lib:+MIDAS_HIP_LIB=$lib} timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-loop --no-diffuse > $OUT/$name.json 2> $OUT/$name.err
+  env ${lib:+MIDAS_HIP_LIB=$lib} timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-loop --no-diffuse > $OUT/$name.json 2> $OUT/$name.err
   python - "$name" "$OUT/$name.json" <<'P'
 import json, sys
 try:

@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 TAG=${1:-abdense}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 one() { local name=$1 lib=$2
-  env ${lib:+MIDAS_HIP_LIB=$lib} MIDAS_DENSE_SCORES=1 timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-loop --no-diffuse --no-extras > $OUT/$name.json 2> $OUT/$name.err
+  env ${lib:+MIDAS_HIP_LIB=$lib} MIDAS_DENSE_SCORES=1 timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-loop --no-diffuse --no-extras > $OUT/$name.json 2> $OUT/$name.err
   python - "$name" "$OUT/$name.json" <<'P'
 import json, sys
 try:

@@ -9,7 +9,7 @@ python -m pytest tests/test_gpu_pipelined.py tests/test_gpu_step.py tests/test_g
 fi
 run() { # name, env...
   local name=$1; shift
-  env "$@" timeout 300 python bench.py --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --no-loop > $OUT/$name.json 2> $OUT/$name.err
+  env "$@" timeout 300 python bench.py --full --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --no-loop > $OUT/$name.json 2> $OUT/$name.err
   python - "$name" "$OUT/$name.json" <<'P'
 import json, sys
 try:

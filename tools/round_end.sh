@@ -5,13 +5,15 @@
 # usage: tools/round_end.sh <tag>   -> gpurun_out/<tag>_*      (copy what is to be judged into profiles/)
 cd "$(dirname "$0")/.."
 T=${1:-rXX}
-B200="python bench.py --steps 200 --warmup 100 --no-cpu-baseline --no-loop --no-diffuse --no-extras"
-B30="python bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-profile --no-loop --no-extras --no-diffuse"
+B200="python bench.py --full --steps 200 --warmup 100 --no-cpu-baseline --no-loop --no-diffuse --no-extras"
+B30="python bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-profile --no-loop --no-extras --no-diffuse"
 python -m pytest tests -m gpu -q > gpurun_out/${T}_gputests.log 2>&1; grep -aE "passed|failed" gpurun_out/${T}_gputests.log
-python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${T}_bench_driver_line.json 2> gpurun_out/${T}_bench_driver.err; cut -c1-300 gpurun_out/${T}_bench_driver_line.json
-python bench.py --no-cpu-baseline --no-extras > gpurun_out/${T}_bench_line_200.json 2> gpurun_out/${T}_bench_200.err; cut -c1-300 gpurun_out/${T}_bench_line_200.json
+# the bench lines (every figure: --full) go beside the test log
+R=$(dirname "$(ls -t */"${T}_gputests.log" | head -1)")
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$R/${T}_bench_driver_line.json" 2> "$R/${T}_bench_driver.err"; cut -c1-300 "$R/${T}_bench_driver_line.json"
+python bench.py --full --no-cpu-baseline --no-extras > "$R/${T}_bench_line_200.json" 2> "$R/${T}_bench_200.err"; cut -c1-300 "$R/${T}_bench_line_200.json"
 # kernel traces: the driver's command (per-launch statistics of its timed region), the steady state, the dense front (all K rows streamed)
-tools/prof_stats.sh ${T}_driver 400 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-loop | head -8
+tools/prof_stats.sh ${T}_driver 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-loop | head -8
 f=$(find gpurun_out/prof_${T}_driver -name "*kernel_trace.csv" | head -1)
 [ -n "$f" ] && python tools/driver_trace_stats.py $f 5 20 gpurun_out/${T}_driver_trace.json | grep -E "mean_us|per_frame"
 tools/prof_stats.sh ${T}_steady 300 $B200 | head -8
