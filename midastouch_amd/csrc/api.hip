@@ -501,16 +501,6 @@ MIDAS_EXPORT int midas_rmse(midas_ctx* ctx, int64_t N, const float* poses_dev, c
 }
 
 // ---- fused step ----------------------------------------------------------------------------------
-// largest float64 t2 with sqrt(t2) <= thr, so that  sqrt(d2) > thr  <=>  d2 > t2  exactly
-static double squared_threshold(double thr) {
-    if (!(thr >= 0.0)) return -1.0;  // nothing is within a negative / NaN threshold
-    if (std::isinf(thr)) return INFINITY;
-    double t = thr * thr;
-    while (std::sqrt(t) > thr) t = std::nextafter(t, 0.0);
-    while (std::sqrt(std::nextafter(t, INFINITY)) <= thr) t = std::nextafter(t, INFINITY);
-    return t;
-}
-
 static int filter_step_impl(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                             const midas_step_args* args, int32_t B);
 
@@ -595,36 +585,16 @@ static int filter_step_impl(midas_ctx* ctx, const midas_codebook* cb, const mida
         (void)hipEventRecord(ctx->ev[7], ctx->stream);
     }
     ParticleUpdateArgs pa;
+    fill_particle_update(pa, s, tree6, tree3, N, s.poses_in_dev, s.hint_in_dev, (uint8_t*)valid, B == 1 ? s.score_stamps_dev : nullptr,
+                         prm ? s.gt16_dev : nullptr, (double*)prm);
     pa.batch = B;
     pa.score_stride = cb->K;
-    pa.N = N;
-    pa.poses_in = s.poses_in_dev;
-    pa.poses_prop = s.poses_prop_dev;
-    pa.odom16 = s.odom16_dev;
-    pa.tn = s.tn_dev;
-    pa.rot = s.rot_dev;
-    pa.std_t = s.std_t;
-    pa.std_r = s.std_r;
-    pa.seed = s.seed;
-    pa.step = s.step;
-    pa.hint_in = s.hint_in_dev;
-    pa.nn_idx = s.nn_idx_dev;
     pa.scores = (const double*)scores;
     pa.x = (double*)x;
     pa.e = (double*)e;
-    pa.valid = (uint8_t*)valid;
-    pa.t2 = squared_threshold(s.prune_thr);
-    pa.thr = s.prune_thr;
-    pa.vlist = (tree6->vlist && tree6->vlist_mesh == tree3) ? (const MeshRec*)tree6->vlist : nullptr;
-    pa.vscr = pa.vlist ? (const MeshScr*)tree6->vscr : nullptr;
-    pa.field = tree3->field;
-    pa.telemetry = (unsigned long long*)s.telemetry_dev;
     pa.status_reset = s.status_dev;
     pa.part_max = (double*)pmax;
     pa.part_min = (double*)pmin;
-    pa.gt16 = prm ? s.gt16_dev : nullptr;
-    pa.part_rmse = (double*)prm;
-    if (B == 1 && s.score_stamps_dev && s.score_epoch) { pa.sp.stamps = s.score_stamps_dev; pa.sp.epoch = s.score_epoch; }
     bool defer = false;
     // a batch with stamps (B x K of them): every trajectory's particle waves score the rows they need from its own code -
     // the float64 arithmetic of the single-trajectory step, no matrix-core pass, no side stream
@@ -805,45 +775,16 @@ static int lazy_step_impl(midas_ctx* ctx, const midas_codebook* cb, const midas_
         tb.guide_raw = tb.guide + ceil_div(N, SCAN_BLOCK) * GUIDE_STRIDE;
     }
     ParticleUpdateArgs pa;
-    pa.N = N;
+    fill_particle_update(pa, s, tree6, tree3, N, s.poses_in_dev, s.hint_in_dev, s.valid_dev, s.score_stamps_dev,
+                         (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
     pa.batch = B;
     pa.score_stride = cb->K;
-    pa.poses_in = s.poses_in_dev;
-    pa.poses_prop = s.poses_prop_dev;
-    pa.odom16 = s.odom16_dev;
-    pa.tn = s.tn_dev;
-    pa.rot = s.rot_dev;
-    pa.std_t = s.std_t;
-    pa.std_r = s.std_r;
-    pa.seed = s.seed;
-    pa.step = s.step;
-    pa.hint_in = s.hint_in_dev;
-    pa.nn_idx = s.nn_idx_dev;
     pa.scores = nullptr;
-    pa.valid = s.valid_dev;
-    pa.t2 = squared_threshold(s.prune_thr);
-    pa.thr = s.prune_thr;
-    pa.vlist = (tree6->vlist && tree6->vlist_mesh == tree3) ? (const MeshRec*)tree6->vlist : nullptr;
-    pa.vscr = pa.vlist ? (const MeshScr*)tree6->vscr : nullptr;
-    pa.field = tree3->field;
-    pa.telemetry = (unsigned long long*)s.telemetry_dev;
     pa.status_reset = s.status_dev;
-    pa.gt16 = (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr;
-    pa.part_rmse = s.part_rmse_dev;
-    if (s.score_stamps_dev && s.score_epoch) { pa.sp.stamps = s.score_stamps_dev; pa.sp.epoch = s.score_epoch; }
     ScorePredict predict;
     if (pa.sp.stamps && s.score_list_dev && B == 1 && s.score_epoch >= 2 && N >= SCAN_CHUNK) {
         MIDAS_REQUIRE(ctx, s.score_epoch < MIDAS_EPOCH_LIMIT);  // (bit 31 of a stamp flags a listed row's second chance)
-        const int par = (int)((s.score_epoch >> 1) & 1u);
-        int32_t* base = s.score_list_dev;
-        pa.sp.pred_tag = s.score_epoch - 1u;
-        pa.sp.list_count = base + par;
-        pa.sp.list = base + 2 + (int64_t)par * cb->K;
-        pa.sp.list_cap = (int32_t)(cb->K < 0x7fffffff ? cb->K : 0x7fffffff);
-        pa.sp.next_count = base + (par ^ 1);
-        predict.stamps = s.score_stamps_dev; predict.epoch = s.score_epoch; predict.K = cb->K;
-        predict.count = base + (par ^ 1);
-        predict.list = base + 2 + (int64_t)(par ^ 1) * cb->K;
+        predict = wire_score_list(pa.sp, s.score_list_dev, cb->K);
     }
     if (s.resample_prev) {
         LazyResample& r = pa.rs;
@@ -946,12 +887,7 @@ MIDAS_EXPORT int midas_score_list_seed(midas_ctx* ctx, int64_t K, uint32_t* scor
                                        int64_t N, const int32_t* nn_idx_dev) {
     MIDAS_ENTER(ctx);
     MIDAS_REQUIRE(ctx, K > 0 && score_stamps_dev && score_epoch >= 2 && score_epoch < MIDAS_EPOCH_LIMIT && score_list_dev && N > 0 && nn_idx_dev);
-    const int par = (int)((score_epoch >> 1) & 1u);
-    ScorePredict pr;
-    pr.stamps = score_stamps_dev; pr.epoch = score_epoch; pr.K = K;
-    pr.count = score_list_dev + (par ^ 1);
-    pr.list = score_list_dev + 2 + (int64_t)(par ^ 1) * K;
-    return launch_predict_seed(ctx, N, nn_idx_dev, pr);
+    return launch_predict_seed(ctx, N, nn_idx_dev, next_score_list(score_stamps_dev, score_epoch, score_list_dev, K));
 }
 
 // ---- pipelined batch (config 5): B trajectories, grid.y, one table block per trajectory -------------------------------
@@ -1008,47 +944,18 @@ static int shard_front_impl(midas_ctx* ctx, const midas_codebook* cb, const mida
     if (s.gt16_dev && s.rmse_sums_dev)
         if ((rc = midas_scratch(ctx, (size_t)npart * 2 * sizeof(double), &prm))) return rc;
     ParticleUpdateArgs pa;
-    pa.N = s.N;
-    pa.poses_in = s.poses_in_dev;
-    pa.poses_prop = s.poses_prop_dev;
-    pa.odom16 = s.odom16_dev;
-    pa.tn = s.tn_dev;
-    pa.rot = s.rot_dev;
-    pa.std_t = s.std_t;
-    pa.std_r = s.std_r;
-    pa.seed = s.seed;
-    pa.step = s.step;
+    fill_particle_update(pa, s, tree6, tree3, s.N, s.poses_in_dev, s.hint_in_dev, s.valid_dev, s.scores_ready ? nullptr : s.score_stamps_dev,
+                         prm ? s.gt16_dev : nullptr, (double*)prm);
     pa.slot_base = s.slot_base;
-    pa.hint_in = s.hint_in_dev;
-    pa.nn_idx = s.nn_idx_dev;
     pa.scores = nullptr;  // deferred: midas_shard_tail_a gathers the scores
-    pa.valid = s.valid_dev;
-    pa.t2 = squared_threshold(s.prune_thr);
-    pa.thr = s.prune_thr;
-    pa.vlist = (tree6->vlist && tree6->vlist_mesh == tree3) ? (const MeshRec*)tree6->vlist : nullptr;
-    pa.vscr = pa.vlist ? (const MeshScr*)tree6->vscr : nullptr;
-    pa.field = tree3->field;
-    pa.telemetry = (unsigned long long*)s.telemetry_dev;
     pa.status_reset = s.status_dev;
     pa.flags_reset = s.flags_dev;
-    pa.gt16 = prm ? s.gt16_dev : nullptr;
-    pa.part_rmse = (double*)prm;
     if (inbox) pa.inbox = *inbox;
-    if (!s.scores_ready && s.score_stamps_dev && s.score_epoch) { pa.sp.stamps = s.score_stamps_dev; pa.sp.epoch = s.score_epoch; }
     // (an epoch at the limit is an error here as in lazy_step_impl - bits 31:30 of a stamp are a listed row's age -, not a frame
     // that silently runs without its list)
     MIDAS_REQUIRE(ctx, !(pa.sp.stamps && score_list && predict_out) || s.score_epoch < MIDAS_EPOCH_LIMIT);
-    if (pa.sp.stamps && score_list && predict_out && s.score_epoch >= 2 && s.N >= SCAN_CHUNK && cb) {
-        const int par = (int)((s.score_epoch >> 1) & 1u);
-        pa.sp.pred_tag = s.score_epoch - 1u;
-        pa.sp.list_count = score_list + par;
-        pa.sp.list = score_list + 2 + (int64_t)par * cb->K;
-        pa.sp.list_cap = (int32_t)(cb->K < 0x7fffffff ? cb->K : 0x7fffffff);
-        pa.sp.next_count = score_list + (par ^ 1);
-        predict_out->stamps = s.score_stamps_dev; predict_out->epoch = s.score_epoch; predict_out->K = cb->K;
-        predict_out->count = score_list + (par ^ 1);
-        predict_out->list = score_list + 2 + (int64_t)(par ^ 1) * cb->K;
-    }
+    if (pa.sp.stamps && score_list && predict_out && s.score_epoch >= 2 && s.N >= SCAN_CHUNK && cb)
+        *predict_out = wire_score_list(pa.sp, score_list, cb->K);
     bool fused = false;
     if (!s.scores_ready && ctx->overlap)
         if ((rc = launch_frame_front(ctx, tree6, tree3, pa, cb, s.code_dev, s.scores_dev, &fused))) return rc;

@@ -1139,16 +1139,6 @@ __global__ __launch_bounds__(256) void k_loop_resample(LoopResampleArgs a) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// largest float64 t2 with sqrt(t2) <= thr (see api.hip)
-static double loop_squared_threshold(double thr) {
-    if (!(thr >= 0.0)) return -1.0;
-    if (std::isinf(thr)) return INFINITY;
-    double t = thr * thr;
-    while (std::sqrt(t) > thr) t = std::nextafter(t, 0.0);
-    while (std::sqrt(std::nextafter(t, INFINITY)) <= thr) t = std::nextafter(t, INFINITY);
-    return t;
-}
-
 struct SelectScratch {
     uint32_t* hist;
     int32_t *state, *c_less, *c_eq, *sel_idx, *srt_idx;
@@ -1243,30 +1233,10 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
     bool weights_merged = false;
     if (phases & MIDAS_LOOP_FRONT) {
         ParticleUpdateArgs pa;
-        pa.N = cap;
+        fill_particle_update(pa, s, t6, t3, cap, s.poses_dev, s.hint_dev, s.valid_dev, s.score_stamps_dev,
+                             (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
         pa.n_live = s.ctl_i_dev + LOOP_I_N;
-        pa.poses_in = s.poses_dev;
-        pa.poses_prop = s.poses_prop_dev;
-        pa.odom16 = s.odom16_dev;
-        pa.tn = s.tn_dev;
-        pa.rot = s.rot_dev;
-        pa.std_t = s.std_t;
-        pa.std_r = s.std_r;
-        pa.seed = s.seed;
-        pa.step = s.step;
-        pa.hint_in = s.hint_dev;
-        pa.nn_idx = s.nn_idx_dev;
         pa.scores = nullptr;  // deferred: k_loop_xe gathers the scores
-        pa.valid = s.valid_dev;
-        pa.t2 = loop_squared_threshold(s.prune_thr);
-        pa.thr = s.prune_thr;
-        pa.vlist = (t6->vlist && t6->vlist_mesh == t3) ? (const MeshRec*)t6->vlist : nullptr;
-        pa.vscr = pa.vlist ? (const MeshScr*)t6->vscr : nullptr;
-        pa.field = t3->field;
-        pa.telemetry = (unsigned long long*)s.telemetry_dev;
-        pa.gt16 = (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr;
-        pa.part_rmse = s.part_rmse_dev;
-        if (s.score_stamps_dev && s.score_epoch) { pa.sp.stamps = s.score_stamps_dev; pa.sp.epoch = s.score_epoch; }
         bool fused = false;
         if (ctx->overlap)
             if ((rc = launch_frame_front(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, &fused))) return rc;

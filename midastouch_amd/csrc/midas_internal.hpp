@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <string>
 
 #include "../../include/midas_hip.h"
@@ -369,6 +370,71 @@ int launch_knn6(midas_ctx* ctx, const midas_tree* t, int64_t N, const float* fea
 int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a,
                        const midas_codebook* cb, const double* code, double* scores, bool* launched);
 int launch_particle_update(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a);
+
+// ---- host: a frame's particle-update arguments ------------------------------------------------------------------------
+// largest float64 t2 with sqrt(t2) <= thr, so that  sqrt(d2) > thr  <=>  d2 > t2  exactly
+inline double squared_threshold(double thr) {
+    if (!(thr >= 0.0)) return -1.0;  // nothing is within a negative / NaN threshold
+    if (std::isinf(thr)) return INFINITY;
+    double t = thr * thr;
+    while (std::sqrt(t) > thr) t = std::nextafter(t, 0.0);
+    while (std::sqrt(std::nextafter(t, INFINITY)) <= thr) t = std::nextafter(t, INFINITY);
+    return t;
+}
+
+// The fields every frame form fills alike from its arguments (midas_step_args, midas_lazy_args, midas_shard_front_args and
+// midas_loop_args name them the same): motion and its draws, the nearest-entry search, the prune, telemetry and the score
+// stamps (`stamps`: the frame's, or nullptr where the form does not score sparsely).  Where the particles come from and where
+// the rmse sums go differ between the forms; every other field of `pa` is the caller's.
+template <class FrameArgs>
+inline void fill_particle_update(ParticleUpdateArgs& pa, const FrameArgs& s, const midas_tree* t6, const midas_tree* t3, int64_t N,
+                                 const float* poses_in, const int32_t* hint_in, uint8_t* valid, uint32_t* stamps, const float* gt16,
+                                 double* part_rmse) {
+    pa.N = N;
+    pa.poses_in = poses_in;
+    pa.poses_prop = s.poses_prop_dev;
+    pa.odom16 = s.odom16_dev;
+    pa.tn = s.tn_dev;
+    pa.rot = s.rot_dev;
+    pa.std_t = s.std_t;
+    pa.std_r = s.std_r;
+    pa.seed = s.seed;
+    pa.step = s.step;
+    pa.hint_in = hint_in;
+    pa.nn_idx = s.nn_idx_dev;
+    pa.valid = valid;
+    pa.t2 = squared_threshold(s.prune_thr);
+    pa.thr = s.prune_thr;
+    pa.vlist = (t6->vlist && t6->vlist_mesh == t3) ? (const MeshRec*)t6->vlist : nullptr;
+    pa.vscr = pa.vlist ? (const MeshScr*)t6->vscr : nullptr;
+    pa.field = t3->field;
+    pa.telemetry = (unsigned long long*)s.telemetry_dev;
+    pa.gt16 = gt16;
+    pa.part_rmse = part_rmse;
+    if (stamps && s.score_epoch) { pa.sp.stamps = stamps; pa.sp.epoch = s.score_epoch; }
+}
+
+// Prediction lists of the sparse scoring (include/midas_hip.h score_list_dev: two counts, then two lists of K rows): the frame
+// with epoch e scores list (e >> 1) & 1, which the frame before tagged e - 1, and its tail builds the other one for the next
+// frame.  next_score_list: what that tail needs.
+inline ScorePredict next_score_list(uint32_t* stamps, uint32_t epoch, int32_t* lists, int64_t K) {
+    const int par = (int)((epoch >> 1) & 1u) ^ 1;
+    ScorePredict p;
+    p.stamps = stamps; p.epoch = epoch; p.K = K;
+    p.count = lists + par;
+    p.list = lists + 2 + (int64_t)par * K;
+    return p;
+}
+// sp (stamps and epoch set) scores this frame's list -> next_score_list
+inline ScorePredict wire_score_list(SparseScore& sp, int32_t* lists, int64_t K) {
+    const int par = (int)((sp.epoch >> 1) & 1u);
+    sp.pred_tag = sp.epoch - 1u;
+    sp.list_count = lists + par;
+    sp.list = lists + 2 + (int64_t)par * K;
+    sp.list_cap = (int32_t)(K < 0x7fffffff ? K : 0x7fffffff);
+    sp.next_count = lists + (par ^ 1);
+    return next_score_list(sp.stamps, sp.epoch, lists, K);
+}
 
 // resample.hip
 int launch_gather_f64(midas_ctx* ctx, int64_t N, const double* table, const int32_t* idx, double* out);

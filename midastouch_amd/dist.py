@@ -40,6 +40,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import MidasError, ShardFrontArgs, ShardRouteArgs, TailResampleArgs, _ptr
+from .engine import RESAMPLE_MODES, advance_epoch, check_motion_draws, codebook_index, frame_operands, operand, sparse_scoring
 
 BLOCK = 4096  # summation block of the CDF spec (csrc/resample.hip)
 ROUTE_REC = 88  # bytes per routed particle row in the all_to_all forms (include/midas_hip.h)
@@ -57,36 +58,22 @@ class HipShardBackend:
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, device, row_shard=None, share=None):
         """share: another backend of the SAME process and codebook whose replicated indices (poses, 6-d features, neighbour /
         vertex lists, mesh tree) this one uses instead of building its own (several shards on one GPU: tests, row sharding)."""
-        self.ctx = _lib.context(device)
+        self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3 = codebook_index(
+            cb_poses, cb_embeddings, mesh_vertices, device, rows=row_shard, share=share)
         self.device = self.ctx.device
-        if share is not None:
-            self.cb_poses, self.cb_feat, self.tree6 = share.cb_poses, share.cb_feat, share.tree6
-        else:
-            self.cb_poses = torch.as_tensor(cb_poses).to(self.device, torch.float32).contiguous()
-            self.cb_feat = ops.se3_feature(self.cb_poses)
-            self.tree6 = ops.Tree(self.cb_feat)
-        emb = torch.as_tensor(cb_embeddings)
         self.row_shard = row_shard
-        if row_shard is not None:
-            r, w = row_shard
-            K = emb.shape[0]
-            if K % w:
-                raise MidasError("codebook-row sharding needs K divisible by the number of ranks")
-            emb = emb[r * (K // w):(r + 1) * (K // w)]
-        self.codebook = ops.Codebook(emb.to(self.device))
-        if share is not None:
-            self.tree3 = share.tree3
-        else:
-            self.tree3 = ops.Tree(torch.as_tensor(mesh_vertices).to(self.device, torch.float64))
-            self.tree6.attach_mesh(self.tree3, self.cb_poses)
         self.K = int(self.cb_poses.shape[0])
-        self.D = int(emb.shape[1])
-        import os
-        self._sparse = (row_shard is None and self.codebook.emb.dtype == torch.float32 and self.D in (128, 256, 512, 1024) and
-                        os.environ.get("MIDAS_DENSE_SCORES", "0") != "1")
+        self.D = int(self.codebook.D)
+        self._sparse = row_shard is None and sparse_scoring(self.codebook)
 
     def empty(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def _stamps_of(self, st):
+        """The shard's sparse-scoring stamps (`st._stamps`, with `st._epoch`: advance_epoch), made on first use."""
+        if getattr(st, "_stamps", None) is None:
+            st._stamps, st._epoch = torch.zeros(self.codebook.K, dtype=torch.int32, device=st.poses.device), 0
+        return st._stamps
 
     def project(self, poses):
         idx = ops.nn6(self.tree6, ops.se3_feature(poses))
@@ -112,14 +99,7 @@ class HipShardBackend:
         a.flags = _ptr(st.r1[5 * st.nb:])
         if not scores_ready and self._sparse:
             # sparse scoring (replicated codebook): this rank's particle waves score the rows they need, one stamp array per state
-            stamps = getattr(st, "_stamps", None)
-            if stamps is None:
-                st._stamps = stamps = torch.zeros(self.codebook.K, dtype=torch.int32, device=st.poses.device)
-                st._epoch = 0
-            st._epoch = st._epoch + 1 if st._epoch < 0x7FFFFFF0 else 1
-            if st._epoch == 1:
-                stamps.zero_()
-            a.score_stamps, a.score_epoch = _ptr(stamps), st._epoch
+            a.score_stamps, a.score_epoch = _ptr(self._stamps_of(st)), advance_epoch(st)
         self.ctx.bind_current_stream()
         self.ctx.check(self.ctx.lib.midas_shard_front(self.ctx.h, None if scores_ready else self.codebook.h,
                                                       self.tree6.h, self.tree3.h, C.byref(a)))
@@ -242,11 +222,7 @@ class HipShardBackend:
         f.std_t, f.std_r, f.seed, f.step, f.prune_thr = std_t, std_r, seed, step, prune_thr
         f.telemetry, f.status, f.flags = _ptr(st.telemetry), _ptr(st.status), _ptr(st.r1[5 * st.nb:])
         if self._sparse:
-            stamps = getattr(st, "_stamps", None)
-            if stamps is None:
-                st._stamps = stamps = torch.zeros(self.codebook.K, dtype=torch.int32, device=st.poses.device)
-                st._epoch = 0
-            f.score_stamps = _ptr(stamps)
+            f.score_stamps = _ptr(self._stamps_of(st))
             if getattr(st, "_score_list", None) is None:  # prediction lists (include/midas_hip.h score_list_dev)
                 st._score_list = torch.zeros(2 + 2 * self.codebook.K, dtype=torch.int32, device=st.poses.device)
             a.score_list = _ptr(st._score_list)
@@ -263,20 +239,9 @@ class HipShardBackend:
         a.ridx, a.poses_out, a.weights_out, a.hint_out = _ptr(st.ridx), _ptr(st.poses), _ptr(st.weights_res), _ptr(st.hint)
         return a
 
-    def next_epochs(self, st, n=1) -> int:
-        """First of n consecutive sparse-scoring epochs of this shard's stamps, spaced by two (the value between two epochs
-        tags the rows of the prediction list); restart + zeroed stamps and list lengths long before a wrap."""
-        if st._epoch + 2 * n >= 0x3FFFFFF0:  # (bits 31:30 of a stamp are the listed rows' age: csrc/midas_internal.hpp)
-            st._stamps.zero_()
-            st._score_list[:2].zero_()
-            st._epoch = 0
-        first = st._epoch + 2
-        st._epoch += 2 * n
-        return first
-
     def step_c(self, st, a, comm_h, phases, T=None):
         if self._sparse and (phases & 1):
-            a.front.score_epoch = self.next_epochs(st, 1 if T is None else T)
+            a.front.score_epoch = advance_epoch(st, 1 if T is None else T)
         self.ctx.bind_current_stream()
         if T is None:
             self.ctx.check(self.ctx.lib.midas_shard_step(self.ctx.h, comm_h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(phases)))
@@ -447,8 +412,7 @@ class ShardedFilterEngine:
         self.st = ShardState(self.backend, self.N, self.rank * self.N, self.backend.K)
         self.sig_t, self.sig_r, self.pen_max = float(sig_t), float(sig_r), float(pen_max)
         self.seed, self.softmax = int(seed), bool(softmax)
-        self.mode = {"weighted_random": _lib.RESAMPLE_MULTINOMIAL, "low_var": _lib.RESAMPLE_SYSTEMATIC,
-                     "low_var_batch": _lib.RESAMPLE_SYSTEMATIC}[resample]
+        self.mode = RESAMPLE_MODES[resample]
         self.step_count = 0
         self.use_hint = True
         if exchange not in ("auto", "a2a", "a2a_fixed", "allgather", "peer", "peer_c"):
@@ -537,12 +501,8 @@ class ShardedFilterEngine:
         """T frames by ONE C call (midas_shard_run; exchange "peer_c" on the library's communicator, device draws)."""
         if self.exchange != "peer_c" or self._ccomm is None:
             raise MidasError("run() needs exchange='peer_c' with the library-owned RCCL communicator")
-        from .engine import operand
-        d, D = self.st.poses.device, int(self.backend.D)
         T = int(torch.as_tensor(odoms).shape[0])
-        odoms = operand(odoms, "odoms", torch.float32, (T, 4, 4), d)
-        codes = operand(codes, "tactile codes", torch.float64, (T, D), d)
-        gts = operand(gts, "gt poses", torch.float32, (T, 4, 4), d)
+        odoms, codes, gts = frame_operands(self.st.poses.device, (T,), int(self.backend.D), odoms, codes, gts)
         self._keep = (odoms, codes, gts)
         a = self._c_args(odoms, codes, gts, None, -1.0, 1.0, self._r1_all_buf(), frames=T)
         self.backend.step_c(self.st, a, self._ccomm, 15, T=T)
@@ -686,12 +646,9 @@ class ShardedFilterEngine:
         st, b, G = self.st, self.backend, self.world
         mul = max(float(multiplier), 1.0)
         # the kernels read raw pointers: operands on the shard's device, in the ABI's dtypes, contiguous, right sizes
-        from .engine import operand
         d, D = st.poses.device, int(getattr(b, "D", torch.as_tensor(code).numel()))
-        if (tn is None) != (rot is None):
-            raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
-        odom, gt = operand(odom, "odom", torch.float32, (4, 4), d), operand(gt, "gt pose", torch.float32, (4, 4), d)
-        code = operand(code, "tactile code", torch.float64, (D,), d)
+        check_motion_draws(tn, rot)
+        odom, code, gt = frame_operands(d, (), D, odom, code, gt)
         tn, rot = operand(tn, "tn", torch.float32, (self.N, 3), d), operand(rot, "rot", torch.float32, (self.N, 3), d)
         u = operand(u, "u (the uniforms of all slots of the filter)", torch.float64, (self.N_total,), d)
         self._keep = (odom, code, gt, tn, rot, u)

@@ -9,6 +9,9 @@ Two random-draw modes:
   * parity mode  - the caller supplies the host draws of the reference (torch CPU mt19937:
                    tn, rot from torch.normal in that order, then N float64 uniforms);
   * device mode  - the kernels draw from the Philox spec streams keyed by (seed, step).
+
+The frame setup every engine form shares (single, batch, loop, shard: midastouch_amd/loop_engine.py, dist.py) lives here too:
+`codebook_index`, `RESAMPLE_MODES`, `sparse_scoring`, `advance_epoch` and the operand checks.
 """
 from __future__ import annotations
 
@@ -23,12 +26,16 @@ from ._lib import LazyArgs, LazyFlushArgs, MidasError, StepArgs, _ptr
 
 EPOCH_LIMIT = 0x3FFFFFF0  # (bits 31:30 of a stamp count the frames a listed row went unused: csrc/midas_internal.hpp)
 
+# the reference's `resample` option -> the kernels' draw rule
+RESAMPLE_MODES = {"weighted_random": _lib.RESAMPLE_MULTINOMIAL, "low_var": _lib.RESAMPLE_SYSTEMATIC,
+                  "low_var_batch": _lib.RESAMPLE_SYSTEMATIC}
+
 
 def advance_epoch(eng, n: int = 1) -> int:
-    """First of n consecutive sparse-scoring epochs of an engine (`_epoch`, `_stamps`, optionally `_score_list`): non-zero,
-    spaced by 2 when the engine keeps a prediction list (the value between two epochs tags the listed rows), never reused
-    while the stamps live - before the 32-bit counter could wrap (2.5 days at 20k frames/s) the stamps and the list lengths
-    are zeroed and the count restarts, so a stale stamp can never equal a current epoch."""
+    """First of n consecutive sparse-scoring epochs of an engine or a shard's state (`_epoch`, `_stamps`, optionally
+    `_score_list`): non-zero, spaced by 2 when the holder keeps a prediction list (the value between two epochs tags the listed
+    rows), never reused while the stamps live - before the 32-bit counter could wrap (2.5 days at 20k frames/s) the stamps and
+    the list lengths are zeroed and the count restarts, so a stale stamp can never equal a current epoch."""
     lst = getattr(eng, "_score_list", None)
     inc = 2 if lst is not None else 1
     if eng._epoch + inc * n >= EPOCH_LIMIT:
@@ -39,6 +46,50 @@ def advance_epoch(eng, n: int = 1) -> int:
     first = eng._epoch + inc
     eng._epoch += inc * n
     return first
+
+
+def sparse_scoring(codebook, switch: bool = True) -> bool:
+    """Whether the particle kernels can score `codebook`'s rows themselves (sparse scoring, include/midas_hip.h
+    score_stamps_dev: float32 rows, D in {128, 256, 512, 1024}) - and, with `switch`, whether MIDAS_DENSE_SCORES=1 (read at
+    every call) leaves them to: with it every row is scored every frame.  Same scores either way."""
+    return (codebook.emb.dtype == torch.float32 and codebook.D in (128, 256, 512, 1024) and
+            not (switch and os.environ.get("MIDAS_DENSE_SCORES", "0") == "1"))
+
+
+def codebook_index(cb_poses, cb_embeddings, mesh_vertices, device, *, rows=None, share=None):
+    """The codebook as the kernels read it -> (context, float32 poses, 6-d features, NN index, embeddings, mesh index).
+
+    cb_poses may be a tactile_tree already on the device (cb_embeddings None: its index is shared) and mesh_vertices an ops.Tree.
+    share: another engine or shard backend of the same process and codebook whose poses, features, NN index and mesh index are
+    used as they are (only the embeddings are built).  rows = (rank, world): only that rank's contiguous slice of the embedding
+    rows (codebook-row sharding)."""
+    ctx = _lib.context(torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
+    d = ctx.device
+    if hasattr(cb_poses, "SE3_NN") and cb_embeddings is None:  # a tactile_tree already on the device: share its index
+        tt = cb_poses
+        poses, feat, tree6, codebook = tt.poses, tt.logmap_pose, tt.tree, tt.codebook
+    else:
+        if share is not None:
+            poses, feat, tree6 = share.cb_poses, share.cb_feat, share.tree6
+        else:
+            poses = torch.as_tensor(cb_poses).to(d, torch.float32).contiguous()
+            feat = ops.se3_feature(poses)
+            tree6 = ops.Tree(feat)
+        emb = torch.as_tensor(cb_embeddings)
+        if rows is not None:
+            r, w = rows
+            if emb.shape[0] % w:
+                raise MidasError("codebook-row sharding needs K divisible by the number of ranks")
+            k = emb.shape[0] // w
+            emb = emb[r * k:(r + 1) * k]
+        codebook = ops.Codebook(emb.to(d))
+    if share is not None:
+        tree3 = share.tree3
+    else:
+        tree3 = mesh_vertices if isinstance(mesh_vertices, ops.Tree) else ops.Tree(torch.as_tensor(mesh_vertices).to(d, torch.float64))
+    if getattr(tree6, "_mesh", None) is not tree3:  # vertex lists of this mesh not yet on the codebook index
+        tree6.attach_mesh(tree3, poses)
+    return ctx, poses, feat, tree6, codebook, tree3
 
 
 def operand(t, name: str, dtype, shape, device):
@@ -60,77 +111,90 @@ def operand(t, name: str, dtype, shape, device):
     return t.contiguous().reshape(shape)
 
 
-class FilterEngine:
-    def __init__(self, cb_poses, cb_embeddings, mesh_vertices, num_particles: int, *, sig_t=2e-4, sig_r=0.5,
-                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None):
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.ctx = _lib.context(dev)
+def frame_specs(lead, D):
+    """(name, dtype, shape) of the odometry, tactile code and ground truth of one frame (lead = ()), or of T frames / B
+    trajectories (lead = (T,) / (B,))."""
+    s = "s" if lead else ""
+    return (("odom" + s, torch.float32, lead + (4, 4)), ("tactile code" + s, torch.float64, lead + (D,)),
+            ("gt pose" + s, torch.float32, lead + (4, 4)))
+
+
+def frame_operands(device, lead, D, odom, code, gt):
+    """Odometry, tactile code and ground truth (or None) as the C ABI reads them (frame_specs)."""
+    so, sc, sg = frame_specs(lead, D)
+    return operand(odom, *so, device), operand(code, *sc, device), operand(gt, *sg, device)
+
+
+def check_motion_draws(tn, rot):
+    if (tn is None) != (rot is None):
+        raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
+
+
+class _Engine:
+    """What FilterEngine and BatchFilterEngine share: the codebook index, the filter's parameters, the particle set of one
+    trajectory or of B (`_lead` = (N,) or (B, N)) and the eager frame."""
+
+    def _setup(self, cb_poses, cb_embeddings, mesh_vertices, device, lead, sig_t, sig_r, pen_max, seed, softmax, resample):
+        self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3 = codebook_index(
+            cb_poses, cb_embeddings, mesh_vertices, device)
         self.device = self.ctx.device
-        f32 = dict(dtype=torch.float32, device=self.device)
-        if hasattr(cb_poses, "SE3_NN") and cb_embeddings is None:  # a tactile_tree already on the device: share its index
-            tt = cb_poses
-            self.cb_poses, self.cb_feat, self.tree6, self.codebook = tt.poses, tt.logmap_pose, tt.tree, tt.codebook
-        else:
-            self.cb_poses = torch.as_tensor(cb_poses).to(**f32).contiguous()
-            self.cb_feat = ops.se3_feature(self.cb_poses)
-            self.tree6 = ops.Tree(self.cb_feat)
-            self.codebook = ops.Codebook(torch.as_tensor(cb_embeddings).to(self.device))
-        self.tree3 = mesh_vertices if isinstance(mesh_vertices, ops.Tree) else ops.Tree(torch.as_tensor(mesh_vertices).to(self.device, torch.float64))
-        if getattr(self.tree6, "_mesh", None) is not self.tree3:
-            self.tree6.attach_mesh(self.tree3, self.cb_poses)
         self.K, self.D = self.codebook.K, self.codebook.D
         self.sig_t, self.sig_r, self.pen_max = float(sig_t), float(sig_r), float(pen_max)
         self.seed, self.softmax = int(seed), bool(softmax)
-        self.mode = {"weighted_random": _lib.RESAMPLE_MULTINOMIAL, "low_var": _lib.RESAMPLE_SYSTEMATIC,
-                     "low_var_batch": _lib.RESAMPLE_SYSTEMATIC}[resample]
-        self.N = int(num_particles)
-        N = self.N
-        self.poses = torch.zeros((N, 4, 4), **f32)
-        self.poses_prop = torch.zeros((N, 4, 4), **f32)
-        self.weights = torch.zeros(N, dtype=torch.float64, device=self.device)      # pre-resample, masked
-        self.weights_res = torch.ones(N, dtype=torch.float64, device=self.device)   # gathered by resample
-        self.nn_idx = torch.zeros(N, dtype=torch.int32, device=self.device)
-        self.hint = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        self.hint_next = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        self.ridx = torch.zeros(N, dtype=torch.int32, device=self.device)
-        self.status = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.rmse = torch.zeros(2, dtype=torch.float64, device=self.device)
-        # 16 cumulative counters ([0], [1] = tree-search fallbacks); with MIDAS_ABLATE=4 (profiling) the kernel
-        # also keeps 16 statistics slots per wave behind them
-        extra = 16 * ((N + 15) // 16) if int(os.environ.get("MIDAS_ABLATE", "0")) & 4 else 0
-        self.telemetry = torch.zeros(16 + extra, dtype=torch.int64, device=self.device)
+        self.mode = RESAMPLE_MODES[resample]
+        self._lead = lead
+        self.N = lead[-1]
+        # what _operands makes of a frame's odom, code, gt, tn, rot and u (per trajectory for a batch)
+        self._specs = frame_specs(lead[:-1], self.D) + (("tn", torch.float32, lead + (3,)), ("rot", torch.float32, lead + (3,)),
+                                                        ("u", torch.float64, lead))
         self.step_count = 0
         self.use_hint = True
         # sparse scoring: only the rows that are some particle's nearest entry are scored, by the particle kernels
         # themselves (stamps of the frame that last scored a row; include/midas_hip.h score_stamps_dev).  Same scores.
-        _os = os
-        self.sparse_scores = self.codebook.emb.dtype == torch.float32 and self.D in (128, 256, 512, 1024) and \
-            _os.environ.get("MIDAS_DENSE_SCORES", "0") != "1"
-        self._stamps = torch.zeros(self.K, dtype=torch.int32, device=self.device)
+        self.sparse_scores = sparse_scoring(self.codebook)
         self._epoch = 0
 
-    def _next_epoch(self, n: int = 1) -> int:
-        """First of n consecutive score epochs (see advance_epoch)."""
-        return advance_epoch(self, n)
+    def _alloc_state(self):
+        """The particle set and the latest frame's outputs (the pipelined engines keep theirs double-buffered)."""
+        lead, bz, d = self._lead, self._lead[:-1], self.device
+        f32, f64, i32 = dict(dtype=torch.float32, device=d), dict(dtype=torch.float64, device=d), dict(dtype=torch.int32, device=d)
+        self.poses = torch.zeros(lead + (4, 4), **f32)
+        self.poses_prop = torch.zeros(lead + (4, 4), **f32)
+        self.weights = torch.zeros(lead, **f64)      # pre-resample, masked
+        self.weights_res = torch.ones(lead, **f64)   # gathered by resample
+        self.nn_idx = torch.zeros(lead, **i32)
+        self.hint = torch.full(lead, -1, **i32)
+        self.hint_next = torch.full(lead, -1, **i32)
+        self.ridx = torch.zeros(lead, **i32)
+        self.status = torch.zeros(bz + (2,), **i32)
+        self.rmse = torch.zeros(bz + (2,), **f64)
 
     # ---- state ----------------------------------------------------------------------------------
-    def set_particles(self, poses: torch.Tensor):
-        poses = torch.as_tensor(poses).to(self.device, torch.float32).contiguous()
-        if poses.shape != (self.N, 4, 4):
-            raise MidasError(f"expected ({self.N},4,4) poses, got {tuple(poses.shape)}")
+    def set_particles(self, poses):
+        poses = torch.as_tensor(poses).to(self.device, torch.float32)
+        if tuple(poses.shape) != self._lead + (4, 4):
+            raise MidasError(f"expected ({','.join(map(str, self._lead))},4,4) poses, got {tuple(poses.shape)}")
         self.poses.copy_(poses)
         self.hint.fill_(-1)
 
     def project_to_codebook(self):
         """poses := codebook pose nearest to each particle (filter/filter.py:159-160)."""
-        idx = ops.nn6(self.tree6, ops.se3_feature(self.poses))
-        self.poses.copy_(ops.gather_rows(self.cb_poses, idx))
-        self.hint.copy_(idx)
+        poses = self.poses
+        idx = ops.nn6(self.tree6, ops.se3_feature(poses.view(-1, 4, 4)))
+        poses.copy_(ops.gather_rows(self.cb_poses, idx).view_as(poses))
+        self.hint.copy_(idx.view_as(self.hint))
         return idx
 
     # ---- one frame ------------------------------------------------------------------------------
-    def step(self, odom, code, gt=None, tn=None, rot=None, u=None, u32=-1.0, multiplier: float = 1.0):
-        """Runs one frame; results stay on the device (self.poses, self.weights, self.ridx ...)."""
+    def _operands(self, odom, code, gt, tn, rot, u):
+        """A frame's operands as the C ABI reads them: per trajectory odom (4,4), code (D,), gt (4,4), tn / rot (N,3), u (N,)."""
+        check_motion_draws(tn, rot)
+        d, (so, sc, sg, st, sr, su) = self.device, self._specs
+        return (operand(odom, *so, d), operand(code, *sc, d), operand(gt, *sg, d), operand(tn, *st, d), operand(rot, *sr, d),
+                operand(u, *su, d))
+
+    def _eager_step(self, call, odom, code, gt, tn, rot, u, u32, std_t, std_r, *batch):
+        """The frame by one C call (midas_filter_step / midas_filter_step_batch, whose trailing argument is B)."""
         odom, code, gt, tn, rot, u = self._operands(odom, code, gt, tn, rot, u)
         a = StepArgs()
         a.N = self.N
@@ -138,34 +202,38 @@ class FilterEngine:
         a.weights, a.weights_out = _ptr(self.weights), _ptr(self.weights_res)
         a.hint_in = _ptr(self.hint) if self.use_hint else None
         a.nn_idx, a.hint_out, a.ridx = _ptr(self.nn_idx), _ptr(self.hint_next), _ptr(self.ridx)
-        a.odom16, a.code = _ptr(odom), _ptr(code)
-        a.gt16 = _ptr(gt)
+        a.odom16, a.code, a.gt16 = _ptr(odom), _ptr(code), _ptr(gt)
         a.rmse = _ptr(self.rmse) if gt is not None else None
-        a.tn, a.rot, a.u = _ptr(tn), _ptr(rot), _ptr(u)
-        a.u32 = float(u32)
-        mul = max(float(multiplier), 1.0)  # motionModel clamps multiplier >= 1 (particle_filter.py:365-366)
-        a.std_t, a.std_r = mul * self.sig_t, mul * self.sig_r
-        a.seed, a.step = self.seed, self.step_count
-        a.prune_thr = self.pen_max
-        a.softmax, a.resample_mode = int(self.softmax), self.mode
-        a.status = _ptr(self.status)
-        a.telemetry = _ptr(self.telemetry)
+        a.tn, a.rot, a.u, a.u32 = _ptr(tn), _ptr(rot), _ptr(u), float(u32)
+        a.std_t, a.std_r, a.seed, a.step = std_t, std_r, self.seed, self.step_count
+        a.prune_thr, a.softmax, a.resample_mode = self.pen_max, int(self.softmax), self.mode
+        a.status, a.telemetry = _ptr(self.status), _ptr(self.telemetry)
         if self.sparse_scores:
-            a.score_stamps, a.score_epoch = _ptr(self._stamps), self._next_epoch()
+            a.score_stamps, a.score_epoch = _ptr(self._stamps), advance_epoch(self)
         self._keep = (odom, code, gt, tn, rot, u)  # keep operands alive until the stream has consumed them
         self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_filter_step(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h,
-                                                      C.byref(a)))
+        self.ctx.check(call(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), *batch))
         self.hint, self.hint_next = self.hint_next, self.hint
         self.step_count += 1
 
-    def _operands(self, odom, code, gt, tn, rot, u):
-        d, N = self.device, self.N
-        if (tn is None) != (rot is None):
-            raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
-        return (operand(odom, "odom", torch.float32, (4, 4), d), operand(code, "tactile code", torch.float64, (self.D,), d),
-                operand(gt, "gt pose", torch.float32, (4, 4), d), operand(tn, "tn", torch.float32, (N, 3), d),
-                operand(rot, "rot", torch.float32, (N, 3), d), operand(u, "u", torch.float64, (N,), d))
+
+class FilterEngine(_Engine):
+    def __init__(self, cb_poses, cb_embeddings, mesh_vertices, num_particles: int, *, sig_t=2e-4, sig_r=0.5,
+                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None):
+        N = int(num_particles)
+        self._setup(cb_poses, cb_embeddings, mesh_vertices, device, (N,), sig_t, sig_r, pen_max, seed, softmax, resample)
+        # 16 cumulative counters ([0], [1] = tree-search fallbacks); with MIDAS_ABLATE=4 (profiling) the kernel
+        # also keeps 16 statistics slots per wave behind them
+        extra = 16 * ((N + 15) // 16) if int(os.environ.get("MIDAS_ABLATE", "0")) & 4 else 0
+        self.telemetry = torch.zeros(16 + extra, dtype=torch.int64, device=self.device)
+        self._stamps = torch.zeros(self.K, dtype=torch.int32, device=self.device)
+        self._alloc_state()
+
+    # ---- one frame ------------------------------------------------------------------------------
+    def step(self, odom, code, gt=None, tn=None, rot=None, u=None, u32=-1.0, multiplier: float = 1.0):
+        """Runs one frame; results stay on the device (self.poses, self.weights, self.ridx ...)."""
+        mul = max(float(multiplier), 1.0)  # motionModel clamps multiplier >= 1 (particle_filter.py:365-366)
+        self._eager_step(self.ctx.lib.midas_filter_step, odom, code, gt, tn, rot, u, u32, mul * self.sig_t, mul * self.sig_r)
 
     # ---- profiling --------------------------------------------------------------------------------
     def profile(self, on, only_slot: int = None):
@@ -193,18 +261,13 @@ def _materialised(name):
     return property(get, put)
 
 
-class PipelinedFilterEngine(FilterEngine):
-    """FilterEngine with the resample of frame t folded into the front kernel of frame t+1 (midas_lazy_step).
+class _FoldedResample:
+    """The folded-resample state machine of PipelinedFilterEngine and PipelinedBatchFilterEngine, written for one trajectory or B
+    (`_lead` = (N,) or (B, N)) and the entry points `_lazy_calls` names (the batch ones take B as their trailing argument).
 
-    Slot n of the next frame is particle src(n) of this one, a per-slot dependence: the resampler's search and
-    gather run as a prologue of the next particle update, the resampled poses never travel through HBM and a
-    frame is two launches instead of three.  The resampled particle set of the latest frame therefore exists only
-    implicitly (tables + draws) until somebody reads it: `poses`, `weights`, `weights_res`, `hint`, `ridx`, `status`
-    and `rmse` materialise it on access (`flush()`, the same kernel as the eager engine's tail - bit-identical
-    results); `nn_idx` and `poses_prop` of the latest frame are always there.  A caller that looks at the particles
-    every frame gets the eager engine's launches; one that only steps gets the pipelined ones.
-    Needs a float32 codebook with D in {128, 256, 512, 1024} and N <= 1 M (MidasError otherwise: use FilterEngine).
-    """
+    The resampled particle set of the latest frame exists only implicitly (tables + draws) until somebody reads it: `poses`,
+    `weights`, `weights_res`, `hint`, `ridx` and `status` materialise it on access (`flush()`); `nn_idx`, `poses_prop` and `rmse`
+    of the latest frame are always there (double buffers, `_cur` is the latest frame's set)."""
 
     poses = _materialised("poses")
     weights = _materialised("weights")
@@ -213,76 +276,55 @@ class PipelinedFilterEngine(FilterEngine):
     ridx = _materialised("ridx")
 
     @property
-    def rmse(self):
-        """rmse of the latest frame's propagated particles (filter.py:164): written by the frame itself, no materialisation."""
-        return self._rmse_last[:2] if self._pending else self._rmse
-
-    @rmse.setter
-    def rmse(self, v):
-        self._rmse = v
-
-    def __init__(self, *args, **kw):
-        self._pending = False
-        self._flushed = True
-        super().__init__(*args, **kw)
-        N, dev = self.N, self.device
-        if self.codebook.emb.dtype != torch.float32 or self.D not in (128, 256, 512, 1024) or N > (1 << 20):
-            raise MidasError("PipelinedFilterEngine needs a float32 codebook with D in {128,256,512,1024} and N <= 2^20")
-        f64 = dict(dtype=torch.float64, device=dev)
-        self._prop = [self.poses_prop, torch.zeros_like(self.poses_prop)]
-        self._nn = [self.nn_idx, torch.zeros_like(self.nn_idx)]
-        self._st = [torch.zeros(2, dtype=torch.int32, device=dev) for _ in range(2)]
-        self._valid = torch.zeros(N, dtype=torch.uint8, device=dev)
-        ng, nb = (N + 15) // 16, (N + 4095) // 4096
-        self._tables = torch.zeros(4 * (-(-N // 16) * 16) + 2 * (-(-ng // 16) * 16) + 37 * nb, **f64)
-        # guide tables of the folded resample's search (midas_lazy_args.guide_dev; MIDAS_GUIDE=0: the three-line search alone)
-        self._guide = (torch.zeros(int(self.ctx.lib.midas_lazy_guide_bytes(N)), dtype=torch.uint8, device=dev)
-                       if os.environ.get("MIDAS_GUIDE", "1") != "0" else None)
-        self._scores = torch.zeros(self.K, **f64)
-        self._part_rmse = torch.zeros(2 * ((N + 63) // 64), **f64)
-        self._cur = 0
-        self._draw = (None, -1.0, 0)
-        self._had_gt = False
-        self._rmse_frame = torch.zeros(3, **f64)
-        self._rmse_last = self._rmse_frame   # where the latest frame left {rmse_t, rmse_r, clock}: _rmse_frame or a row of the run log
-        # prediction lists of the sparse scoring (include/midas_hip.h score_list_dev): the rows a frame used are scored for
-        # the next frame by streaming workgroups of its front launch.  MIDAS_SCORE_LIST=0: every row by its first particle.
-        self._score_list = torch.zeros(2 + 2 * self.K, dtype=torch.int32, device=dev) \
-            if self.sparse_scores and os.environ.get("MIDAS_SCORE_LIST", "1") != "0" and N >= 16 else None
-
-    def check(self):
-        """Raises if a frame's tail reported its tables undefined (status bit 4, value 16: a wave of the grouped tail waited
-        0.2 s for its block's records - include/midas_hip.h, midas_lazy_args.status_dev).  One small read-back."""
-        st = torch.stack([self._st[0][0], self._st[1][0]]).cpu()
-        if int(st[0]) & 16 or int(st[1]) & 16:
-            raise MidasError("grouped tail: a wave did not receive its block's records in time - the frame's CDF tables are undefined "
-                             "(foreign work on the device?); MIDAS_TAIL_GROUPED=0 selects the form without waits")
-
-    # the latest frame's own outputs
-    @property
     def status(self):
         self.flush()
         return self._st[self._cur]
 
-    @status.setter
-    def status(self, v):
-        pass  # the base constructor's tensor is not used
-
     @property
     def nn_idx(self):
-        return self._nn[self._cur] if hasattr(self, "_nn") else self._nn0
-
-    @nn_idx.setter
-    def nn_idx(self, v):
-        self._nn0 = v
+        return self._nn[self._cur]
 
     @property
     def poses_prop(self):
-        return self._prop[self._cur] if hasattr(self, "_prop") else self._prop0
+        return self._prop[self._cur]
 
-    @poses_prop.setter
-    def poses_prop(self, v):
-        self._prop0 = v
+    @property
+    def rmse(self):
+        """rmse of the latest frame's propagated particles (filter.py:164): written by the frame itself, no materialisation."""
+        return self._rmse_last[..., :2] if self._pending else self._rmse
+
+    def _alloc_state(self):
+        lead, bz, N, d = self._lead, self._lead[:-1], self.N, self.device
+        f32, f64, i32 = dict(dtype=torch.float32, device=d), dict(dtype=torch.float64, device=d), dict(dtype=torch.int32, device=d)
+        self._poses = torch.zeros(lead + (4, 4), **f32)
+        self._weights = torch.zeros(lead, **f64)
+        self._weights_res = torch.ones(lead, **f64)
+        self._hint = torch.full(lead, -1, **i32)
+        self._ridx = torch.zeros(lead, **i32)
+        self._rmse = torch.zeros(bz + (2,), **f64)
+        self._prop = [torch.zeros(lead + (4, 4), **f32) for _ in range(2)]
+        self._nn = [torch.zeros(lead, **i32) for _ in range(2)]
+        self._st = [torch.zeros(bz + (2,), **i32) for _ in range(2)]
+        self._valid = torch.zeros(lead, dtype=torch.uint8, device=d)
+        lib = self.ctx.lib
+        B = bz[0] if bz else 1
+        self._tables = torch.zeros(B * int(lib.midas_lazy_tables_doubles(N)), **f64)  # one block per trajectory
+        # guide tables of the folded resample's search (midas_lazy_args.guide_dev, one trajectory; MIDAS_GUIDE=0: the three-line
+        # search alone)
+        self._guide = (torch.zeros(int(lib.midas_lazy_guide_bytes(N)), dtype=torch.uint8, device=d)
+                       if not bz and os.environ.get("MIDAS_GUIDE", "1") != "0" else None)
+        self._scores = torch.zeros(bz + (self.K,), **f64)
+        self._part_rmse = torch.zeros(bz + (2 * ((N + 63) // 64),), **f64)
+        self._rmse_frame = torch.zeros(bz + (3,), **f64)
+        self._rmse_last = self._rmse_frame   # where the latest frame left {rmse_t, rmse_r, clock}: _rmse_frame or a row of the run log
+        # prediction lists of the sparse scoring (include/midas_hip.h score_list_dev, one trajectory): the rows a frame used are
+        # scored for the next frame by streaming workgroups of its front launch.  MIDAS_SCORE_LIST=0: every row by its first particle.
+        self._score_list = torch.zeros(2 + 2 * self.K, **i32) \
+            if not bz and self.sparse_scores and os.environ.get("MIDAS_SCORE_LIST", "1") != "0" and N >= 16 else None
+        self._lazy_step, self._lazy_flush = (getattr(lib, name) for name in self._lazy_calls)
+        self._batch = bz
+        self._cur, self._draw, self._had_gt = 0, (None, -1.0, 0), False
+        self._pending, self._flushed = False, True
 
     def set_particles(self, poses):
         self._pending, self._flushed = False, True
@@ -295,8 +337,109 @@ class PipelinedFilterEngine(FilterEngine):
             # every particle's nearest entry is known: the first frame's rows go on the prediction list right away (they would
             # otherwise all be claimed by whichever particle wave touches them first - up to 64 rows a wave after a wide start)
             self.ctx.bind_current_stream()
-            self.ctx.call("midas_score_list_seed", self.K, _ptr(self._stamps), self._next_epoch(), _ptr(self._score_list), self.N, _ptr(idx))
+            self.ctx.call("midas_score_list_seed", self.K, _ptr(self._stamps), advance_epoch(self), _ptr(self._score_list), self.N, _ptr(idx))
         return idx
+
+    def _wait_draws(self):
+        """The pending frame's draws may still be in flight on the generator's stream (TorchCpuStream(s)): order this stream
+        behind them."""
+        ev = getattr(self, "_draw_event", None)
+        if ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(ev)
+            self._draw_event = None
+
+    def _lazy_args(self, cur):
+        """The buffers of a frame that follows the frame on buffer set `cur` (no per-frame values)."""
+        nxt = cur ^ 1
+        a = LazyArgs()
+        a.N = self.N
+        a.poses_prop_prev, a.nn_idx_prev, a.status_prev = _ptr(self._prop[cur]), _ptr(self._nn[cur]), _ptr(self._st[cur])
+        a.poses_prop, a.nn_idx, a.valid, a.status = _ptr(self._prop[nxt]), _ptr(self._nn[nxt]), _ptr(self._valid), _ptr(self._st[nxt])
+        a.tables, a.scores, a.guide = _ptr(self._tables), _ptr(self._scores), _ptr(self._guide)
+        a.poses_in, a.telemetry = _ptr(self._poses), _ptr(self.telemetry)
+        return a
+
+    def _lazy_frame(self, odom, code, gt, tn, rot, u, u32, own_u, u_event, std_t, std_r):
+        """One frame on the other buffer set with the pending resample folded in.  u: this frame's resample draws, consumed by
+        the next frame or by flush() - a caller's tensor is copied (it may be mutated before then), one generated here (own_u)
+        is kept as it is; u_event: their event on the generator's stream."""
+        self._wait_draws()
+        odom, code, gt, tn, rot, u = self._operands(odom, code, gt, tn, rot, u)
+        cur = self._cur
+        fold = self._pending and not self._flushed
+        a = self._lazy_args(cur)
+        a.part_rmse = _ptr(self._part_rmse) if gt is not None else None
+        a.resample_prev = int(fold)
+        a.hint_in = _ptr(self._hint) if self.use_hint else None
+        pu, pu32, pstep = self._draw
+        a.resample_mode, a.u_prev, a.u32_prev, a.step_prev = self.mode, _ptr(pu), float(pu32), int(pstep)
+        a.ridx = _ptr(self._ridx) if fold else None
+        a.odom16, a.code, a.gt16 = _ptr(odom), _ptr(code), _ptr(gt)
+        a.tn, a.rot = _ptr(tn), _ptr(rot)
+        a.std_t, a.std_r, a.seed, a.step = std_t, std_r, self.seed, self.step_count
+        a.prune_thr, a.softmax = self.pen_max, int(self.softmax)
+        if self.sparse_scores:
+            a.score_stamps, a.score_epoch, a.score_list = _ptr(self._stamps), advance_epoch(self), _ptr(self._score_list)
+        a.rmse = _ptr(self._rmse_frame) if gt is not None else None
+        self._keep = (odom, code, gt, tn, rot, pu)
+        self.ctx.bind_current_stream()
+        self.ctx.check(self._lazy_step(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), *self._batch))
+        self._draw = (None if u is None else (u if own_u else u.clone()), float(u32), self.step_count)
+        self._draw_event = u_event
+        self._rmse_last = self._rmse_frame
+        self._had_gt = gt is not None
+        self._pending, self._flushed, self._cur = True, False, cur ^ 1
+        self.step_count += 1
+
+    def flush(self):
+        """Materialise the latest frame's resample (poses, weights, weights_res, hint, ridx, status, rmse)."""
+        if not self._pending or self._flushed:
+            return
+        self._wait_draws()
+        cur = self._cur
+        u, u32, stp = self._draw
+        a = LazyFlushArgs()
+        a.N = self.N
+        a.tables, a.valid, a.nn_idx, a.poses_prop = _ptr(self._tables), _ptr(self._valid), _ptr(self._nn[cur]), _ptr(self._prop[cur])
+        a.status = _ptr(self._st[cur])
+        a.part_rmse = _ptr(self._part_rmse) if self._had_gt else None
+        a.softmax, a.resample_mode, a.u, a.u32 = int(self.softmax), self.mode, _ptr(u), float(u32)
+        a.seed, a.step = self.seed, int(stp)
+        a.weights, a.ridx, a.poses_out = _ptr(self._weights), _ptr(self._ridx), _ptr(self._poses)
+        a.weights_out, a.hint_out = _ptr(self._weights_res), _ptr(self._hint)
+        a.rmse = _ptr(self._rmse) if self._had_gt else None
+        self.ctx.bind_current_stream()
+        self.ctx.check(self._lazy_flush(self.ctx.h, C.byref(a), *self._batch))
+        self._flushed = True
+
+
+class PipelinedFilterEngine(_FoldedResample, FilterEngine):
+    """FilterEngine with the resample of frame t folded into the front kernel of frame t+1 (midas_lazy_step).
+
+    Slot n of the next frame is particle src(n) of this one, a per-slot dependence: the resampler's search and
+    gather run as a prologue of the next particle update, the resampled poses never travel through HBM and a
+    frame is two launches instead of three.  The resampled particle set of the latest frame therefore exists only
+    implicitly (tables + draws) until somebody reads it: `poses`, `weights`, `weights_res`, `hint`, `ridx`, `status`
+    and `rmse` materialise it on access (`flush()`, the same kernel as the eager engine's tail - bit-identical
+    results); `nn_idx` and `poses_prop` of the latest frame are always there.  A caller that looks at the particles
+    every frame gets the eager engine's launches; one that only steps gets the pipelined ones.
+    Needs a float32 codebook with D in {128, 256, 512, 1024} and N <= 1 M (MidasError otherwise: use FilterEngine).
+    """
+
+    _lazy_calls = ("midas_lazy_step", "midas_lazy_flush")
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not sparse_scoring(self.codebook, switch=False) or self.N > (1 << 20):
+            raise MidasError("PipelinedFilterEngine needs a float32 codebook with D in {128,256,512,1024} and N <= 2^20")
+
+    def check(self):
+        """Raises if a frame's tail reported its tables undefined (status bit 4, value 16: a wave of the grouped tail waited
+        0.2 s for its block's records - include/midas_hip.h, midas_lazy_args.status_dev).  One small read-back."""
+        st = torch.stack([self._st[0][0], self._st[1][0]]).cpu()
+        if int(st[0]) & 16 or int(st[1]) & 16:
+            raise MidasError("grouped tail: a wave did not receive its block's records in time - the frame's CDF tables are undefined "
+                             "(foreign work on the device?); MIDAS_TAIL_GROUPED=0 selects the form without waits")
 
     def seed_torch_stream(self, seed, motion: bool = False):
         """Resample draws from the device replica of torch's CPU generator under torch.manual_seed(seed) (torch_rng.py):
@@ -344,45 +487,8 @@ class PipelinedFilterEngine(FilterEngine):
                 self._unit_noise = (a, b, ev)
             else:
                 u, u_event = stream.rand64_async(self.N)
-        self._wait_draws()
-        odom, code, gt, tn, rot, u = self._operands(odom, code, gt, tn, rot, u)
-        cur, nxt = self._cur, self._cur ^ 1
-        fold = self._pending and not self._flushed
-        a = LazyArgs()
-        a.N = self.N
-        a.poses_prop_prev, a.nn_idx_prev, a.status_prev = _ptr(self._prop[cur]), _ptr(self._nn[cur]), _ptr(self._st[cur])
-        a.poses_prop, a.nn_idx, a.valid, a.status = _ptr(self._prop[nxt]), _ptr(self._nn[nxt]), _ptr(self._valid), _ptr(self._st[nxt])
-        a.tables, a.scores = _ptr(self._tables), _ptr(self._scores)
-        a.guide = _ptr(self._guide) if self._guide is not None else None
-        a.part_rmse = _ptr(self._part_rmse) if gt is not None else None
-        a.resample_prev = int(fold)
-        a.poses_in = _ptr(self._poses)
-        a.hint_in = _ptr(self._hint) if self.use_hint else None
-        pu, pu32, pstep = self._draw
-        a.resample_mode, a.u_prev, a.u32_prev, a.step_prev = self.mode, _ptr(pu), float(pu32), int(pstep)
-        a.ridx = _ptr(self._ridx) if fold else None
-        a.odom16, a.code, a.gt16 = _ptr(odom), _ptr(code), _ptr(gt)
-        a.tn, a.rot = _ptr(tn), _ptr(rot)
         mul = max(float(multiplier), 1.0)
-        a.std_t, a.std_r = mul * self.sig_t, mul * self.sig_r
-        a.seed, a.step = self.seed, self.step_count
-        a.prune_thr, a.softmax = self.pen_max, int(self.softmax)
-        a.telemetry = _ptr(self.telemetry)
-        if self.sparse_scores:
-            a.score_stamps, a.score_epoch = _ptr(self._stamps), self._next_epoch()
-            a.score_list = _ptr(self._score_list)
-        a.rmse = _ptr(self._rmse_frame) if gt is not None else None
-        self._keep = (odom, code, gt, tn, rot, pu)
-        self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_lazy_step(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a)))
-        # this frame's resample draws, consumed by the next step or by flush()
-        # (a caller's tensor is copied: it may be mutated before the next step() / flush() consumes it)
-        self._draw = (None if u is None else (u if own_u else u.clone()), float(u32), self.step_count)
-        self._draw_event = u_event
-        self._rmse_last = self._rmse_frame
-        self._had_gt = gt is not None
-        self._pending, self._flushed, self._cur = True, False, nxt
-        self.step_count += 1
+        self._lazy_frame(odom, code, gt, tn, rot, u, u32, own_u, u_event, mul * self.sig_t, mul * self.sig_r)
 
     def run(self, odoms, codes, gts=None):
         """T frames by ONE C-ABI call (midas_lazy_run; device draws): odoms (T,4,4) f32, codes (T,D) f64, gts (T,4,4) f32 or
@@ -391,9 +497,7 @@ class PipelinedFilterEngine(FilterEngine):
         calls of step() - same kernels, same results - without the per-frame turn-around through Python."""
         d = self.device
         T = int(torch.as_tensor(odoms).shape[0])
-        odoms = operand(odoms, "odoms", torch.float32, (T, 4, 4), d)
-        codes = operand(codes, "tactile codes", torch.float64, (T, self.D), d)
-        gts = operand(gts, "gt poses", torch.float32, (T, 4, 4), d)
+        odoms, codes, gts = frame_operands(d, (T,), self.D, odoms, codes, gts)
         cur, nxt = self._cur, self._cur ^ 1
         fold = self._pending and not self._flushed
         # the argument block with every pointer that does not change from call to call, one per buffer parity, built once (the
@@ -405,16 +509,7 @@ class PipelinedFilterEngine(FilterEngine):
         cache = self.__dict__.setdefault("_run_args", {})
         a, have = cache.get(cur, (None, None))
         if have != sig:
-            a = LazyArgs()
-            a.N = self.N
-            a.poses_prop_prev, a.nn_idx_prev, a.status_prev = _ptr(self._prop[cur]), _ptr(self._nn[cur]), _ptr(self._st[cur])
-            a.poses_prop, a.nn_idx, a.valid, a.status = _ptr(self._prop[nxt]), _ptr(self._nn[nxt]), _ptr(self._valid), _ptr(self._st[nxt])
-            a.tables, a.scores = _ptr(self._tables), _ptr(self._scores)
-            a.guide = _ptr(self._guide) if self._guide is not None else None
-            a.poses_in = _ptr(self._poses)
-            a.telemetry = _ptr(self.telemetry)
-            a.ridx = None
-            a.u_prev = None
+            a = self._lazy_args(cur)  # (ridx and u_prev stay NULL: device draws, the ridx of a folded frame are not kept)
             cache[cur] = (a, sig)
         a.part_rmse = _ptr(self._part_rmse) if gts is not None else None
         a.resample_prev = int(fold)
@@ -429,7 +524,7 @@ class PipelinedFilterEngine(FilterEngine):
         a.seed, a.step = self.seed, self.step_count
         a.prune_thr, a.softmax = self.pen_max, int(self.softmax)
         if self.sparse_scores:  # (a caller may switch the scoring form between calls)
-            a.score_stamps, a.score_epoch, a.score_list = _ptr(self._stamps), self._next_epoch(T), _ptr(self._score_list)
+            a.score_stamps, a.score_epoch, a.score_list = _ptr(self._stamps), advance_epoch(self, T), _ptr(self._score_list)
         else:
             a.score_stamps, a.score_epoch, a.score_list = None, 0, None
         # a FRESH tensor per call (caching allocator: no launch, no fill - every row is written by its frame): the log belongs
@@ -447,36 +542,8 @@ class PipelinedFilterEngine(FilterEngine):
         self._cur = nxt if T % 2 else cur
         return log
 
-    def _wait_draws(self):
-        """The pending frame's draws may still be in flight on the generator's stream (TorchCpuStream): order this stream behind them."""
-        ev = getattr(self, "_draw_event", None)
-        if ev is not None:
-            torch.cuda.current_stream(self.device).wait_event(ev)
-            self._draw_event = None
 
-    def flush(self):
-        """Materialise the latest frame's resample (poses, weights, weights_res, hint, ridx, status, rmse)."""
-        if not self._pending or self._flushed:
-            return
-        self._wait_draws()
-        cur = self._cur
-        u, u32, stp = self._draw
-        a = LazyFlushArgs()
-        a.N = self.N
-        a.tables, a.valid, a.nn_idx, a.poses_prop = _ptr(self._tables), _ptr(self._valid), _ptr(self._nn[cur]), _ptr(self._prop[cur])
-        a.status = _ptr(self._st[cur])
-        a.part_rmse = _ptr(self._part_rmse) if self._had_gt else None
-        a.softmax, a.resample_mode, a.u, a.u32 = int(self.softmax), self.mode, _ptr(u), float(u32)
-        a.seed, a.step = self.seed, int(stp)
-        a.weights, a.ridx, a.poses_out = _ptr(self._weights), _ptr(self._ridx), _ptr(self._poses)
-        a.weights_out, a.hint_out = _ptr(self._weights_res), _ptr(self._hint)
-        a.rmse = _ptr(self._rmse) if self._had_gt else None
-        self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_lazy_flush(self.ctx.h, C.byref(a)))
-        self._flushed = True
-
-
-class BatchFilterEngine:
+class BatchFilterEngine(_Engine):
     """B independent trajectories against one codebook, one C-ABI call per frame of the whole batch
     (BASELINE config 5, "throughput mode": SURVEY.md 8(e) batch mode).
 
@@ -497,58 +564,18 @@ class BatchFilterEngine:
                  pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None, scores="auto"):
         if scores not in ("auto", "dense_f64"):
             raise MidasError(f"scores must be 'auto' or 'dense_f64', got {scores!r}")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.ctx = _lib.context(dev)
-        self.device = self.ctx.device
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.cb_poses = torch.as_tensor(cb_poses).to(**f32).contiguous()
-        self.cb_feat = ops.se3_feature(self.cb_poses)
-        self.tree6 = ops.Tree(self.cb_feat)
-        self.codebook = ops.Codebook(torch.as_tensor(cb_embeddings).to(self.device))
-        self.tree3 = ops.Tree(torch.as_tensor(mesh_vertices).to(self.device, torch.float64))
-        self.tree6.attach_mesh(self.tree3, self.cb_poses)
-        self.B, self.N = int(batch), int(num_particles)
-        self.sig_t, self.sig_r, self.pen_max = float(sig_t), float(sig_r), float(pen_max)
-        self.seed, self.softmax = int(seed), bool(softmax)
-        self.mode = {"weighted_random": _lib.RESAMPLE_MULTINOMIAL, "low_var": _lib.RESAMPLE_SYSTEMATIC,
-                     "low_var_batch": _lib.RESAMPLE_SYSTEMATIC}[resample]
-        B, N, d = self.B, self.N, self.device
-        self.poses = torch.zeros((B, N, 4, 4), **f32)
-        self.poses_prop = torch.zeros((B, N, 4, 4), **f32)
-        self.weights = torch.zeros((B, N), dtype=torch.float64, device=d)
-        self.weights_res = torch.ones((B, N), dtype=torch.float64, device=d)
-        self.nn_idx = torch.zeros((B, N), dtype=torch.int32, device=d)
-        self.hint = torch.full((B, N), -1, dtype=torch.int32, device=d)
-        self.hint_next = torch.full((B, N), -1, dtype=torch.int32, device=d)
-        self.ridx = torch.zeros((B, N), dtype=torch.int32, device=d)
-        self.status = torch.zeros((B, 2), dtype=torch.int32, device=d)
-        self.rmse = torch.zeros((B, 2), dtype=torch.float64, device=d)
+        B, N = int(batch), int(num_particles)
+        self._setup(cb_poses, cb_embeddings, mesh_vertices, device, (B, N), sig_t, sig_r, pen_max, seed, softmax, resample)
+        self.B = B
         extra = 16 * B * ((N + 63) // 64) if int(os.environ.get("MIDAS_ABLATE", "0")) & 4 else 0  # per-wave statistics (profiling)
-        self.telemetry = torch.zeros(16 + extra, dtype=torch.int64, device=d)
-        self.step_count = 0
+        self.telemetry = torch.zeros(16 + extra, dtype=torch.int64, device=self.device)
         # sparse scoring per trajectory (B x K stamps): the particle waves score the rows their trajectory needs with the
         # float64 arithmetic of the single-trajectory step; MIDAS_DENSE_SCORES=1 keeps the matrix-core pass over all rows
-        _os = os
-        self.sparse_scores = self.codebook.emb.dtype == torch.float32 and self.codebook.D in (128, 256, 512, 1024) and \
-            _os.environ.get("MIDAS_DENSE_SCORES", "0") != "1"
         if scores == "dense_f64":  # no stamps: every frame is one float64 pass over all rows on the matrix cores
             self.sparse_scores = False
             self.codebook.set_batch_precision("f64")
-        self._stamps = torch.zeros((B, self.codebook.K), dtype=torch.int32, device=d) if self.sparse_scores else None
-        self._epoch = 0
-
-    def set_particles(self, poses):
-        poses = torch.as_tensor(poses).to(self.device, torch.float32)
-        if tuple(poses.shape) != (self.B, self.N, 4, 4):
-            raise MidasError(f"expected ({self.B},{self.N},4,4) poses, got {tuple(poses.shape)}")
-        self.poses.copy_(poses)
-        self.hint.fill_(-1)
-
-    def project_to_codebook(self):
-        flat = self.poses.view(-1, 4, 4)
-        idx = ops.nn6(self.tree6, ops.se3_feature(flat))
-        self.poses.copy_(ops.gather_rows(self.cb_poses, idx).view_as(self.poses))
-        self.hint.copy_(idx.view_as(self.hint))
+        self._stamps = torch.zeros((B, self.K), dtype=torch.int32, device=self.device) if self.sparse_scores else None
+        self._alloc_state()
 
     def seed_torch_streams(self, seeds, motion: bool = False, pieces: int = 0):
         """Trajectory b draws from the device replica of torch's CPU generator under torch.manual_seed(seeds[b]) - B seeded runs of
@@ -608,38 +635,14 @@ class BatchFilterEngine:
 
     def step(self, odoms, codes, gts=None, tn=None, rot=None, u=None, u32=-1.0):
         """odoms (B,4,4) f32, codes (B,D) f64, gts (B,4,4) f32 or None; optional host draws tn/rot (B,N,3), u (B,N)."""
-        d, B, N = self.device, self.B, self.N
-        if (tn is None) != (rot is None):
-            raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
+        check_motion_draws(tn, rot)  # (before the streams draw)
         tn, rot, u, ev = self._stream_draws(tn, rot, u)
         if ev is not None:
-            torch.cuda.current_stream(d).wait_event(ev)
-        odoms, gts = operand(odoms, "odoms", torch.float32, (B, 4, 4), d), operand(gts, "gt poses", torch.float32, (B, 4, 4), d)
-        codes = operand(codes, "tactile codes", torch.float64, (B, self.codebook.D), d)
-        tn, rot = operand(tn, "tn", torch.float32, (B, N, 3), d), operand(rot, "rot", torch.float32, (B, N, 3), d)
-        u = operand(u, "u", torch.float64, (B, N), d)
-        a = StepArgs()
-        a.N = self.N
-        a.poses_in, a.poses_prop, a.poses_out = _ptr(self.poses), _ptr(self.poses_prop), _ptr(self.poses)
-        a.weights, a.weights_out = _ptr(self.weights), _ptr(self.weights_res)
-        a.hint_in, a.nn_idx, a.hint_out, a.ridx = _ptr(self.hint), _ptr(self.nn_idx), _ptr(self.hint_next), _ptr(self.ridx)
-        a.odom16, a.code, a.gt16 = _ptr(odoms), _ptr(codes), _ptr(gts)
-        a.rmse = _ptr(self.rmse) if gts is not None else None
-        a.tn, a.rot, a.u, a.u32 = _ptr(tn), _ptr(rot), _ptr(u), float(u32)
-        a.std_t, a.std_r, a.seed, a.step = self.sig_t, self.sig_r, self.seed, self.step_count
-        a.prune_thr, a.softmax, a.resample_mode = self.pen_max, int(self.softmax), self.mode
-        a.status, a.telemetry = _ptr(self.status), _ptr(self.telemetry)
-        if self.sparse_scores:
-            a.score_stamps, a.score_epoch = _ptr(self._stamps), advance_epoch(self)
-        self._keep = (odoms, codes, gts, tn, rot, u)
-        self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_filter_step_batch(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h,
-                                                            C.byref(a), self.B))
-        self.hint, self.hint_next = self.hint_next, self.hint
-        self.step_count += 1
+            torch.cuda.current_stream(self.device).wait_event(ev)
+        self._eager_step(self.ctx.lib.midas_filter_step_batch, odoms, codes, gts, tn, rot, u, u32, self.sig_t, self.sig_r, self.B)
 
 
-class PipelinedBatchFilterEngine(BatchFilterEngine):
+class PipelinedBatchFilterEngine(_FoldedResample, BatchFilterEngine):
     """BatchFilterEngine with every trajectory's resample folded into the next frame's front kernel (midas_lazy_step_batch):
     two launches per batch frame - the front with the trajectory as grid.y (one-wave workgroups, per-wave resample tables)
     and the LDS-free tail - instead of particle update + tail + resample-gather.  As with PipelinedFilterEngine the
@@ -648,78 +651,13 @@ class PipelinedBatchFilterEngine(BatchFilterEngine):
     `rmse` of the latest frame are always there.  Needs sparse scoring (float32 codebook, D in {128, 256, 512, 1024}) and
     16 <= N <= 262144 particles per trajectory."""
 
-    poses = _materialised("poses")
-    weights = _materialised("weights")
-    weights_res = _materialised("weights_res")
-    hint = _materialised("hint")
-    ridx = _materialised("ridx")
+    _lazy_calls = ("midas_lazy_step_batch", "midas_lazy_flush_batch")
 
     def __init__(self, *args, **kw):
-        self._pending, self._flushed = False, True
         super().__init__(*args, **kw)
-        B, N, d = self.B, self.N, self.device
-        if not self.sparse_scores or N < 16 or N > 262144:
+        if not self.sparse_scores or self.N < 16 or self.N > 262144:
             raise MidasError("PipelinedBatchFilterEngine needs a float32 codebook with D in {128,256,512,1024} (sparse scoring) "
                              "and 16 <= N <= 262144")
-        f64 = dict(dtype=torch.float64, device=d)
-        self._prop = [self.poses_prop, torch.zeros_like(self.poses_prop)]
-        self._nn = [self.nn_idx, torch.zeros_like(self.nn_idx)]
-        self._st = [torch.zeros((B, 2), dtype=torch.int32, device=d) for _ in range(2)]
-        self._valid = torch.zeros((B, N), dtype=torch.uint8, device=d)
-        self._tstride = int(self.ctx.lib.midas_lazy_tables_doubles(N))
-        self._tables = torch.zeros(B * self._tstride, **f64)
-        self._scores = torch.zeros((B, self.codebook.K), **f64)
-        self._part_rmse = torch.zeros((B, 2 * ((N + 63) // 64)), **f64)
-        self._rmse_frame = torch.zeros((B, 3), **f64)
-        self._cur, self._draw, self._had_gt = 0, (None, -1.0, 0), False
-
-    # storage behind the materialised properties (the base constructor assigns them)
-    @property
-    def status(self):
-        self.flush()
-        return self._st[self._cur]
-
-    @status.setter
-    def status(self, v):
-        pass
-
-    @property
-    def nn_idx(self):
-        return self._nn[self._cur] if hasattr(self, "_nn") else self._nn0
-
-    @nn_idx.setter
-    def nn_idx(self, v):
-        self._nn0 = v
-
-    @property
-    def poses_prop(self):
-        return self._prop[self._cur] if hasattr(self, "_prop") else self._prop0
-
-    @poses_prop.setter
-    def poses_prop(self, v):
-        self._prop0 = v
-
-    @property
-    def rmse(self):
-        return self._rmse_frame[:, :2] if self._pending else self._rmse
-
-    @rmse.setter
-    def rmse(self, v):
-        self._rmse = v
-
-    def set_particles(self, poses):
-        self._pending, self._flushed = False, True
-        poses = torch.as_tensor(poses).to(self.device, torch.float32)
-        if tuple(poses.shape) != (self.B, self.N, 4, 4):
-            raise MidasError(f"expected ({self.B},{self.N},4,4) poses, got {tuple(poses.shape)}")
-        self._poses.copy_(poses)
-        self._hint.fill_(-1)
-
-    def project_to_codebook(self):
-        self.flush()
-        idx = ops.nn6(self.tree6, ops.se3_feature(self._poses.view(-1, 4, 4)))
-        self._poses.copy_(ops.gather_rows(self.cb_poses, idx).view_as(self._poses))
-        self._hint.copy_(idx.view_as(self._hint))
 
     def _seeded_frame(self):
         """motion=True: this frame's normals were drawn a frame ahead, behind the previous frame's uniforms; this frame's uniforms
@@ -737,71 +675,9 @@ class PipelinedBatchFilterEngine(BatchFilterEngine):
         self._unit_noise = (a, b, ev)
         return tn, rot, u, ev
 
-    def _wait_draws(self):
-        """The pending frame's uniforms may still be in flight on the generators' stream: order this stream behind them."""
-        ev = getattr(self, "_draw_event", None)
-        if ev is not None:
-            torch.cuda.current_stream(self.device).wait_event(ev)
-            self._draw_event = None
-
     def step(self, odoms, codes, gts=None, tn=None, rot=None, u=None, u32=-1.0):
-        d, B, N = self.device, self.B, self.N
-        if (tn is None) != (rot is None):
-            raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
+        check_motion_draws(tn, rot)  # (before the streams draw)
         own_u = u is None
         tn, rot, u, u_event = self._stream_draws(tn, rot, u)
         own_u = own_u and u is not None  # generated here (a tensor nobody else holds): kept for the folded resample without a copy
-        self._wait_draws()
-        odoms, gts = operand(odoms, "odoms", torch.float32, (B, 4, 4), d), operand(gts, "gt poses", torch.float32, (B, 4, 4), d)
-        codes = operand(codes, "tactile codes", torch.float64, (B, self.codebook.D), d)
-        tn, rot = operand(tn, "tn", torch.float32, (B, N, 3), d), operand(rot, "rot", torch.float32, (B, N, 3), d)
-        u = operand(u, "u", torch.float64, (B, N), d)
-        cur, nxt = self._cur, self._cur ^ 1
-        fold = self._pending and not self._flushed
-        a = LazyArgs()
-        a.N = N
-        a.poses_prop_prev, a.nn_idx_prev, a.status_prev = _ptr(self._prop[cur]), _ptr(self._nn[cur]), _ptr(self._st[cur])
-        a.poses_prop, a.nn_idx, a.valid, a.status = _ptr(self._prop[nxt]), _ptr(self._nn[nxt]), _ptr(self._valid), _ptr(self._st[nxt])
-        a.tables, a.scores = _ptr(self._tables), _ptr(self._scores)
-        a.part_rmse = _ptr(self._part_rmse) if gts is not None else None
-        a.resample_prev = int(fold)
-        a.poses_in, a.hint_in = _ptr(self._poses), _ptr(self._hint)
-        pu, pu32, pstep = self._draw
-        a.resample_mode, a.u_prev, a.u32_prev, a.step_prev = self.mode, _ptr(pu), float(pu32), int(pstep)
-        a.ridx = _ptr(self._ridx) if fold else None
-        a.odom16, a.code, a.gt16 = _ptr(odoms), _ptr(codes), _ptr(gts)
-        a.tn, a.rot = _ptr(tn), _ptr(rot)
-        a.std_t, a.std_r, a.seed, a.step = self.sig_t, self.sig_r, self.seed, self.step_count
-        a.prune_thr, a.softmax = self.pen_max, int(self.softmax)
-        a.telemetry = _ptr(self.telemetry)
-        a.score_stamps, a.score_epoch = _ptr(self._stamps), advance_epoch(self)
-        a.rmse = _ptr(self._rmse_frame) if gts is not None else None
-        self._keep = (odoms, codes, gts, tn, rot, pu)
-        self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_lazy_step_batch(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), B))
-        self._draw = (None if u is None else (u if own_u else u.clone()), float(u32), self.step_count)
-        self._draw_event = u_event
-        self._had_gt = gts is not None
-        self._pending, self._flushed, self._cur = True, False, nxt
-        self.step_count += 1
-
-    def flush(self):
-        """Materialise the latest frame's resample of every trajectory."""
-        if not self._pending or self._flushed:
-            return
-        self._wait_draws()
-        cur = self._cur
-        u, u32, stp = self._draw
-        a = LazyFlushArgs()
-        a.N = self.N
-        a.tables, a.valid, a.nn_idx, a.poses_prop = _ptr(self._tables), _ptr(self._valid), _ptr(self._nn[cur]), _ptr(self._prop[cur])
-        a.status = _ptr(self._st[cur])
-        a.part_rmse = _ptr(self._part_rmse) if self._had_gt else None
-        a.softmax, a.resample_mode, a.u, a.u32 = int(self.softmax), self.mode, _ptr(u), float(u32)
-        a.seed, a.step = self.seed, int(stp)
-        a.weights, a.ridx, a.poses_out = _ptr(self._weights), _ptr(self._ridx), _ptr(self._poses)
-        a.weights_out, a.hint_out = _ptr(self._weights_res), _ptr(self._hint)
-        a.rmse = _ptr(self._rmse) if self._had_gt else None
-        self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_lazy_flush_batch(self.ctx.h, C.byref(a), self.B))
-        self._flushed = True
+        self._lazy_frame(odoms, codes, gts, tn, rot, u, u32, own_u, u_event, self.sig_t, self.sig_r)

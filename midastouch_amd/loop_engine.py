@@ -27,7 +27,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import LoopArgs, MidasError, _ptr
-from .engine import operand
+from .engine import RESAMPLE_MODES, advance_epoch, check_motion_draws, codebook_index, frame_operands, operand, sparse_scoring
 
 ALL_PHASES = _lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL | _lib.LOOP_RESAMPLE
 
@@ -37,20 +37,9 @@ class LoopEngine:
                  seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2, cluster: bool = True,
                  cluster_every: int = 50, log_frames: int = 4096, device=None,
                  topk_ties: str = "index"):
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.ctx = _lib.context(dev)
+        self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3 = codebook_index(
+            cb_poses, cb_embeddings, mesh_vertices, device)
         self.device = d = self.ctx.device
-        if hasattr(cb_poses, "SE3_NN") and cb_embeddings is None:  # a tactile_tree already on the device: share its index
-            tt = cb_poses
-            self.cb_poses, self.cb_feat, self.tree6, self.codebook = tt.poses, tt.logmap_pose, tt.tree, tt.codebook
-        else:
-            self.cb_poses = torch.as_tensor(cb_poses).to(d, torch.float32).contiguous()
-            self.cb_feat = ops.se3_feature(self.cb_poses)
-            self.tree6 = ops.Tree(self.cb_feat)
-            self.codebook = ops.Codebook(torch.as_tensor(cb_embeddings).to(d))
-        self.tree3 = mesh_vertices if isinstance(mesh_vertices, ops.Tree) else ops.Tree(torch.as_tensor(mesh_vertices).to(d, torch.float64))
-        if getattr(self.tree6, "_mesh", None) is not self.tree3:  # vertex lists of this mesh not yet on the codebook index
-            self.tree6.attach_mesh(self.tree3, self.cb_poses)
         self.K, self.D = self.codebook.K, self.codebook.D
         self.sig_t, self.sig_r, self.pen_max = float(sig_t), float(sig_r), float(pen_max)
         self.seed, self.softmax, self.floor, self.eps = int(seed), bool(softmax), int(floor), float(eps)
@@ -58,8 +47,7 @@ class LoopEngine:
         # whom annealing's torch.topk takes inside a tie: "index" (torch's CUDA rule, the radix select) or "aten_cpu" (the
         # reference as it runs on the CPU - the rule of a seeded replay; topk_aten.hip)
         self.topk_ties = {"index": _lib.TOPK_TIES_INDEX, "aten_cpu": _lib.TOPK_TIES_ATEN_CPU}[topk_ties]
-        self.mode = {"weighted_random": _lib.RESAMPLE_MULTINOMIAL, "low_var": _lib.RESAMPLE_SYSTEMATIC,
-                     "low_var_batch": _lib.RESAMPLE_SYSTEMATIC}[resample]
+        self.mode = RESAMPLE_MODES[resample]
         self.cap = cap = int(num_particles)
         if cap < 1 or cap > (1 << 20):
             raise MidasError("LoopEngine holds 1 .. 2^20 particles")
@@ -77,9 +65,7 @@ class LoopEngine:
         self.log_frames = int(log_frames)
         self._log = z((self.log_frames, _lib.LOOP_LOG_DOUBLES), torch.float64)
         self.telemetry = z(16, torch.int64)
-        import os as _os
-        self.sparse_scores = self.codebook.emb.dtype == torch.float32 and self.D in (128, 256, 512, 1024) and \
-            _os.environ.get("MIDAS_DENSE_SCORES", "0") != "1"
+        self.sparse_scores = sparse_scoring(self.codebook)
         self._stamps, self._epoch = z(self.K, torch.int32), 0  # sparse scoring (include/midas_hip.h score_stamps_dev)
         # {frames completed, live count} as the device last reported them, in pinned host memory: lets step() size its launches
         # to the live set without waiting for anything (an upper bound is all it needs, see _count_bound)
@@ -240,11 +226,8 @@ class LoopEngine:
         a.log = C.c_void_p(self._log.data_ptr() + (self.step_count % self.log_frames) * _lib.LOOP_LOG_DOUBLES * 8)
         keep = []
         if phases & _lib.LOOP_FRONT:
-            if (tn is None) != (rot is None):
-                raise MidasError("tn and rot (the motion model's host draws) come together or not at all")
-            odom = operand(odom, "odom", torch.float32, (4, 4), d)
-            code = operand(code, "tactile code", torch.float64, (self.D,), d)
-            gt = operand(gt, "gt pose", torch.float32, (4, 4), d)
+            check_motion_draws(tn, rot)
+            odom, code, gt = frame_operands(d, (), self.D, odom, code, gt)
             if tn is not None:
                 n = self.n
                 tn, rot = operand(tn, "tn", torch.float32, (n, 3), d), operand(rot, "rot", torch.float32, (n, 3), d)
@@ -271,7 +254,6 @@ class LoopEngine:
         a.topk_ties = self.topk_ties
         a.telemetry = _ptr(self.telemetry)
         if self.sparse_scores and phases & _lib.LOOP_FRONT:
-            from .engine import advance_epoch
             a.score_stamps, a.score_epoch = _ptr(self._stamps), advance_epoch(self)
         self._keep = keep
         self.ctx.bind_current_stream()
