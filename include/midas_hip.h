@@ -470,6 +470,37 @@ int midas_score_list_seed(midas_ctx* ctx, int64_t K, uint32_t* score_stamps_dev,
 int midas_lazy_run(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                    const midas_lazy_args* first, int32_t T, double* rmse_log_dev);
 
+/* ---- pose estimate of a fixed-N frame ---------------------------------------------------------- */
+/* The filter's output, taken every frame between the measurement update and the resample (filter/filter.py:184-186):
+ * get_cluster_centers(particles, method="quat_avg") (modules/particle_filter.py:153-206, modules/pose.py:112-147) of a particle
+ * set nobody has clustered (labels all 0, particle_filter.py:47) - Markley's weighted quaternion mean, the weighted mean
+ * translation and the per-axis spread - for B trajectories by one call: row b of centers_dev / stds_dev is, bit for bit, what
+ * midas_cluster_centers gives on trajectory b's propagated poses and masked pre-resample weights with every label 0 (same
+ * contributions, same summation order; the flatten rule isclose(max - min, 0) -> weights 1 included).
+ * The weights: weights_dev (B x N float64, what midas_filter_step / midas_filter_step_batch leave in weights_dev), or - NULL -
+ * formed from the table blocks a pipelined frame left (midas_lazy_step / _batch: tables_dev, valid_dev and the frame's softmax
+ * switch): the value midas_lazy_flush would write to weights_dev, without the flush.  Exactly one of weights_dev / tables_dev is
+ * non-NULL; tables_dev 128-byte aligned, B blocks of midas_lazy_tables_doubles(N) doubles; valid_dev is read with tables_dev only.
+ * Two launches on the context's stream behind the frame; B * ceil(N / 256) * 36 doubles of the context's scratch. */
+typedef struct midas_estimate_args {
+    int64_t N;
+    int32_t B;
+    const float* poses_prop_dev;    /* B x N x 16 */
+    const double* weights_dev;      /* B x N masked pre-resample weights, or NULL: made from */
+    const double* tables_dev;       /*   the frame's table blocks, B x midas_lazy_tables_doubles(N), */
+    const uint8_t* valid_dev;       /*   B x N, */
+    int32_t softmax;                /*   as the frame ran */
+    float* centers_dev;             /* B x 16 out */
+    float* stds_dev;                /* B x 3 out */
+} midas_estimate_args;
+int midas_pose_estimate(midas_ctx* ctx, const midas_estimate_args* args);
+/* midas_lazy_run that also leaves every frame's estimate (the reference takes it inside the loop body, filter/filter.py:184-186):
+ * est_centers_dev T x 16, est_stds_dev T x 3 float32, row f enqueued behind frame f's tail from that frame's poses_prop, tables
+ * and valid mask.  Frames, draws, rmse_log_dev and the buffers' parity afterwards are midas_lazy_run's. */
+int midas_lazy_run_estimate(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                            const midas_lazy_args* first, int32_t T, double* rmse_log_dev,
+                            float* est_centers_dev, float* est_stds_dev);
+
 typedef struct midas_lazy_flush_args {
     int64_t N;
     const double* tables_dev;          /* the frame's tables, valid mask, NN indices, propagated poses (midas_lazy_step) */

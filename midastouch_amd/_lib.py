@@ -112,6 +112,16 @@ class LazyFlushArgs(C.Structure):
     ]
 
 
+class EstimateArgs(C.Structure):
+    """midas_estimate_args (include/midas_hip.h)."""
+
+    _fields_ = [
+        ("N", C.c_int64), ("B", C.c_int32),
+        ("poses_prop", C.c_void_p), ("weights", C.c_void_p), ("tables", C.c_void_p), ("valid", C.c_void_p),
+        ("softmax", C.c_int32), ("centers", C.c_void_p), ("stds", C.c_void_p),
+    ]
+
+
 class ShardRouteArgs(C.Structure):
     """midas_shard_route_args (include/midas_hip.h)."""
 
@@ -252,6 +262,8 @@ SIGNATURES = {
     "midas_filter_step_batch": (C.c_int, [_P, _P, _P, _P, C.POINTER(StepArgs), _I32]),
     "midas_lazy_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(LazyArgs)]),
     "midas_lazy_run": (C.c_int, [_P, _P, _P, _P, C.POINTER(LazyArgs), _I32, _P]),
+    "midas_lazy_run_estimate": (C.c_int, [_P, _P, _P, _P, C.POINTER(LazyArgs), _I32, _P, _P, _P]),
+    "midas_pose_estimate": (C.c_int, [_P, C.POINTER(EstimateArgs)]),
     "midas_lazy_flush": (C.c_int, [_P, C.POINTER(LazyFlushArgs)]),
     "midas_lazy_tables_doubles": (C.c_int64, [_I64]),
     "midas_lazy_guide_bytes": (C.c_int64, [_I64]),

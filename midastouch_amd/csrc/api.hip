@@ -718,9 +718,11 @@ MIDAS_EXPORT int midas_lazy_step(midas_ctx* ctx, const midas_codebook* cb, const
     return lazy_step_impl(ctx, cb, tree6, tree3, *args, (args->gt16_dev && args->part_rmse_dev) ? args->rmse_dev : nullptr);
 }
 
-MIDAS_EXPORT int midas_lazy_run(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
-                                const midas_lazy_args* first, int32_t T, double* rmse_log_dev) {
-    MIDAS_ENTER(ctx);
+static int pose_estimate_impl(midas_ctx* ctx, const midas_estimate_args& s);
+
+// the frame loop of midas_lazy_run and midas_lazy_run_estimate (est_centers / est_stds: NULL, or every frame's estimate)
+static int lazy_run_impl(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                         const midas_lazy_args* first, int32_t T, double* rmse_log_dev, float* est_centers, float* est_stds) {
     MIDAS_REQUIRE(ctx, cb && tree6 && tree3 && first && tree6->dim == 6 && tree3->dim == 3 && tree6->K == cb->K && T >= 1);
     MIDAS_REQUIRE(ctx, first->poses_prop_prev_dev && first->nn_idx_prev_dev && first->status_prev_dev && !first->tn_dev &&
                            !first->rot_dev && !first->u_prev_dev);
@@ -736,6 +738,13 @@ MIDAS_EXPORT int midas_lazy_run(midas_ctx* ctx, const midas_codebook* cb, const 
         if (rc) return rc;
         rc = lazy_step_impl(ctx, cb, tree6, tree3, a, rmse_log_dev ? rmse_log_dev + 3 * f : nullptr);
         if (rc) return rc;
+        if (est_centers) {  // behind this frame's tail: the next front only reads these tables, its tail rewrites them afterwards
+            midas_estimate_args e;
+            e.N = a.N; e.B = 1; e.poses_prop_dev = a.poses_prop_dev; e.weights_dev = nullptr; e.tables_dev = a.tables_dev;
+            e.valid_dev = a.valid_dev; e.softmax = a.softmax;
+            e.centers_dev = est_centers + 16 * (size_t)f; e.stds_dev = est_stds + 3 * (size_t)f;
+            if ((rc = pose_estimate_impl(ctx, e))) return rc;
+        }
         // next frame: the buffer sets swap, the resample of this frame is folded in, the inputs advance
         float* pp = const_cast<float*>(a.poses_prop_prev_dev);
         int32_t* np = const_cast<int32_t*>(a.nn_idx_prev_dev);
@@ -754,6 +763,40 @@ MIDAS_EXPORT int midas_lazy_run(midas_ctx* ctx, const midas_codebook* cb, const 
         if (a.gt16_dev) a.gt16_dev += 16;
     }
     return MIDAS_OK;
+}
+
+MIDAS_EXPORT int midas_lazy_run(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                                const midas_lazy_args* first, int32_t T, double* rmse_log_dev) {
+    MIDAS_ENTER(ctx);
+    return lazy_run_impl(ctx, cb, tree6, tree3, first, T, rmse_log_dev, nullptr, nullptr);
+}
+
+MIDAS_EXPORT int midas_lazy_run_estimate(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                                         const midas_lazy_args* first, int32_t T, double* rmse_log_dev, float* est_centers_dev,
+                                         float* est_stds_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, est_centers_dev && est_stds_dev);
+    return lazy_run_impl(ctx, cb, tree6, tree3, first, T, rmse_log_dev, est_centers_dev, est_stds_dev);
+}
+
+// ---- pose estimate of a fixed-N frame (filter/filter.py:184-186) ----------------------------------------
+static int pose_estimate_impl(midas_ctx* ctx, const midas_estimate_args& s) {
+    MIDAS_REQUIRE(ctx, s.N > 0 && s.B >= 1 && s.B <= 65535 && s.poses_prop_dev && s.centers_dev && s.stds_dev &&
+                           (uintptr_t)s.poses_prop_dev % 16 == 0);
+    MIDAS_REQUIRE(ctx, (s.weights_dev == nullptr) != (s.tables_dev == nullptr));
+    if (s.weights_dev)
+        return launch_pose_estimate(ctx, s.N, s.B, s.poses_prop_dev, s.weights_dev, nullptr, 0, nullptr, s.softmax, s.centers_dev,
+                                    s.stds_dev);
+    MIDAS_REQUIRE(ctx, s.valid_dev && (uintptr_t)s.tables_dev % 128 == 0 && ceil_div(s.N, SCAN_BLOCK) <= LAZY_MAX_BLOCKS);
+    const TailTables tb = tables_of(const_cast<double*>(s.tables_dev), s.N);
+    return launch_pose_estimate(ctx, s.N, s.B, s.poses_prop_dev, nullptr, &tb, tables_doubles(s.N), s.valid_dev, s.softmax,
+                                s.centers_dev, s.stds_dev);
+}
+
+MIDAS_EXPORT int midas_pose_estimate(midas_ctx* ctx, const midas_estimate_args* args) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, args != nullptr);
+    return pose_estimate_impl(ctx, *args);
 }
 
 static int lazy_step_impl(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,

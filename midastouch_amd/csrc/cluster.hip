@@ -63,13 +63,16 @@ struct MomIn {
     int64_t lab;
     double w;
 };
+MD void moments_load_pose(int64_t nc, const float* __restrict__ poses, MomIn& in) {
+    const float4* p4 = reinterpret_cast<const float4*>(poses + nc * 16);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { const float4 r = p4[i]; in.P[4 * i] = r.x; in.P[4 * i + 1] = r.y; in.P[4 * i + 2] = r.z; in.P[4 * i + 3] = r.w; }
+}
 template <typename LabelT>
 MD MomIn moments_load(int64_t nc, const float* __restrict__ poses, const double* __restrict__ w64, const float* __restrict__ w32,
                       const LabelT* __restrict__ labels) {
     MomIn in;
-    const float4* p4 = reinterpret_cast<const float4*>(poses + nc * 16);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { const float4 r = p4[i]; in.P[4 * i] = r.x; in.P[4 * i + 1] = r.y; in.P[4 * i + 2] = r.z; in.P[4 * i + 3] = r.w; }
+    moments_load_pose(nc, poses, in);
     in.lab = (int64_t)labels[nc];
     // particles.weights.float() (:161): the reference averages with float32 weights
     in.w = w64 ? (double)(float)w64[nc] : w32 ? (double)w32[nc] : 0.0;  // (neither: the caller computes the weight itself)
@@ -402,6 +405,86 @@ __global__ __launch_bounds__(256) void k_loop_cluster_finish(const int32_t* __re
     cluster_finish_body((int)((n + 255) / 256), (size_t)nbs, blockIdx.x, part, centers, stds, counts, s_m, rot);
 }
 
+// ---- fixed-N engines: the pose estimate of a frame, B trajectories at once (midas_pose_estimate) ----------------------------
+// filter.py:184-186 takes get_cluster_centers of a particle set nobody has clustered (labels all 0, particle_filter.py:47):
+// every particle of trajectory b = blockIdx.y is a member of its one cluster.  part[(b * nbs + block) * CL_MOM + m] - the layout
+// cluster_finish_body walks with "cluster" = trajectory; contribution, wave tree, waves in order and blocks in order are
+// moments_accumulate's (a workgroup always holds a member, so nothing is ever skipped): the bits of midas_cluster_centers on
+// trajectory b alone.  Two weight sources:
+//   w64     B x N masked pre-resample weights (what the eager engines hold);
+//   tables  the pipelined frame's table blocks (tables_of, api.hip), tstride doubles apart: the weight k_tail_b2 would write
+//           (resample.hip, a.weights[i]) is formed here - guard and S by every workgroup for itself from the at most
+//           LAZY_MAX_BLOCKS block records, no flush, no N-sized temporary.
+struct EstimateArgs {
+    int64_t N;
+    const float* poses;                               // B x N x 16
+    const double* w64;                                // B x N, or nullptr: from the tables
+    const double *e, *x_raw, *bsum_e, *bmax, *bmin;   // trajectory 0's arrays
+    int64_t tstride;
+    const uint8_t* valid;                             // B x N
+    int32_t softmax;
+    int32_t nbl;                                      // 4096-slot summation blocks of a trajectory (<= LAZY_MAX_BLOCKS)
+    double* part;
+};
+constexpr double EST_ISCLOSE_ATOL = 1e-8;  // torch.isclose default atol (particle_filter.py:460-463; ISCLOSE_ATOL of resample.hip)
+
+__global__ __launch_bounds__(256) void k_estimate_moments(EstimateArgs a) {
+    __shared__ double s_w[4][CL_MOM];
+    __shared__ double s_sum[LAZY_MAX_BLOCKS];
+    __shared__ double s_ex[12];
+    const int t = threadIdx.x;
+    const int64_t N = a.N, b = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * 256 + t;
+    const bool live = n < N;
+    const int64_t nc = live ? n : N - 1;
+    MomIn in;
+    in.lab = 0;
+    moments_load_pose(b * N + nc, a.poses, in);
+    if (a.w64) {  // (launch-uniform)
+        in.w = (double)(float)a.w64[b * N + nc];  // particles.weights.float() (:161)
+    } else {
+        // everything that does not depend on the guard is requested first (the softmax variant is the common one)
+        const int64_t ts = b * a.tstride;
+        const bool has = t < a.nbl;
+        const int tb = has ? t : a.nbl - 1;
+        const double bs = a.bsum_e[ts + tb], bx = a.bmax[ts + tb], bn = a.bmin[ts + tb];
+        double e_i = a.e[ts + nc];
+        const bool ok_i = a.valid[b * N + nc] != 0;
+        // the guard of k_tail_b2: global extrema of x from the per-block ones, NaN propagates
+        const bool nan = has && ((bx != bx) || (bn != bn));
+        double mx = has && bx > -INFINITY ? bx : -INFINITY, mn = has && bn < INFINITY ? bn : INFINITY;
+        if (has) s_sum[t] = bs;
+        mx = cl_wmax(mx);
+        mn = cl_wmin(mn);
+        const bool wn = __any(nan);
+        if ((t & 63) == 0) { s_ex[t >> 6] = mx; s_ex[4 + (t >> 6)] = mn; s_ex[8 + (t >> 6)] = wn ? 1.0 : 0.0; }
+        __syncthreads();
+        mx = s_ex[0]; mn = s_ex[4];
+        double f = s_ex[8];
+        for (int w = 1; w < 4; ++w) { mx = s_ex[w] > mx ? s_ex[w] : mx; mn = s_ex[4 + w] < mn ? s_ex[4 + w] : mn; f += s_ex[8 + w]; }
+        if (f != 0.0) { mx = NAN; mn = NAN; }
+        const bool apply = a.softmax && !(__builtin_fabs(mx - mn) <= EST_ISCLOSE_ATOL);  // (workgroup-uniform)
+        double S = 1.0;
+        if (apply) {  // the block sums of e one after the other, in block order (the spec)
+            S = 0.0;
+            for (int i = 0; i < a.nbl; ++i) S = S + s_sum[i];
+        } else {      // rare: every particle has the same score, or the softmax is off - the raw variant
+            e_i = a.x_raw[ts + nc];
+        }
+        const double w = (e_i / S) * (ok_i ? 1.0 : 0.0);
+        in.w = (double)(float)w;  // particles.weights.float() (:161)
+    }
+    moments_accumulate(live, in, 1, [](int) { return (int64_t)0; }, a.part + (size_t)b * gridDim.x * CL_MOM, s_w, false);
+}
+
+// one 256-thread workgroup per trajectory (k_loop_cluster_finish's shape: a chunk of partials is one batch of loads, the extrema
+// walk on the second wave)
+__global__ __launch_bounds__(256) void k_estimate_finish(int nblocks, const double* __restrict__ part, float* __restrict__ centers,
+                                                        float* __restrict__ stds) {
+    __shared__ double s_m[CL_MOM];
+    cluster_finish_body(nblocks, (size_t)nblocks, blockIdx.x, part, centers, stds, nullptr, s_m);
+}
+
 static bool moments_skip() {  // MIDAS_MOMENTS_SKIP=0: every cluster summed by every workgroup (the parity test's other side)
     static const bool on = !(getenv("MIDAS_MOMENTS_SKIP") && atoi(getenv("MIDAS_MOMENTS_SKIP")) == 0);
     return on;
@@ -435,6 +518,24 @@ int launch_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses, const 
                        label_values, (double*)part, moments_skip());
     hipLaunchKernelGGL(k_cluster_finish, dim3((unsigned)C), dim3(64), 0, ctx->stream, nb, (int)C, (const double*)part, centers,
                        stds, counts);
+    MIDAS_HIP_CHECK(ctx, hipGetLastError());
+    return MIDAS_OK;
+}
+
+int launch_pose_estimate(midas_ctx* ctx, int64_t N, int32_t B, const float* poses, const double* w64, const TailTables* tb,
+                         int64_t tstride, const uint8_t* valid, int32_t softmax, float* centers, float* stds) {
+    const int nb = (int)ceil_div(N, 256);
+    void* part;
+    int rc = midas_scratch(ctx, (size_t)B * nb * CL_MOM * sizeof(double), &part);
+    if (rc) return rc;
+    EstimateArgs a;
+    a.N = N; a.poses = poses; a.w64 = w64;
+    a.e = a.x_raw = a.bsum_e = a.bmax = a.bmin = nullptr;
+    if (tb) { a.e = tb->e; a.x_raw = tb->x_raw; a.bsum_e = tb->bsum_e; a.bmax = tb->bmax; a.bmin = tb->bmin; }
+    a.tstride = tstride; a.valid = valid; a.softmax = softmax; a.nbl = (int32_t)ceil_div(N, SCAN_BLOCK);
+    a.part = (double*)part;
+    hipLaunchKernelGGL(k_estimate_moments, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_estimate_finish, dim3((unsigned)B), dim3(256), 0, ctx->stream, nb, (const double*)part, centers, stds);
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
 }

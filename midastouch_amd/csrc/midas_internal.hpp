@@ -529,6 +529,11 @@ int launch_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses, const 
                            const int64_t* labels, int32_t C, const int64_t* label_values, float* centers, float* stds,
                            int64_t* counts);
 
+// the pose estimate of a fixed-N frame for B trajectories (midas_pose_estimate): weights w64 (B x N), or - nullptr - made from
+// the pipelined frame's table blocks tb (trajectory 0's, tstride doubles apart) and the valid mask
+int launch_pose_estimate(midas_ctx* ctx, int64_t N, int32_t B, const float* poses, const double* w64, const TailTables* tb,
+                         int64_t tstride, const uint8_t* valid, int32_t softmax, float* centers, float* stds);
+
 struct LoopWeightsArgs;  // loop_weights.hpp
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,

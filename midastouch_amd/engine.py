@@ -3,7 +3,8 @@
 `FilterEngine.step()` is the fast path behind the north-star aliases `step()/update_weights()/
 resample()` (midastouch_amd/filter.py): score codebook -> propagate -> feature -> NN -> gather score ->
 softmax -> prune -> CDF -> resample -> gather, all on the GPU with no host synchronisation
-(reference loop body: filter/filter.py:150-190, clustering/annealing excluded = fixed N).
+(reference loop body: filter/filter.py:150-190, clustering/annealing excluded = fixed N).  With `estimate=True` an engine also
+leaves the frame's pose estimate (filter.py:184-186 on the unclustered set: `eng.estimate`), one more C call behind the frame.
 
 Two random-draw modes:
   * parity mode  - the caller supplies the host draws of the reference (torch CPU mt19937:
@@ -21,7 +22,7 @@ import os
 import torch
 
 from . import _lib, ops
-from ._lib import LazyArgs, LazyFlushArgs, MidasError, StepArgs, _ptr
+from ._lib import EstimateArgs, LazyArgs, LazyFlushArgs, MidasError, StepArgs, _ptr
 
 
 EPOCH_LIMIT = 0x3FFFFFF0  # (bits 31:30 of a stamp count the frames a listed row went unused: csrc/midas_internal.hpp)
@@ -169,6 +170,40 @@ class _Engine:
         self.status = torch.zeros(bz + (2,), **i32)
         self.rmse = torch.zeros(bz + (2,), **f64)
 
+    # ---- per-frame pose estimate (estimate=True) -------------------------------------------------------
+    def _alloc_estimate(self, on):
+        """estimate=True: every frame leaves its pose estimate (filter/filter.py:184-186: the quaternion-mean centre and the
+        per-axis spread of the propagated particles under the masked pre-resample weights) by one midas_pose_estimate behind the
+        frame.  The output rows are allocated here, once; off, the engine holds nothing for it."""
+        self._estimate_on = bool(on)
+        if not on:
+            return
+        bz, d = self._lead[:-1], self.device
+        B = bz[0] if bz else 1
+        self._est_rows = (torch.zeros(bz + (4, 4), dtype=torch.float32, device=d), torch.zeros(bz + (3,), dtype=torch.float32, device=d))
+        self._est = self._est_rows  # what `estimate` returns: these rows, or the last rows of a run()'s log
+        a = EstimateArgs()
+        a.N, a.B = self.N, B
+        a.centers, a.stds = _ptr(self._est_rows[0]), _ptr(self._est_rows[1])
+        self._est_args = a
+        # the block partials of the moments come from the context's scratch: held before the first frame asks
+        self.ctx.call("midas_scratch_reserve", B * ((self.N + 255) // 256) * 36 * 8 + 256)
+
+    @property
+    def estimate(self):
+        """(centre (4,4), stds (3,)) - (B,4,4), (B,3) for a batch - float32 device tensors of the latest frame; no synchronisation
+        and, on the pipelined engines, no flush.  Needs estimate=True at construction."""
+        if not self._estimate_on:
+            raise MidasError("the engine was built without estimate=True")
+        return self._est
+
+    def _enqueue_estimate(self, poses_prop, weights=None, tables=None, valid=None):
+        a = self._est_args
+        a.poses_prop, a.weights, a.tables, a.valid = _ptr(poses_prop), _ptr(weights), _ptr(tables), _ptr(valid)
+        a.softmax = int(self.softmax)
+        self.ctx.check(self.ctx.lib.midas_pose_estimate(self.ctx.h, C.byref(a)))
+        self._est = self._est_rows
+
     # ---- state ----------------------------------------------------------------------------------
     def set_particles(self, poses):
         poses = torch.as_tensor(poses).to(self.device, torch.float32)
@@ -213,13 +248,15 @@ class _Engine:
         self._keep = (odom, code, gt, tn, rot, u)  # keep operands alive until the stream has consumed them
         self.ctx.bind_current_stream()
         self.ctx.check(call(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), *batch))
+        if self._estimate_on:
+            self._enqueue_estimate(self.poses_prop, weights=self.weights)
         self.hint, self.hint_next = self.hint_next, self.hint
         self.step_count += 1
 
 
 class FilterEngine(_Engine):
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, num_particles: int, *, sig_t=2e-4, sig_r=0.5,
-                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None):
+                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None, estimate: bool = False):
         N = int(num_particles)
         self._setup(cb_poses, cb_embeddings, mesh_vertices, device, (N,), sig_t, sig_r, pen_max, seed, softmax, resample)
         # 16 cumulative counters ([0], [1] = tree-search fallbacks); with MIDAS_ABLATE=4 (profiling) the kernel
@@ -228,6 +265,7 @@ class FilterEngine(_Engine):
         self.telemetry = torch.zeros(16 + extra, dtype=torch.int64, device=self.device)
         self._stamps = torch.zeros(self.K, dtype=torch.int32, device=self.device)
         self._alloc_state()
+        self._alloc_estimate(estimate)
 
     # ---- one frame ------------------------------------------------------------------------------
     def step(self, odom, code, gt=None, tn=None, rot=None, u=None, u32=-1.0, multiplier: float = 1.0):
@@ -384,6 +422,8 @@ class _FoldedResample:
         self._keep = (odom, code, gt, tn, rot, pu)
         self.ctx.bind_current_stream()
         self.ctx.check(self._lazy_step(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), *self._batch))
+        if self._estimate_on:  # from where the frame left its weights (the tables): nothing is materialised
+            self._enqueue_estimate(self._prop[cur ^ 1], tables=self._tables, valid=self._valid)
         self._draw = (None if u is None else (u if own_u else u.clone()), float(u32), self.step_count)
         self._draw_event = u_event
         self._rmse_last = self._rmse_frame
@@ -532,7 +572,15 @@ class PipelinedFilterEngine(_FoldedResample, FilterEngine):
         log = torch.empty((T, 3), dtype=torch.float64, device=d) if gts is not None else None
         self._keep = (odoms, codes, gts, log)
         self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_lazy_run(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), T, _ptr(log)))
+        if self._estimate_on:  # every frame's estimate, enqueued behind its tail inside the same call; fresh tensors like the log
+            ec = torch.empty((T, 4, 4), dtype=torch.float32, device=d)
+            es = torch.empty((T, 3), dtype=torch.float32, device=d)
+            self.ctx.check(self.ctx.lib.midas_lazy_run_estimate(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), T,
+                                                                _ptr(log), _ptr(ec), _ptr(es)))
+            self.estimate_log = (ec, es)
+            self._est = (ec[T - 1], es[T - 1])
+        else:
+            self.ctx.check(self.ctx.lib.midas_lazy_run(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), T, _ptr(log)))
         self.step_count += T
         if log is not None:
             self._rmse_last = log[T - 1]
@@ -561,7 +609,8 @@ class BatchFilterEngine(_Engine):
     """
 
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, batch: int, num_particles: int, *, sig_t=1e-4, sig_r=0.5,
-                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None, scores="auto"):
+                 pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None, scores="auto",
+                 estimate: bool = False):
         if scores not in ("auto", "dense_f64"):
             raise MidasError(f"scores must be 'auto' or 'dense_f64', got {scores!r}")
         B, N = int(batch), int(num_particles)
@@ -576,6 +625,7 @@ class BatchFilterEngine(_Engine):
             self.codebook.set_batch_precision("f64")
         self._stamps = torch.zeros((B, self.K), dtype=torch.int32, device=self.device) if self.sparse_scores else None
         self._alloc_state()
+        self._alloc_estimate(estimate)
 
     def seed_torch_streams(self, seeds, motion: bool = False, pieces: int = 0):
         """Trajectory b draws from the device replica of torch's CPU generator under torch.manual_seed(seeds[b]) - B seeded runs of

@@ -304,6 +304,26 @@ def cluster_centers(poses: torch.Tensor, weights: torch.Tensor, labels: torch.Te
     return centers, stds, counts
 
 
+def pose_estimate(poses_prop: torch.Tensor, weights: torch.Tensor):
+    """The per-frame pose estimate of B particle sets by one call (midas_pose_estimate; filter/filter.py:184-186 on a set nobody
+    has clustered): poses_prop (B,N,4,4), weights (B,N) -> (centres (B,4,4) f32, stds (B,3) f32).  Row b is bit for bit
+    `cluster_centers(poses_prop[b], weights[b], zeros(N), [0])[:2]` with float64 weights."""
+    if poses_prop.dim() != 4 or tuple(poses_prop.shape[2:]) != (4, 4) or tuple(weights.shape) != tuple(poses_prop.shape[:2]):
+        raise MidasError(f"pose_estimate: expected (B,N,4,4) poses and (B,N) weights, got {tuple(poses_prop.shape)} and {tuple(weights.shape)}")
+    poses = _poses(poses_prop)
+    dev = poses.device
+    ctx = _ctx(poses)
+    weights = weights.to(dev, torch.float64).contiguous()
+    B, N = int(poses.shape[0]), int(poses.shape[1])
+    centers = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+    stds = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    a = _lib.EstimateArgs()
+    a.N, a.B = N, B
+    a.poses_prop, a.weights, a.centers, a.stds = _ptr(poses), _ptr(weights), _ptr(centers), _ptr(stds)
+    ctx.call("midas_pose_estimate", C.byref(a))
+    return centers, stds
+
+
 def dbscan(poses: torch.Tensor, eps: float = 1e-2, min_samples: int = -1):
     """cluster_particles(method="euclidean") labels (particle_filter.py:208-217): DBSCAN of the translations on the device.
     min_samples < 0 -> N // 5.  Returns (labels int32 (N,), info int32 (2,) = [clusters, limit flag])."""
