@@ -737,6 +737,43 @@ int midas_shard_step(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb,
 int midas_shard_run(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                     const midas_shard_step_args* first, int32_t T);
 
+/* ---- pose estimate of a sharded frame --------------------------------------------------------------------------------
+ * The reference takes the filter's output every frame between the measurement update and the resample
+ * (filter/filter.py:184-186: get_cluster_centers(particles, "quat_avg")).  For the particle-sharded frame it is
+ * midas_pose_estimate's definition with "the trajectory" = ALL G * N propagated poses and masked pre-resample weights, the
+ * shards in rank order, and every rank ends up holding the same bits:
+ *   midas_shard_estimate_moments  (filter/filter.py:184-186) this rank's moment partials: 36 doubles per 256-particle block of
+ *       its own N particles (midas_pose_estimate's contributions, wave tree and wave order) from poses_prop_dev (N x 16,
+ *       16-byte aligned) and weights_dev (N doubles: what midas_shard_route_pack / midas_shard_tail_fin / the ROUTE phase
+ *       left) -> part_dev, ceil(N / 256) x 36 doubles owned by the caller, 16-byte aligned (it is exchanged, hence no
+ *       context scratch);
+ *   the caller gathers the partials of all ranks in rank order (G * ceil(N / 256) * 288 bytes arrive per frame and rank);
+ *   midas_shard_estimate_finish   (filter/filter.py:184-186) adds the nblocks = G * ceil(N / 256) gathered partials one after
+ *       the other in that order and closes them: center_dev 16 floats, stds_dev 3 floats.  part_all_dev 16-byte aligned.  The
+ *       additions and their order are those of midas_pose_estimate's finish, so on equal partials the bits are equal; the
+ *       kernel is built for thousands of blocks (one wave walks the chain, the others stream the partials through LDS).
+ * With N a multiple of 4096 the sharded frame equals the one-process frame of G * N particles bit for bit, the rank-ordered
+ * partials are that frame's blocks in order, and the result equals midas_pose_estimate's on it bit for bit.  Other N: "each
+ * rank's own blocks, ranks in order" - deterministic, equal on all ranks.  One launch each, no scratch.
+ * midas_shard_step_estimate (filter/filter.py:184-186): midas_shard_step with all four phases LOCAL | GATHER | ROUTE | UNPACK
+ * on the library's communicator, and between ROUTE and UNPACK the moments, an ncclAllGather of the partials (part_dev ->
+ * part_all_dev, G x ceil(N / 256) x 36 doubles) and the finish.  The moments read weights_dev, which the route kernel writes:
+ * they start when it ends (without FLAG that is when every rank's rows have arrived).
+ * midas_shard_run_estimate (filter/filter.py:184-186): midas_shard_run that leaves every frame's estimate: est_centers_dev
+ * T x 16, est_stds_dev T x 3, row f = frame f.  Frame f's estimate reads frame f's poses_prop and weights_dev before frame
+ * f + 1's front and route kernels rewrite them: everything is enqueued on the context's stream in that order, in every form
+ * (the folded unpack included).  Every rank issues its collectives in the same order (records, partials, records, ...).
+ * Like all midas_shard_* calls these are issued, never replayed from a captured graph (see midas_lazy_run). */
+int midas_shard_estimate_moments(midas_ctx* ctx, int64_t N, const float* poses_prop_dev, const double* weights_dev,
+                                 double* part_dev);
+int midas_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* part_all_dev, float* center_dev, float* stds_dev);
+int midas_shard_step_estimate(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6,
+                              const midas_tree* tree3, const midas_shard_step_args* args, double* part_dev, double* part_all_dev,
+                              float* center_dev, float* stds_dev);
+int midas_shard_run_estimate(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6,
+                             const midas_tree* tree3, const midas_shard_step_args* first, int32_t T, double* part_dev,
+                             double* part_all_dev, float* est_centers_dev, float* est_stds_dev);
+
 /* ---- the all_gather form of the exchange (every rank materialises its slice of the global CDF and gathers every
  * shard's packed block; G-1 times the bytes of the owner-side form, no read-back of counts) ---- */
 /* midas_shard_tail_fin: softmax applied unless softmax == 0 or |max x - min x| over r1_all <= 1e-8 (then e := x);

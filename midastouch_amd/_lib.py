@@ -290,6 +290,10 @@ SIGNATURES = {
     "midas_comm_all_gather": (C.c_int, [_P, _P, _P, _I64]),
     "midas_shard_step": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(ShardStepArgs), _I32]),
     "midas_shard_run": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(ShardStepArgs), _I32]),
+    "midas_shard_estimate_moments": (C.c_int, [_P, _I64, _P, _P, _P]),
+    "midas_shard_estimate_finish": (C.c_int, [_P, _I64, _P, _P, _P]),
+    "midas_shard_step_estimate": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(ShardStepArgs), _P, _P, _P, _P]),
+    "midas_shard_run_estimate": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(ShardStepArgs), _I32, _P, _P, _P, _P]),
     "midas_peer_alloc": (C.c_int, [_P, _I64, C.POINTER(C.c_void_p), _P]),
     "midas_peer_free": (C.c_int, [_P, _P]),
     "midas_peer_open": (C.c_int, [_P, _P, C.POINTER(C.c_void_p)]),

@@ -1169,10 +1169,21 @@ MIDAS_EXPORT int midas_peer_probe_check(midas_ctx* ctx, const void* inbox_dev, i
 struct midas_comm;
 extern "C" int midas_comm_all_gather(midas_comm* c, const void* send_dev, void* recv_dev, int64_t bytes);
 
+// The frame's pose estimate across the ranks (filter/filter.py:184-186; midas_shard_step_estimate / midas_shard_run_estimate)
+struct ShardEstimate {
+    double* part;      // ceil(N / 256) x 36: this rank's moment partials
+    double* part_all;  // G x the same, in rank order
+    float* center;     // 16 out
+    float* stds;       // 3 out
+};
+static int64_t estimate_blocks(int64_t N) { return ceil_div(N, (int64_t)256); }
+
 // from_inbox (midas_shard_run): the front takes its particles from the rows of the inbox (the previous frame ran without its
 // UNPACK phase; its route kernel ended with the inbox complete)
+// est: behind ROUTE (which leaves the masked weights in weights_dev) the rank's moment partials, their all_gather and the finish -
+// in front of UNPACK and of the next frame's front, which rewrites poses_prop
 static int shard_step_impl(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
-                           const midas_shard_step_args& s, int32_t phases, bool from_inbox = false) {
+                           const midas_shard_step_args& s, int32_t phases, bool from_inbox = false, const ShardEstimate* est = nullptr) {
     MIDAS_REQUIRE(ctx, phases != 0 && (phases & ~31) == 0);
     MIDAS_REQUIRE(ctx, s.front.N >= 256 && s.G >= 1 && s.G <= 64 && s.rank >= 0 && s.rank < s.G && s.tables_dev && s.r1_dev);
     MIDAS_REQUIRE(ctx, s.r1_all_dev || !(phases & (MIDAS_SHARD_PHASE_GATHER | MIDAS_SHARD_PHASE_ROUTE)));
@@ -1225,6 +1236,12 @@ static int shard_step_impl(midas_ctx* ctx, midas_comm* comm, const midas_codeboo
         if (phases & MIDAS_SHARD_PHASE_FLAG)  // shards of one process on one stream: the flags must be out before ANY shard waits
             if ((rc = launch_peer_flag_write(ctx, s.peers_dev, s.G, s.rank, s.flag_offset, s.frame_tag))) return rc;
     }
+    if (est) {
+        const int64_t nbm = estimate_blocks(N);
+        if ((rc = launch_shard_estimate_moments(ctx, N, s.front.poses_prop_dev, s.weights_dev, est->part))) return rc;
+        if ((rc = midas_comm_all_gather(comm, est->part, est->part_all, nbm * ESTIMATE_PART_DOUBLES * (int64_t)sizeof(double)))) return rc;
+        if ((rc = launch_shard_estimate_finish(ctx, s.G * nbm, est->part_all, est->center, est->stds))) return rc;
+    }
     if (phases & MIDAS_SHARD_PHASE_UNPACK) {  // inbox -> slots; with FLAG behind a wait for every rank's flag in the own inbox
         if (phases & MIDAS_SHARD_PHASE_FLAG)
             rc = launch_shard_unpack_peer_wait(ctx, N, s.inbox_dev, s.ridx_dev, s.poses_out_dev, s.weights_out_dev, s.hint_out_dev,
@@ -1243,9 +1260,57 @@ MIDAS_EXPORT int midas_shard_step(midas_ctx* ctx, midas_comm* comm, const midas_
     return shard_step_impl(ctx, comm, cb, tree6, tree3, *args, phases);
 }
 
+static bool shard_estimate_ok(const ShardEstimate& e) {
+    return e.part && e.part_all && e.center && e.stds && (uintptr_t)e.part % 16 == 0 && (uintptr_t)e.part_all % 16 == 0;
+}
+
+MIDAS_EXPORT int midas_shard_estimate_moments(midas_ctx* ctx, int64_t N, const float* poses_prop_dev, const double* weights_dev,
+                                              double* part_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, N > 0 && poses_prop_dev && weights_dev && part_dev && (uintptr_t)poses_prop_dev % 16 == 0 &&
+                           (uintptr_t)part_dev % 16 == 0);
+    return launch_shard_estimate_moments(ctx, N, poses_prop_dev, weights_dev, part_dev);
+}
+
+MIDAS_EXPORT int midas_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* part_all_dev, float* center_dev,
+                                             float* stds_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, nblocks > 0 && nblocks <= (int64_t)1 << 24 && part_all_dev && center_dev && stds_dev && (uintptr_t)part_all_dev % 16 == 0);
+    return launch_shard_estimate_finish(ctx, nblocks, part_all_dev, center_dev, stds_dev);
+}
+
+static const int32_t SHARD_WHOLE_FRAME = MIDAS_SHARD_PHASE_LOCAL | MIDAS_SHARD_PHASE_GATHER | MIDAS_SHARD_PHASE_ROUTE | MIDAS_SHARD_PHASE_UNPACK;
+
+MIDAS_EXPORT int midas_shard_step_estimate(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6,
+                                           const midas_tree* tree3, const midas_shard_step_args* args, double* part_dev,
+                                           double* part_all_dev, float* center_dev, float* stds_dev) {
+    MIDAS_ENTER(ctx);
+    const ShardEstimate est{part_dev, part_all_dev, center_dev, stds_dev};
+    MIDAS_REQUIRE(ctx, args != nullptr && comm != nullptr && shard_estimate_ok(est));
+    return shard_step_impl(ctx, comm, cb, tree6, tree3, *args, SHARD_WHOLE_FRAME, false, &est);
+}
+
+static int shard_run_impl(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                          const midas_shard_step_args* first, int32_t T, const ShardEstimate* est_log);
+
 MIDAS_EXPORT int midas_shard_run(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6,
                                  const midas_tree* tree3, const midas_shard_step_args* first, int32_t T) {
     MIDAS_ENTER(ctx);
+    return shard_run_impl(ctx, comm, cb, tree6, tree3, first, T, nullptr);
+}
+
+MIDAS_EXPORT int midas_shard_run_estimate(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6,
+                                          const midas_tree* tree3, const midas_shard_step_args* first, int32_t T, double* part_dev,
+                                          double* part_all_dev, float* est_centers_dev, float* est_stds_dev) {
+    MIDAS_ENTER(ctx);
+    const ShardEstimate est{part_dev, part_all_dev, est_centers_dev, est_stds_dev};
+    MIDAS_REQUIRE(ctx, shard_estimate_ok(est));
+    return shard_run_impl(ctx, comm, cb, tree6, tree3, first, T, &est);
+}
+
+// est_log: NULL, or the partial buffers and the T x 16 / T x 3 logs (row f: frame f's estimate)
+static int shard_run_impl(midas_ctx* ctx, midas_comm* comm, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                          const midas_shard_step_args* first, int32_t T, const ShardEstimate* est_log) {
     MIDAS_REQUIRE(ctx, first != nullptr && comm != nullptr && cb != nullptr && T >= 1);
     MIDAS_REQUIRE(ctx, !first->front.tn_dev && !first->front.rot_dev && !first->u_all_dev && !first->front.scores_ready);
     midas_shard_step_args a = *first;
@@ -1261,7 +1326,9 @@ MIDAS_EXPORT int midas_shard_run(midas_ctx* ctx, midas_comm* comm, const midas_c
         if (rc) return rc;
         const bool last = f == T - 1;
         const int32_t phases = MIDAS_SHARD_PHASE_LOCAL | MIDAS_SHARD_PHASE_GATHER | MIDAS_SHARD_PHASE_ROUTE | ((last || !fold) ? MIDAS_SHARD_PHASE_UNPACK : 0);
-        if ((rc = shard_step_impl(ctx, comm, cb, tree6, tree3, a, phases, fold && f > 0))) return rc;
+        ShardEstimate est;
+        if (est_log) est = ShardEstimate{est_log->part, est_log->part_all, est_log->center + 16 * (size_t)f, est_log->stds + 3 * (size_t)f};
+        if ((rc = shard_step_impl(ctx, comm, cb, tree6, tree3, a, phases, fold && f > 0, est_log ? &est : nullptr))) return rc;
         // next frame: the resampled particles are in poses_out / hint_out (= the front's inputs: the engine passes the same buffers)
         a.front.step += 1;
         a.frame_tag += 1;

@@ -485,6 +485,127 @@ __global__ __launch_bounds__(256) void k_estimate_finish(int nblocks, const doub
     cluster_finish_body(nblocks, (size_t)nblocks, blockIdx.x, part, centers, stds, nullptr, s_m);
 }
 
+// ---- sharded engine: the finish over the gathered partials of ALL ranks (midas_shard_estimate_finish) ------------------------
+// k_estimate_finish's interface and result on G * ceil(N / 256) blocks - thousands at the sizes the sharded engine is for (3907
+// at a million particles).  The additions and their order are cluster_finish_body's (r = block 0's value, then r = r + block b
+// for b = 1, 2, ...; the extrema by lanes that take every 64th block and meet in wave_max_dpp / wave_min_dpp; cluster_close), so
+// the bits are k_estimate_finish's on the same partials; what differs is who does what.  There every thread loads, stores to LDS
+// and meets two barriers a chunk, the walking lanes included; here the chain of dependent float64 additions is the only serial part:
+//   wave 0        the 36 lanes that carry the sums: they read the LDS window a batch ahead of the batch they add, nothing else;
+//   wave 1        the two extrema (no order), one block a lane and window;
+//   waves 2 .. 7  stream the partials (288 bytes a block): wave 2 + k % 6 holds window k in registers from SF_LOADERS windows
+//                 ahead and stores it into the half of the double-buffered LDS window the walkers are NOT reading.
+// One barrier a window of SF_CB blocks.  A loader's requests have six windows of walking (~384 blocks) to arrive.
+constexpr int SF_CB = 64;                         // blocks of one LDS window
+constexpr int SF_LOADERS = 6;                     // loader waves
+constexpr int SF_LD = SF_CB * CL_MOM / 2 / 64;    // 16-byte loads of a loader lane per window
+static_assert(SF_CB == 64, "the extrema wave takes one block a lane and window");
+static_assert(ESTIMATE_PART_DOUBLES == CL_MOM, "what the ranks exchange is a block's CL_MOM moments");
+
+typedef double sf_d2 __attribute__((ext_vector_type(2)));  // one 16-byte request
+// window k's partials -> registers (every request out before anything waits), and from there into a half of the LDS window
+MD void sf_issue(const double* __restrict__ pc, int nblocks, int k, int lane, sf_d2 (&x)[SF_LD]) {
+    const int nd2 = (nblocks - k * SF_CB < SF_CB ? nblocks - k * SF_CB : SF_CB) * (CL_MOM / 2);
+    const sf_d2* __restrict__ src = reinterpret_cast<const sf_d2*>(pc + (size_t)k * SF_CB * CL_MOM);
+#pragma unroll
+    for (int j = 0; j < SF_LD; ++j) {
+        const int i = lane + 64 * j;
+        x[j] = src[i < nd2 ? i : nd2 - 1];
+    }
+}
+MD void sf_store(double* win, int nblocks, int k, int lane, const sf_d2 (&x)[SF_LD]) {
+    const int nd2 = (nblocks - k * SF_CB < SF_CB ? nblocks - k * SF_CB : SF_CB) * (CL_MOM / 2);
+    sf_d2* dst = reinterpret_cast<sf_d2*>(win);
+#pragma unroll
+    for (int j = 0; j < SF_LD; ++j) {
+        const int i = lane + 64 * j;
+        if (i < nd2) dst[i] = x[j];
+    }
+}
+
+__global__ __launch_bounds__(64 * (2 + SF_LOADERS)) void k_shard_estimate_finish(int nblocks, const double* __restrict__ part,
+                                                                                float* __restrict__ centers, float* __restrict__ stds) {
+    __shared__ double s_m[CL_MOM];
+    __shared__ __attribute__((aligned(16))) double s_win[2][SF_CB * CL_MOM];
+    const int t = threadIdx.x, wv = t >> 6, lane = t & 63, lw = wv - 2;
+    const int nwin = (nblocks + SF_CB - 1) / SF_CB;
+    const double* __restrict__ pc = part + (size_t)blockIdx.x * nblocks * CL_MOM;
+    sf_d2 x[SF_LD];
+    auto issue = [&](int k) { sf_issue(pc, nblocks, k, lane, x); };
+    auto store = [&](int k) { sf_store(s_win[k & 1], nblocks, k, lane, x); };
+    if (lw >= 0 && lw < nwin) issue(lw);
+    if (lw == 0) {
+        store(0);
+        if (SF_LOADERS < nwin) issue(SF_LOADERS);
+    }
+    __syncthreads();
+    double r = 0.0, e_mx = -INFINITY, e_mn = INFINITY, e_first_mx = 0.0, e_first_mn = 0.0;
+    for (int c = 0; c < nwin; ++c) {
+        const int nb = nblocks - c * SF_CB < SF_CB ? nblocks - c * SF_CB : SF_CB;
+        const double* b = s_win[c & 1];
+        if (wv == 0) {
+            // the chain: one dependent addition a block.  Sixteen LDS reads are in flight while the sixteen before them are added;
+            // the last, partial batch reads clamped and adds under a wave-uniform count (no read waits inside the chain)
+            const double* bm = b + (lane < CL_MOM ? lane : 0);  // (lanes without a moment walk moment 0; nothing of theirs is kept)
+            int j = 0;
+            if (c == 0) { r = bm[0]; j = 1; }
+            double xa[16], xb[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { const int jj = j + i; xa[i] = bm[(jj < nb ? jj : nb - 1) * CL_MOM]; }
+            for (; j + 32 <= nb; j += 32) {  // (two batches a trip: the registers swap roles, nothing is copied)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { const int jj = j + 16 + i; xb[i] = bm[(jj < nb ? jj : nb - 1) * CL_MOM]; }
+#pragma unroll
+                for (int i = 0; i < 16; ++i) r = r + xa[i];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { const int jj = j + 32 + i; xa[i] = bm[(jj < nb ? jj : nb - 1) * CL_MOM]; }
+#pragma unroll
+                for (int i = 0; i < 16; ++i) r = r + xb[i];
+            }
+            if (j + 16 <= nb) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { const int jj = j + 16 + i; xb[i] = bm[(jj < nb ? jj : nb - 1) * CL_MOM]; }
+#pragma unroll
+                for (int i = 0; i < 16; ++i) r = r + xa[i];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) xa[i] = xb[i];
+                j += 16;
+            }
+            const int rem = nb - j;
+#pragma unroll
+            for (int i = 0; i < 15; ++i)
+                if (i < rem) r = r + xa[i];
+        } else if (wv == 1) {
+            // (cluster_finish_body's rule: NaN never wins a select, unless the FIRST block's value is NaN)
+            if (c == 0) { e_first_mx = b[M_WMAX]; e_first_mn = b[M_WMIN]; }
+            if (lane < nb) {
+                const double vx = b[lane * CL_MOM + M_WMAX], vy = b[lane * CL_MOM + M_WMIN];
+                e_mx = vx > e_mx ? vx : e_mx;
+                e_mn = vy < e_mn ? vy : e_mn;
+            }
+        } else {
+            const int k = c + 1;  // into the half nobody reads during this window
+            if (k < nwin && k % SF_LOADERS == lw) {
+                store(k);
+                if (k + SF_LOADERS < nwin) issue(k + SF_LOADERS);
+            }
+        }
+        __syncthreads();
+    }
+    if (wv == 1) {
+        const double mx = wave_max_dpp(e_mx), mn = wave_min_dpp(e_mn);
+        if (lane == 0) {
+            s_m[M_WMAX] = e_first_mx != e_first_mx ? e_first_mx : mx;
+            s_m[M_WMIN] = e_first_mn != e_first_mn ? e_first_mn : mn;
+        }
+    } else if (wv == 0 && lane < CL_MOM && lane != M_WMAX && lane != M_WMIN) {
+        s_m[lane] = r;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    cluster_close(s_m, centers + (size_t)blockIdx.x * 16, stds + (size_t)blockIdx.x * 3, nullptr, nullptr);
+}
+
 static bool moments_skip() {  // MIDAS_MOMENTS_SKIP=0: every cluster summed by every workgroup (the parity test's other side)
     static const bool on = !(getenv("MIDAS_MOMENTS_SKIP") && atoi(getenv("MIDAS_MOMENTS_SKIP")) == 0);
     return on;
@@ -536,6 +657,24 @@ int launch_pose_estimate(midas_ctx* ctx, int64_t N, int32_t B, const float* pose
     a.part = (double*)part;
     hipLaunchKernelGGL(k_estimate_moments, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(k_estimate_finish, dim3((unsigned)B), dim3(256), 0, ctx->stream, nb, (const double*)part, centers, stds);
+    MIDAS_HIP_CHECK(ctx, hipGetLastError());
+    return MIDAS_OK;
+}
+
+// sharded engine: the moment partials of this rank's blocks into a caller-owned buffer (it is exchanged), from the eager weights
+int launch_shard_estimate_moments(midas_ctx* ctx, int64_t N, const float* poses, const double* w64, double* part) {
+    EstimateArgs a;
+    a.N = N; a.poses = poses; a.w64 = w64;
+    a.e = a.x_raw = a.bsum_e = a.bmax = a.bmin = nullptr;
+    a.tstride = 0; a.valid = nullptr; a.softmax = 0; a.nbl = 0;
+    a.part = part;
+    hipLaunchKernelGGL(k_estimate_moments, dim3((unsigned)ceil_div(N, 256), 1), dim3(256), 0, ctx->stream, a);
+    MIDAS_HIP_CHECK(ctx, hipGetLastError());
+    return MIDAS_OK;
+}
+
+int launch_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* part_all, float* center, float* stds) {
+    hipLaunchKernelGGL(k_shard_estimate_finish, dim3(1), dim3(64 * (2 + SF_LOADERS)), 0, ctx->stream, (int)nblocks, part_all, center, stds);
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
 }

@@ -534,6 +534,12 @@ int launch_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses, const 
 int launch_pose_estimate(midas_ctx* ctx, int64_t N, int32_t B, const float* poses, const double* w64, const TailTables* tb,
                          int64_t tstride, const uint8_t* valid, int32_t softmax, float* centers, float* stds);
 
+// the sharded engine's estimate (midas_shard_estimate_*): this rank's ceil(N / 256) x 36 moment partials from its eager weights;
+// the finish over the partials of all ranks in rank order (nblocks = G * ceil(N / 256))
+constexpr int ESTIMATE_PART_DOUBLES = 36;  // doubles of one 256-particle block's partial (CL_MOM, cluster_rot.hpp)
+int launch_shard_estimate_moments(midas_ctx* ctx, int64_t N, const float* poses, const double* w64, double* part);
+int launch_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* part_all, float* center, float* stds);
+
 struct LoopWeightsArgs;  // loop_weights.hpp
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,

@@ -25,6 +25,10 @@ The float64 summation order is the single-GPU one (per-block totals are gathered
 them sequentially in global block order), so with N a multiple of 4096 the sharded run reproduces the
 single-GPU run of G*N particles bit for bit - same weights, same resample indices.
 
+estimate=True: the frame's pose estimate (filter/filter.py:184-186) of ALL particles on every rank - one more all_gather, of
+the per-rank moment partials (36 doubles per 256-particle block), added in rank order by every rank: the single-GPU estimate's
+block order, so with N a multiple of 4096 its bits (`ShardedFilterEngine.estimate`).
+
 The frame is written as a generator that yields at every exchange, so the same code runs under
 torch.distributed (`step`) and, for tests, as several shards of one process stepped in lock-step by
 `run_lockstep` (no collective library involved).  Compute goes through a backend object: the product
@@ -43,6 +47,7 @@ from ._lib import MidasError, ShardFrontArgs, ShardRouteArgs, TailResampleArgs, 
 from .engine import RESAMPLE_MODES, advance_epoch, check_motion_draws, codebook_index, frame_operands, operand, sparse_scoring
 
 BLOCK = 4096  # summation block of the CDF spec (csrc/resample.hip)
+EST_BLOCK, EST_MOM = 256, 36  # the estimate's moment partials: 36 doubles per 256-particle block (include/midas_hip.h)
 ROUTE_REC = 88  # bytes per routed particle row in the all_to_all forms (include/midas_hip.h)
 PEER_ROW = 128  # bytes per row of a peer-mapped inbox: one line, written by sixteen lanes (csrc/peer_row.hpp)
 
@@ -239,11 +244,37 @@ class HipShardBackend:
         a.ridx, a.poses_out, a.weights_out, a.hint_out = _ptr(st.ridx), _ptr(st.poses), _ptr(st.weights_res), _ptr(st.hint)
         return a
 
-    def step_c(self, st, a, comm_h, phases, T=None):
+    # ---- the frame's pose estimate across the ranks (filter/filter.py:184-186; include/midas_hip.h midas_shard_estimate_*) ----
+    def estimate_alloc(self, st, world):
+        """The partial tensor a rank exchanges (opaque to the engine: fixed size, float64) and where the result goes."""
+        st.est_part = torch.zeros(-(-st.N // EST_BLOCK) * EST_MOM, dtype=torch.float64, device=self.device)
+        st.est_center = torch.zeros((4, 4), dtype=torch.float32, device=self.device)
+        st.est_stds = torch.zeros((3,), dtype=torch.float32, device=self.device)
+        # receive buffer of the one-call forms (the library's communicator gathers into it): allocated here, no cold frame
+        st.est_part_all = torch.zeros(world * st.est_part.numel(), dtype=torch.float64, device=self.device)
+
+    def estimate_moments(self, st):
+        """This rank's moment partials, from `poses_prop` and the masked weights the exchange form has written -> the tensor to gather."""
+        self.ctx.call("midas_shard_estimate_moments", st.N, _ptr(st.poses_prop), _ptr(st.weights), _ptr(st.est_part))
+        return st.est_part
+
+    def estimate_finish(self, st, part_all, world):
+        """The partials of all ranks in rank order -> st.est_center / st.est_stds."""
+        self.ctx.call("midas_shard_estimate_finish", part_all.numel() // EST_MOM, _ptr(part_all), _ptr(st.est_center), _ptr(st.est_stds))
+
+    def step_c(self, st, a, comm_h, phases, T=None, est=None):
+        """est: None, or (centres, spreads) - the frame's estimate(s) by the `_estimate` entries (all four phases, a communicator)."""
         if self._sparse and (phases & 1):
             a.front.score_epoch = advance_epoch(st, 1 if T is None else T)
         self.ctx.bind_current_stream()
-        if T is None:
+        if est is not None:
+            tail = (_ptr(st.est_part), _ptr(st.est_part_all), _ptr(est[0]), _ptr(est[1]))
+            head = (self.ctx.h, comm_h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a))
+            if T is None:
+                self.ctx.check(self.ctx.lib.midas_shard_step_estimate(*head, *tail))
+            else:
+                self.ctx.check(self.ctx.lib.midas_shard_run_estimate(*head, int(T), *tail))
+        elif T is None:
             self.ctx.check(self.ctx.lib.midas_shard_step(self.ctx.h, comm_h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(phases)))
         else:
             self.ctx.check(self.ctx.lib.midas_shard_run(self.ctx.h, comm_h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(T)))
@@ -287,7 +318,7 @@ class HipShardBackend:
 class ShardState:
     """Per-shard tensors (allocated through the backend so tests can keep them on the CPU)."""
 
-    def __init__(self, backend, N, slot_base, K):
+    def __init__(self, backend, N, slot_base, K, estimate=False, world=1):
         e = backend.empty
         self.N, self.slot_base = int(N), int(slot_base)
         self.nb = (self.N + BLOCK - 1) // BLOCK
@@ -323,6 +354,8 @@ class ShardState:
         self.sync = e((1,), torch.int32)            # what the ranks gather as a barrier (peer-mapped exchange)
         self.sync.zero_()
         self._inbox = self._peers = None
+        if estimate:  # est_part (what a rank exchanges), est_center (4,4), est_stds (3,): the backend's own layout
+            backend.estimate_alloc(self, world)
 
 
 class TorchDistComm:
@@ -395,7 +428,8 @@ class SingleComm:
 class ShardedFilterEngine:
     def __init__(self, cb_poses=None, cb_embeddings=None, mesh_vertices=None, num_particles: int = 0, *, sig_t=2e-4,
                  sig_r=0.5, pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", device=None,
-                 comm=None, backend=None, rank=None, world=None, shard_codebook_rows=False, exchange="auto"):
+                 comm=None, backend=None, rank=None, world=None, shard_codebook_rows=False, exchange="auto",
+                 estimate: bool = False):
         if comm is None:
             import torch.distributed as dist
 
@@ -409,7 +443,17 @@ class ShardedFilterEngine:
         self.backend = backend
         self.N = int(num_particles)
         self.N_total = self.N * self.world
-        self.st = ShardState(self.backend, self.N, self.rank * self.N, self.backend.K)
+        # estimate=True: every frame leaves, on every rank, the pose estimate of ALL N_total particles (filter/filter.py:184-186:
+        # quaternion-mean centre and per-axis spread of the propagated poses under the masked pre-resample weights): the ranks
+        # exchange their moment partials, every rank adds them in rank order (`estimate`).  Off: nothing allocated or exchanged.
+        self._estimate_on = bool(estimate)
+        if self._estimate_on:
+            if not hasattr(self.backend, "estimate_moments"):
+                raise MidasError("estimate=True: the backend has no estimate_moments / estimate_finish")
+            self.st = ShardState(self.backend, self.N, self.rank * self.N, self.backend.K, estimate=True, world=self.world)
+            self._est = (self.st.est_center, self.st.est_stds)
+        else:
+            self.st = ShardState(self.backend, self.N, self.rank * self.N, self.backend.K)
         self.sig_t, self.sig_r, self.pen_max = float(sig_t), float(sig_r), float(pen_max)
         self.seed, self.softmax = int(seed), bool(softmax)
         self.mode = RESAMPLE_MODES[resample]
@@ -505,8 +549,33 @@ class ShardedFilterEngine:
         odoms, codes, gts = frame_operands(self.st.poses.device, (T,), int(self.backend.D), odoms, codes, gts)
         self._keep = (odoms, codes, gts)
         a = self._c_args(odoms, codes, gts, None, -1.0, 1.0, self._r1_all_buf(), frames=T)
-        self.backend.step_c(self.st, a, self._ccomm, 15, T=T)
+        if self._estimate_on:  # every frame's estimate inside the same call; fresh tensors per call, like PipelinedFilterEngine.run
+            d = self.st.poses.device
+            log = (torch.empty((T, 4, 4), dtype=torch.float32, device=d), torch.empty((T, 3), dtype=torch.float32, device=d))
+            self.backend.step_c(self.st, a, self._ccomm, 15, T=T, est=log)
+            self.estimate_log = log
+            self._est = (log[0][T - 1], log[1][T - 1])
+        else:
+            self.backend.step_c(self.st, a, self._ccomm, 15, T=T)
         self.step_count += T
+
+    @property
+    def estimate(self):
+        """(centre (4,4), spreads (3,)) of the latest frame: float32 device tensors, the same bits on every rank, written behind
+        the frame on its stream - reading them synchronises nothing and looks at no overflow check.  After run(): the last row
+        of `estimate_log`.  Needs estimate=True at construction."""
+        if not self._estimate_on:
+            raise MidasError("the engine was built without estimate=True")
+        return self._est
+
+    def _estimate_gen(self):
+        """The estimate of the frame just computed, as one more exchange: `poses_prop` and the masked `weights` are this frame's
+        until the next front, in every exchange form."""
+        st, b = self.st, self.backend
+        part_all = yield b.estimate_moments(st)
+        self._keep = self._keep + (part_all,)
+        b.estimate_finish(st, part_all, self.world)
+        self._est = (st.est_center, st.est_stds)
 
     def connect_peers(self) -> bool:
         """Collective: allocate this rank's inbox, swap the interprocess handles, map the others' inboxes, run the self test
@@ -658,7 +727,10 @@ class ShardedFilterEngine:
             if st._peers is None:
                 raise MidasError("peer-mapped exchange: the inboxes are not connected (connect_peers / connect_local_peers)")
             if self._ccomm is not None:  # kernels, RCCL all_gather of the records, flags, unpack: one call
-                b.step_c(st, self._c_args(odom, code, gt, u, u32, mul, self._r1_all_buf()), self._ccomm, 15)
+                if self._estimate_on:    # ... and, between route and unpack, the moments, their all_gather and the finish
+                    self._est = (st.est_center, st.est_stds)
+                b.step_c(st, self._c_args(odom, code, gt, u, u32, mul, self._r1_all_buf()), self._ccomm, 15,
+                         est=self._est if self._estimate_on else None)
             else:                        # no RCCL between the ranks: the record gather goes through `comm`
                 a = self._c_args(odom, code, gt, u, u32, mul, None)
                 b.step_c(st, a, None, 1)
@@ -671,6 +743,8 @@ class ShardedFilterEngine:
                     b.step_c(st, a, None, 8 | 16)
                 else:
                     b.step_c(st, a, None, 12)
+                if self._estimate_on:  # split phases: the partials travel like the records
+                    yield from self._estimate_gen()
             self.step_count += 1
             return
         ready = False
@@ -706,6 +780,8 @@ class ShardedFilterEngine:
             pack_all = yield st.pack
             u_loc = None if u is None else u[self.rank * self.N:(self.rank + 1) * self.N]
             b.tail_resample(st, pack_all, self.N_total, self.mode, u_loc, u32, self.seed, self.step_count)
+        if self._estimate_on:  # every form has written st.weights by now and none has touched poses_prop since the front
+            yield from self._estimate_gen()
         self.step_count += 1
 
     def _exchange(self, msg):

@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """What the per-frame pose estimate of the fixed-N engines costs (`estimate=True`, midas_pose_estimate / midas_lazy_run_estimate).
 
-Two workloads:
+Workloads:
   c2  PipelinedFilterEngine, N = 100 000 particles, K = 50 000 x D = 512 (the headline of bench.py);
-  c5  PipelinedBatchFilterEngine, B = 64 trajectories x N = 10 000, cotter pin 50k x 512 (BASELINE config 5).
+  c5  PipelinedBatchFilterEngine, B = 64 trajectories x N = 10 000, cotter pin 50k x 512 (BASELINE config 5);
+  s2  ShardedFilterEngine at c2's size on ONE GPU: world 1 under a one-rank nccl group, exchange "peer_c" (the whole frame by one
+      C call on the library's communicator), step() and run().  Column c is the only route a caller had before the keyword:
+      all_gather of poses_prop and weights over the group, then one ops.cluster_centers.  (`--configs s2` only: not in the default.)
+  finish  no timing of its own: `--frames` launches of the fixed-N finish (ops.pose_estimate) and of the sharded engine's finish
+      (midas_shard_estimate_moments / _finish) on one trajectory of 1 000 000, 100 000 and 10 240 particles (3907, 391 and 40
+      blocks) - to be run under `rocprofv3 --kernel-trace --stats`, which gives the kernels' own times.
 Three columns, us per (batch) frame over `--frames` frames after `--warmup`, device events around the whole run as bench.py
 takes them, median of `--repeats` with min / max, the columns interleaved inside every repeat:
   a  estimate=False;
@@ -48,6 +54,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--finish-sizes", default="1000000,100000,10240", help="particle counts of the `finish` workload (one per profiled run keeps the kernels' statistics apart)")
     ap.add_argument("--out", help="also write the result as JSON to this file")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.package_root))
@@ -73,9 +80,9 @@ def main():
             for b in range(pp.shape[0]):
                 ops.cluster_centers(pp[b], w[b], zeros, lab0)
 
-    def measure(name, engines, start, step, runner=None):
+    def measure(name, engines, start, step, runner=None, today=today):
         """engines: column -> engine; start(eng): the particle set of a repeat; step(eng, i): frame i; runner(eng, i0, n): n frames
-        by one call."""
+        by one call; today(eng, zeros): column c's extra work per frame."""
         zeros = torch.zeros(next(iter(engines.values())).N, dtype=torch.int64, device=dev)
         us = {}
         for rep in range(args.repeats):
@@ -136,6 +143,54 @@ def main():
             eng.project_to_codebook()
 
         measure("c5", engines, start5, lambda eng, i: eng.step(od[1 + i], co[1 + i]))
+    if "s2" in args.configs.split(","):
+        import torch.distributed as dist
+
+        from midastouch_amd.dist import ShardedFilterEngine
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if "MASTER_PORT" not in os.environ:  # a free port of this host
+            import socket
+            with socket.socket() as sock:
+                sock.bind(("127.0.0.1", 0))
+                os.environ["MASTER_PORT"] = str(sock.getsockname()[1])
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+        N, K, D = 100_000, 50_000, 512
+        cb = make_codebook("004_sugar_box", K=K, D=D, seed=1001)
+        traj = make_trajectory(cb, T=W + F + 2, seed=2001)
+        od, co, gt = (torch.as_tensor(x).to(dev) for x in (traj.odoms, traj.codes, traj.gt_poses))
+        p0 = torch.as_tensor(wide_start(cb.extents, traj.gt_poses[0], N, 100))
+        engines = build(ShardedFilterEngine, cb.poses, cb.embeddings, cb.mesh_vertices, N, seed=4000, device=dev, exchange="peer_c")
+        def start_s(eng):
+            eng.set_particles(p0)
+            eng.project_to_codebook()
+
+        def today_s(eng, zeros):  # today's route: gather every rank's particles and weights, then the cluster-centre call
+            ops.cluster_centers(eng.comm.all_gather(eng.poses_prop), eng.comm.all_gather(eng.weights), zeros, lab0)
+
+        measure("s2", engines, start_s, lambda eng, i: eng.step(od[1 + i], co[1 + i], gt=gt[1 + i]),
+                lambda eng, i0, n: eng.run(od[1 + i0:1 + i0 + n], co[1 + i0:1 + i0 + n], gt[1 + i0:1 + i0 + n]), today=today_s)
+        for eng in engines.values():
+            eng.close()
+        del engines
+        dist.destroy_process_group()
+    if "finish" in args.configs.split(","):
+        from midastouch_amd import _lib
+        ctx = _lib.context(dev)
+        g = torch.Generator().manual_seed(5)
+        for N in (int(v) for v in args.finish_sizes.split(",")):
+            P = torch.eye(4).repeat(N, 1, 1)
+            P[:, :3, 3] = 0.05 * torch.randn(N, 3, generator=g)
+            P, w = P.to(dev).contiguous(), torch.rand(N, dtype=torch.float64, generator=g).to(dev)
+            nb = -(-N // 256)
+            part = torch.empty(nb * 36, dtype=torch.float64, device=dev)
+            c, s = torch.empty((4, 4), dtype=torch.float32, device=dev), torch.empty(3, dtype=torch.float32, device=dev)
+            for _ in range(W + F):
+                old = ops.pose_estimate(P[None], w[None])
+                ctx.call("midas_shard_estimate_moments", N, _lib._ptr(P), _lib._ptr(w), _lib._ptr(part))
+                ctx.call("midas_shard_estimate_finish", nb, _lib._ptr(part), _lib._ptr(c), _lib._ptr(s))
+            torch.cuda.synchronize()
+            result.setdefault("finish", {})[str(nb)] = {"equal": bool(torch.equal(old[0][0], c) and torch.equal(old[1][0], s))}
+            print(f"finish {nb} blocks: launched {W + F} pairs, results equal: {result['finish'][str(nb)]['equal']}", flush=True)
     gc.enable()
     print(json.dumps(result), flush=True)
     if args.out:
