@@ -237,6 +237,34 @@ int midas_mt19937_draws(midas_ctx* ctx, uint32_t* state_dev, int64_t skip_words,
 int midas_mt19937_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* states_dev, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs,
                               const float* radius_dev, const float* cos_dev, const float* sin_dev, uint32_t* hist_dev,
                               const uint32_t* polys_dev, int32_t pieces);
+/* midas_mt19937_draws whose draw sizes stand in DEVICE memory - the reference's own loop, where annealing changes the particle
+ * count every frame: torch.normal(0, std, (n, 3)) twice with n the live count (add_noise_to_odom, modules/particle_filter.py:326-335)
+ * and n_set float64 uniforms with n_set the annealed count (the resampler, :245).  The host enqueues the call without knowing either.
+ *   count_dev  one device integer, read when the kernels run; the segment draws numel = per x count values (per = 3 for an (n, 3)
+ *              normal, 1 for n uniforms);
+ *   bound      host-known upper bound of the count: sizes the scratch and the grids, nothing else (out_dev holds per x bound values);
+ *   mean / std / out_dev as midas_mt_segment; kind MIDAS_MT_SEGMENT_RAND64 or MIDAS_MT_SEGMENT_NORMAL32.
+ * For the counts found there the call is midas_mt19937_draws with those counts, number for number: the outputs, the state afterwards
+ * and the words consumed (skip_words, then 2 per float64, numel (+ 16 when numel is not a multiple of 16) per normal draw).  A segment
+ * whose count is 0 consumes and writes nothing; output elements at or beyond numel are not written.
+ * status_dev (one int32 the caller zeroes; bits are OR-ed in): when a count is negative or exceeds its bound
+ * (MIDAS_MT_STATUS_COUNT_RANGE), or a normal segment has 0 < numel < 16 (MIDAS_MT_STATUS_NORMAL_SHORT: ATen's scalar path, not
+ * modelled), the call consumes nothing - skip_words included - and writes nothing but these bits.
+ * The sequential walk only (one workgroup, its block loop runs to the words the device counts ask for, not to the bounds): the call
+ * neither reads nor leaves a jump history.  Scratch: (sum over the segments of their words at the bound (normals: + 16) + 1872) x 4 bytes. */
+#define MIDAS_MT_STATUS_COUNT_RANGE 1
+#define MIDAS_MT_STATUS_NORMAL_SHORT 2
+typedef struct midas_mt_counted_segment {
+    int32_t kind;
+    int32_t per;
+    const int32_t* count_dev;
+    int64_t bound;
+    float mean, std;
+    void* out_dev;
+} midas_mt_counted_segment;
+int midas_mt19937_draws_counted(midas_ctx* ctx, uint32_t* state_dev, int64_t skip_words, int32_t nseg,
+                                const midas_mt_counted_segment* segs, const float* radius_dev, const float* cos_dev,
+                                const float* sin_dev, int32_t* status_dev);
 
 /* ---- resample  (K6, K7, K8) ------------------------------------------------------------------ */
 /* cdf = blocked_prefix(w) / total, cdf[N-1] = 1 (float64, fixed summation order - DESIGN.md).

@@ -175,6 +175,16 @@ class MtSegment(C.Structure):
 MT_SEGMENT_RAND64, MT_SEGMENT_NORMAL32 = 0, 1
 
 
+class MtCountedSegment(C.Structure):
+    """midas_mt_counted_segment (include/midas_hip.h): one draw of a midas_mt19937_draws_counted call."""
+
+    _fields_ = [("kind", C.c_int32), ("per", C.c_int32), ("count_dev", C.c_void_p), ("bound", C.c_int64), ("mean", C.c_float),
+                ("std", C.c_float), ("out_dev", C.c_void_p)]
+
+
+MT_STATUS_COUNT_RANGE, MT_STATUS_NORMAL_SHORT = 1, 2  # MIDAS_MT_STATUS_*
+
+
 class LoopArgs(C.Structure):
     """midas_loop_args (include/midas_hip.h)."""
 
@@ -245,6 +255,7 @@ SIGNATURES = {
     "midas_mt19937_normal32": (C.c_int, [_P, _P, _I64, _I64, _F, _F, _P, _P, _P, _P, _P, _P, _I32]),
     "midas_mt19937_draws": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I32]),
     "midas_mt19937_draws_batch": (C.c_int, [_P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I32]),
+    "midas_mt19937_draws_counted": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
     "midas_resample_search": (C.c_int, [_P, _I64, _P, _I64, _I32, _P, _F, _U64, _U64, _P]),
     "midas_gather_rows": (C.c_int, [_P, _I64, _P, _P, _P, _I32]),
     "midas_rmse": (C.c_int, [_P, _I64, _P, _P, _P]),

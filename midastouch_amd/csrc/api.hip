@@ -479,6 +479,20 @@ MIDAS_EXPORT int midas_mt19937_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* 
                                  chunked ? polys_dev : nullptr, chunked ? pieces : 0);
 }
 
+MIDAS_EXPORT int midas_mt19937_draws_counted(midas_ctx* ctx, uint32_t* state_dev, int64_t skip_words, int32_t nseg,
+                                             const midas_mt_counted_segment* segs, const float* radius_dev, const float* cos_dev,
+                                             const float* sin_dev, int32_t* status_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, state_dev != nullptr && skip_words >= 0 && nseg >= 1 && nseg <= 8 && segs != nullptr && status_dev != nullptr);
+    for (int i = 0; i < nseg; ++i) {
+        const midas_mt_counted_segment& g = segs[i];
+        MIDAS_REQUIRE(ctx, g.kind == MIDAS_MT_SEGMENT_RAND64 || (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && radius_dev && cos_dev && sin_dev));
+        // (the grids and the scratch are sized by per x bound: up to 2^31 - 1 values a segment)
+        MIDAS_REQUIRE(ctx, g.count_dev != nullptr && g.per >= 1 && g.bound >= 0 && g.bound <= 0x7fffffff / g.per && (g.bound == 0 || g.out_dev));
+    }
+    return launch_mt_draws_counted(ctx, state_dev, skip_words, nseg, segs, radius_dev, cos_dev, sin_dev, status_dev);
+}
+
 MIDAS_EXPORT int midas_resample_search(midas_ctx* ctx, int64_t N, const double* cdf_dev, int64_t M, int32_t mode,
                                        const double* u_dev, float u32, uint64_t seed, uint64_t step, int32_t* idx_dev) {
     MIDAS_ENTER(ctx);

@@ -568,6 +568,8 @@ int launch_mt_normal32(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int6
                        const float* S, float* out, uint32_t* hist, const uint32_t* polys, int32_t G);
 int launch_mt_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs,
                           const float* R, const float* C, const float* S, uint32_t* hist, const uint32_t* polys, int32_t G);
+int launch_mt_draws_counted(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_counted_segment* segs,
+                            const float* R, const float* C, const float* S, int32_t* status);
 
 // topn.hip
 int launch_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores, int64_t row0, int32_t n,

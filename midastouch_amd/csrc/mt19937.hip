@@ -63,13 +63,11 @@ __device__ __forceinline__ uint32_t mt_twist(uint32_t a, uint32_t b) {
 // and hands out the last nwords of them: raw[(b - b0) * 624 + k] for the blocks b >= b0 = (pos + skip) / 624, meta[0] = the
 // offset of the first wanted word in raw.  Several streams (midas_mt19937_draws_batch): workgroup b walks state row b (MT_N + 2 words)
 // into raw + b raw_stride, meta[b].
-__global__ __launch_bounds__(MT_THREADS) void k_mt_blocks(uint32_t* __restrict__ state, long long skip, long long nwords,
-                                                          uint32_t* __restrict__ raw, int32_t* __restrict__ meta, long long raw_stride = 0) {
+// (a function: k_mt_counted's workgroup walks the same way, with skip and nwords it has read from device memory)
+__device__ __forceinline__ void mt_walk(uint32_t* __restrict__ state, long long skip, long long nwords, uint32_t* __restrict__ raw,
+                                        int32_t* __restrict__ meta) {
     __shared__ uint32_t s_mt[2][MT_N];
     const int c = threadIdx.x;
-    state += (size_t)blockIdx.x * (MT_N + 2);
-    if (raw) raw += (size_t)blockIdx.x * raw_stride;
-    if (meta) meta += blockIdx.x;
     for (int k = c; k < MT_N; k += MT_THREADS) s_mt[0][k] = state[k];
     const long long pos = (long long)state[MT_N];
     const long long w0 = pos + skip, e = w0 + nwords;
@@ -126,8 +124,20 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_blocks(uint32_t* __restrict__
     if (c == 0) state[MT_N] = (uint32_t)(e - bl * MT_N);
 }
 
+__global__ __launch_bounds__(MT_THREADS) void k_mt_blocks(uint32_t* __restrict__ state, long long skip, long long nwords,
+                                                          uint32_t* __restrict__ raw, int32_t* __restrict__ meta, long long raw_stride = 0) {
+    state += (size_t)blockIdx.x * (MT_N + 2);
+    if (raw) raw += (size_t)blockIdx.x * raw_stride;
+    if (meta) meta += blockIdx.x;
+    mt_walk(state, skip, nwords, raw, meta);
+}
+
 // 2 N words -> N doubles: (hi << 32 | lo) & (2^53 - 1), times 2^-53 (at::uniform_real_distribution<double>); hi = the first word.
 // hist (nullable): the first MT_HIST of the raw words are kept for the next call's jump (k_mt_jump).
+__device__ __forceinline__ double mt_u53(uint32_t w0, uint32_t w1) {
+    const unsigned long long r = (((unsigned long long)mt_temper(w0) << 32) | mt_temper(w1)) & ((1ull << 53) - 1ull);
+    return (double)r * 1.1102230246251565e-16;
+}
 constexpr int MT_DEG = 19937;
 constexpr int MT_HIST = MT_DEG + MT_N - 1;  // x[k + i], k < 624, i < 19937
 static_assert(MT_HIST == MIDAS_MT19937_HIST_WORDS, "include/midas_hip.h");
@@ -142,8 +152,7 @@ __global__ __launch_bounds__(256) void k_mt_emit(const uint32_t* __restrict__ ra
     if (hist) hist += (size_t)blockIdx.y * MT_HIST;
     const uint32_t* w = raw + (meta ? meta[0] : 0) + off + 2 * i;  // off: the segment's first word (midas_mt19937_draws)
     const uint32_t w0 = w[0], w1 = w[1];
-    const unsigned long long r = (((unsigned long long)mt_temper(w0) << 32) | mt_temper(w1)) & ((1ull << 53) - 1ull);
-    out[i] = (double)r * 1.1102230246251565e-16;
+    out[i] = mt_u53(w0, w1);
     if (hist) {
         if (2 * i < MT_HIST) hist[2 * i] = w0;
         if (2 * i + 1 < MT_HIST) hist[2 * i + 1] = w1;
@@ -292,6 +301,16 @@ int launch_mt_seed(midas_ctx* ctx, uint64_t seed, uint32_t* state) {
 // cos / sin are TABLES over the 2^24 values a float32 uniform takes, read off torch.normal itself on the host
 // (midastouch_amd/torch_normal.py): bit-identical to whatever math library ATen dispatches to.
 constexpr uint32_t MT_U24 = (1u << 24) - 1u;
+// value i of a draw of numel (>= 16) values whose words start at w
+__device__ __forceinline__ float mt_normal_value(const uint32_t* __restrict__ w, long long numel, long long i, const float* __restrict__ R,
+                                                 const float* __restrict__ C, const float* __restrict__ S, float mean, float std) {
+    const bool tail = (numel & 15) && i >= numel - 16;        // redrawn from the sixteen words behind the first numel
+    const long long base = tail ? numel : (i & ~15ll);
+    const int j = (int)(tail ? i - (numel - 16) : (i & 15));
+    const uint32_t k1 = mt_temper(w[base + (j & 7)]) & MT_U24, k2 = mt_temper(w[base + 8 + (j & 7)]) & MT_U24;
+    const float n = R[k1] * (j < 8 ? C[k2] : S[k2]);
+    return __builtin_fmaf(n, std, mean);
+}
 __global__ __launch_bounds__(256) void k_mt_normal(const uint32_t* __restrict__ raw, const int32_t* __restrict__ meta, long long numel, long long nwords,
                                                    const float* __restrict__ R, const float* __restrict__ C, const float* __restrict__ S,
                                                    float mean, float std, float* __restrict__ out, uint32_t* __restrict__ hist, long long off = 0,
@@ -303,12 +322,7 @@ __global__ __launch_bounds__(256) void k_mt_normal(const uint32_t* __restrict__ 
     const uint32_t* w = raw + (size_t)blockIdx.y * raw_stride + (meta ? meta[0] : 0) + off;
     if (hist && i < MT_HIST && i < nwords) hist[i] = w[i];
     if (i >= numel) return;
-    const bool tail = (numel & 15) && i >= numel - 16;        // redrawn from the sixteen words behind the first numel
-    const long long base = tail ? numel : (i & ~15ll);
-    const int j = (int)(tail ? i - (numel - 16) : (i & 15));
-    const uint32_t k1 = mt_temper(w[base + (j & 7)]) & MT_U24, k2 = mt_temper(w[base + 8 + (j & 7)]) & MT_U24;
-    const float n = R[k1] * (j < 8 ? C[k2] : S[k2]);
-    out[i] = __builtin_fmaf(n, std, mean);
+    out[i] = mt_normal_value(w, numel, i, R, C, S, mean, std);
 }
 
 // The words of a call: sequential walk (k_mt_blocks; raw + meta offset) or in pieces (k_mt_jump + k_mt_chunks; offset 0, meta null).
@@ -453,6 +467,109 @@ int launch_mt_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t sk
 int launch_mt_draws(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_segment* segs, const float* R,
                     const float* C, const float* S, uint32_t* hist, const uint32_t* polys, int32_t G) {
     return launch_mt_draws_batch(ctx, 1, state, skip_words, nseg, segs, R, C, S, hist, polys, G);
+}
+
+// ---- draws whose sizes stand in device memory (midas_mt19937_draws_counted) ---------------------------------------------------
+// The reference's own loop: annealing changes the particle count every frame, so the (n, 3) normals and the n_set uniforms of a frame
+// (particle_filter.py:326-335, :245) have sizes only the device knows when the frame is enqueued.  The walking workgroup reads the
+// counts, leaves what the transforms need in meta - [0] the offset of the first wanted word in raw, [1 + 2 i] segment i's numel,
+// [2 + 2 i] its first word behind that offset - and walks the words those counts ask for; the transforms' grids are sized by the
+// bounds, a workgroup beyond the live numel returns after one load.  A count outside [0, bound] or a normal draw of 1 .. 15 values
+// sets its status bit; every numel in meta is then 0 and the state stays as it is.
+struct mt_counted_segs {
+    const int32_t* count[8];
+    long long bound[8];
+    int32_t per[8], kind[8];
+    int32_t nseg;
+};
+constexpr int MT_COUNTED_META = 1 + 2 * 8;
+
+__global__ __launch_bounds__(MT_THREADS) void k_mt_counted(uint32_t* __restrict__ state, long long skip, mt_counted_segs a,
+                                                           uint32_t* __restrict__ raw, long long* __restrict__ meta,
+                                                           int32_t* __restrict__ status) {
+    long long numel[8], total = 0;
+    int bad = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        numel[i] = 0;
+        if (i < a.nseg) {
+            const long long cnt = *a.count[i];
+            if (cnt < 0 || cnt > a.bound[i]) bad |= MIDAS_MT_STATUS_COUNT_RANGE;
+            numel[i] = cnt * a.per[i];
+            if (a.kind[i] == MIDAS_MT_SEGMENT_NORMAL32 && numel[i] > 0 && numel[i] < 16) bad |= MIDAS_MT_STATUS_NORMAL_SHORT;
+        }
+    }
+    if (threadIdx.x == 0) {
+        meta[0] = (long long)(((long long)state[MT_N] + skip) % MT_N);
+        if (bad) atomicOr(status, bad);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const long long n = bad ? 0 : numel[i];
+        if (threadIdx.x == 0) {
+            meta[1 + 2 * i] = n;
+            meta[2 + 2 * i] = total;
+        }
+        total += a.kind[i] == MIDAS_MT_SEGMENT_RAND64 ? 2 * n : n + ((n & 15) ? 16 : 0);
+    }
+    if (bad) return;  // (uniform)
+    mt_walk(state, skip, total, raw, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_mt_emit_counted(const uint32_t* __restrict__ raw, const long long* __restrict__ meta, int seg,
+                                                         double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= meta[1 + 2 * seg]) return;
+    const uint32_t* w = raw + meta[0] + meta[2 + 2 * seg] + 2 * i;
+    out[i] = mt_u53(w[0], w[1]);
+}
+
+__global__ __launch_bounds__(256) void k_mt_normal_counted(const uint32_t* __restrict__ raw, const long long* __restrict__ meta, int seg,
+                                                           const float* __restrict__ R, const float* __restrict__ C, const float* __restrict__ S,
+                                                           float mean, float std, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, numel = meta[1 + 2 * seg];
+    if (i >= numel) return;
+    out[i] = mt_normal_value(raw + meta[0] + meta[2 + 2 * seg], numel, i, R, C, S, mean, std);
+}
+
+static int64_t mt_counted_raw_words(int32_t nseg, const midas_mt_counted_segment* segs) {
+    int64_t words = 3 * MT_N;  // as mt_words: the rest of the block the words start in and of the one they end in
+    for (int i = 0; i < nseg; ++i) {
+        const int64_t n = segs[i].per * segs[i].bound;
+        words += segs[i].kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * n : n + 16;
+    }
+    return words;
+}
+
+int launch_mt_draws_counted(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_counted_segment* segs,
+                            const float* R, const float* C, const float* S, int32_t* status) {
+    void* p;
+    int rc;
+    if ((rc = midas_scratch(ctx, (size_t)mt_counted_raw_words(nseg, segs) * sizeof(uint32_t), &p))) return rc;
+    uint32_t* raw = (uint32_t*)p;
+    if ((rc = midas_scratch(ctx, MT_COUNTED_META * sizeof(long long), &p))) return rc;
+    long long* meta = (long long*)p;
+    mt_counted_segs a = {};
+    a.nseg = nseg;
+    for (int i = 0; i < nseg; ++i) {
+        a.count[i] = segs[i].count_dev;
+        a.bound[i] = segs[i].bound;
+        a.per[i] = segs[i].per;
+        a.kind[i] = segs[i].kind;
+    }
+    hipLaunchKernelGGL(k_mt_counted, dim3(1), dim3(MT_THREADS), 0, ctx->stream, state, (long long)skip_words, a, raw, meta, status);
+    for (int i = 0; i < nseg; ++i) {
+        const int64_t n = segs[i].per * segs[i].bound;
+        if (n == 0) continue;
+        if (segs[i].kind == MIDAS_MT_SEGMENT_RAND64)
+            hipLaunchKernelGGL(k_mt_emit_counted, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
+                               (const long long*)meta, i, (double*)segs[i].out_dev);
+        else
+            hipLaunchKernelGGL(k_mt_normal_counted, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
+                               (const long long*)meta, i, R, C, S, segs[i].mean, segs[i].std, (float*)segs[i].out_dev);
+    }
+    MIDAS_HIP_CHECK(ctx, hipGetLastError());
+    return MIDAS_OK;
 }
 
 MIDAS_WARM_TU(mt19937, k_mt_seed)

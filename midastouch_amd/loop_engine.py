@@ -15,6 +15,8 @@ i.e. `n` (one small read-back per frame), and may split the frame with `phases` 
 size is known, as the reference does.  Such a replay also wants `topk_ties="aten_cpu"`: inside a tie (the normal case:
 particles on one codebook entry share a weight) annealing's `torch.topk` keeps whomever ATen's CPU kernel happens to reach,
 and the device then walks that kernel's algorithm (topk_aten.hip) instead of its own radix select (ties by index).
+`seed_torch_stream(seed)` takes those same draws from torch's CPU stream on the device, sized by the counts in the control
+block: the replay without the read-backs and without splitting the frame by hand.
 """
 from __future__ import annotations
 
@@ -78,6 +80,7 @@ class LoopEngine:
         self._n_host = None        # particle count as last known by the host (None: ask the device)
         self._pending_phases = 0
         self.use_hint = True
+        self.torch_stream = None   # seed_torch_stream
         # the scratch every phase combination of a frame at this capacity can ask for (DBSCAN's cell tables 84 MB + 41 B per
         # particle, the cluster-centre partials 72 B per particle, selection tables) reserved now: no frame of the run
         # allocates (MIDAS_SCRATCH_LOG=1 prints nothing after this line; the cold frame of BENCH_r03's floor_N run)
@@ -200,11 +203,77 @@ class LoopEngine:
         self._n_host = ns
         return rec
 
+    # ---- seeded runs ----------------------------------------------------------------------------------------------
+    def seed_torch_stream(self, seed):
+        """Every draw of a frame from the device replica of torch's CPU generator under torch.manual_seed(seed) (torch_rng.py),
+        in the reference's order and with the reference's sizes: `torch.normal(0, mul * sig_t, (n, 3))`, `torch.normal(0, mul *
+        sig_r, (n, 3))` with n the live count (add_noise_to_odom, particle_filter.py:326-335) and, behind annealing, n_set float64
+        uniforms (the resampler's torch.multinomial, :245).  Both counts are read on the device (midas_mt19937_draws_counted): a
+        step() without tn / rot / u enqueues the whole frame and reads nothing back.  A run that also draws on the host (init_filter)
+        hands the stream over with the returned TorchCpuStream's from_host() / to_host().  seed=None: back to Philox.
+        The generator runs on the engine's stream, in front of the kernels that read its numbers; its scratch at the engine's
+        capacity is reserved here, so no frame allocates.  A live count below 6 (fewer than 16 normal values: ATen's scalar path,
+        not modelled) is reported by read_log()."""
+        if seed is None:
+            self.torch_stream = None
+            return None
+        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
+            raise MidasError("a seeded torch stream reproduces torch.multinomial's draws: resample='weighted_random' only")
+        from .torch_rng import TorchCpuStream
+        st = TorchCpuStream(seed, self.device, overlap=False, pieces=0)
+        st._normal_tables()  # (uploaded now, not by the first frame)
+        cap, d = self.cap, self.device
+        self._tn, self._rot, self._no_noise = (torch.zeros((cap, 3), dtype=torch.float32, device=d) for _ in range(3))
+        self._u = torch.zeros(cap, dtype=torch.float64, device=d)
+        self._mt_status = torch.zeros(self.log_frames, dtype=torch.int32, device=d)  # the counted calls' status, a word per log row
+        ci = (self.ctl_i, _lib.LOOP_I_N)
+        need = max(st.counted_scratch_bytes([("normal", 0.0, 1.0, *ci, 3, cap)] * 2), st.counted_scratch_bytes([("rand64", *ci, cap)]))
+        self.ctx.call("midas_scratch_reserve", max((128 << 20) + 256 * cap, need))  # (the generator shares the engine's context)
+        self.torch_stream = st
+        return st
+
+    def _seeded_step(self, odom, code, gt, u32, multiplier, dbscan, std_override, unit_weights, motion_draws):
+        """One frame with the stream's draws: the motion noise sized by the live count, the frame up to annealing, the uniforms sized
+        by the annealed count, the resample - four enqueues, the counts never leave the device."""
+        st, ci = self.torch_stream, self.ctl_i
+        if self._pending_phases:
+            raise MidasError("a seeded frame is enqueued whole: finish the frame in progress first")
+        b = self._count_bound()
+        slot = self.step_count % self.log_frames
+        if slot == 0:
+            self._mt_status.zero_()  # (the ring starts over, as the log's rows do)
+        status = (self._mt_status, slot)
+        if motion_draws:
+            mul = max(float(multiplier), 1.0)
+            std_t, std_r = (mul * self.sig_t, mul * self.sig_r) if std_override is None else std_override
+            st.draws_counted_async([("normal", 0.0, std_t, ci, _lib.LOOP_I_N, 3, b), ("normal", 0.0, std_r, ci, _lib.LOOP_I_N, 3, b)],
+                                   outs=[self._tn, self._rot], status=status)
+            tn, rot = self._tn, self._rot
+        else:
+            tn = rot = self._no_noise
+        self._enqueue(odom, code, gt, tn, rot, None, u32, multiplier, dbscan, _lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL,
+                      std_override, unit_weights, bound=b)
+        st.draws_counted_async([("rand64", ci, _lib.LOOP_I_NSET, min(self.cap, b + b // 3))], outs=[self._u], status=status)
+        self._enqueue(None, None, None, None, None, self._u, u32, multiplier, dbscan, _lib.LOOP_RESAMPLE, std_override, unit_weights)
+
     # ---- one frame ------------------------------------------------------------------------------------------------
     def step(self, odom, code, gt=None, tn=None, rot=None, u=None, u32=-1.0, multiplier: float = 1.0, dbscan=None,
-             phases: int = None, std_override=None, unit_weights: bool = False):
+             phases: int = None, std_override=None, unit_weights: bool = False, motion_draws: bool = True):
         """Enqueues one frame (or the given phases of it).  dbscan: None = on every `cluster_every`-th frame (count % 50 ==
-        0, filter.py:182), True / False to force.  Host draws tn / rot (n, 3) and u (>= n_set,) as in FilterEngine.step."""
+        0, filter.py:182), True / False to force.  Host draws tn / rot (n, 3) and u (>= n_set,) as in FilterEngine.step.
+        With seed_torch_stream the draws are the stream's and the engine splits the frame itself: tn / rot / u / phases are then an
+        error; motion_draws=False draws no motion noise and propagates with zeros (the frames the reference starts from, where it
+        does not call motionModel)."""
+        if self.torch_stream is None:
+            return self._enqueue(odom, code, gt, tn, rot, u, u32, multiplier, dbscan, phases, std_override, unit_weights)
+        if tn is not None or rot is not None or u is not None or phases is not None:
+            raise MidasError("seed_torch_stream: the stream draws tn, rot and u and the engine splits the frame - passing them would "
+                             "desynchronise the stream from the reference's")
+        self._seeded_step(odom, code, gt, u32, multiplier, dbscan, std_override, unit_weights, motion_draws)
+
+    def _enqueue(self, odom, code, gt, tn, rot, u, u32, multiplier, dbscan, phases, std_override, unit_weights, bound: int = None):
+        """bound: the frame's _count_bound() when the caller has taken it already; tn / rot are then the engine's own capacity-sized
+        buffers (tn[3 i + j] for particle i, as the kernels index them)."""
         d = self.device
         frame_start = self._pending_phases == 0
         if phases is None:
@@ -228,7 +297,7 @@ class LoopEngine:
         if phases & _lib.LOOP_FRONT:
             check_motion_draws(tn, rot)
             odom, code, gt = frame_operands(d, (), self.D, odom, code, gt)
-            if tn is not None:
+            if tn is not None and bound is None:
                 n = self.n
                 tn, rot = operand(tn, "tn", torch.float32, (n, 3), d), operand(rot, "rot", torch.float32, (n, 3), d)
             a.odom16, a.code, a.gt16, a.tn, a.rot = _ptr(odom), _ptr(code), _ptr(gt), _ptr(tn), _ptr(rot)
@@ -246,7 +315,7 @@ class LoopEngine:
         a.floor, a.eps = self.floor, self.eps
         a.unit_weights = int(bool(unit_weights))
         if frame_start:
-            self._grid_n = self._count_bound()
+            self._grid_n = self._count_bound() if bound is None else bound
         a.host_mirror = C.c_void_p(self._mirror.data_ptr())
         a.grid_n = self._grid_n
         a.anneal_small = int(self._grid_n <= 16384)
@@ -271,11 +340,13 @@ class LoopEngine:
         """Per-frame records of frames [first, last) as a list of dicts (one read-back): frame, n (before annealing),
         n_after, rmse_t, rmse_r, kept, drifted, status, mode, k, clusters, var, cluster_poses (C,4,4), cluster_stds (C,3), err.
         Conditions that leave a frame's particles or labels UNDEFINED (err bit 2: the live count exceeded the bound the launches
-        were sized for; bits 5 / 6: DBSCAN's cell structure did not apply) raise MidasError once every row is parsed (the records
-        are attached to the exception as `.records`); strict=False reports them as warnings like the benign ones (cluster limits)."""
+        were sized for; bits 5 / 6: DBSCAN's cell structure did not apply; a seeded stream's counted draw that set its status)
+        raise MidasError once every row is parsed (the records are attached to the exception as `.records`); strict=False reports
+        them as warnings like the benign ones (cluster limits)."""
         last = self.step_count if last is None else min(last, self.step_count)
         first = max(first, last - self.log_frames)
         rows = self._log.cpu().numpy()
+        mt = self._mt_status.cpu().numpy() if self.torch_stream is not None else None  # (seed_torch_stream: the counted draws' status)
         out, fatal = [], []
         import warnings
         for f in range(first, last):
@@ -299,6 +370,12 @@ class LoopEngine:
             if err & 128:
                 fatal.append(f"frame {f}: the engine stated that annealing could not act (live count == floor == init_particles) and the "
                              "rule wanted to: the set was left as it was")
+            bits = int(mt[f % self.log_frames]) if mt is not None else 0
+            if bits:
+                why = [w for b, w in ((_lib.MT_STATUS_COUNT_RANGE, "a count exceeded the bound its draw was sized for"),
+                                      (_lib.MT_STATUS_NORMAL_SHORT, "a live count below 6 - fewer than 16 normal values, ATen's scalar path"))
+                       if bits & b]
+                fatal.append(f"frame {f}: the seeded stream drew nothing ({'; '.join(why)}): the frame's draws are undefined")
             out.append(dict(frame=f, n=int(L[1]), n_after=int(L[2]), rmse_t=float(L[3]), rmse_r=float(L[4]), kept=int(L[5]),
                             drifted=bool(L[6]), status=int(L[7]), mode=int(L[8]), k=int(L[9]), clusters=npres, var=float(L[11]),
                             S=float(L[12]), raw=bool(L[13]), ncl=int(L[14]), err=int(L[15]),

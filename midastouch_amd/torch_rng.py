@@ -356,6 +356,76 @@ class TorchCpuStream(_GeneratorSide):
         _, ev = self._drawn(words, None)
         return outs, ev
 
+    @staticmethod
+    def _counted_items(spec):
+        """spec of draws_counted_async -> [(kind, mean, std, count tensor, index, per, bound)]."""
+        items = []
+        for item in spec:
+            if item[0] == "rand64":
+                _, cnt, idx, bound = item
+                items.append((_lib.MT_SEGMENT_RAND64, 0.0, 1.0, cnt, int(idx), 1, int(bound)))
+            elif item[0] == "normal":
+                _, mean, std, cnt, idx, per, bound = item
+                items.append((_lib.MT_SEGMENT_NORMAL32, float(mean), float(std), cnt, int(idx), int(per), int(bound)))
+            else:
+                raise ValueError(f"unknown draw {item[0]!r}")
+            if cnt.dtype != torch.int32 or not cnt.is_cuda or not cnt.is_contiguous() or not 0 <= int(idx) < cnt.numel():
+                raise _lib.MidasError("a counted draw takes its size from element `index` of a contiguous int32 device tensor")
+        return items
+
+    @classmethod
+    def counted_scratch_bytes(cls, spec) -> int:
+        """Scratch one draws_counted_async(spec) call takes of the generator's context (sized by the bounds)."""
+        words = 3 * 624
+        for kind, _, _, _, _, per, bound in cls._counted_items(spec):
+            words += 2 * per * bound if kind == _lib.MT_SEGMENT_RAND64 else per * bound + 16
+        return (4 * words + 255) // 256 * 256 + 256
+
+    def draws_counted_async(self, spec, outs=None, status=None):
+        """draws_async for draws whose sizes stand in device memory (midas_mt19937_draws_counted): spec = sequence of
+        ("rand64", count_tensor, index, bound) and ("normal", mean, std, count_tensor, index, per, bound) in the stream's order -
+        the draw takes per x count_tensor[index] values (rand64: per = 1) as that element stands when the kernels run, `bound` is
+        what the host knows it cannot exceed.  The reference's loop, whose particle count annealing changes every frame: normal
+        (n, 3) twice, then rand64 n_set (particle_filter.py:326-335, :245), enqueued without reading either count back.
+        Returns ([tensors], event or None): flat tensors of per x bound elements (float64 / float32) of which the first
+        per x count hold the draw and the rest are left as they were; `outs` gives the tensors to write into (each at least that
+        long).  A count beyond its bound or a normal draw of 1 .. 15 values cannot raise here: the call then draws nothing and
+        sets _lib.MT_STATUS_* bits in `status` = (int32 device tensor, index), by default the stream's own word, which
+        counted_status() reads.  Always the sequential walk; the next draw of any kind walks sequentially too."""
+        import ctypes as C
+        items = self._counted_items(spec)
+        if not 1 <= len(items) <= 8:
+            raise _lib.MidasError("1 .. 8 draws a call")
+        if status is None:
+            if getattr(self, "_status", None) is None:
+                self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            status = (self._status, 0)
+        outs = [None] * len(items) if outs is None else list(outs)
+        arr = (_lib.MtCountedSegment * len(items))()
+        need_tables = False
+        for i, (a, (kind, mean, std, cnt, idx, per, bound)) in enumerate(zip(arr, items)):
+            if outs[i] is None:
+                outs[i] = torch.empty(per * bound, dtype=torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32, device=self.device)
+                if self.side is not None:
+                    outs[i].record_stream(self.side)
+            elif (outs[i].dtype != (torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32) or outs[i].numel() < per * bound
+                  or not outs[i].is_contiguous() or outs[i].device != self.device):
+                raise _lib.MidasError(f"draw {i}: `outs` wants a contiguous device tensor of at least {per * bound} values of the draw's type")
+            need_tables |= kind == _lib.MT_SEGMENT_NORMAL32
+            a.kind, a.per, a.count_dev, a.bound, a.mean, a.std = kind, per, cnt.data_ptr() + 4 * idx, bound, mean, std
+            a.out_dev = outs[i].data_ptr()
+        R, Ct, S = self._normal_tables() if need_tables else (None, None, None)
+        self._enter()
+        self._call("midas_mt19937_draws_counted", _ptr(self.state), self.pending_skip, len(items), C.cast(arr, C.c_void_p), _ptr(R), _ptr(Ct),
+                   _ptr(S), C.c_void_p(status[0].data_ptr() + 4 * int(status[1])))
+        _, ev = self._drawn(0, None)  # (no history: the next call walks sequentially)
+        return outs, ev
+
+    def counted_status(self) -> int:
+        """The _lib.MT_STATUS_* bits draws_counted_async calls have set in the stream's own status word (one small read-back)."""
+        st = getattr(self, "_status", None)
+        return 0 if st is None else int(st.item())
+
     def rand64(self, N: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """The next N values of torch.rand(N, dtype=torch.float64) (== the draws of torch.multinomial(w64, N, True)), ordered
         behind the caller's current stream; a fresh tensor unless `out` is given."""

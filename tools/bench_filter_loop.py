@@ -23,7 +23,7 @@ run_filter(cfg, seq, device=dev, max_frames=20)  # warm-up (library load, alloca
 for cluster, draws, floor in ((True, "device", 1000), (True, "device", 100000), (False, "device", 1000), (True, "host", 1000), (True, "seeded", 1000)):
     torch.cuda.synchronize()
     t0 = time.time()
-    st = run_filter(cfg, seq, device=dev, cluster=cluster, draws=draws, floor=floor, max_frames=T if draws == "device" else 60)
+    st = run_filter(cfg, seq, device=dev, cluster=cluster, draws=draws, floor=floor, max_frames=60 if draws == "host" else T)
     wall = time.time() - t0
     n = len(st["time"])
     steady = st["time"][2:]  # without the two initial frames (host-side init_filter, filter.py:156-160)
