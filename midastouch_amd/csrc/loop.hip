@@ -5,7 +5,7 @@
 // (ctl_i[LOOP_I_N]); every kernel is launched over the capacity of the arrays and reads the live count itself, so a frame
 // needs no host round trip:
 //
-//   FRONT     k_frame_front (particles.hip, live count from the control block; sets up to 16 384: k_front_small) ->
+//   FRONT     k_frame_front (front.hip, live count from the control block; sets up to 16 384: k_front_small) ->
 //             k_loop_xe (scores gathered, softmax numerators, per-block sums in the spec order) -> k_loop_weights (S,
 //             isclose guard, masked weights, drift re-projection, rmse; loop_weights.hpp - in frames without DBSCAN this
 //             work sits at the head of the cluster-moment launch instead, k_loop_weights_moments in cluster.hip)

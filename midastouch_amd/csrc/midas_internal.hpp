@@ -165,6 +165,8 @@ int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* deta
         return (int)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&kernel));     \
     }
 #define MIDAS_WARM_DECL(name) int warm_##name();
+// (warm_particles also loads the units cut out of particles.hip - tree, front, front_folded, front_batch: their warm functions are
+// declared and chained in particles.hip, so midas_ctx_create's list of units stays as it is)
 namespace midas {
 MIDAS_WARM_DECL(score) MIDAS_WARM_DECL(particles) MIDAS_WARM_DECL(resample) MIDAS_WARM_DECL(cluster) MIDAS_WARM_DECL(topn)
 MIDAS_WARM_DECL(selfsim) MIDAS_WARM_DECL(loop) MIDAS_WARM_DECL(dbscan) MIDAS_WARM_DECL(dbscan_nd) MIDAS_WARM_DECL(index_build)
@@ -228,7 +230,7 @@ int launch_score_batch(midas_ctx* ctx, const midas_codebook* cb, int32_t B, cons
 int launch_score_batch_f64(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes, double* scores);
 int launch_score_dense_batch(midas_ctx* ctx, const midas_codebook* cb, int32_t B, const double* codes, double* scores);
 
-// particles.hip
+// particles.hip (launch_nn6, launch_nn3, launch_nn6_stats, launch_knn6: tree.hip)
 int launch_se3_feature(midas_ctx* ctx, int64_t N, const float* poses, float w, float* feat6);
 int launch_propagate(midas_ctx* ctx, int64_t N, const float* in, float* out, const float* odom,
                      const float* tn, const float* rot, float std_t, float std_r, uint64_t seed, uint64_t step);
@@ -367,9 +369,22 @@ int build_neighbour_graph_device(midas_ctx* ctx, midas_tree* t);
 int build_vertex_screen(midas_ctx* ctx, midas_tree* t6);  // t6->vscr from t6->vlist (MIDAS_NO_VSCR=1: none)
 int build_vertex_lists_device(midas_ctx* ctx, midas_tree* t6, const midas_tree* t3, const float* cb_poses_dev);
 int launch_knn6(midas_ctx* ctx, const midas_tree* t, int64_t N, const float* feat6, int32_t k, int32_t* idx, float* d2);
+// front.hip
 int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a,
                        const midas_codebook* cb, const double* code, double* scores, bool* launched);
 int launch_particle_update(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a);
+// One launch of a front as launch_frame_front hands it to the units that hold the kernels, and the form of k_frame_front it asks
+// for (the template's LAZY, FW, SCR, PREF, STATS: front_wave.hpp).  A family's launcher launches the form if it is one of its own
+// and says whether it was.
+struct FrontForm { int lazy, fw; bool scr, pref, stats; };
+struct FrontLaunch {
+    midas_ctx* ctx; const midas_tree *t6, *t3; const ParticleUpdateArgs& a; const midas_codebook* cb; const double* code; double* scores;
+    dim3 grid; int n_pu, nwaves;  // the launch's grid; its workgroups of particle waves, particle waves per trajectory
+};
+bool launch_front_plain(const FrontLaunch& L, const FrontForm& f);   // front.hip: no folded resample
+bool launch_front_folded(const FrontLaunch& L, const FrontForm& f);  // front_folded.hip: folded resample, one trajectory
+bool launch_front_batch(const FrontLaunch& L, const FrontForm& f);   // front_batch.hip: a batch of trajectories (+ k_rmse_parts behind a presorted launch)
+int launch_presort(midas_ctx* ctx, ParticleUpdateArgs& a);           // front_batch.hip: fills a.pre_order / a.pre_src
 
 // ---- host: a frame's particle-update arguments ------------------------------------------------------------------------
 // largest float64 t2 with sqrt(t2) <= thr, so that  sqrt(d2) > thr  <=>  d2 > t2  exactly

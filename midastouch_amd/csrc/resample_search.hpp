@@ -1,5 +1,5 @@
 // resample_search.hpp - the slot of a draw inside a 4096-slot summation block, shared by the pipelined front
-// (particles.hip, lazy_source) and the owner-side routing of the sharded step (resample.hip, k_shard_route_*).
+// (front_wave.hpp, lazy_source) and the owner-side routing of the sharded step (resample.hip, k_shard_route_*).
 #pragma once
 #include "midas_internal.hpp"
 #include <type_traits>
@@ -21,7 +21,7 @@ namespace midas {
 // midas_internal.hpp) - the bin of the draw's block-local target names a unit of GUIDE_UNIT slots, or two neighbouring units
 // whose slots are fetched together; the group-end and chunk-end lines are read only where a bin spans more (runs of pruned
 // particles) or the totals are not positive.  Which slots the search starts from changes nothing in the result: the fix-up is
-// exact.  mid: see lazy_source (particles.hip).  Measured at N = 100k (rocprofv3 means): front 29.4 -> 26.5 us, the tail's guide pass + 0.5 - 0.9 us.
+// exact.  mid: see lazy_source (front_wave.hpp).  Measured at N = 100k (rocprofv3 means): front 29.4 -> 26.5 us, the tail's guide pass + 0.5 - 0.9 us.
 typedef const __attribute__((address_space(3))) double* lds_cdp;
 struct NoMid { MD void operator()() const {} };
 template <typename LPT, typename GT, typename MID = NoMid>

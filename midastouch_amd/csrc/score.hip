@@ -532,7 +532,7 @@ int launch_score_batch(midas_ctx* ctx, const midas_codebook* cb, int32_t B, cons
         hipLaunchKernelGGL(k_codes_prepare, dim3((unsigned)ceil_div(Bpad, 16)), dim3(256), 0, ctx->stream, codes, (float*)c32,
                            (double*)cn, B, Bpad, D);
     }
-    // per device (the same rule as launch_presort, particles.hip): a second GPU's context must not inherit the first one's
+    // per device (the same rule as launch_presort, front_batch.hip): a second GPU's context must not inherit the first one's
     // dynamic-LDS limit and CU count
     constexpr int MAXDEV = 64;
     static bool attr_set[MAXDEV] = {};

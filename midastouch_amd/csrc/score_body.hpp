@@ -1,5 +1,5 @@
 // score_body.hpp - the per-wave body of the codebook scoring (K1), shared by k_score_reg (score.hip) and
-// the fused front kernel of the step (particles.hip).  A wave owns four consecutive rows (one per quarter-wave).
+// the fused front kernel of the step (front_wave.hpp).  A wave owns four consecutive rows (one per quarter-wave).
 #pragma once
 #include "midas_internal.hpp"
 #include "midas_math.hpp"

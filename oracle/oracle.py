@@ -229,7 +229,7 @@ def softmax_numerators(x, softmax: bool = True, shift=None, exp: str = "spec"):
 
     shift None -> max(x) (torch's Softmax).  The fused step uses the constant shift 1.0: the scores are
     cosines (<= 1), the softmax is shift-invariant, and a constant lets every particle take its exponential
-    without waiting for a global maximum (csrc/particles.hip k_particle_update)."""
+    without waiting for a global maximum (csrc/front.hip k_particle_update)."""
     x = _f64(x).ravel()
     mx, mn = float(np.max(x)), float(np.min(x))
     applied = bool(softmax) and not (abs(mx - mn) <= 1e-8)

@@ -1,4 +1,4 @@
-"""The float32 screen of the prune (csrc/particles.hip mesh_screen_check / screen_thresholds): a restatement of its
+"""The float32 screen of the prune (csrc/list_scan.hpp mesh_screen_check / screen_thresholds): a restatement of its
 thresholds in numpy float32, checked against the exact float64 predicate of the reference's prune
 (/root/reference/midastouch/modules/particle_filter.py:332-346: distance to the nearest mesh vertex > threshold) on random and
 on adversarial (within rounding of the threshold) pairs.  The claims under test: a "sure hit" is a hit, a "sure miss" is a
