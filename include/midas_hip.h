@@ -949,6 +949,27 @@ typedef struct midas_loop_args {
 } midas_loop_args;
 int midas_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                     const midas_loop_args* args, int32_t phases);
+/* B trajectories' loop bodies per launch set (BASELINE config 5 with the reference's real loop; bash/run_filter.sh: objects x logs
+ * x trials): filter/filter.py:150-190 - measurement update, DBSCAN on the frames the caller asks for (particle_filter.py:208-228),
+ * cluster centres (:153-206), annealing (:405-447) and resampler (:230-307) - for B particle sets that each change their own size,
+ * against one codebook, one pair of trees and one mesh.  `args` is midas_loop_step's, every per-trajectory array with a leading
+ * batch dimension, contiguous, and the capacity `cap` as the per-trajectory extent: the particle arrays (B, cap, ...), ctl_i
+ * (B, 32), ctl_d (B, 16), scores and score_stamps (B, K), part_rmse (B, 2 ceil(cap / 64)), odom16 (B, 16), code (B, D), gt16
+ * (B, 16), cluster_poses (B, MIDAS_LOOP_MAX_CLUSTERS, 16), cluster_stds (B, MIDAS_LOOP_MAX_CLUSTERS, 3); log_dev is NULL or
+ * trajectory 0's row of this frame, trajectory b's lies b * log_stride doubles behind it; host_mirror is NULL or 2 B ints;
+ * cb_poses and the scalars are shared.  `phases` as in midas_loop_step; a frame's DBSCAN flag applies to every trajectory.
+ * The kernels run with the trajectory as grid.y and every trajectory reads its own live and annealed counts; the DBSCAN phase
+ * runs midas_loop_step's pass once per trajectory, one after the other on the stream, on one shared set of cell tables.
+ * Trajectory b draws from the Philox streams keyed (seed + b, step) with slot keys from 0: frame for frame the bits of
+ * midas_loop_step on trajectory b alone with seed + b.
+ * The small-set regime only - anything else is MIDAS_ERR_INVALID with nothing enqueued: cap <= MIDAS_LOOP_BATCH_MAX_CAP; device
+ * draws (tn_dev, rot_dev, u_dev NULL); topk_ties == MIDAS_TOPK_TIES_INDEX; grid_n == 0 and anneal_frozen == 0; a float32 codebook
+ * with sparse scoring (score_stamps_dev and a non-zero score_epoch, D in {128, 256, 512, 1024}); 1 <= B <= 65535.
+ * Within that regime there is one path: args->anneal_small and the MIDAS_LOOP_MERGE / MIDAS_FRONT_SMALL switches, which choose
+ * between bit-identical paths of midas_loop_step, are not consulted here. */
+#define MIDAS_LOOP_BATCH_MAX_CAP 16384
+int midas_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                          const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);
 /* cluster_particles(method="euclidean") alone (particle_filter.py:208-217): labels_dev[i] = DBSCAN label of pose i's
  * translation, eps as given, min_samples < 0 -> N / 5.  Exact float64 predicate |dx|^2 <= eps^2, clusters numbered by their
  * first core point, border points to the smallest adjacent cluster - what sklearn's DBSCAN returns.  Any extent (dense cell grid

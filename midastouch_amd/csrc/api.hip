@@ -66,6 +66,16 @@ int midas_scratch(midas_ctx* ctx, size_t bytes, void** out) {
     return MIDAS_OK;
 }
 
+midas_scratch_pos midas_scratch_mark(midas_ctx* ctx) {
+    const ScratchState* s = scratch_of(ctx);
+    return {s->cur, s->used, s->total};
+}
+
+void midas_scratch_rewind(midas_ctx* ctx, const midas_scratch_pos& pos) {
+    ScratchState* s = scratch_of(ctx);
+    s->cur = pos.cur; s->used = pos.used; s->total = pos.total;
+}
+
 int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* detail) {
     if (ctx) {
         ctx->last_error = std::string(midas_strerror(code)) + ": " + (what ? what : "") + " (" + (detail ? detail : "") + ")";
@@ -1387,6 +1397,35 @@ MIDAS_EXPORT int midas_loop_step(midas_ctx* ctx, const midas_codebook* cb, const
     if (phases & MIDAS_LOOP_RESAMPLE)
         MIDAS_REQUIRE(ctx, s.resample_mode == MIDAS_RESAMPLE_MULTINOMIAL || s.resample_mode == MIDAS_RESAMPLE_SYSTEMATIC);
     return launch_loop_step(ctx, cb, tree6, tree3, s, phases);
+}
+
+MIDAS_EXPORT int midas_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                                       const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, args != nullptr && phases != 0 && (phases & ~15) == 0);
+    const midas_loop_args& s = *args;
+    MIDAS_REQUIRE(ctx, B >= 1 && B <= 65535);
+    MIDAS_REQUIRE(ctx, s.cap > 0 && s.cap <= MIDAS_LOOP_BATCH_MAX_CAP && s.ctl_i_dev && s.ctl_d_dev);
+    MIDAS_REQUIRE(ctx, s.poses_dev && s.poses_prop_dev && s.poses_dev != s.poses_prop_dev && s.hint_dev && s.nn_idx_dev && s.valid_dev &&
+                           s.x_dev && s.e_dev && s.weights_dev && s.weights_out_dev && s.labels_dev && s.labels_out_dev &&
+                           s.labels_dev != s.labels_out_dev && s.src_dev && s.ridx_dev && s.scores_dev && s.cluster_poses_dev &&
+                           s.cluster_stds_dev);
+    MIDAS_REQUIRE(ctx, (uintptr_t)s.poses_dev % 16 == 0 && (uintptr_t)s.poses_prop_dev % 16 == 0);
+    // the small-set regime with device draws (include/midas_hip.h)
+    MIDAS_REQUIRE(ctx, s.tn_dev == nullptr && s.rot_dev == nullptr && s.u_dev == nullptr);
+    MIDAS_REQUIRE(ctx, s.topk_ties == MIDAS_TOPK_TIES_INDEX && s.grid_n == 0 && s.anneal_frozen == 0);
+    MIDAS_REQUIRE(ctx, s.log_dev == nullptr || log_stride >= MIDAS_LOOP_LOG_DOUBLES || B == 1);
+    if (phases & MIDAS_LOOP_FRONT) {
+        MIDAS_REQUIRE(ctx, cb && tree6 && tree3 && tree6->dim == 6 && tree3->dim == 3 && tree6->K == cb->K);
+        MIDAS_REQUIRE(ctx, s.odom16_dev && s.code_dev && s.cb_poses_dev && (uintptr_t)s.cb_poses_dev % 16 == 0);
+        MIDAS_REQUIRE(ctx, cb->dtype == MIDAS_F32 && (cb->D == 128 || cb->D == 256 || cb->D == 512 || cb->D == 1024) &&
+                               (uintptr_t)cb->emb % 16 == 0 && (uintptr_t)s.code_dev % 16 == 0);
+        MIDAS_REQUIRE(ctx, s.score_stamps_dev != nullptr && s.score_epoch != 0);
+    }
+    if (phases & MIDAS_LOOP_DBSCAN) MIDAS_REQUIRE(ctx, s.eps > 0.0);
+    if (phases & MIDAS_LOOP_RESAMPLE)
+        MIDAS_REQUIRE(ctx, s.resample_mode == MIDAS_RESAMPLE_MULTINOMIAL || s.resample_mode == MIDAS_RESAMPLE_SYSTEMATIC);
+    return launch_loop_step_batch(ctx, cb, tree6, tree3, s, phases, B, log_stride);
 }
 
 MIDAS_EXPORT int midas_anneal_select(midas_ctx* ctx, int64_t N, const double* weights_dev, int32_t mode, int64_t k,

@@ -200,8 +200,13 @@ __global__ __launch_bounds__(256) void k_cluster_moments(int64_t N, const float*
 // and ncl come from the control block (midas_loop_step)
 __global__ __launch_bounds__(256) void k_loop_cluster_moments(const int32_t* __restrict__ ctl_i, const float* __restrict__ poses,
                                                               const double* __restrict__ w64, const int32_t* __restrict__ labels,
-                                                              double* __restrict__ part, bool skip) {
+                                                              double* __restrict__ part, bool skip, int32_t cap) {
     __shared__ double s_w[4][CL_MOM];
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): `cap` particles and a launch's partials per trajectory
+        const int64_t b = blockIdx.y, o = b * cap;
+        ctl_i += b * LOOP_CTL_I; poses += o * 16; w64 += o; labels += o;
+        part += (size_t)b * gridDim.x * LOOP_MAX_CLUSTERS * CL_MOM;
+    }
     const int64_t n = ctl_i[LOOP_I_N];
     int C = ctl_i[LOOP_I_NCL] + 1;
     C = C > LOOP_MAX_CLUSTERS ? LOOP_MAX_CLUSTERS : C;
@@ -227,6 +232,11 @@ __global__ __launch_bounds__(256) void k_loop_weights_moments(LoopWeightsArgs a,
     __shared__ double s_sum[LAZY_MAX_BLOCKS];
     __shared__ double s_red[8], s_ab[8];
     __shared__ int s_ired[8];
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch)
+        labels += (int64_t)blockIdx.y * a.grid_n;
+        part += (size_t)blockIdx.y * gridDim.x * LOOP_MAX_CLUSTERS * CL_MOM;
+        loop_weights_batch(a, blockIdx.y);
+    }
     const int t = threadIdx.x;
     const int64_t idx = (int64_t)blockIdx.x * 256 + t, ic = idx < a.grid_n ? idx : a.grid_n - 1;
     const LoopWeightsPre pre = loop_weights_prefetch(a, blockIdx.x == 0);
@@ -398,6 +408,12 @@ __global__ __launch_bounds__(256) void k_loop_cluster_finish(const int32_t* __re
                                                             float* __restrict__ centers, float* __restrict__ stds,
                                                             int64_t* __restrict__ counts, double* __restrict__ rot, int32_t nbs) {
     __shared__ double s_m[CL_MOM];
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): LOOP_MAX_CLUSTERS rows of everything per trajectory
+        const size_t b = blockIdx.y;
+        ctl_i += b * LOOP_CTL_I; part += b * (size_t)nbs * LOOP_MAX_CLUSTERS * CL_MOM;
+        centers += b * LOOP_MAX_CLUSTERS * 16; stds += b * LOOP_MAX_CLUSTERS * 3; counts += b * LOOP_MAX_CLUSTERS;
+        rot += b * LOOP_MAX_CLUSTERS * 10;
+    }
     const int64_t n = ctl_i[LOOP_I_N];
     int C = ctl_i[LOOP_I_NCL] + 1;
     C = C > LOOP_MAX_CLUSTERS ? LOOP_MAX_CLUSTERS : C;
@@ -615,14 +631,15 @@ static bool moments_skip() {  // MIDAS_MOMENTS_SKIP=0: every cluster summed by e
 // (the decision only needs the translation spreads: the eigenvector runs beside the selection)
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsArgs* weights) {
+                        const LoopWeightsArgs* weights, int32_t B) {
+    const unsigned by = (unsigned)(B > 1 ? B : 1);
     if (weights)
-        hipLaunchKernelGGL(k_loop_weights_moments, dim3((unsigned)ceil_div(cap, 256)), dim3(256), 0, ctx->stream, *weights, labels, part,
+        hipLaunchKernelGGL(k_loop_weights_moments, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream, *weights, labels, part,
                            moments_skip());
     else
-        hipLaunchKernelGGL(k_loop_cluster_moments, dim3((unsigned)ceil_div(cap, 256)), dim3(256), 0, ctx->stream, ctl_i, poses, w64,
-                           labels, part, moments_skip());
-    hipLaunchKernelGGL(k_loop_cluster_finish, dim3(LOOP_MAX_CLUSTERS), dim3(256), 0, ctx->stream, ctl_i, (const double*)part, centers,
+        hipLaunchKernelGGL(k_loop_cluster_moments, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream, ctl_i, poses, w64,
+                           labels, part, moments_skip(), (int32_t)cap);
+    hipLaunchKernelGGL(k_loop_cluster_finish, dim3(LOOP_MAX_CLUSTERS, by), dim3(256), 0, ctx->stream, ctl_i, (const double*)part, centers,
                        stds, counts, rot, (int32_t)ceil_div(cap, 256));
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;

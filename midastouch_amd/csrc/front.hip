@@ -274,8 +274,23 @@ __global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_particle_nn_prune(TreeVi
 // workgroup's first wave is part A for the 64 particles the workgroup's four waves then search with four lanes each.  Part A is
 // a chain of round trips that one wave per 64 particles carries as well as four waves per 256 did; what goes is a launch
 // boundary (~4 us of a frame of 85) and the first touch of the hand-over records by another launch.
+// A batch of trajectories (midas_loop_step_batch; trajectory = blockIdx.y): every per-trajectory array is (B, ...) contiguous with
+// the launch's capacity a.N as the extent - taken HERE, before the waves clamp a.N to the live count, which every trajectory reads
+// from its own control block - its own stamps, tactile code and score row, its own hand-over records, and the Philox key
+// seed + trajectory with slot keys from 0: the draws of a single engine built with that seed.
 __global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small(TreeView<Kd6> t6, TreeView<Kd3> t3, ParticleUpdateArgs a, int nwaves,
                                                                     PuFeat* __restrict__ feat) {
+    if (blockIdx.y) {
+        const int64_t b = blockIdx.y, o = b * a.N;
+        a.n_live += b * LOOP_CTL_I;
+        a.poses_in += o * 16; a.poses_prop += o * 16; a.odom16 += b * 16;
+        if (a.hint_in) a.hint_in += o;
+        a.nn_idx += o; a.valid += o;
+        if (a.gt16) { a.gt16 += b * 16; a.part_rmse += 2 * b * nwaves; }
+        a.sp.stamps += b * a.score_stride; a.sp.scores += b * a.score_stride; a.sp.code += b * (int64_t)(a.sp.nj * 64);
+        a.seed += (uint64_t)b;
+        feat += o;
+    }
     if (threadIdx.x < 64 && (int)blockIdx.x < nwaves) particle_front_wave(a, (int64_t)blockIdx.x, nullptr, feat);
     __syncthreads();  // (drains the first wave's stores of the hand-over records: the other waves read them through the L2)
     particle_nn_prune_wg<4>(t6, t3, a, feat);
@@ -409,6 +424,27 @@ int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t
         return midas_set_error(ctx, MIDAS_ERR_INVALID, "launch_frame_front", "no kernel for this form of the front");
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     *launched = true;
+    return MIDAS_OK;
+}
+
+int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a_in,
+                             const midas_codebook* cb, const double* code, double* scores, int32_t B) {
+    ParticleUpdateArgs a = a_in;
+    if (!(a.n_live && a.N > 0 && a.N <= 16384 && a.sp.stamps && !a.rs.enabled && !a.tn && cb->dtype == MIDAS_F32 &&
+          (cb->D == 512 || cb->D == 256 || cb->D == 128 || cb->D == 1024) && (uintptr_t)cb->emb % 16 == 0 && (uintptr_t)code % 16 == 0))
+        return midas_set_error(ctx, MIDAS_ERR_INVALID, "launch_front_small_batch", "no small-set front for these arguments");
+    a.scores = nullptr;  // deferred: k_loop_xe gathers the scores
+    a.sp.emb = (const float*)cb->emb; a.sp.norms = cb->norms; a.sp.code = code; a.sp.scores = scores; a.sp.nj = cb->D / 64;
+    a.sp.K = cb->K; a.sp.pred_tag = 0; a.sp.list = nullptr;
+    a.score_stride = cb->K;
+    a.batch = B;
+    const int nwaves = particle_update_blocks(a.N);
+    void* feat;
+    const int rc = midas_scratch(ctx, (size_t)B * a.N * sizeof(PuFeat), &feat);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_front_small, dim3((unsigned)ceil_div(a.N, 64), (unsigned)B), dim3(256), 0, ctx->stream, view_of<Kd6>(t6),
+                       view_of<Kd3>(t3), a, nwaves, (PuFeat*)feat);
+    MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
 }
 

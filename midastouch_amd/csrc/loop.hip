@@ -78,6 +78,11 @@ __global__ __launch_bounds__(256) void k_loop_xe(const int32_t* __restrict__ ctl
     __shared__ double s_mx[4], s_mn[4];
     __shared__ int s_k[4], s_f[4];
     __shared__ double s_t[LDS_CHUNK_DOUBLES];
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): cap_n slots, K scores and a launch's block results per trajectory
+        const int64_t b = blockIdx.y, o = b * cap_n, ob = b * gridDim.x;
+        ctl_i += b * LOOP_CTL_I; scores += b * K; nn_idx += o; valid += o; x_out += o; e_out += o;
+        bsum += ob; bmax += ob; bmin += ob; bkept += ob; bnan += ob;
+    }
     const int blk = blockIdx.x, t = threadIdx.x;
     const int64_t bbase = (int64_t)blk * SCAN_BLOCK;
     // batched, unconditional loads on clamped indices (a branch around a load makes hipcc wait for each one in turn); clamped to
@@ -167,6 +172,7 @@ __global__ __launch_bounds__(256) void k_loop_weights(LoopWeightsArgs a) {
     __shared__ double s_sum[LAZY_MAX_BLOCKS];
     __shared__ double s_red[8], s_ab[8];
     __shared__ int s_ired[8];
+    if (blockIdx.y) loop_weights_batch(a, blockIdx.y);  // a batch of trajectories (midas_loop_step_batch)
     const int blk = blockIdx.x, t = threadIdx.x;
     const int64_t bbase = (int64_t)blk * SCAN_BLOCK;
     // Everything this workgroup reads leaves before the live count is looked at (the control block is a trip of its own): the block
@@ -556,6 +562,7 @@ __global__ __launch_bounds__(256) void k_loop_sort_rank(const int32_t* __restric
 // last by the largest growth annealing allows per frame) one 1024-thread workgroup does the same steps - sixteen keys per
 // thread in registers, LDS histograms, the k duplicates sorted in LDS - with identical results.
 constexpr int LOOP_SMALL_MAX = 16384, LOOP_SMALL_PAIRS = 8192;
+static_assert(LOOP_SMALL_MAX == MIDAS_LOOP_BATCH_MAX_CAP, "midas_loop_step_batch runs this regime's kernels");
 
 // exclusive prefix over the 1024 threads of (a, b); totals returned in ta / tb.  s_w: 32 ints of LDS.
 MD void small_scan2(int a, int b, int& ea, int& eb, int& ta, int& tb, int* s_w) {
@@ -861,12 +868,19 @@ __global__ __launch_bounds__(1024) void k_loop_anneal_small(int32_t* __restrict_
                                                             const int64_t* __restrict__ counts_all, float* __restrict__ centers_out,
                                                             float* __restrict__ stds_out, int32_t floor_n,
                                                             const double* __restrict__ w, int32_t* __restrict__ src,
-                                                            const double* __restrict__ rot) {
+                                                            const double* __restrict__ rot, int32_t cap = 0) {
 #ifdef MIDAS_ANNEAL_CLOCKS
     const long long ck0 = wall_clock64();
 #else
     const long long ck0 = 0;
 #endif
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): `cap` particles and LOOP_MAX_CLUSTERS cluster rows per trajectory
+        const int64_t b = blockIdx.y;
+        ctl_i += b * LOOP_CTL_I; ctl_d += b * LOOP_CTL_D;
+        centers_all += b * LOOP_MAX_CLUSTERS * 16; stds_all += b * LOOP_MAX_CLUSTERS * 3; counts_all += b * LOOP_MAX_CLUSTERS;
+        centers_out += b * LOOP_MAX_CLUSTERS * 16; stds_out += b * LOOP_MAX_CLUSTERS * 3; rot += b * LOOP_MAX_CLUSTERS * 10;
+        w += b * cap; src += b * cap;
+    }
     if (DECIDE && blockIdx.x == 1) { loop_rotations(ctl_i, counts_all, rot, centers_out); ACK(7); return; }
     __shared__ int s_w[40];
     const int t = threadIdx.x;
@@ -894,9 +908,14 @@ __global__ __launch_bounds__(1024) void k_loop_anneal_small(int32_t* __restrict_
 __global__ __launch_bounds__(256) void k_loop_scan(const int32_t* __restrict__ ctl_i, const double* __restrict__ x,
                                                    const double* __restrict__ e, const uint8_t* __restrict__ valid,
                                                    const int32_t* __restrict__ src, double* __restrict__ lp,
-                                                   double* __restrict__ btot, int32_t* __restrict__ bnan) {
+                                                   double* __restrict__ btot, int32_t* __restrict__ bnan, int32_t cap = 0,
+                                                   int32_t lp_stride = 0) {
     __shared__ double s_gtot[16];
     __shared__ double s_t[LDS_CHUNK_DOUBLES];  // (k_loop_xe: slot-per-lane in memory, chunk-per-thread for the sums)
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): `cap` particles, lp_stride prefix values, a launch's block totals each
+        const int64_t b = blockIdx.y, o = b * cap, ob = b * gridDim.x;
+        ctl_i += b * LOOP_CTL_I; x += o; e += o; valid += o; src += o; lp += b * lp_stride; btot += ob; bnan += ob;
+    }
     const int64_t n2 = ctl_i[LOOP_I_NSET];
     const int raw = ctl_i[LOOP_I_RAW];
     const int blk = blockIdx.x, t = threadIdx.x;
@@ -958,6 +977,10 @@ struct LoopResampleArgs {
     const float* cluster_stds;
     int32_t* host_mirror;
     int32_t cap2;  // slots the prefix array holds (the launch's bound of the annealed set)
+    // a batch of trajectories (midas_loop_step_batch; blockIdx.y): particles per trajectory in the (B, ...) arrays, prefix values
+    // between two trajectories' tables, doubles between their log rows
+    int32_t cap = 0, lp_stride = 0;
+    int64_t log_stride = 0;
 };
 
 // n_set draws over cdf_i = (BP_b + lp_i) / total (last slot 1): lower bound (multinomial) / upper bound (systematic) by
@@ -979,6 +1002,17 @@ __global__ __launch_bounds__(256) void k_loop_resample(LoopResampleArgs a) {
     // search finds the same slot in a non-decreasing sequence (the values compared are the same exact quotients).
     constexpr int RS_CHUNKS = 2048;
     __shared__ double s_ce[RS_CHUNKS];
+    if (blockIdx.y) {  // trajectory b draws with the key seed + b, slot keys from 0: the draws of a single engine built with that seed
+        const int64_t b = blockIdx.y, o = b * a.cap, ob = b * ((a.cap2 + SCAN_BLOCK - 1) / SCAN_BLOCK);
+        a.ctl_i += b * LOOP_CTL_I; a.ctl_d += b * LOOP_CTL_D;
+        a.lp += b * a.lp_stride; a.btot += ob; a.bnan += ob;
+        a.src += o; a.poses_prop += o * 16; a.w += o; a.nn_idx += o; a.labels += o;
+        a.poses_out += o * 16; a.weights_out += o; a.hint_out += o; a.labels_out += o; a.ridx += o;
+        a.seed += (uint64_t)b;
+        if (a.log) a.log += b * a.log_stride;
+        a.cluster_poses += b * LOOP_MAX_CLUSTERS * 16; a.cluster_stds += b * LOOP_MAX_CLUSTERS * 3;
+        if (a.host_mirror) a.host_mirror += 2 * b;
+    }
     const int t = threadIdx.x;
     // Chunk ends, block totals and NaN flags leave before the control block is looked at (it is a trip of its own): by position,
     // bounded by what the launch was sized for - what lies behind the live count is not used.
@@ -1222,6 +1256,37 @@ int launch_anneal_select(midas_ctx* ctx, int64_t N, const double* w, int32_t mod
     return launch_select(ctx, N, (const int32_t*)ctl, w, src, ss);
 }
 
+// What launch_loop_step and launch_loop_step_batch fill alike (the batch's arrays are the same pointers with B slices behind them):
+// the block results of k_loop_xe for `count` blocks, the weights' arguments, the resample's arguments.
+struct LoopBlockResults { double *bsum, *bmax, *bmin; int32_t *bkept, *bnan; };
+static int carve_block_results(midas_ctx* ctx, size_t count, LoopBlockResults& br) {
+    void* p;
+    if (int rc = midas_scratch(ctx, count * (3 * sizeof(double) + 2 * sizeof(int32_t)), &p)) return rc;
+    br.bsum = (double*)p;
+    br.bmax = br.bsum + count; br.bmin = br.bmax + count;
+    br.bkept = (int32_t*)(br.bmin + count);
+    br.bnan = br.bkept + count;
+    return MIDAS_OK;
+}
+static void fill_loop_weights(LoopWeightsArgs& wa, const midas_loop_args& s, const LoopBlockResults& br, int32_t grid_n, unsigned nbcap,
+                              bool rmse) {
+    wa.ctl_i = s.ctl_i_dev; wa.ctl_d = s.ctl_d_dev; wa.grid_n = grid_n; wa.nbl = (int32_t)nbcap;
+    wa.bsum = br.bsum; wa.bmax = br.bmax; wa.bmin = br.bmin; wa.bkept = br.bkept; wa.bnan = br.bnan;
+    wa.x = (const double*)s.x_dev; wa.e = (const double*)s.e_dev; wa.valid = (const uint8_t*)s.valid_dev;
+    wa.nn_idx = (const int32_t*)s.nn_idx_dev; wa.cb_poses = s.cb_poses_dev; wa.poses_prop = s.poses_prop_dev;
+    wa.w_out = s.weights_dev; wa.src = s.src_dev; wa.part_rmse = (const double*)(rmse ? s.part_rmse_dev : nullptr);
+    wa.softmax = s.softmax;
+}
+static void fill_loop_resample(LoopResampleArgs& r, const midas_loop_args& s, const void* lp, const void* bt, const void* bn) {
+    r.ctl_i = s.ctl_i_dev; r.ctl_d = s.ctl_d_dev;
+    r.lp = (const double*)lp; r.btot = (const double*)bt; r.bnan = (const int32_t*)bn;
+    r.src = s.src_dev; r.poses_prop = s.poses_prop_dev; r.w = s.weights_dev; r.nn_idx = s.nn_idx_dev; r.labels = s.labels_dev;
+    r.poses_out = s.poses_dev; r.weights_out = s.weights_out_dev; r.hint_out = s.hint_dev; r.labels_out = s.labels_out_dev;
+    r.ridx = s.ridx_dev; r.mode = s.resample_mode; r.u = s.u_dev; r.u32 = s.u32; r.seed = s.seed; r.step = s.step;
+    r.log = s.log_dev; r.cluster_poses = s.cluster_poses_dev; r.cluster_stds = s.cluster_stds_dev;
+    r.host_mirror = s.host_mirror;
+}
+
 int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                      const midas_loop_args& s, int32_t phases) {
     // the grids cover `cap` particles: the capacity, or the caller's upper bound of the live count
@@ -1245,27 +1310,18 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
             pa.sp.stamps = nullptr;  // scored densely just above
             if ((rc = launch_particle_update(ctx, t6, t3, pa))) return rc;
         }
-        void* p;
-        if ((rc = midas_scratch(ctx, (size_t)nbcap * (3 * sizeof(double) + 2 * sizeof(int32_t)), &p))) return rc;
-        double* bsum = (double*)p;
-        double *bmax = bsum + nbcap, *bmin = bmax + nbcap;
-        int32_t* bkept = (int32_t*)(bmin + nbcap);
-        int32_t* bnan = bkept + nbcap;
+        LoopBlockResults br;
+        if ((rc = carve_block_results(ctx, nbcap, br))) return rc;
         hipLaunchKernelGGL(k_loop_xe, dim3(nbcap), dim3(256), 0, st, (const int32_t*)s.ctl_i_dev, (const double*)s.scores_dev,
-                           (const int32_t*)s.nn_idx_dev, (const uint8_t*)s.valid_dev, s.softmax, s.unit_weights, s.x_dev, s.e_dev, bsum, bmax, bmin,
-                           bkept, bnan, (int32_t)(cap < (1 << 30) ? cap : (1 << 30)), cb->K,
+                           (const int32_t*)s.nn_idx_dev, (const uint8_t*)s.valid_dev, s.softmax, s.unit_weights, s.x_dev, s.e_dev, br.bsum, br.bmax,
+                           br.bmin, br.bkept, br.bnan, (int32_t)(cap < (1 << 30) ? cap : (1 << 30)), cb->K,
 #ifdef MIDAS_ANNEAL_CLOCKS
                            s.ctl_d_dev
 #else
                            (double*)nullptr
 #endif
                            );
-        wa.ctl_i = s.ctl_i_dev; wa.ctl_d = s.ctl_d_dev; wa.grid_n = (int32_t)(cap < (1 << 30) ? cap : (1 << 30)); wa.nbl = (int32_t)nbcap;
-        wa.bsum = bsum; wa.bmax = bmax; wa.bmin = bmin; wa.bkept = bkept; wa.bnan = bnan;
-        wa.x = (const double*)s.x_dev; wa.e = (const double*)s.e_dev; wa.valid = (const uint8_t*)s.valid_dev;
-        wa.nn_idx = (const int32_t*)s.nn_idx_dev; wa.cb_poses = s.cb_poses_dev; wa.poses_prop = s.poses_prop_dev;
-        wa.w_out = s.weights_dev; wa.src = s.src_dev; wa.part_rmse = (const double*)(pa.gt16 ? s.part_rmse_dev : nullptr);
-        wa.softmax = s.softmax;
+        fill_loop_weights(wa, s, br, (int32_t)(cap < (1 << 30) ? cap : (1 << 30)), nbcap, pa.gt16 != nullptr);
         // the weights at the head of the cluster-moment launch when that launch follows in this call with nothing in between
         // (DBSCAN reads the re-projected poses: frames that cluster keep the launch of their own)
         static const bool merge_env = !(getenv("MIDAS_LOOP_MERGE") && atoi(getenv("MIDAS_LOOP_MERGE")) == 0);
@@ -1324,15 +1380,84 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
                            (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)lp, (double*)bt,
                            (int32_t*)bn);
         LoopResampleArgs r;
-        r.ctl_i = s.ctl_i_dev; r.ctl_d = s.ctl_d_dev;
-        r.lp = (const double*)lp; r.btot = (const double*)bt; r.bnan = (const int32_t*)bn;
-        r.src = s.src_dev; r.poses_prop = s.poses_prop_dev; r.w = s.weights_dev; r.nn_idx = s.nn_idx_dev; r.labels = s.labels_dev;
-        r.poses_out = s.poses_dev; r.weights_out = s.weights_out_dev; r.hint_out = s.hint_dev; r.labels_out = s.labels_out_dev;
-        r.ridx = s.ridx_dev; r.mode = s.resample_mode; r.u = s.u_dev; r.u32 = s.u32; r.seed = s.seed; r.step = s.step;
-        r.log = s.log_dev; r.cluster_poses = s.cluster_poses_dev; r.cluster_stds = s.cluster_stds_dev;
-        r.host_mirror = s.host_mirror;
+        fill_loop_resample(r, s, lp, bt, bn);
         r.cap2 = (int32_t)(cap2 < (1 << 30) ? cap2 : (1 << 30));
         hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap2, 256)), dim3(256), 0, st, r);
+        LAUNCH_CHECK(ctx);
+    }
+    return MIDAS_OK;
+}
+
+// B trajectories per launch (midas_loop_step_batch): the launches of the small-set frame above with the trajectory as grid.y,
+// every array - the caller's and the scratch - (B, ...) contiguous.  The arguments are the regime the entry point checked:
+// cap <= LOOP_SMALL_MAX, device draws, ties by index, no bound below the capacity, sparse scoring.  The regime has one path: the
+// single call's `anneal_small` field and its MIDAS_LOOP_MERGE / MIDAS_FRONT_SMALL switches (which pick between bit-identical
+// paths there) are not consulted - k_front_small, the merged weights launch and k_loop_anneal_small always run.
+int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
+                           const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride) {
+    const int64_t cap = s.cap;
+    const size_t Bz = (size_t)B;
+    const unsigned nbcap = (unsigned)ceil_div(cap, SCAN_BLOCK), by = (unsigned)B;
+    int rc;
+    hipStream_t st = ctx->stream;
+    LoopWeightsArgs wa{};
+    bool weights_merged = false;
+    if (phases & MIDAS_LOOP_FRONT) {
+        ParticleUpdateArgs pa;
+        fill_particle_update(pa, s, t6, t3, cap, s.poses_dev, s.hint_dev, s.valid_dev, s.score_stamps_dev,
+                             (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
+        pa.n_live = s.ctl_i_dev + LOOP_I_N;
+        if ((rc = launch_front_small_batch(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, B))) return rc;
+        LoopBlockResults br;
+        if ((rc = carve_block_results(ctx, Bz * nbcap, br))) return rc;
+        hipLaunchKernelGGL(k_loop_xe, dim3(nbcap, by), dim3(256), 0, st, (const int32_t*)s.ctl_i_dev, (const double*)s.scores_dev,
+                           (const int32_t*)s.nn_idx_dev, (const uint8_t*)s.valid_dev, s.softmax, s.unit_weights, s.x_dev, s.e_dev, br.bsum, br.bmax,
+                           br.bmin, br.bkept, br.bnan, (int32_t)cap, cb->K, (double*)nullptr);
+        fill_loop_weights(wa, s, br, (int32_t)cap, nbcap, pa.gt16 != nullptr);
+        weights_merged = (phases & MIDAS_LOOP_ANNEAL) && !(phases & MIDAS_LOOP_DBSCAN);  // (as launch_loop_step: DBSCAN reads the re-projected poses)
+        if (!weights_merged) hipLaunchKernelGGL(k_loop_weights, dim3(nbcap, by), dim3(256), 0, st, wa);
+        LAUNCH_CHECK(ctx);
+    }
+    if (phases & MIDAS_LOOP_DBSCAN) {
+        // one trajectory after the other on the stream, each on its slices; the passes take the same scratch (one set of cell tables)
+        const midas_scratch_pos pos = midas_scratch_mark(ctx);
+        for (int32_t b = 0; b < B; ++b) {
+            midas_scratch_rewind(ctx, pos);
+            int32_t* ci = s.ctl_i_dev + (size_t)b * LOOP_CTL_I;
+            if ((rc = launch_dbscan(ctx, cap, ci + LOOP_I_N, s.poses_prop_dev + (size_t)b * cap * 16, s.eps, -1, s.labels_dev + (size_t)b * cap,
+                                    ci + LOOP_I_NCL, ci + LOOP_I_ERR, LOOP_MAX_CLUSTERS - 1)))
+                return rc;
+        }
+    }
+    if (phases & MIDAS_LOOP_ANNEAL) {
+        void *part, *cen, *sd, *cnt, *rot;
+        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 10 * sizeof(double), &rot))) return rc;
+        if ((rc = midas_scratch(ctx, Bz * (size_t)ceil_div(cap, 256) * LOOP_MAX_CLUSTERS * 36 * sizeof(double), &part))) return rc;
+        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 16 * sizeof(float), &cen))) return rc;
+        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 3 * sizeof(float), &sd))) return rc;
+        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * sizeof(int64_t), &cnt))) return rc;
+        if ((rc = launch_loop_cluster(ctx, cap, s.ctl_i_dev, s.poses_prop_dev, s.weights_dev, s.labels_dev, (double*)part, (float*)cen,
+                                      (float*)sd, (int64_t*)cnt, (double*)rot, weights_merged ? &wa : nullptr, B)))
+            return rc;
+        hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, by), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
+                           (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor, (const double*)s.weights_dev, s.src_dev,
+                           (const double*)rot, (int32_t)cap);
+        LAUNCH_CHECK(ctx);
+    }
+    if (phases & MIDAS_LOOP_RESAMPLE) {
+        const unsigned nb2 = nbcap;  // (the annealed set never exceeds the capacity)
+        const int64_t lp_stride = cap + SCAN_CHUNK;  // (the resample reads whole chunks)
+        void *lp, *bt, *bn;
+        if ((rc = midas_scratch(ctx, Bz * (size_t)lp_stride * sizeof(double), &lp))) return rc;
+        if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(double), &bt))) return rc;
+        if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(int32_t), &bn))) return rc;
+        hipLaunchKernelGGL(k_loop_scan, dim3(nb2, by), dim3(256), 0, st, (const int32_t*)s.ctl_i_dev, (const double*)s.x_dev,
+                           (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)lp, (double*)bt,
+                           (int32_t*)bn, (int32_t)cap, (int32_t)lp_stride);
+        LoopResampleArgs r;
+        fill_loop_resample(r, s, lp, bt, bn);  // (u_dev is NULL here: the entry point checked)
+        r.cap2 = (int32_t)cap; r.cap = (int32_t)cap; r.lp_stride = (int32_t)lp_stride; r.log_stride = log_stride;
+        hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, st, r);
         LAUNCH_CHECK(ctx);
     }
     return MIDAS_OK;

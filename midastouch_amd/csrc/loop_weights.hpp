@@ -33,6 +33,16 @@ struct LoopWeightsArgs {
     int32_t softmax;
 };
 
+// trajectory b of a batch (midas_loop_step_batch; blockIdx.y): every array is (B, ...) contiguous - grid_n particles (the capacity),
+// nbl block results, ceil(grid_n / 64) pairs of rmse partials and one control block per trajectory; the codebook poses are shared
+MD void loop_weights_batch(LoopWeightsArgs& a, int64_t b) {
+    const int64_t o = b * a.grid_n, ob = b * a.nbl;
+    a.ctl_i += b * LOOP_CTL_I; a.ctl_d += b * LOOP_CTL_D;
+    a.bsum += ob; a.bmax += ob; a.bmin += ob; a.bkept += ob; a.bnan += ob;
+    a.x += o; a.e += o; a.valid += o; a.nn_idx += o; a.poses_prop += o * 16; a.w_out += o; a.src += o;
+    if (a.part_rmse) a.part_rmse += 2 * b * (((int64_t)a.grid_n + 63) / 64);
+}
+
 // what a thread requests before the live count is looked at (the control block is another launch's output: these travel with it)
 struct LoopWeightsPre {
     double sum, mx, mn;

@@ -176,6 +176,11 @@ MIDAS_WARM_DECL(tsne)
 
 // scratch carve-out (stream-ordered reuse; one stream per context)
 int midas_scratch(midas_ctx* ctx, size_t bytes, void** out);
+// where the carve-out stands / back to there: passes that follow each other on the stream take the same bytes (the DBSCAN passes of
+// midas_loop_step_batch share one set of cell tables)
+struct midas_scratch_pos { size_t cur, used, total; };
+midas_scratch_pos midas_scratch_mark(midas_ctx* ctx);
+void midas_scratch_rewind(midas_ctx* ctx, const midas_scratch_pos& pos);
 
 namespace midas {
 
@@ -190,6 +195,7 @@ enum : int {
     LOOP_D_RMSE_T = MIDAS_LOOP_D_RMSE_T, LOOP_D_RMSE_R = MIDAS_LOOP_D_RMSE_R, LOOP_D_XMAX = MIDAS_LOOP_D_XMAX,
     LOOP_D_XMIN = MIDAS_LOOP_D_XMIN, LOOP_D_TOTAL = MIDAS_LOOP_D_TOTAL,
     LOOP_MAX_CLUSTERS = MIDAS_LOOP_MAX_CLUSTERS,
+    LOOP_CTL_I = 32, LOOP_CTL_D = 16,  // entries of one trajectory's control blocks (midas_loop_step_batch: (B, 32) / (B, 16))
 };
 
 // blocked-scan spec constants (DESIGN.md "Summation order")
@@ -373,6 +379,10 @@ int launch_knn6(midas_ctx* ctx, const midas_tree* t, int64_t N, const float* fea
 int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a,
                        const midas_codebook* cb, const double* code, double* scores, bool* launched);
 int launch_particle_update(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a);
+// the loop step's small-set front (k_front_small) for B trajectories with their live counts (midas_loop_step_batch): a.N = the
+// capacity, a.n_live = trajectory 0's count, LOOP_CTL_I entries apart
+int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a,
+                             const midas_codebook* cb, const double* code, double* scores, int32_t B);
 // One launch of a front as launch_frame_front hands it to the units that hold the kernels, and the form of k_frame_front it asks
 // for (the template's LAZY, FW, SCR, PREF, STATS: front_wave.hpp).  A family's launcher launches the form if it is one of its own
 // and says whether it was.
@@ -558,11 +568,14 @@ int launch_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* 
 struct LoopWeightsArgs;  // loop_weights.hpp
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsArgs* weights = nullptr);  // weights: computed at the head of the moment launch (loop.hip)
+                        const LoopWeightsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop.hip)
+                        int32_t B = 1);  // trajectories (grid.y): every array (B, ...) contiguous, the scratch ones included
 
 // loop.hip / dbscan.hip - the reference's whole loop body on a variable-size particle set (midas_loop_step)
 int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                      const midas_loop_args& a, int32_t phases);
+int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
+                           const midas_loop_args& a, int32_t phases, int32_t B, int64_t log_stride);
 // src[0 .. n_set): the annealed particle set as indices - mode 1: the N particles minus the k of smallest weight, in
 // order; mode 2: all N followed by the k of largest weight, best first; ties to the smaller index
 int launch_anneal_select(midas_ctx* ctx, int64_t N, const double* w, int32_t mode, int64_t k, int32_t ties, int32_t* src, int32_t* info);

@@ -347,43 +347,51 @@ class LoopEngine:
         first = max(first, last - self.log_frames)
         rows = self._log.cpu().numpy()
         mt = self._mt_status.cpu().numpy() if self.torch_stream is not None else None  # (seed_torch_stream: the counted draws' status)
-        out, fatal = [], []
-        import warnings
-        for f in range(first, last):
-            L = rows[f % self.log_frames]
-            npres = int(L[10])
-            cl = L[16:16 + 19 * min(npres, 8)].reshape(-1, 19)
-            err = int(L[15])
-            # condition bits of THIS frame (the device clears the word once the row holds it)
-            if err & (1 | 2):
-                warnings.warn(f"frame {f}: more than {_lib.LOOP_MAX_CLUSTERS - 2} clusters in one frame - the labels beyond that limit, and the "
-                              "annealing driven by them, are not the reference's (min_samples = n / 5 allows about five)")
-            if err & 8:
-                warnings.warn(f"frame {f}: {npres} cluster labels present, the log row keeps the centres of the first 8")
-            if err & 4:
-                fatal.append(f"frame {f}: the live particle count exceeded the bound the launches were sized for; "
-                             "the particles beyond it were not processed in this frame")
-            if err & 32:
-                fatal.append(f"frame {f}: DBSCAN saw non-finite particle translations or a cloud of more than 2^21 cells per axis; labels undefined")
-            if err & 64:
-                fatal.append(f"frame {f}: DBSCAN on a cloud wider than 128 cells per axis with more than 2^20 particles (hash table capacity); labels undefined")
-            if err & 128:
-                fatal.append(f"frame {f}: the engine stated that annealing could not act (live count == floor == init_particles) and the "
-                             "rule wanted to: the set was left as it was")
-            bits = int(mt[f % self.log_frames]) if mt is not None else 0
-            if bits:
-                why = [w for b, w in ((_lib.MT_STATUS_COUNT_RANGE, "a count exceeded the bound its draw was sized for"),
-                                      (_lib.MT_STATUS_NORMAL_SHORT, "a live count below 6 - fewer than 16 normal values, ATen's scalar path"))
-                       if bits & b]
-                fatal.append(f"frame {f}: the seeded stream drew nothing ({'; '.join(why)}): the frame's draws are undefined")
-            out.append(dict(frame=f, n=int(L[1]), n_after=int(L[2]), rmse_t=float(L[3]), rmse_r=float(L[4]), kept=int(L[5]),
-                            drifted=bool(L[6]), status=int(L[7]), mode=int(L[8]), k=int(L[9]), clusters=npres, var=float(L[11]),
-                            S=float(L[12]), raw=bool(L[13]), ncl=int(L[14]), err=int(L[15]),
-                            cluster_poses=cl[:, :16].reshape(-1, 4, 4).astype(np.float32), cluster_stds=cl[:, 16:].astype(np.float32)))
-        if fatal and strict:
-            e = MidasError("; ".join(fatal))
-            e.records = out
-            raise e
-        for msg in fatal:
-            warnings.warn(msg)
-        return out
+        return log_records(rows, first, last, mt=mt, strict=strict)
+
+
+def log_records(rows, first: int, last: int, mt=None, strict: bool = True, who: str = ""):
+    """Frames [first, last) of a log ring `rows` (log_frames x LOOP_LOG_DOUBLES, on the host) as LoopEngine.read_log's records,
+    with its handling of the frames' condition bits; mt: the counted draws' status words of a seeded stream, a word per row;
+    who: what the messages call the ring's owner (a batch's "trajectory b, ")."""
+    import warnings
+    log_frames = rows.shape[0]
+    out, fatal = [], []
+    for f in range(first, last):
+        L = rows[f % log_frames]
+        npres = int(L[10])
+        cl = L[16:16 + 19 * min(npres, 8)].reshape(-1, 19)
+        err = int(L[15])
+        # condition bits of THIS frame (the device clears the word once the row holds it)
+        if err & (1 | 2):
+            warnings.warn(f"{who}frame {f}: more than {_lib.LOOP_MAX_CLUSTERS - 2} clusters in one frame - the labels beyond that limit, and the "
+                          "annealing driven by them, are not the reference's (min_samples = n / 5 allows about five)")
+        if err & 8:
+            warnings.warn(f"{who}frame {f}: {npres} cluster labels present, the log row keeps the centres of the first 8")
+        if err & 4:
+            fatal.append(f"{who}frame {f}: the live particle count exceeded the bound the launches were sized for; "
+                         "the particles beyond it were not processed in this frame")
+        if err & 32:
+            fatal.append(f"{who}frame {f}: DBSCAN saw non-finite particle translations or a cloud of more than 2^21 cells per axis; labels undefined")
+        if err & 64:
+            fatal.append(f"{who}frame {f}: DBSCAN on a cloud wider than 128 cells per axis with more than 2^20 particles (hash table capacity); labels undefined")
+        if err & 128:
+            fatal.append(f"{who}frame {f}: the engine stated that annealing could not act (live count == floor == init_particles) and the "
+                         "rule wanted to: the set was left as it was")
+        bits = int(mt[f % log_frames]) if mt is not None else 0
+        if bits:
+            why = [w for b, w in ((_lib.MT_STATUS_COUNT_RANGE, "a count exceeded the bound its draw was sized for"),
+                                  (_lib.MT_STATUS_NORMAL_SHORT, "a live count below 6 - fewer than 16 normal values, ATen's scalar path"))
+                   if bits & b]
+            fatal.append(f"{who}frame {f}: the seeded stream drew nothing ({'; '.join(why)}): the frame's draws are undefined")
+        out.append(dict(frame=f, n=int(L[1]), n_after=int(L[2]), rmse_t=float(L[3]), rmse_r=float(L[4]), kept=int(L[5]),
+                        drifted=bool(L[6]), status=int(L[7]), mode=int(L[8]), k=int(L[9]), clusters=npres, var=float(L[11]),
+                        S=float(L[12]), raw=bool(L[13]), ncl=int(L[14]), err=int(L[15]),
+                        cluster_poses=cl[:, :16].reshape(-1, 4, 4).astype(np.float32), cluster_stds=cl[:, 16:].astype(np.float32)))
+    if fatal and strict:
+        e = MidasError("; ".join(fatal))
+        e.records = out
+        raise e
+    for msg in fatal:
+        warnings.warn(msg)
+    return out

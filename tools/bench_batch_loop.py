@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Batch frame of BatchLoopEngine (midas_loop_step_batch: B clustering and annealing filters per set of launches) against what the
+same trajectories cost one after the other: B x the frame of a single LoopEngine with the same settings.
+
+usage: bench_batch_loop.py [B [N0 [K [T [repeats]]]]]   (64, 10000, 50000, 300 frames, 3 repeats; D = 512, floor 1000, DBSCAN
+every 50th frame).  Every frame is bracketed by device events.  Per repeat: median and mean of the DBSCAN frames and of the others.
+One JSON line per engine form with each figure's median over the repeats and [min, max]:
+  batch_loop      BatchLoopEngine, B trajectories per frame
+  single_loop     one LoopEngine on trajectory 0 (seed + 0) - and B x its median frame, the figure the batch frame has to beat
+  pipelined_fixed PipelinedBatchFilterEngine at the same B and N0: the fixed-N frame without clustering or annealing (orientation)
+--profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats), no timing."""
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from midastouch_amd import BatchLoopEngine
+from midastouch_amd.engine import PipelinedBatchFilterEngine
+from midastouch_amd.loop_engine import LoopEngine
+from midastouch_amd.synthetic import make_codebook, make_trajectory, wide_start
+
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+profile = "--profile" in sys.argv
+B, N0, K, T, R = (int(argv[i]) if len(argv) > i else d for i, d in enumerate((64, 10000, 50000, 300, 3)))
+D, FLOOR, EVERY, SEED = 512, 1000, 50, 4000
+dev = torch.device("cuda", 0)
+cb = make_codebook(K=K, D=D, seed=1000)
+trajs = [make_trajectory(cb, T=T + 1, seed=2000 + b) for b in range(B)]
+odoms = torch.as_tensor(np.stack([tr.odoms for tr in trajs], axis=1)).to(dev)            # (T + 1, B, 4, 4)
+codes = torch.as_tensor(np.stack([tr.codes for tr in trajs], axis=1)).to(dev)            # (T + 1, B, D)
+gts = torch.as_tensor(np.stack([tr.gt_poses for tr in trajs], axis=1)).to(dev, torch.float32)
+starts = torch.as_tensor(np.stack([wide_start(cb.extents, trajs[b].gt_poses[0], N0, 3000 + b) for b in range(B)])).to(dev, torch.float32)
+kw = dict(floor=FLOOR, cluster_every=EVERY, device=dev)
+
+
+def timed(step, frames):
+    """ms of every frame by events around its enqueue (the stream is idle at the start, the frames queue behind each other)."""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(frames + 1)]
+    torch.cuda.synchronize()
+    ev[0].record()
+    for t in range(frames):
+        step(t)
+        ev[t + 1].record()
+    torch.cuda.synchronize()
+    return [ev[t].elapsed_time(ev[t + 1]) for t in range(frames)]
+
+
+def summary(ms):
+    db = [v for t, v in enumerate(ms) if t % EVERY == 0]
+    rest = [v for t, v in enumerate(ms) if t % EVERY != 0]
+    us = lambda v: round(1e3 * v, 2)  # noqa: E731
+    return {"frame_median_us": us(statistics.median(rest)), "frame_mean_us": us(statistics.fmean(rest)),
+            "dbscan_frame_median_us": us(statistics.median(db)), "dbscan_frame_mean_us": us(statistics.fmean(db))}
+
+
+def over_repeats(rows):
+    return {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)} for k in rows[0]}
+
+
+def run_batch():
+    eng = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, **kw)
+    eng.set_particles(starts)
+    eng.project_to_codebook()
+    ms = timed(lambda t: eng.step(odoms[t + 1], codes[t + 1], gts=gts[t + 1]), T)
+    n = eng.n
+    return ms, {"n_final_min": min(n), "n_final_max": max(n)}
+
+
+def run_single():
+    eng = LoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N0, seed=SEED, **kw)
+    eng.set_particles(starts[0])
+    eng.project_to_codebook()
+    ms = timed(lambda t: eng.step(odoms[t + 1, 0], codes[t + 1, 0], gt=gts[t + 1, 0]), T)
+    return ms, {"n_final": eng.n}
+
+
+def run_fixed():
+    eng = PipelinedBatchFilterEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, device=dev)
+    eng.set_particles(starts)
+    eng.project_to_codebook()
+    ms = timed(lambda t: eng.step(odoms[t + 1], codes[t + 1], gts=gts[t + 1]), T)
+    eng.flush()
+    return ms, {}
+
+
+if profile:
+    run_batch()
+    torch.cuda.synchronize()
+    sys.exit(0)
+
+head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R}
+out = {}
+for name, run in (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed)):
+    run()  # warm-up: code objects, scratch, allocator
+    rows, extra = [], {}
+    for _ in range(R):
+        ms, extra = run()
+        rows.append(summary(ms))
+    out[name] = over_repeats(rows)
+    print(json.dumps({"form": name, **head, **out[name], **extra, "per_repeat": rows}), flush=True)
+one, batch = out["single_loop"], out["batch_loop"]
+print(json.dumps({"form": "comparison", **head,
+                  "B_single_frames_us": round(B * one["frame_median_us"]["median"], 1),
+                  "batch_frame_us": batch["frame_median_us"]["median"],
+                  "speedup_frame": round(B * one["frame_median_us"]["median"] / batch["frame_median_us"]["median"], 2),
+                  "B_single_dbscan_frames_us": round(B * one["dbscan_frame_median_us"]["median"], 1),
+                  "batch_dbscan_frame_us": batch["dbscan_frame_median_us"]["median"],
+                  "speedup_dbscan_frame": round(B * one["dbscan_frame_median_us"]["median"] / batch["dbscan_frame_median_us"]["median"], 2)}), flush=True)
