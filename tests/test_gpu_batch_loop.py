@@ -3,7 +3,10 @@ LoopEngines - engine b built with seed + b and the same settings, stepped with r
 every trajectory: the whole log row, the frame's per-particle arrays, the annealed set and the resampled set, bit for bit.
 
 In every case the first half of the single engines is stepped before the batch frame and the rest after it, so the single path is
-exercised on both sides of the batch launches in one process."""
+exercised on both sides of the batch launches in one process.
+
+tests/test_gpu_batch_loop_regime.py takes the same comparison to the rest of the regime: 16 384 particles, B = 64, D = 512, every
+option of step() and set_particles(), the log ring and the epoch restart."""
 import ctypes as C
 
 import numpy as np
@@ -53,11 +56,14 @@ def _wide_start(oracle, cb, traj, N0, gseed):
     return cb.poses[loop.f.SE3_NN_idx(poses)]
 
 
-def _engines(dev, cb, B, cap, seed, **kw):
+def _engines(dev, cb, B, cap, seed, index=None, **kw):
+    """B LoopEngines (seed + b) and the BatchLoopEngine.  index: (tactile_tree on the device, ops.Tree of the mesh) that all of
+    them share instead of an index each (engine.codebook_index)."""
     from midastouch_amd import BatchLoopEngine
     from midastouch_amd.loop_engine import LoopEngine
-    singles = [LoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, cap, seed=seed + b, device=dev, **kw) for b in range(B)]
-    batch = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, cap, seed=seed, device=dev, **kw)
+    src = (cb.poses, cb.embeddings, cb.mesh_vertices) if index is None else (index[0], None, index[1])
+    singles = [LoopEngine(*src, cap, seed=seed + b, device=dev, **kw) for b in range(B)]
+    batch = BatchLoopEngine(*src, B, cap, seed=seed, device=dev, **kw)
     return singles, batch
 
 
@@ -68,30 +74,35 @@ def _start(singles, batch, starts):
     assert batch.n == [len(p) for p in starts]
 
 
-def _frame(singles, batch, trajs, t, **kw):
-    """Frame t of every engine (trajectory row b = trajs[b]'s frame t + 1) and the comparison of everything it left."""
+def _frame(singles, batch, trajs, t, gt=True, rows=None, **kw):
+    """Frame t of every engine (trajectory row b = trajs[b]'s frame t + 1) and the comparison of everything it left.  gt=False:
+    a frame without ground truth; rows: the trajectories whose arrays are compared (default: all) - the log row is compared for
+    every trajectory, and the returned views are those of `rows`."""
     B = len(singles)
     odoms = torch.as_tensor(np.stack([tr.odoms[t + 1] for tr in trajs]))
     codes = torch.as_tensor(np.stack([tr.codes[t + 1] for tr in trajs]))
     gts = torch.as_tensor(np.stack([tr.gt_poses[t + 1] for tr in trajs]))
     first = (B + 1) // 2
     for b in range(first):
-        singles[b].step(odoms[b], codes[b], gt=gts[b], **kw)
-    batch.step(odoms, codes, gts=gts, **kw)
+        singles[b].step(odoms[b], codes[b], gt=gts[b] if gt else None, **kw)
+    batch.step(odoms, codes, gts=gts if gt else None, **kw)
     for b in range(first, B):
-        singles[b].step(odoms[b], codes[b], gt=gts[b], **kw)
+        singles[b].step(odoms[b], codes[b], gt=gts[b] if gt else None, **kw)
     views = []
+    slot = (batch.step_count - 1) % batch.log_frames
     for b in range(B):
-        fs, fb = singles[b].frame_view(), batch.frame_view(b)
-        slot = t % batch.log_frames
         # the whole log row, as bits (NaN fields included)
         assert torch.equal(batch._log[b, slot].view(torch.int64), singles[b]._log[slot].view(torch.int64)), f"frame {t}, trajectory {b}: log row"
+        if rows is not None and b not in rows:
+            continue
+        fs, fb = singles[b].frame_view(), batch.frame_view(b)
         assert (fb["n"], fb["n_after"]) == (fs["n"], fs["n_after"])
         for k in PER_PARTICLE:
             assert fb[k].shape == fs[k].shape and torch.equal(fb[k], fs[k]), f"frame {t}, trajectory {b}: {k}"
         assert np.array_equal(fb["cluster_poses"], fs["cluster_poses"]) and np.array_equal(fb["cluster_stds"], fs["cluster_stds"])
         views.append(fb)
-    assert batch.n == [v["n_after"] for v in views]
+    if rows is None:
+        assert batch.n == [v["n_after"] for v in views]
     return views
 
 
