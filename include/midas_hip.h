@@ -265,6 +265,21 @@ typedef struct midas_mt_counted_segment {
 int midas_mt19937_draws_counted(midas_ctx* ctx, uint32_t* state_dev, int64_t skip_words, int32_t nseg,
                                 const midas_mt_counted_segment* segs, const float* radius_dev, const float* cos_dev,
                                 const float* sin_dev, int32_t* status_dev);
+/* midas_mt19937_draws_counted for B streams by one call - B seeded runs of the reference's own loop, one trajectory each, whose
+ * particle counts differ from row to row and from frame to frame (a sweep over trials: torch.manual_seed(s_b) per process,
+ * modules/particle_filter.py:326-335, :245), drawn for BatchLoopEngine without reading a count back.
+ *   states_dev    (in/out) B rows of 626 uint32; rows may stand at different positions inside their blocks.
+ *   segs          describe row 0: stream b reads segment i's count at count_dev + b x count_stride (int32 units - a (B, stride) array
+ *                 of control blocks), and writes its draw at out_dev + b x per x bound elements.
+ *   status_dev    stream b ORs its bits into status_dev[b x status_stride].
+ * One workgroup per stream (grid = B) walks state row b as far as ITS counts ask; the transforms take the stream as grid.y.  Row b
+ * is, number for number, midas_mt19937_draws_counted on that state row alone: the outputs, the state afterwards and the words
+ * consumed.  A zero count consumes nothing; a count out of range or a normal draw of 1 .. 15 values sets only that row's status and
+ * consumes nothing of that row - the other rows proceed; elements beyond a row's count are not written.  B = 1 is the single call
+ * (the strides are then unused); B > 1 wants both strides positive.  Scratch: B x the single call's. */
+int midas_mt19937_draws_counted_batch(midas_ctx* ctx, int32_t B, uint32_t* states_dev, int64_t skip_words, int32_t nseg,
+                                      const midas_mt_counted_segment* segs, int64_t count_stride, const float* radius_dev,
+                                      const float* cos_dev, const float* sin_dev, int32_t* status_dev, int64_t status_stride);
 
 /* ---- resample  (K6, K7, K8) ------------------------------------------------------------------ */
 /* cdf = blocked_prefix(w) / total, cdf[N-1] = 1 (float64, fixed summation order - DESIGN.md).
@@ -970,6 +985,22 @@ int midas_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* 
 #define MIDAS_LOOP_BATCH_MAX_CAP 16384
 int midas_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                           const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);
+/* midas_loop_step_batch with the draws and the tie rule of a seeded run of the reference - B processes of bash/run_filter.sh under
+ * torch.manual_seed(s_b), each replayed particle for particle: the motion noise of add_noise_to_odom (modules/particle_filter.py:326-335),
+ * the uniforms of the resampler's torch.multinomial (:245) and, inside a tie, the members annealing's torch.topk keeps on the CPU
+ * (:433-441).  The same arguments, layout and regime (cap <= MIDAS_LOOP_BATCH_MAX_CAP, grid_n == 0, anneal_frozen == 0, a float32
+ * codebook with sparse scoring, 1 <= B <= 65535; anything else is MIDAS_ERR_INVALID with nothing enqueued), and in addition:
+ *   tn_dev, rot_dev  both NULL (Philox keyed (seed + b, step)) or both (B, cap, 3) float32: trajectory b's draws from b x cap x 3 on,
+ *                    the first 3 n_b of them read (n_b its live count);
+ *   u_dev            NULL (Philox) or (B, cap) float64: trajectory b's n_set_b uniforms from b x cap on;
+ *   topk_ties        MIDAS_TOPK_TIES_INDEX, or MIDAS_TOPK_TIES_ATEN_CPU: every trajectory's decision (cluster rows, variance,
+ *                    ctl_i[MODE, K, NSET]) by the kernel midas_loop_step runs for it, then B one-wave walks of ATen's algorithm side
+ *                    by side, the other kernels of that path with the trajectory as grid.y.
+ * `phases` may be a subset: a seeded frame is FRONT | DBSCAN | ANNEAL, then - once the uniforms are drawn for the annealed counts
+ * (midas_mt19937_draws_counted_batch on ctl_i[b][MIDAS_LOOP_I_NSET]) - RESAMPLE.  With NULL draws and ties by index the call is
+ * midas_loop_step_batch; with these draws trajectory b holds the bits of midas_loop_step on it alone with the same draws. */
+int midas_loop_step_batch_draws(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                                const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);
 /* cluster_particles(method="euclidean") alone (particle_filter.py:208-217): labels_dev[i] = DBSCAN label of pose i's
  * translation, eps as given, min_samples < 0 -> N / 5.  Exact float64 predicate |dx|^2 <= eps^2, clusters numbered by their
  * first core point, border points to the smallest adjacent cluster - what sklearn's DBSCAN returns.  Any extent (dense cell grid

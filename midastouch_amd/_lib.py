@@ -257,6 +257,7 @@ SIGNATURES = {
     "midas_mt19937_draws": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I32]),
     "midas_mt19937_draws_batch": (C.c_int, [_P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _I32]),
     "midas_mt19937_draws_counted": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
+    "midas_mt19937_draws_counted_batch": (C.c_int, [_P, _I32, _P, _I64, _I32, _P, _I64, _P, _P, _P, _P, _I64]),
     "midas_resample_search": (C.c_int, [_P, _I64, _P, _I64, _I32, _P, _F, _U64, _U64, _P]),
     "midas_gather_rows": (C.c_int, [_P, _I64, _P, _P, _P, _I32]),
     "midas_rmse": (C.c_int, [_P, _I64, _P, _P, _P]),
@@ -284,6 +285,7 @@ SIGNATURES = {
     "midas_lazy_flush_batch": (C.c_int, [_P, C.POINTER(LazyFlushArgs), _I32]),
     "midas_loop_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32]),
     "midas_loop_step_batch": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64]),
+    "midas_loop_step_batch_draws": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64]),
     "midas_dbscan": (C.c_int, [_P, _I64, _P, _D, _I64, _P, _P]),
     "midas_dbscan_points": (C.c_int, [_P, _I64, C.c_int32, _P, _D, _I64, _P, _P]),
     "midas_anneal_select": (C.c_int, [_P, _I64, _P, _I32, _I64, _P]),

@@ -7,10 +7,16 @@ block, its own labels, cluster rows and log ring - and the kernels of the small-
 Trajectory b draws from the Philox streams keyed (seed + b, frame): frame for frame it holds the bits of a LoopEngine built with
 seed + b and stepped with row b of the operands.
 
-The first version covers the small-set regime only: at most 16 384 particles per trajectory (`_lib.LOOP_BATCH_MAX_CAP`), device
-Philox draws, ties of annealing's top-k by index, a float32 codebook scored sparsely.  Host draws (`tn` / `rot` / `u`), seeded torch
-streams, the ATen tie rule, larger sets and sharding stay with LoopEngine and the sharded engine.  DBSCAN frames run the single
-pass once per trajectory, one after the other on the stream, on one shared set of cell tables.
+The regime is the small set: at most 16 384 particles per trajectory (`_lib.LOOP_BATCH_MAX_CAP`), a float32 codebook scored
+sparsely.  Larger sets and sharding stay with LoopEngine and the sharded engine.  DBSCAN frames run the single pass once per
+trajectory, one after the other on the stream, on one shared set of cell tables.
+
+Seeded runs: `seed_torch_streams(seeds)` makes trajectory b a process of the reference under `torch.manual_seed(seeds[b])` - its
+motion noise and its resampler's uniforms come from a device replica of torch's CPU generator (torch_rng.TorchCpuStreams), sized by
+the live and annealed counts in ITS control block, and ties of annealing's `torch.topk` go to the members ATen's CPU kernel keeps
+(`topk_ties = "aten_cpu"`, settable on its own too).  Row b then holds, frame for frame, the bits of a LoopEngine built with
+`topk_ties="aten_cpu"` and `seed_torch_stream(seeds[b])` - the reference's particles - through `midas_loop_step_batch_draws`; a frame
+is four enqueues and reads nothing back.
 """
 from __future__ import annotations
 
@@ -76,17 +82,40 @@ class BatchLoopEngine:
         a.floor, a.eps = self.floor, self.eps
         a.telemetry, a.score_stamps = _ptr(self.telemetry), _ptr(self._stamps)
         a.topk_ties = _lib.TOPK_TIES_INDEX
+        self._topk_ties = "index"
+        self.torch_streams = None  # seed_torch_streams
         # The scratch every phase combination of a batch frame asks for, reserved now so that no frame allocates: per trajectory the
         # hand-over records of the front (32 B a particle), the block results, the cluster-moment partials (64 x 36 doubles per 256
         # particles) and cluster rows, the resample's prefix values; once, DBSCAN's cell tables (84 MB + 41 B a particle).
+        per_traj = self._per_traj()
+        self._scratch = (128 << 20) + 256 * cap + B * per_traj + 64 * 256
+        self.ctx.call("midas_scratch_reserve", self._scratch)
+
+    # whom annealing's torch.topk takes inside a tie: "index" (torch's CUDA rule, the radix select: midas_loop_step_batch as ever) or
+    # "aten_cpu" (the reference as it runs on the CPU, topk_aten.hip: midas_loop_step_batch_draws); settable between frames
+    @property
+    def topk_ties(self):
+        return self._topk_ties
+
+    @topk_ties.setter
+    def topk_ties(self, rule):
+        self._args.topk_ties = {"index": _lib.TOPK_TIES_INDEX, "aten_cpu": _lib.TOPK_TIES_ATEN_CPU}[rule]
+        if rule == "aten_cpu":  # the walk's queue, stopper lists, marks and block counts per trajectory, beside the frame's own
+            cap = self.cap
+            self._scratch = max(self._scratch, (128 << 20) + 256 * cap + self.B * (self._per_traj() + 25 * cap + 4 * ((cap + 4095) // 4096)) + 80 * 256)
+            self.ctx.call("midas_scratch_reserve", self._scratch)
+        self._topk_ties = rule
+
+    def _per_traj(self):
+        cap = self.cap
         nb, nb256 = (cap + 4095) // 4096, (cap + 255) // 256
-        per_traj = (32 * cap + 32 * nb + 8 * 64 * 10 + 8 * 36 * 64 * nb256 + 4 * 64 * 16 + 4 * 64 * 3 + 8 * 64 + 8 * (cap + 16) + 12 * nb)
-        self.ctx.call("midas_scratch_reserve", (128 << 20) + 256 * cap + B * per_traj + 64 * 256)
+        return 32 * cap + 32 * nb + 8 * 64 * 10 + 8 * 36 * 64 * nb256 + 4 * 64 * 16 + 4 * 64 * 3 + 8 * 64 + 8 * (cap + 16) + 12 * nb
 
     # ---- state ----------------------------------------------------------------------------------------------------
-    def set_particles(self, poses, labels=None):
+    def set_particles(self, poses, labels=None, reset_annealing: bool = True):
         """Start (or restart) every trajectory: poses (B, n, 4, 4), or a list of B tensors (n_b, 4, 4) with n_b <= capacity each;
-        labels likewise, default 0 like `Particles` (particle_filter.py:47).  Annealing starts over."""
+        labels likewise, default 0 like `Particles` (particle_filter.py:47).  Annealing starts over, unless reset_annealing=False:
+        every trajectory then keeps its particle_var, init_particles and frame count, as LoopEngine.set_particles does."""
         if isinstance(poses, (list, tuple)):
             poses = [torch.as_tensor(p).to(self.device, torch.float32).reshape(-1, 4, 4) for p in poses]
         else:
@@ -108,6 +137,10 @@ class BatchLoopEngine:
                 if lb.numel() != n:
                     raise MidasError(f"trajectory {b}: {lb.numel()} labels for {n} particles")
         ci = torch.zeros((self.B, 32), dtype=torch.int32)
+        if not reset_annealing:
+            old = self.ctl_i.cpu()
+            for k in (_lib.LOOP_I_INIT, _lib.LOOP_I_VARSET, _lib.LOOP_I_FRAME):
+                ci[:, k] = old[:, k]
         self._hint.fill_(-1)
         self._labels.zero_()
         for b, (p, n) in enumerate(zip(poses, ns)):
@@ -119,9 +152,60 @@ class BatchLoopEngine:
             ci[b, _lib.LOOP_I_N] = n
             ci[b, _lib.LOOP_I_NSET] = n
             ci[b, _lib.LOOP_I_NCL] = ncl
-        self.ctl_d.zero_()
+        if reset_annealing:
+            self.ctl_d.zero_()
         self.ctl_i.copy_(ci)
         self._n_host = ns
+
+    def set_annealing_state(self, particle_vars, init_particles):
+        """particle_filter.particle_var / init_particles (particle_filter.py:413-417) of every trajectory, B of each - for restarts
+        and replays, as LoopEngine.set_annealing_state per row."""
+        import numpy as np
+        pv, ip = [float(v) for v in particle_vars], [int(v) for v in init_particles]
+        if len(pv) != self.B or len(ip) != self.B:
+            raise MidasError(f"{len(pv)} variances and {len(ip)} counts for a batch of {self.B} trajectories")
+        ci, cd = self.ctl_i.cpu(), self.ctl_d.cpu()
+        for b in range(self.B):
+            ci[b, _lib.LOOP_I_VARSET] = 0 if np.isinf(pv[b]) else 1
+            ci[b, _lib.LOOP_I_INIT] = ip[b]
+            cd[b, _lib.LOOP_D_VARPREV] = float(np.float32(pv[b])) if not np.isinf(pv[b]) else 0.0
+        self.ctl_i.copy_(ci)
+        self.ctl_d.copy_(cd)
+
+    # ---- seeded runs ----------------------------------------------------------------------------------------------
+    def seed_torch_streams(self, seeds):
+        """Trajectory b draws as a process of the reference under torch.manual_seed(seeds[b]) (or continues the torch.Generator
+        seeds[b]): `torch.normal(0, mul * sig_t, (n_b, 3))`, `torch.normal(0, mul * sig_r, (n_b, 3))` with n_b ITS live count
+        (add_noise_to_odom, particle_filter.py:326-335) and, behind annealing, n_set_b float64 uniforms (the resampler's
+        torch.multinomial, :245), all counts read on the device (midas_mt19937_draws_counted_batch); ties of annealing's top-k follow
+        ATen's CPU kernel (`topk_ties` becomes "aten_cpu").  Returns the TorchCpuStreams (manual_seed / from_host / to_host per
+        row).  seeds=None: back to Philox draws and ties by index.
+        The generator runs on the engine's stream; its scratch and the walk's are reserved here, so no frame allocates.  A live
+        count below 6 (fewer than 16 normal values: ATen's scalar path, not modelled) or beyond the capacity is reported per
+        trajectory by read_log()."""
+        if seeds is None:
+            self.torch_streams = None
+            self.topk_ties = "index"
+            return None
+        seeds = list(seeds)
+        if len(seeds) != self.B:
+            raise MidasError(f"{len(seeds)} seeds for a batch of {self.B} trajectories")
+        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
+            raise MidasError("a seeded torch stream reproduces torch.multinomial's draws: resample='weighted_random' only")
+        from .torch_rng import TorchCpuStreams
+        st = TorchCpuStreams(seeds, self.device, overlap=False, pieces=0)
+        st._normal_tables()  # (uploaded now, not by the first frame)
+        B, cap, d = self.B, self.cap, self.device
+        self._tn, self._rot = (torch.zeros((B, cap, 3), dtype=torch.float32, device=d) for _ in range(2))
+        self._u = torch.zeros((B, cap), dtype=torch.float64, device=d)
+        self._mt_status = torch.zeros((B, self.log_frames), dtype=torch.int32, device=d)  # the counted calls' status, a word per log row
+        self.topk_ties = "aten_cpu"
+        ci = (self.ctl_i, _lib.LOOP_I_N)
+        self._scratch = max(self._scratch, st.counted_scratch_bytes([("normal", 0.0, 1.0, *ci, 3, cap)] * 2),
+                            st.counted_scratch_bytes([("rand64", *ci, cap)]))
+        self.ctx.call("midas_scratch_reserve", self._scratch)  # (the generator shares the engine's context)
+        self.torch_streams = st
+        return st
 
     def project_to_codebook(self):
         """poses := codebook pose nearest to each particle (filter/filter.py:159-160), every trajectory's live set."""
@@ -174,9 +258,32 @@ class BatchLoopEngine:
         a.unit_weights = int(bool(unit_weights))
         a.score_epoch = advance_epoch(self)
         self._keep = (odoms, codes, gts)  # keep operands alive until the stream has consumed them
-        self.ctx.bind_current_stream()
-        self.ctx.check(self.ctx.lib.midas_loop_step_batch(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(phases),
-                                                          self.B, self.log_frames * _lib.LOOP_LOG_DOUBLES))
+        st, log_stride = self.torch_streams, self.log_frames * _lib.LOOP_LOG_DOUBLES
+
+        def call(entry, ph):
+            self.ctx.bind_current_stream()
+            self.ctx.check(entry(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(ph), self.B, log_stride))
+
+        if st is not None:
+            # the stream's draws: the motion noise sized by every row's live count, the frame up to annealing, the uniforms sized by
+            # every row's annealed count, the resample - four enqueues, the counts never leave the device
+            slot = self.step_count % self.log_frames
+            if slot == 0:
+                self._mt_status.zero_()  # (the ring starts over, as the log's rows do)
+            status = (self._mt_status, slot, self.log_frames)
+            st.draws_counted_async([("normal", 0.0, a.std_t, self.ctl_i, _lib.LOOP_I_N, 3, self.cap),
+                                    ("normal", 0.0, a.std_r, self.ctl_i, _lib.LOOP_I_N, 3, self.cap)], outs=[self._tn, self._rot], status=status)
+            a.tn, a.rot, a.u = _ptr(self._tn), _ptr(self._rot), _ptr(self._u)
+            try:
+                call(self.ctx.lib.midas_loop_step_batch_draws, phases & ~_lib.LOOP_RESAMPLE)
+                st.draws_counted_async([("rand64", self.ctl_i, _lib.LOOP_I_NSET, self.cap)], outs=[self._u], status=status)
+                call(self.ctx.lib.midas_loop_step_batch_draws, _lib.LOOP_RESAMPLE)
+            finally:
+                a.tn = a.rot = a.u = None
+        elif self._topk_ties == "aten_cpu":
+            call(self.ctx.lib.midas_loop_step_batch_draws, phases)  # (Philox draws, the ATen tie rule)
+        else:
+            call(self.ctx.lib.midas_loop_step_batch, phases)
         self._labels_prev = self._labels
         self._labels, self._labels_next = self._labels_next, self._labels
         self.step_count += 1
@@ -185,9 +292,14 @@ class BatchLoopEngine:
     # ---- results --------------------------------------------------------------------------------------------------
     def read_log(self, first: int = 0, last: int = None, strict: bool = True, rows=None):
         """Per trajectory, LoopEngine.read_log's records of frames [first, last) - a list of B lists, one read-back - with its
-        handling of the frames' condition bits.  rows: only these trajectories (a list in their order)."""
+        handling of the frames' condition bits, a seeded stream's short or out-of-range draw included (reported for the trajectory
+        it happened to).  rows: only these trajectories (a list in their order)."""
         last = self.step_count if last is None else min(last, self.step_count)
         first = max(first, last - self.log_frames)
         which = range(self.B) if rows is None else rows
         log = (self._log if rows is None else self._log[list(rows)]).cpu().numpy()
-        return [log_records(log[i], first, last, strict=strict, who=f"trajectory {b}, ") for i, b in enumerate(which)]
+        mt = None
+        if self.torch_streams is not None:  # (seed_torch_streams: the counted draws' status, a word per trajectory and row)
+            mt = (self._mt_status if rows is None else self._mt_status[list(rows)]).cpu().numpy()
+        return [log_records(log[i], first, last, mt=None if mt is None else mt[i], strict=strict, who=f"trajectory {b}, ")
+                for i, b in enumerate(which)]

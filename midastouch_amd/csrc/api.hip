@@ -503,6 +503,22 @@ MIDAS_EXPORT int midas_mt19937_draws_counted(midas_ctx* ctx, uint32_t* state_dev
     return launch_mt_draws_counted(ctx, state_dev, skip_words, nseg, segs, radius_dev, cos_dev, sin_dev, status_dev);
 }
 
+MIDAS_EXPORT int midas_mt19937_draws_counted_batch(midas_ctx* ctx, int32_t B, uint32_t* states_dev, int64_t skip_words, int32_t nseg,
+                                                   const midas_mt_counted_segment* segs, int64_t count_stride, const float* radius_dev,
+                                                   const float* cos_dev, const float* sin_dev, int32_t* status_dev, int64_t status_stride) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, B >= 1 && B <= 65535 && states_dev != nullptr && skip_words >= 0 && nseg >= 1 && nseg <= 8 && segs != nullptr &&
+                           status_dev != nullptr && count_stride >= 0 && status_stride >= 0);
+    MIDAS_REQUIRE(ctx, B == 1 || (count_stride > 0 && status_stride > 0));  // (every stream its own counts and status word)
+    for (int i = 0; i < nseg; ++i) {
+        const midas_mt_counted_segment& g = segs[i];
+        MIDAS_REQUIRE(ctx, g.kind == MIDAS_MT_SEGMENT_RAND64 || (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && radius_dev && cos_dev && sin_dev));
+        MIDAS_REQUIRE(ctx, g.count_dev != nullptr && g.per >= 1 && g.bound >= 0 && g.bound <= 0x7fffffff / g.per && (g.bound == 0 || g.out_dev));
+    }
+    return launch_mt_draws_counted_batch(ctx, B, states_dev, skip_words, nseg, segs, count_stride, radius_dev, cos_dev, sin_dev, status_dev,
+                                         status_stride);
+}
+
 MIDAS_EXPORT int midas_resample_search(midas_ctx* ctx, int64_t N, const double* cdf_dev, int64_t M, int32_t mode,
                                        const double* u_dev, float u32, uint64_t seed, uint64_t step, int32_t* idx_dev) {
     MIDAS_ENTER(ctx);
@@ -1414,6 +1430,36 @@ MIDAS_EXPORT int midas_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb,
     // the small-set regime with device draws (include/midas_hip.h)
     MIDAS_REQUIRE(ctx, s.tn_dev == nullptr && s.rot_dev == nullptr && s.u_dev == nullptr);
     MIDAS_REQUIRE(ctx, s.topk_ties == MIDAS_TOPK_TIES_INDEX && s.grid_n == 0 && s.anneal_frozen == 0);
+    MIDAS_REQUIRE(ctx, s.log_dev == nullptr || log_stride >= MIDAS_LOOP_LOG_DOUBLES || B == 1);
+    if (phases & MIDAS_LOOP_FRONT) {
+        MIDAS_REQUIRE(ctx, cb && tree6 && tree3 && tree6->dim == 6 && tree3->dim == 3 && tree6->K == cb->K);
+        MIDAS_REQUIRE(ctx, s.odom16_dev && s.code_dev && s.cb_poses_dev && (uintptr_t)s.cb_poses_dev % 16 == 0);
+        MIDAS_REQUIRE(ctx, cb->dtype == MIDAS_F32 && (cb->D == 128 || cb->D == 256 || cb->D == 512 || cb->D == 1024) &&
+                               (uintptr_t)cb->emb % 16 == 0 && (uintptr_t)s.code_dev % 16 == 0);
+        MIDAS_REQUIRE(ctx, s.score_stamps_dev != nullptr && s.score_epoch != 0);
+    }
+    if (phases & MIDAS_LOOP_DBSCAN) MIDAS_REQUIRE(ctx, s.eps > 0.0);
+    if (phases & MIDAS_LOOP_RESAMPLE)
+        MIDAS_REQUIRE(ctx, s.resample_mode == MIDAS_RESAMPLE_MULTINOMIAL || s.resample_mode == MIDAS_RESAMPLE_SYSTEMATIC);
+    return launch_loop_step_batch(ctx, cb, tree6, tree3, s, phases, B, log_stride);
+}
+
+MIDAS_EXPORT int midas_loop_step_batch_draws(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                                             const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, args != nullptr && phases != 0 && (phases & ~15) == 0);
+    const midas_loop_args& s = *args;
+    MIDAS_REQUIRE(ctx, B >= 1 && B <= 65535);
+    MIDAS_REQUIRE(ctx, s.cap > 0 && s.cap <= MIDAS_LOOP_BATCH_MAX_CAP && s.ctl_i_dev && s.ctl_d_dev);
+    MIDAS_REQUIRE(ctx, s.poses_dev && s.poses_prop_dev && s.poses_dev != s.poses_prop_dev && s.hint_dev && s.nn_idx_dev && s.valid_dev &&
+                           s.x_dev && s.e_dev && s.weights_dev && s.weights_out_dev && s.labels_dev && s.labels_out_dev &&
+                           s.labels_dev != s.labels_out_dev && s.src_dev && s.ridx_dev && s.scores_dev && s.cluster_poses_dev &&
+                           s.cluster_stds_dev);
+    MIDAS_REQUIRE(ctx, (uintptr_t)s.poses_dev % 16 == 0 && (uintptr_t)s.poses_prop_dev % 16 == 0);
+    // midas_loop_step_batch's regime, with host draws and either tie rule (include/midas_hip.h)
+    MIDAS_REQUIRE(ctx, (s.tn_dev == nullptr) == (s.rot_dev == nullptr));
+    MIDAS_REQUIRE(ctx, s.topk_ties == MIDAS_TOPK_TIES_INDEX || s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU);
+    MIDAS_REQUIRE(ctx, s.grid_n == 0 && s.anneal_frozen == 0);
     MIDAS_REQUIRE(ctx, s.log_dev == nullptr || log_stride >= MIDAS_LOOP_LOG_DOUBLES || B == 1);
     if (phases & MIDAS_LOOP_FRONT) {
         MIDAS_REQUIRE(ctx, cb && tree6 && tree3 && tree6->dim == 6 && tree3->dim == 3 && tree6->K == cb->K);

@@ -289,6 +289,7 @@ __global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small(TreeView<Kd6
         if (a.gt16) { a.gt16 += b * 16; a.part_rmse += 2 * b * nwaves; }
         a.sp.stamps += b * a.score_stride; a.sp.scores += b * a.score_stride; a.sp.code += b * (int64_t)(a.sp.nj * 64);
         a.seed += (uint64_t)b;
+        if (a.tn) { a.tn += o * 3; a.rot += o * 3; }  // (midas_loop_step_batch_draws: (B, N, 3) host draws)
         feat += o;
     }
     if (threadIdx.x < 64 && (int)blockIdx.x < nwaves) particle_front_wave(a, (int64_t)blockIdx.x, nullptr, feat);
@@ -430,7 +431,7 @@ int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t
 int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a_in,
                              const midas_codebook* cb, const double* code, double* scores, int32_t B) {
     ParticleUpdateArgs a = a_in;
-    if (!(a.n_live && a.N > 0 && a.N <= 16384 && a.sp.stamps && !a.rs.enabled && !a.tn && cb->dtype == MIDAS_F32 &&
+    if (!(a.n_live && a.N > 0 && a.N <= 16384 && a.sp.stamps && !a.rs.enabled && cb->dtype == MIDAS_F32 &&
           (cb->D == 512 || cb->D == 256 || cb->D == 128 || cb->D == 1024) && (uintptr_t)cb->emb % 16 == 0 && (uintptr_t)code % 16 == 0))
         return midas_set_error(ctx, MIDAS_ERR_INVALID, "launch_front_small_batch", "no small-set front for these arguments");
     a.scores = nullptr;  // deferred: k_loop_xe gathers the scores

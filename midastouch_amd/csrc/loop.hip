@@ -285,8 +285,20 @@ __global__ __launch_bounds__(256) void k_loop_decide(int32_t* __restrict__ ctl_i
                                                      float* __restrict__ stds_out, uint32_t* __restrict__ hist,
                                                      int32_t* __restrict__ sel_state, int32_t floor_n, const double* __restrict__ rot,
                                                      int32_t frozen = 0) {
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch_draws): LOOP_MAX_CLUSTERS cluster rows each, no select state
+        const int64_t b = blockIdx.y;
+        ctl_i += b * LOOP_CTL_I; ctl_d += b * LOOP_CTL_D;
+        centers_all += b * LOOP_MAX_CLUSTERS * 16; stds_all += b * LOOP_MAX_CLUSTERS * 3; counts_all += b * LOOP_MAX_CLUSTERS;
+        centers_out += b * LOOP_MAX_CLUSTERS * 16; stds_out += b * LOOP_MAX_CLUSTERS * 3; rot += b * LOOP_MAX_CLUSTERS * 10;
+    }
     if (blockIdx.x == 1) { loop_rotations(ctl_i, counts_all, rot, centers_out); return; }
     const int t = threadIdx.x;
+    if (!hist) {  // the decision alone (the batch's ATen walk: no radix select follows)
+        if (t != 0) return;
+        int mode, k;
+        loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k);
+        return;
+    }
     for (int i = t; i < SEL_PASSES * SEL_BINS; i += 256) hist[i] = 0u;
     for (int i = t; i < 4 * (SEL_PASSES + 2); i += 256) sel_state[i] = 0;
     __syncthreads();
@@ -1009,6 +1021,7 @@ __global__ __launch_bounds__(256) void k_loop_resample(LoopResampleArgs a) {
         a.src += o; a.poses_prop += o * 16; a.w += o; a.nn_idx += o; a.labels += o;
         a.poses_out += o * 16; a.weights_out += o; a.hint_out += o; a.labels_out += o; a.ridx += o;
         a.seed += (uint64_t)b;
+        if (a.u) a.u += o;  // (midas_loop_step_batch_draws: (B, cap) host draws)
         if (a.log) a.log += b * a.log_stride;
         a.cluster_poses += b * LOOP_MAX_CLUSTERS * 16; a.cluster_stds += b * LOOP_MAX_CLUSTERS * 3;
         if (a.host_mirror) a.host_mirror += 2 * b;
@@ -1390,7 +1403,9 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 
 // B trajectories per launch (midas_loop_step_batch): the launches of the small-set frame above with the trajectory as grid.y,
 // every array - the caller's and the scratch - (B, ...) contiguous.  The arguments are the regime the entry point checked:
-// cap <= LOOP_SMALL_MAX, device draws, ties by index, no bound below the capacity, sparse scoring.  The regime has one path: the
+// cap <= LOOP_SMALL_MAX, no bound below the capacity, sparse scoring; through midas_loop_step_batch device draws and ties by index,
+// through midas_loop_step_batch_draws also host draws (tn / rot (B, cap, 3), u (B, cap)) and the ATen tie rule, any subset of phases
+// (the decision by k_loop_decide per trajectory and launch_topk_aten's B walks in place of k_loop_anneal_small).  One path each: the
 // single call's `anneal_small` field and its MIDAS_LOOP_MERGE / MIDAS_FRONT_SMALL switches (which pick between bit-identical
 // paths there) are not consulted - k_front_small, the merged weights launch and k_loop_anneal_small always run.
 int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
@@ -1439,9 +1454,16 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
         if ((rc = launch_loop_cluster(ctx, cap, s.ctl_i_dev, s.poses_prop_dev, s.weights_dev, s.labels_dev, (double*)part, (float*)cen,
                                       (float*)sd, (int64_t*)cnt, (double*)rot, weights_merged ? &wa : nullptr, B)))
             return rc;
-        hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, by), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
-                           (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor, (const double*)s.weights_dev, s.src_dev,
-                           (const double*)rot, (int32_t)cap);
+        if (s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU) {  // the decision alone per trajectory, then B walks side by side
+            hipLaunchKernelGGL(k_loop_decide, dim3(2, by), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
+                               (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, (uint32_t*)nullptr, (int32_t*)nullptr, s.floor,
+                               (const double*)rot);
+            if ((rc = launch_topk_aten(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, nullptr, B))) return rc;
+        } else {
+            hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, by), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen,
+                               (const float*)sd, (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor,
+                               (const double*)s.weights_dev, s.src_dev, (const double*)rot, (int32_t)cap);
+        }
         LAUNCH_CHECK(ctx);
     }
     if (phases & MIDAS_LOOP_RESAMPLE) {
@@ -1455,7 +1477,7 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
                            (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)lp, (double*)bt,
                            (int32_t*)bn, (int32_t)cap, (int32_t)lp_stride);
         LoopResampleArgs r;
-        fill_loop_resample(r, s, lp, bt, bn);  // (u_dev is NULL here: the entry point checked)
+        fill_loop_resample(r, s, lp, bt, bn);  // (u_dev: NULL, or (B, cap) through midas_loop_step_batch_draws)
         r.cap2 = (int32_t)cap; r.cap = (int32_t)cap; r.lp_stride = (int32_t)lp_stride; r.log_stride = log_stride;
         hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, st, r);
         LAUNCH_CHECK(ctx);

@@ -579,7 +579,8 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
 // src[0 .. n_set): the annealed particle set as indices - mode 1: the N particles minus the k of smallest weight, in
 // order; mode 2: all N followed by the k of largest weight, best first; ties to the smaller index
 int launch_anneal_select(midas_ctx* ctx, int64_t N, const double* w, int32_t mode, int64_t k, int32_t ties, int32_t* src, int32_t* info);
-int launch_topk_aten(midas_ctx* ctx, int64_t cap, const int32_t* ci, const double* w, int32_t* src, int32_t* info);
+// B trajectories (grid.y): ci (B, 32), w and src (B, cap); info (the fallback counter) with B == 1 only
+int launch_topk_aten(midas_ctx* ctx, int64_t cap, const int32_t* ci, const double* w, int32_t* src, int32_t* info, int32_t B = 1);
 // labels_out[i] in [-1, ncl) for the n = *n_dev (or N when n_dev is null) poses; min_samples < 0 -> n / 5 (cluster_particles);
 // ncl_out[0] = number of clusters; err_out (nullable) |= 2 when the grid / cluster limits were exceeded
 int launch_dbscan_points(midas_ctx* ctx, int64_t N, int32_t dim, const double* pts, double eps, int64_t min_samples, int32_t* labels, int32_t* info);
@@ -598,6 +599,9 @@ int launch_mt_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t sk
                           const float* R, const float* C, const float* S, uint32_t* hist, const uint32_t* polys, int32_t G);
 int launch_mt_draws_counted(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_counted_segment* segs,
                             const float* R, const float* C, const float* S, int32_t* status);
+int launch_mt_draws_counted_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t skip_words, int32_t nseg,
+                                  const midas_mt_counted_segment* segs, int64_t count_stride, const float* R, const float* C, const float* S,
+                                  int32_t* status, int64_t status_stride);
 
 // topn.hip
 int launch_topn_pose_error(midas_ctx* ctx, int32_t B, int64_t K, const double* scores, int64_t row0, int32_t n,

@@ -476,6 +476,8 @@ int launch_mt_draws(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t
 // [2 + 2 i] its first word behind that offset - and walks the words those counts ask for; the transforms' grids are sized by the
 // bounds, a workgroup beyond the live numel returns after one load.  A count outside [0, bound] or a normal draw of 1 .. 15 values
 // sets its status bit; every numel in meta is then 0 and the state stays as it is.
+// B streams (midas_mt19937_draws_counted_batch: B trajectories whose counts differ) are B such workgroups, each with its own raw
+// words and meta row of MT_COUNTED_META entries.
 struct mt_counted_segs {
     const int32_t* count[8];
     long long bound[8];
@@ -484,16 +486,25 @@ struct mt_counted_segs {
 };
 constexpr int MT_COUNTED_META = 1 + 2 * 8;
 
+// B streams (midas_mt19937_draws_counted_batch): workgroup b walks state row b as far as ITS counts ask - the count of segment i at
+// a.count[i] + b count_stride - into raw + b raw_stride, leaves its meta row and ORs its bits into status[b status_stride]; a row
+// whose counts are bad returns alone.
 __global__ __launch_bounds__(MT_THREADS) void k_mt_counted(uint32_t* __restrict__ state, long long skip, mt_counted_segs a,
                                                            uint32_t* __restrict__ raw, long long* __restrict__ meta,
-                                                           int32_t* __restrict__ status) {
+                                                           int32_t* __restrict__ status, long long count_stride = 0,
+                                                           long long raw_stride = 0, long long status_stride = 0) {
+    const long long b = blockIdx.x;
+    state += (size_t)b * (MT_N + 2);
+    raw += (size_t)b * raw_stride;
+    meta += (size_t)b * MT_COUNTED_META;
+    status += b * status_stride;
     long long numel[8], total = 0;
     int bad = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         numel[i] = 0;
         if (i < a.nseg) {
-            const long long cnt = *a.count[i];
+            const long long cnt = a.count[i][b * count_stride];
             if (cnt < 0 || cnt > a.bound[i]) bad |= MIDAS_MT_STATUS_COUNT_RANGE;
             numel[i] = cnt * a.per[i];
             if (a.kind[i] == MIDAS_MT_SEGMENT_NORMAL32 && numel[i] > 0 && numel[i] < 16) bad |= MIDAS_MT_STATUS_NORMAL_SHORT;
@@ -516,9 +527,13 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_counted(uint32_t* __restrict_
     mt_walk(state, skip, total, raw, nullptr);
 }
 
+// grid.y = stream b: raw + b raw_stride, its meta row, out + b out_stride (the segment's per x bound values)
 __global__ __launch_bounds__(256) void k_mt_emit_counted(const uint32_t* __restrict__ raw, const long long* __restrict__ meta, int seg,
-                                                         double* __restrict__ out) {
+                                                         double* __restrict__ out, long long raw_stride = 0, long long out_stride = 0) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    raw += (size_t)blockIdx.y * raw_stride;
+    meta += (size_t)blockIdx.y * MT_COUNTED_META;
+    out += (size_t)blockIdx.y * out_stride;
     if (i >= meta[1 + 2 * seg]) return;
     const uint32_t* w = raw + meta[0] + meta[2 + 2 * seg] + 2 * i;
     out[i] = mt_u53(w[0], w[1]);
@@ -526,7 +541,11 @@ __global__ __launch_bounds__(256) void k_mt_emit_counted(const uint32_t* __restr
 
 __global__ __launch_bounds__(256) void k_mt_normal_counted(const uint32_t* __restrict__ raw, const long long* __restrict__ meta, int seg,
                                                            const float* __restrict__ R, const float* __restrict__ C, const float* __restrict__ S,
-                                                           float mean, float std, float* __restrict__ out) {
+                                                           float mean, float std, float* __restrict__ out, long long raw_stride = 0,
+                                                           long long out_stride = 0) {
+    raw += (size_t)blockIdx.y * raw_stride;
+    meta += (size_t)blockIdx.y * MT_COUNTED_META;
+    out += (size_t)blockIdx.y * out_stride;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x, numel = meta[1 + 2 * seg];
     if (i >= numel) return;
     out[i] = mt_normal_value(raw + meta[0] + meta[2 + 2 * seg], numel, i, R, C, S, mean, std);
@@ -541,13 +560,17 @@ static int64_t mt_counted_raw_words(int32_t nseg, const midas_mt_counted_segment
     return words;
 }
 
-int launch_mt_draws_counted(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_counted_segment* segs,
-                            const float* R, const float* C, const float* S, int32_t* status) {
+// B streams: one walking workgroup per stream, the transforms with the stream as grid.y; every stream has the single call's raw
+// words and meta row at the bounds.  B = 1 (strides unused) is the single call, launch for launch.
+int launch_mt_draws_counted_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t skip_words, int32_t nseg,
+                                  const midas_mt_counted_segment* segs, int64_t count_stride, const float* R, const float* C, const float* S,
+                                  int32_t* status, int64_t status_stride) {
     void* p;
     int rc;
-    if ((rc = midas_scratch(ctx, (size_t)mt_counted_raw_words(nseg, segs) * sizeof(uint32_t), &p))) return rc;
+    const int64_t raw_stride = mt_counted_raw_words(nseg, segs);
+    if ((rc = midas_scratch(ctx, (size_t)B * raw_stride * sizeof(uint32_t), &p))) return rc;
     uint32_t* raw = (uint32_t*)p;
-    if ((rc = midas_scratch(ctx, MT_COUNTED_META * sizeof(long long), &p))) return rc;
+    if ((rc = midas_scratch(ctx, (size_t)B * MT_COUNTED_META * sizeof(long long), &p))) return rc;
     long long* meta = (long long*)p;
     mt_counted_segs a = {};
     a.nseg = nseg;
@@ -557,19 +580,26 @@ int launch_mt_draws_counted(midas_ctx* ctx, uint32_t* state, int64_t skip_words,
         a.per[i] = segs[i].per;
         a.kind[i] = segs[i].kind;
     }
-    hipLaunchKernelGGL(k_mt_counted, dim3(1), dim3(MT_THREADS), 0, ctx->stream, state, (long long)skip_words, a, raw, meta, status);
+    hipLaunchKernelGGL(k_mt_counted, dim3((unsigned)B), dim3(MT_THREADS), 0, ctx->stream, state, (long long)skip_words, a, raw, meta, status,
+                       (long long)count_stride, (long long)raw_stride, (long long)status_stride);
     for (int i = 0; i < nseg; ++i) {
         const int64_t n = segs[i].per * segs[i].bound;
         if (n == 0) continue;
         if (segs[i].kind == MIDAS_MT_SEGMENT_RAND64)
-            hipLaunchKernelGGL(k_mt_emit_counted, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
-                               (const long long*)meta, i, (double*)segs[i].out_dev);
+            hipLaunchKernelGGL(k_mt_emit_counted, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
+                               (const long long*)meta, i, (double*)segs[i].out_dev, (long long)raw_stride, (long long)n);
         else
-            hipLaunchKernelGGL(k_mt_normal_counted, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
-                               (const long long*)meta, i, R, C, S, segs[i].mean, segs[i].std, (float*)segs[i].out_dev);
+            hipLaunchKernelGGL(k_mt_normal_counted, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
+                               (const long long*)meta, i, R, C, S, segs[i].mean, segs[i].std, (float*)segs[i].out_dev, (long long)raw_stride,
+                               (long long)n);
     }
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
+}
+
+int launch_mt_draws_counted(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int32_t nseg, const midas_mt_counted_segment* segs,
+                            const float* R, const float* C, const float* S, int32_t* status) {
+    return launch_mt_draws_counted_batch(ctx, 1, state, skip_words, nseg, segs, 0, R, C, S, status, 0);
 }
 
 MIDAS_WARM_TU(mt19937, k_mt_seed)

@@ -21,6 +21,7 @@
 //
 // Spec: oracle/aten_topk.c, pinned against torch.topk (tests/test_aten_topk.py).  One wave per call; 0.3 - 5 ms at
 // N = 100k: this is the mode that follows the reference move for move, not the fast one (loop.hip's radix select, ties by index).
+// A batch of trajectories (midas_loop_step_batch_draws) runs B such waves side by side, one workgroup each, on B queues.
 #include "midas_internal.hpp"
 #include "midas_math.hpp"
 
@@ -318,9 +319,15 @@ MD void tk_topk(TkPair* q, int n, int k, bool sorted, int* lpos_g, int* rpos_g, 
     tk_sync();
 }
 
+// A batch of trajectories (launch_loop_step_batch; trajectory = blockIdx.y): ctl_i (B, 32); weights, src, queue, stopper lists and
+// marks `cap` entries per trajectory, block counts a launch's worth each.
 // queue[j] = (w[j], j); the removal marks cleared
 __global__ __launch_bounds__(256) void k_topk_init(const int32_t* __restrict__ ctl_i, const double* __restrict__ w, TkPair* __restrict__ q,
-                                                   uint8_t* __restrict__ mark) {
+                                                   uint8_t* __restrict__ mark, int32_t cap = 0) {
+    if (blockIdx.y) {
+        const int64_t b = blockIdx.y, o = b * cap;
+        ctl_i += b * LOOP_CTL_I; w += o; q += o; mark += o;
+    }
     const int n = ctl_i[LOOP_I_N], mode = ctl_i[LOOP_I_MODE];
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (!mode || j >= n) return;
@@ -331,11 +338,16 @@ __global__ __launch_bounds__(256) void k_topk_init(const int32_t* __restrict__ c
 }
 
 // One wave: the first k of the queue become torch.topk's output (mode 1: the k smallest, order irrelevant - they are removed;
-// mode 2: the k largest, sorted).  info[0] += depth-limit fallbacks taken (tests).
+// mode 2: the k largest, sorted).  info[0] += depth-limit fallbacks taken (tests).  A batch: one one-wave workgroup per trajectory,
+// each on its own queue and stopper lists, with its own LDS heap and stack.
 __global__ __launch_bounds__(64) void k_topk_select(const int32_t* __restrict__ ctl_i, TkPair* __restrict__ q, int* __restrict__ lpos,
-                                                    int* __restrict__ rpos, int* __restrict__ info) {
+                                                    int* __restrict__ rpos, int* __restrict__ info, int32_t cap = 0) {
     __shared__ TkShared sh;
     __shared__ int stack[3 * TK_STACK];
+    if (blockIdx.y) {
+        const int64_t b = blockIdx.y, o = b * cap;
+        ctl_i += b * LOOP_CTL_I; q += o; lpos += o; rpos += o;
+    }
     const int n = ctl_i[LOOP_I_N], mode = ctl_i[LOOP_I_MODE], k = ctl_i[LOOP_I_K];
     if (!mode || k <= 0 || k > n) return;
     int fb = 0;
@@ -346,7 +358,11 @@ __global__ __launch_bounds__(64) void k_topk_select(const int32_t* __restrict__ 
 
 // mode 1: mark the k removed particles; mode 2: src[n + j] = the j-th best, src[0, n) = identity
 __global__ __launch_bounds__(256) void k_topk_emit(const int32_t* __restrict__ ctl_i, const TkPair* __restrict__ q, uint8_t* __restrict__ mark,
-                                                   int32_t* __restrict__ src) {
+                                                   int32_t* __restrict__ src, int32_t cap = 0) {
+    if (blockIdx.y) {
+        const int64_t b = blockIdx.y, o = b * cap;
+        ctl_i += b * LOOP_CTL_I; q += o; mark += o; src += o;
+    }
     const int n = ctl_i[LOOP_I_N], mode = ctl_i[LOOP_I_MODE], k = ctl_i[LOOP_I_K];
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
@@ -358,8 +374,13 @@ __global__ __launch_bounds__(256) void k_topk_emit(const int32_t* __restrict__ c
 
 // mode 1: the survivors in their order.  Per 4096-slot block the number of marks, then every block adds up the blocks
 // before it (at most 256) and writes its survivors.
-__global__ __launch_bounds__(256) void k_topk_count(const int32_t* __restrict__ ctl_i, const uint8_t* __restrict__ mark, int32_t* __restrict__ cnt) {
+__global__ __launch_bounds__(256) void k_topk_count(const int32_t* __restrict__ ctl_i, const uint8_t* __restrict__ mark, int32_t* __restrict__ cnt,
+                                                    int32_t cap = 0) {
     __shared__ int s_w[4];
+    if (blockIdx.y) {
+        const int64_t b = blockIdx.y;
+        ctl_i += b * LOOP_CTL_I; mark += b * cap; cnt += b * gridDim.x;
+    }
     const int n = ctl_i[LOOP_I_N];
     if (ctl_i[LOOP_I_MODE] != 1) return;
     const int64_t bbase = (int64_t)blockIdx.x * SCAN_BLOCK;
@@ -376,9 +397,13 @@ __global__ __launch_bounds__(256) void k_topk_count(const int32_t* __restrict__ 
 }
 
 __global__ __launch_bounds__(256) void k_topk_compact(const int32_t* __restrict__ ctl_i, const uint8_t* __restrict__ mark,
-                                                      const int32_t* __restrict__ cnt, int32_t* __restrict__ src) {
+                                                      const int32_t* __restrict__ cnt, int32_t* __restrict__ src, int32_t cap = 0) {
     __shared__ int s_w[4];
     __shared__ int s_before;
+    if (blockIdx.y) {
+        const int64_t b = blockIdx.y, o = b * cap;
+        ctl_i += b * LOOP_CTL_I; mark += o; cnt += b * gridDim.x; src += o;
+    }
     const int n = ctl_i[LOOP_I_N];
     if (ctl_i[LOOP_I_MODE] != 1) return;
     const int blk = blockIdx.x, t = threadIdx.x;
@@ -416,28 +441,31 @@ __global__ __launch_bounds__(256) void k_topk_compact(const int32_t* __restrict_
     }
 }
 
-// ctl_i[N, MODE, K] are in place (k_loop_decide / k_anneal_plan): src = the annealed set under ATen's CPU rule
-int launch_topk_aten(midas_ctx* ctx, int64_t cap, const int32_t* ci, const double* w, int32_t* src, int32_t* info) {
+// ctl_i[N, MODE, K] are in place (k_loop_decide / k_anneal_plan): src = the annealed set under ATen's CPU rule.  B trajectories: the
+// same five launches with the trajectory as grid.y, B slices of every scratch array.
+int launch_topk_aten(midas_ctx* ctx, int64_t cap, const int32_t* ci, const double* w, int32_t* src, int32_t* info, int32_t B) {
     void* p;
     int rc;
-    if ((rc = midas_scratch(ctx, (size_t)cap * sizeof(TkPair), &p))) return rc;
+    const size_t Bz = (size_t)B;
+    if ((rc = midas_scratch(ctx, Bz * cap * sizeof(TkPair), &p))) return rc;
     TkPair* q = (TkPair*)p;
-    if ((rc = midas_scratch(ctx, (size_t)cap * sizeof(int), &p))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * cap * sizeof(int), &p))) return rc;
     int* lpos = (int*)p;
-    if ((rc = midas_scratch(ctx, (size_t)cap * sizeof(int), &p))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * cap * sizeof(int), &p))) return rc;
     int* rpos = (int*)p;
-    if ((rc = midas_scratch(ctx, (size_t)cap, &p))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * cap, &p))) return rc;
     uint8_t* mark = (uint8_t*)p;
-    const unsigned nb = (unsigned)ceil_div(cap, SCAN_BLOCK);
-    if ((rc = midas_scratch(ctx, (size_t)nb * sizeof(int32_t), &p))) return rc;
+    const unsigned nb = (unsigned)ceil_div(cap, SCAN_BLOCK), by = (unsigned)B;
+    if ((rc = midas_scratch(ctx, Bz * nb * sizeof(int32_t), &p))) return rc;
     int32_t* cnt = (int32_t*)p;
     hipStream_t st = ctx->stream;
     const unsigned g = (unsigned)ceil_div(cap, 256);
-    hipLaunchKernelGGL(k_topk_init, dim3(g), dim3(256), 0, st, ci, w, q, mark);
-    hipLaunchKernelGGL(k_topk_select, dim3(1), dim3(64), 0, st, ci, q, lpos, rpos, (int*)info);
-    hipLaunchKernelGGL(k_topk_emit, dim3(g), dim3(256), 0, st, ci, (const TkPair*)q, mark, src);
-    hipLaunchKernelGGL(k_topk_count, dim3(nb), dim3(256), 0, st, ci, (const uint8_t*)mark, cnt);
-    hipLaunchKernelGGL(k_topk_compact, dim3(nb), dim3(256), 0, st, ci, (const uint8_t*)mark, (const int32_t*)cnt, src);
+    const int32_t stride = (int32_t)cap;  // (between two trajectories' slices)
+    hipLaunchKernelGGL(k_topk_init, dim3(g, by), dim3(256), 0, st, ci, w, q, mark, stride);
+    hipLaunchKernelGGL(k_topk_select, dim3(1, by), dim3(64), 0, st, ci, q, lpos, rpos, (int*)info, stride);
+    hipLaunchKernelGGL(k_topk_emit, dim3(g, by), dim3(256), 0, st, ci, (const TkPair*)q, mark, src, stride);
+    hipLaunchKernelGGL(k_topk_count, dim3(nb, by), dim3(256), 0, st, ci, (const uint8_t*)mark, cnt, stride);
+    hipLaunchKernelGGL(k_topk_compact, dim3(nb, by), dim3(256), 0, st, ci, (const uint8_t*)mark, (const int32_t*)cnt, src, stride);
     LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }

@@ -8,7 +8,8 @@ same uniforms without a host generator or a per-frame upload; `skip_normal(numel
 its motion noise on the host generator stays aligned with the reference's stream.
 
 `TorchCpuStreams(seeds)` holds B such streams - B seeded runs of the reference, one trajectory each, as a batch engine runs
-them - and draws a frame of all of them by one call (midas_mt19937_draws_batch).
+them - and draws a frame of all of them by one call (midas_mt19937_draws_batch), or, where every trajectory's particle count is its own and changes every frame
+(BatchLoopEngine.seed_torch_streams), with the sizes read from B control blocks on the device (midas_mt19937_draws_counted_batch).
 """
 from __future__ import annotations
 
@@ -577,3 +578,69 @@ class TorchCpuStreams(_GeneratorSide):
         need = max(self.scratch_bytes(s) for s in specs)
         self.ctx.check(self.ctx.lib.midas_scratch_reserve(self.ctx.h, need))
         return self
+
+    # ---- draws whose sizes stand in device memory, a count per stream ------------------------------------------------
+    def _counted_items(self, spec):
+        items = TorchCpuStream._counted_items(spec)
+        for _, _, _, cnt, idx, _, _ in items:
+            if cnt.dim() != 2 or cnt.shape[0] != self.B or not 0 <= idx < cnt.shape[1]:
+                raise _lib.MidasError(f"a counted draw of {self.B} streams takes stream b's size from [b, index] of a ({self.B}, stride) int32 tensor")
+        return items
+
+    def counted_scratch_bytes(self, spec) -> int:
+        """Scratch one draws_counted_async(spec) call takes of the generator's context: B x TorchCpuStream's at the same bounds."""
+        words = 3 * 624
+        for kind, _, _, _, _, per, bound in self._counted_items(spec):
+            words += 2 * per * bound if kind == _lib.MT_SEGMENT_RAND64 else per * bound + 16
+        r = lambda b: (b + 255) // 256 * 256  # noqa: E731  (the allocator's rounding)
+        return r(4 * words * self.B) + r(8 * 17 * self.B)
+
+    def draws_counted_async(self, spec, outs=None, status=None):
+        """TorchCpuStream.draws_counted_async for every stream by ONE call (midas_mt19937_draws_counted_batch), with its spec:
+        ("rand64", count_tensor, index, bound) and ("normal", mean, std, count_tensor, index, per, bound) - here count_tensor is
+        (B, stride) int32 and stream b draws per x count_tensor[b, index] values, as that element stands when the kernels run (B
+        control blocks of a BatchLoopEngine).  Returns ([tensors], event or None): (B, per x bound) tensors, row b's first
+        per x count values hold stream b's draw, the rest is left as it was; `outs` gives the tensors to write into (contiguous,
+        B x per x bound values each).  Stream b is, number for number, TorchCpuStream.draws_counted_async on it alone: a count of 0
+        consumes nothing, a count beyond its bound or a normal draw of 1 .. 15 values draws nothing OF THAT STREAM and sets
+        _lib.MT_STATUS_* bits in its status word - `status` = (int32 device tensor, index of stream 0's word, elements between two
+        streams' words), by default the streams' own B words, which counted_status() reads.  Always the sequential walk."""
+        import ctypes as C
+        items = self._counted_items(spec)
+        if not 1 <= len(items) <= 8:
+            raise _lib.MidasError("1 .. 8 draws a call")
+        if len({it[3].shape[1] for it in items}) != 1:
+            raise _lib.MidasError("the count tensors of one call share their row stride")
+        if status is None:
+            if getattr(self, "_status", None) is None:
+                self._status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            status = (self._status, 0, 1)
+        st_t, st_i, st_stride = status[0], int(status[1]), int(status[2])
+        if (st_t.dtype != torch.int32 or not st_t.is_contiguous() or st_stride < 1 or st_i < 0
+                or st_i + (self.B - 1) * st_stride >= st_t.numel()):
+            raise _lib.MidasError(f"`status` wants {self.B} words of a contiguous int32 device tensor")
+        outs = [None] * len(items) if outs is None else list(outs)
+        arr = (_lib.MtCountedSegment * len(items))()
+        need_tables = False
+        for i, (a, (kind, mean, std, cnt, idx, per, bound)) in enumerate(zip(arr, items)):
+            dt = torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32
+            if outs[i] is None:
+                outs[i] = torch.empty((self.B, per * bound), dtype=dt, device=self.device)
+                if self.side is not None:
+                    outs[i].record_stream(self.side)
+            elif outs[i].dtype != dt or outs[i].numel() != self.B * per * bound or not outs[i].is_contiguous() or outs[i].device != self.device:
+                raise _lib.MidasError(f"draw {i}: `outs` wants a contiguous device tensor of {self.B} x {per * bound} values of the draw's type")
+            need_tables |= kind == _lib.MT_SEGMENT_NORMAL32
+            a.kind, a.per, a.count_dev, a.bound, a.mean, a.std = kind, per, cnt.data_ptr() + 4 * idx, bound, mean, std
+            a.out_dev = outs[i].data_ptr()
+        R, Ct, S = self._normal_tables() if need_tables else (None, None, None)
+        self._enter()
+        self._call("midas_mt19937_draws_counted_batch", self.B, _ptr(self.state), self.pending_skip, len(items), C.cast(arr, C.c_void_p),
+                   int(items[0][3].shape[1]), _ptr(R), _ptr(Ct), _ptr(S), C.c_void_p(st_t.data_ptr() + 4 * st_i), st_stride)
+        _, ev = self._drawn(0, None)  # (no history: the next call walks sequentially)
+        return outs, ev
+
+    def counted_status(self):
+        """The _lib.MT_STATUS_* bits draws_counted_async calls have set in the streams' own status words: B ints (one read-back)."""
+        st = getattr(self, "_status", None)
+        return [0] * self.B if st is None else [int(v) for v in st.cpu()]

@@ -8,7 +8,11 @@ One JSON line per engine form with each figure's median over the repeats and [mi
   batch_loop      BatchLoopEngine, B trajectories per frame
   single_loop     one LoopEngine on trajectory 0 (seed + 0) - and B x its median frame, the figure the batch frame has to beat
   pipelined_fixed PipelinedBatchFilterEngine at the same B and N0: the fixed-N frame without clustering or annealing (orientation)
---profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats), no timing."""
+--seeded: the seeded forms instead - B runs of the reference under torch.manual_seed(s + b), ATen's tie rule:
+  batch_loop_seeded   BatchLoopEngine.seed_torch_streams (midas_loop_step_batch_draws, the draws sized on the device per trajectory)
+  single_loop_seeded  one LoopEngine(topk_ties="aten_cpu").seed_torch_stream on trajectory 0 - B x its frame is what the sweep cost before
+  batch_loop          the Philox batch frame (orientation: the seeded batch frame should sit near it plus one seeded single frame)
+--profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch), no timing."""
 import json
 import os
 import statistics
@@ -24,7 +28,7 @@ from midastouch_amd.loop_engine import LoopEngine
 from midastouch_amd.synthetic import make_codebook, make_trajectory, wide_start
 
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
-profile = "--profile" in sys.argv
+profile, seeded = "--profile" in sys.argv, "--seeded" in sys.argv
 B, N0, K, T, R = (int(argv[i]) if len(argv) > i else d for i, d in enumerate((64, 10000, 50000, 300, 3)))
 D, FLOOR, EVERY, SEED = 512, 1000, 50, 4000
 dev = torch.device("cuda", 0)
@@ -61,8 +65,10 @@ def over_repeats(rows):
     return {k: {"median": statistics.median(r[k] for r in rows), "min": min(r[k] for r in rows), "max": max(r[k] for r in rows)} for k in rows[0]}
 
 
-def run_batch():
+def run_batch(seeds=None):
     eng = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, **kw)
+    if seeds is not None:
+        eng.seed_torch_streams(seeds)
     eng.set_particles(starts)
     eng.project_to_codebook()
     ms = timed(lambda t: eng.step(odoms[t + 1], codes[t + 1], gts=gts[t + 1]), T)
@@ -70,8 +76,10 @@ def run_batch():
     return ms, {"n_final_min": min(n), "n_final_max": max(n)}
 
 
-def run_single():
-    eng = LoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N0, seed=SEED, **kw)
+def run_single(seed=None):
+    eng = LoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N0, seed=SEED, topk_ties="index" if seed is None else "aten_cpu", **kw)
+    if seed is not None:
+        eng.seed_torch_stream(seed)
     eng.set_particles(starts[0])
     eng.project_to_codebook()
     ms = timed(lambda t: eng.step(odoms[t + 1, 0], codes[t + 1, 0], gt=gts[t + 1, 0]), T)
@@ -87,14 +95,25 @@ def run_fixed():
     return ms, {}
 
 
+def run_batch_seeded():
+    return run_batch([SEED + b for b in range(B)])
+
+
+def run_single_seeded():
+    return run_single(SEED)
+
+
 if profile:
-    run_batch()
+    (run_batch_seeded if seeded else run_batch)()
     torch.cuda.synchronize()
     sys.exit(0)
 
 head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R}
 out = {}
-for name, run in (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed)):
+forms = (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed))
+if seeded:
+    forms = (("batch_loop_seeded", run_batch_seeded), ("single_loop_seeded", run_single_seeded), ("batch_loop", run_batch))
+for name, run in forms:
     run()  # warm-up: code objects, scratch, allocator
     rows, extra = [], {}
     for _ in range(R):
@@ -102,8 +121,8 @@ for name, run in (("batch_loop", run_batch), ("single_loop", run_single), ("pipe
         rows.append(summary(ms))
     out[name] = over_repeats(rows)
     print(json.dumps({"form": name, **head, **out[name], **extra, "per_repeat": rows}), flush=True)
-one, batch = out["single_loop"], out["batch_loop"]
-print(json.dumps({"form": "comparison", **head,
+one, batch = (out["single_loop_seeded"], out["batch_loop_seeded"]) if seeded else (out["single_loop"], out["batch_loop"])
+print(json.dumps({"form": "comparison_seeded" if seeded else "comparison", **head,
                   "B_single_frames_us": round(B * one["frame_median_us"]["median"], 1),
                   "batch_frame_us": batch["frame_median_us"]["median"],
                   "speedup_frame": round(B * one["frame_median_us"]["median"] / batch["frame_median_us"]["median"], 2),
