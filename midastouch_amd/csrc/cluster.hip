@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256) void k_loop_cluster_finish(const int32_t* __re
 // trajectory b alone.  Two weight sources:
 //   w64     B x N masked pre-resample weights (what the eager engines hold);
 //   tables  the pipelined frame's table blocks (tables_of, api.hip), tstride doubles apart: the weight k_tail_b2 would write
-//           (resample.hip, a.weights[i]) is formed here - guard and S by every workgroup for itself from the at most
+//           (tail.hip, a.weights[i]) is formed here - guard and S by every workgroup for itself from the at most
 //           LAZY_MAX_BLOCKS block records, no flush, no N-sized temporary.
 struct EstimateArgs {
     int64_t N;
@@ -442,7 +442,6 @@ struct EstimateArgs {
     int32_t nbl;                                      // 4096-slot summation blocks of a trajectory (<= LAZY_MAX_BLOCKS)
     double* part;
 };
-constexpr double EST_ISCLOSE_ATOL = 1e-8;  // torch.isclose default atol (particle_filter.py:460-463; ISCLOSE_ATOL of resample.hip)
 
 __global__ __launch_bounds__(256) void k_estimate_moments(EstimateArgs a) {
     __shared__ double s_w[4][CL_MOM];
@@ -479,7 +478,7 @@ __global__ __launch_bounds__(256) void k_estimate_moments(EstimateArgs a) {
         double f = s_ex[8];
         for (int w = 1; w < 4; ++w) { mx = s_ex[w] > mx ? s_ex[w] : mx; mn = s_ex[4 + w] < mn ? s_ex[4 + w] : mn; f += s_ex[8 + w]; }
         if (f != 0.0) { mx = NAN; mn = NAN; }
-        const bool apply = a.softmax && !(__builtin_fabs(mx - mn) <= EST_ISCLOSE_ATOL);  // (workgroup-uniform)
+        const bool apply = a.softmax && !(__builtin_fabs(mx - mn) <= ISCLOSE_ATOL);  // (workgroup-uniform)
         double S = 1.0;
         if (apply) {  // the block sums of e one after the other, in block order (the spec)
             S = 0.0;

@@ -27,7 +27,6 @@ namespace midas {
 // 514: apply | [516, 516+nb) block sums of e | [LAZY_WG_W, +nb) block totals (the guide tables' bin width).  Same arithmetic as
 // k_tail_b / k_tail_b2.
 constexpr int LAZY_WG_W = 3 * LAZY_MAX_BLOCKS + 8, LAZY_WG_LDS = 4 * LAZY_MAX_BLOCKS + 8;
-constexpr double LAZY_ISCLOSE_ATOL = 1e-8;
 MD void lazy_tables(const LazyResample& rs, double* rs_lds) {
     __shared__ double s_ex[12];
     const int t = threadIdx.x;
@@ -46,7 +45,7 @@ MD void lazy_tables(const LazyResample& rs, double* rs_lds) {
     double f = s_ex[8];
     for (int w = 1; w < 4; ++w) { mx = s_ex[w] > mx ? s_ex[w] : mx; mn = s_ex[4 + w] < mn ? s_ex[4 + w] : mn; f += s_ex[8 + w]; }
     if (f != 0.0) { mx = NAN; mn = NAN; }
-    const bool apply = rs.softmax && !(__builtin_fabs(mx - mn) <= LAZY_ISCLOSE_ATOL);
+    const bool apply = rs.softmax && !(__builtin_fabs(mx - mn) <= ISCLOSE_ATOL);
     double* s_bp = rs_lds;
     double* s_w = rs_lds + 256;
     double* s_se = rs_lds + 516;
@@ -94,7 +93,7 @@ MD void lazy_tables_wave(const LazyResample& rs, const LazyRecords& r, double* r
     mx = wave_max_dpp(mx);  // (DPP moves: midas_math.hpp)
     mn = wave_min_dpp(mn);
     if (__any(nan)) { mx = NAN; mn = NAN; }
-    const bool apply = rs.softmax && !(__builtin_fabs(mx - mn) <= LAZY_ISCLOSE_ATOL);
+    const bool apply = rs.softmax && !(__builtin_fabs(mx - mn) <= ISCLOSE_ATOL);
     const double w = in ? (apply ? r.bt : r.btr) : 0.0;
     // The sequential prefix of the block totals: the totals go through LDS (every lane reads the same eight values a round -
     // broadcast reads, all requested before the first addition) and every lane runs the same chain of additions, keeping the

@@ -9,8 +9,6 @@
 
 namespace midas {
 
-constexpr double LOOP_ISCLOSE_ATOL = 1e-8;  // torch.isclose default atol (particle_filter.py:460-463)
-
 struct LoopWeightsArgs {
     int32_t* ctl_i;
     double* ctl_d;
@@ -106,7 +104,7 @@ MD LoopWeightsHead loop_weights_head(const LoopWeightsArgs& a, const LoopWeights
     double S = 0.0;
     for (int i = 0; i < nb; ++i) S = S + s_sum[i];
     LoopWeightsHead h;
-    const bool close = __builtin_fabs(mx - mn) <= LOOP_ISCLOSE_ATOL;  // false on NaN
+    const bool close = __builtin_fabs(mx - mn) <= ISCLOSE_ATOL;  // false on NaN
     h.n = n; h.mx = mx; h.mn = mn; h.kept = kept; h.f = f;
     h.applied = a.softmax != 0 && !close;
     h.Sd = h.applied ? S : 1.0;

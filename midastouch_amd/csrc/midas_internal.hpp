@@ -165,8 +165,9 @@ int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* deta
         return (int)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&kernel));     \
     }
 #define MIDAS_WARM_DECL(name) int warm_##name();
-// (warm_particles also loads the units cut out of particles.hip - tree, front, front_folded, front_batch: their warm functions are
-// declared and chained in particles.hip, so midas_ctx_create's list of units stays as it is)
+// (warm_particles also loads the units cut out of particles.hip - tree, front, front_folded, front_batch - and warm_resample those
+// cut out of resample.hip - tail, shard_route: their warm functions are declared and chained in particles.hip and resample.hip,
+// so midas_ctx_create's list of units stays as it is)
 namespace midas {
 MIDAS_WARM_DECL(score) MIDAS_WARM_DECL(particles) MIDAS_WARM_DECL(resample) MIDAS_WARM_DECL(cluster) MIDAS_WARM_DECL(topn)
 MIDAS_WARM_DECL(selfsim) MIDAS_WARM_DECL(loop) MIDAS_WARM_DECL(dbscan) MIDAS_WARM_DECL(dbscan_nd) MIDAS_WARM_DECL(index_build)
@@ -461,7 +462,7 @@ inline ScorePredict wire_score_list(SparseScore& sp, int32_t* lists, int64_t K) 
     return next_score_list(sp.stamps, sp.epoch, lists, K);
 }
 
-// resample.hip
+// resample.hip - the weight and resampling operators on their own, and TA of the eager step tail
 int launch_gather_f64(midas_ctx* ctx, int64_t N, const double* table, const int32_t* idx, double* out);
 int launch_softmax(midas_ctx* ctx, int64_t N, const double* x, int32_t softmax, double* w);
 int launch_prune(midas_ctx* ctx, int64_t N, double* w, const double* dist, double thr, int32_t* nvalid);
@@ -469,7 +470,13 @@ int launch_cdf(midas_ctx* ctx, int64_t N, const double* w, double* cdf, int32_t*
 int launch_search(midas_ctx* ctx, int64_t N, const double* cdf, int64_t M, int32_t mode, const double* u,
                   float u32, uint64_t seed, uint64_t step, int32_t* idx);
 int launch_gather_rows(midas_ctx* ctx, int64_t M, const int32_t* idx, const void* src, void* dst, int32_t row_bytes);
-// fused tail of the step: x,valid,partials -> weights (masked) -> cdf -> search -> gather
+int launch_selftest_wave_sums(midas_ctx* ctx, const double* in64, double* out256);
+int launch_tail_a(midas_ctx* ctx, int64_t N, const double* x, const uint8_t* valid, int np, int pstride,
+                  const double* pmax_all, const double* pmin_all, int32_t softmax, double* e_io, double* lp_out,
+                  double* block_sums_e, double* block_totals_em, double* flags_out, int32_t* flag, int32_t* status,
+                  int batch = 1);
+
+// tail.hip - the fused tail of the step: x,valid,partials -> weights (masked) -> cdf -> search -> gather
 struct StepTailArgs {
     int32_t batch = 1;       // trajectories (grid.y)
     int64_t N;
@@ -503,7 +510,6 @@ struct StepTailArgs {
     int64_t score_stride = 0;  // K: scores are (batch, K)
     int64_t tstride = 0;       // pipelined batch: doubles between two trajectories' table blocks (tables_of layout per trajectory)
 };
-int launch_step_tail(midas_ctx* ctx, const StepTailArgs& a, int prof_slot_base);
 // the deferred tail on explicit tables (what k_tail_a2 writes and k_tail_b2 / the lazy front read)
 struct TailTables {
     double *e, *x_raw, *lp, *lp_raw, *gend, *gend_raw;       // [N] x4, [ceil(N/16)] x2
@@ -516,10 +522,21 @@ int launch_tail_a2(midas_ctx* ctx, int64_t N, const double* scores, const int32_
                    bool padded_tables = false, const double* part_rmse = nullptr, double* rmse_out = nullptr, int64_t tstride = 0,
                    const ScorePredict* predict = nullptr);  // padded: per-slot tables hold a multiple of 16 values (tables_of, api.hip)
 int launch_predict_seed(midas_ctx* ctx, int64_t N, const int32_t* idx, const ScorePredict& pr);
-int launch_tail_b2(midas_ctx* ctx, const StepTailArgs& a, const TailTables& tb);  // a.x, a.e, a.cdf, a.lp_raw unused
 int launch_shard_tail_a(midas_ctx* ctx, int64_t N, const double* scores, const int32_t* nn_idx, const uint8_t* valid,
                         int32_t softmax, const TailTables& tb, double* r1, int32_t* status, const double* part_rmse = nullptr,
                         const ScorePredict* predict = nullptr);
+int launch_tail_b2(midas_ctx* ctx, const StepTailArgs& a, const TailTables& tb);  // a.x, a.e, a.cdf, a.lp_raw unused
+int launch_step_tail(midas_ctx* ctx, const StepTailArgs& a, int prof_slot_base);
+int debug_tb2_clocks(long long* out16);
+int debug_ta_clocks(long long* out16);
+int debug_tg_clocks(long long* io64, int reset);
+int debug_tg_waves(long long* out4096);
+
+// shard_route.hip - the sharded engine's exchange behind launch_shard_tail_a
+int launch_tail_fin(midas_ctx* ctx, int64_t N, const double* e, const double* x_raw, const double* lp, const double* lp_raw,
+                    const uint8_t* valid, double* weights, double* cdf_io, int G, int nb, const double* r1_all, int rank,
+                    double n_total, int32_t softmax, double* rmse_out, int32_t* status);
+int launch_tail_resample(midas_ctx* ctx, const midas_tail_resample_args& r);
 // sync (peer form, C-side frame): the route kernel's last workgroup publishes the frame's completion flag and waits for every
 // rank's (the word behind the 64 flags of the own inbox counts the finished workgroups: zero between launches)
 struct PeerRouteSync { const char* inbox; long long flag_off; unsigned long long tag; };
@@ -528,24 +545,13 @@ int launch_shard_unpack(midas_ctx* ctx, int64_t N, const void* recv, int32_t* ri
                         int32_t* hint_out, int32_t dest = -1);
 int launch_shard_unpack_peer(midas_ctx* ctx, int64_t N, const void* inbox, int32_t* ridx, float* poses_out, double* weights_out,
                              int32_t* hint_out);
-int launch_peer_probe(midas_ctx* ctx, void* const* peers, const void* inbox, int G, int rank, int nonce, int32_t* ok);
 int launch_peer_flag_write(midas_ctx* ctx, void* const* peers, int G, int rank, int64_t flag_off, uint64_t tag);
 int launch_shard_unpack_peer_wait(midas_ctx* ctx, int64_t N, const void* inbox, int32_t* ridx, float* poses_out, double* weights_out,
                                   int32_t* hint_out, int G, int64_t flag_off, uint64_t tag, int32_t* status, void* const* peers, int rank);
-int launch_selftest_wave_sums(midas_ctx* ctx, const double* in64, double* out256);
-int debug_tb2_clocks(long long* out16);
-int debug_ta_clocks(long long* out16);
-int debug_tg_clocks(long long* io64, int reset);
-int debug_tg_waves(long long* out4096);
+int launch_peer_probe(midas_ctx* ctx, void* const* peers, const void* inbox, int G, int rank, int nonce, int32_t* ok);
+
+// front_folded.hip, front.hip
 int debug_ff_clocks(long long* io8192, int reset);
-int launch_tail_a(midas_ctx* ctx, int64_t N, const double* x, const uint8_t* valid, int np, int pstride,
-                  const double* pmax_all, const double* pmin_all, int32_t softmax, double* e_io, double* lp_out,
-                  double* block_sums_e, double* block_totals_em, double* flags_out, int32_t* flag, int32_t* status,
-                  int batch = 1);
-int launch_tail_fin(midas_ctx* ctx, int64_t N, const double* e, const double* x_raw, const double* lp, const double* lp_raw,
-                    const uint8_t* valid, double* weights, double* cdf_io, int G, int nb, const double* r1_all, int rank,
-                    double n_total, int32_t softmax, double* rmse_out, int32_t* status);
-int launch_tail_resample(midas_ctx* ctx, const midas_tail_resample_args& r);
 int launch_reduce_partials(midas_ctx* ctx, int np, const double* pmax, const double* pmin, const double* prm,
                            double* extrema2, double* rmse_sums2);
 

@@ -13,6 +13,8 @@ namespace midas {
 
 #define MD __device__ __forceinline__
 
+constexpr double ISCLOSE_ATOL = 1e-8;  // torch.isclose default atol (particle_filter.py:460-463): the softmax guard of every weight kernel
+
 MD float fmaf_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 MD double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
 

@@ -1,5 +1,5 @@
 // resample_search.hpp - the slot of a draw inside a 4096-slot summation block, shared by the pipelined front
-// (front_wave.hpp, lazy_source) and the owner-side routing of the sharded step (resample.hip, k_shard_route_*).
+// (front_wave.hpp, lazy_source) and the owner-side routing of the sharded step (shard_route.hip, k_shard_route).
 #pragma once
 #include "midas_internal.hpp"
 #include <type_traits>

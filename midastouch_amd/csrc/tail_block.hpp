@@ -9,13 +9,12 @@ namespace midas {
 #ifndef MIDAS_TAIL_EXP_ILP
 #define MIDAS_TAIL_EXP_ILP 1
 #endif
-constexpr double TAIL_ISCLOSE_ATOL = 1e-8;
 #ifdef MIDAS_DEBUG_CLOCKS  // phase clocks of one k_tail_a2d workgroup (tools/variants.sh dbg "-DMIDAS_DEBUG_CLOCKS"; tools/ta_clocks.py)
 extern __device__ long long g_ta_clk[16];
 #define TA_CLK(k) do { if (blk == 12 && threadIdx.x == 0) g_ta_clk[k] = clock64(); if (threadIdx.x == 0 && (k) == 0 && blk == 0) g_ta_clk[8] = wall_clock64(); if (threadIdx.x == 0 && (k) == 7 && blk == 0) g_ta_clk[9] = wall_clock64(); if (threadIdx.x == 0 && (k) == 0 && blk == 24) g_ta_clk[10] = wall_clock64(); if (threadIdx.x == 0 && (k) == 7 && blk == 24) g_ta_clk[11] = wall_clock64(); } while (0)
 #else
 #define TA_CLK(k) do { } while (0)
-#endif  // torch.isclose default atol (particle_filter.py:460-463)
+#endif
 
 // Block-local part of the spec scan.  v[16] = this lane's chunk (absent values = +0.0).
 // l[j] = GP_g + (TP_c + local_j) (l may be v itself); returns the block total W (identical in every thread).
@@ -153,7 +152,7 @@ MD void tail_a_direct(int64_t N, int blk, const double* __restrict__ scores, con
         kept_out = (int)kd;
         if (f != 0.0) { mx = NAN; mn = NAN; }
         if (t == 0) { tb.bmax[blk] = mx; tb.bmin[blk] = mn; }
-        close = __builtin_fabs(mx - mn) <= TAIL_ISCLOSE_ATOL;  // false on NaN
+        close = __builtin_fabs(mx - mn) <= ISCLOSE_ATOL;  // false on NaN
     };
     const bool need_soft = softmax != 0;
     bool nan = false;

@@ -363,7 +363,7 @@ MD void tail_group_wave(const TailGroupArgs& a, int G, double* s_E) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) e[j] = (in4 >> j) & 1u ? e[j] : 0.0;
         r0 = tg_variant(a, G, 0, e, ok4, mx, mn, gkept, gxnan, tb.lp, tb.gend, tb.ggend, tb.guide, s_E TG_CLK_PASS);
-        close = __builtin_fabs(r0.mx - r0.mn) <= TAIL_ISCLOSE_ATOL;  // false on NaN
+        close = __builtin_fabs(r0.mx - r0.mn) <= ISCLOSE_ATOL;  // false on NaN
         late |= r0.late;
         nan = r0.vnan;
         if (g == 0 && lane == 0) { tb.bsum_e[blk] = r0.Wa; tb.btot[blk] = r0.W; }

@@ -570,7 +570,7 @@ class OracleFilter:
         dist = nn3_dist(p1, self.verts)
         mask = ~(dist > self.pen_max)
         out["dist"], out["mask"] = dist, mask
-        # fused-step spec (csrc/resample.hip k_tail_a/k_tail_b): e = exp(x - 1) (or x when the softmax is
+        # fused-step spec (csrc/resample.hip k_tail_a, csrc/tail.hip k_tail_b): e = exp(x - 1) (or x when the softmax is
         # skipped); weights = e / blocked_sum(e) * mask; the CDF is built from e * mask directly - the
         # normalisation by sum(e) cancels in prefix / total
         e, applied = softmax_numerators(x, softmax, shift=1.0)
