@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void k_loop_cluster_finish(const int32_t* __re
 // moments_accumulate's (a workgroup always holds a member, so nothing is ever skipped): the bits of midas_cluster_centers on
 // trajectory b alone.  Two weight sources:
 //   w64     B x N masked pre-resample weights (what the eager engines hold);
-//   tables  the pipelined frame's table blocks (tables_of, api.hip), tstride doubles apart: the weight k_tail_b2 would write
+//   tables  the pipelined frame's table blocks (tables_of, api_entry.hpp), tstride doubles apart: the weight k_tail_b2 would write
 //           (tail.hip, a.weights[i]) is formed here - guard and S by every workgroup for itself from the at most
 //           LAZY_MAX_BLOCKS block records, no flush, no N-sized temporary.
 struct EstimateArgs {

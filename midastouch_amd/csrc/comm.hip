@@ -4,7 +4,7 @@
 // node to exchange their per-shard sums "with an RCCL all-reduce ... over xGMI".  Round 2 issued those collectives from Python
 // through torch.distributed - nine host-level calls per frame, which bound the sharded frame.  Here the
 // library holds its own ncclComm_t, so the whole frame - kernels AND the record all_gather - is enqueued on the context's
-// stream by one C call (midas_shard_step, api.hip).
+// stream by one C call (midas_shard_step, api_shard.hip).
 //
 // librccl is opened at run time (dlopen) rather than linked: the process normally has torch's copy loaded already, and two
 // RCCL instances in one process would each set up their own transports.  The caller passes the path of the copy to use

@@ -1269,9 +1269,21 @@ int launch_anneal_select(midas_ctx* ctx, int64_t N, const double* w, int32_t mod
     return launch_select(ctx, N, (const int32_t*)ctl, w, src, ss);
 }
 
-// What launch_loop_step and launch_loop_step_batch fill alike (the batch's arrays are the same pointers with B slices behind them):
-// the block results of k_loop_xe for `count` blocks, the weights' arguments, the resample's arguments.
-struct LoopBlockResults { double *bsum, *bmax, *bmin; int32_t *bkept, *bnan; };
+// ---- the frame: what launch_loop_step and launch_loop_step_batch launch alike, stated once ---------------------------------------
+// What the shared phases are launched over.  The single call: one trajectory, the slice strides 0 (the kernels' defaults).
+struct LoopGrid {
+    int64_t cap;               // particles of a trajectory the grids cover
+    int32_t B = 1;             // trajectories = the grid's y: every array - the caller's and the scratch - (B, ...) contiguous
+    int32_t slice = 0;         // a batch: particles between two trajectories' slices of the (B, ...) arrays,
+    int32_t lp_stride = 0;     //          prefix values between their tables,
+    int64_t log_stride = 0;    //          doubles between their log rows
+    double* clocks = nullptr;  // MIDAS_ANNEAL_CLOCKS (the single call): k_loop_xe's phase clocks
+    unsigned nbcap() const { return (unsigned)ceil_div(cap, SCAN_BLOCK); }
+    unsigned by() const { return (unsigned)B; }
+};
+static int32_t loop_bound(int64_t n) { return (int32_t)(n < (1 << 30) ? n : (1 << 30)); }  // a particle bound as the kernels take it
+
+struct LoopBlockResults { double *bsum, *bmax, *bmin; int32_t *bkept, *bnan; };  // of k_loop_xe, `count` blocks
 static int carve_block_results(midas_ctx* ctx, size_t count, LoopBlockResults& br) {
     void* p;
     if (int rc = midas_scratch(ctx, count * (3 * sizeof(double) + 2 * sizeof(int32_t)), &p)) return rc;
@@ -1300,11 +1312,70 @@ static void fill_loop_resample(LoopResampleArgs& r, const midas_loop_args& s, co
     r.host_mirror = s.host_mirror;
 }
 
+// The weights may run at the head of the cluster-moment launch when that launch follows in this call with nothing in between
+// (DBSCAN reads the re-projected poses: frames that cluster keep the launch of their own).
+static bool loop_weights_mergeable(int32_t phases) { return (phases & MIDAS_LOOP_ANNEAL) && !(phases & MIDAS_LOOP_DBSCAN); }
+
+// behind the front: k_loop_xe, then the weights - launched here, or (merged) left in `wa` for the cluster-moment launch
+static int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t K, bool rmse, bool merged,
+                              LoopWeightsArgs& wa) {
+    const unsigned nbcap = g.nbcap();
+    LoopBlockResults br;
+    if (int rc = carve_block_results(ctx, (size_t)g.B * nbcap, br)) return rc;
+    hipLaunchKernelGGL(k_loop_xe, dim3(nbcap, g.by()), dim3(256), 0, ctx->stream, (const int32_t*)s.ctl_i_dev, (const double*)s.scores_dev,
+                       (const int32_t*)s.nn_idx_dev, (const uint8_t*)s.valid_dev, s.softmax, s.unit_weights, s.x_dev, s.e_dev, br.bsum, br.bmax,
+                       br.bmin, br.bkept, br.bnan, loop_bound(g.cap), K, g.clocks);
+    fill_loop_weights(wa, s, br, loop_bound(g.cap), nbcap, rmse);
+    if (!merged) hipLaunchKernelGGL(k_loop_weights, dim3(nbcap, g.by()), dim3(256), 0, ctx->stream, wa);
+    LAUNCH_CHECK(ctx);
+    return MIDAS_OK;
+}
+
+// ANNEAL, first half: the clusters' moments (with the merged weights at their head) into scratch the selection reads
+struct LoopMoments { float *cen, *sd; int64_t* cnt; double* rot; };
+static int loop_cluster_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopWeightsArgs* merged, LoopMoments& m) {
+    const size_t Bz = (size_t)g.B;
+    void *part, *cen, *sd, *cnt, *rot;
+    int rc;
+    if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 10 * sizeof(double), &rot))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * (size_t)ceil_div(g.cap, 256) * LOOP_MAX_CLUSTERS * 36 * sizeof(double), &part))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 16 * sizeof(float), &cen))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 3 * sizeof(float), &sd))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * sizeof(int64_t), &cnt))) return rc;
+    m = LoopMoments{(float*)cen, (float*)sd, (int64_t*)cnt, (double*)rot};
+    return launch_loop_cluster(ctx, g.cap, s.ctl_i_dev, s.poses_prop_dev, s.weights_dev, s.labels_dev, (double*)part, m.cen, m.sd, m.cnt, m.rot,
+                               merged, g.B);
+}
+
+// RESAMPLE over the cap2 slots a trajectory the annealed set may take
+static int loop_resample_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t cap2) {
+    const size_t Bz = (size_t)g.B;
+    const unsigned nb2 = (unsigned)ceil_div(cap2, SCAN_BLOCK);
+    void *lp, *bt, *bn;
+    int rc;
+    if ((rc = midas_scratch(ctx, Bz * ((size_t)cap2 + SCAN_CHUNK) * sizeof(double), &lp))) return rc;  // (the resample reads whole chunks)
+    if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(double), &bt))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(int32_t), &bn))) return rc;
+    hipLaunchKernelGGL(k_loop_scan, dim3(nb2, g.by()), dim3(256), 0, ctx->stream, (const int32_t*)s.ctl_i_dev, (const double*)s.x_dev,
+                       (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)lp, (double*)bt, (int32_t*)bn,
+                       g.slice, g.lp_stride);
+    LoopResampleArgs r;
+    fill_loop_resample(r, s, lp, bt, bn);  // (a batch's u_dev: NULL, or (B, cap) through midas_loop_step_batch_draws)
+    r.cap2 = loop_bound(cap2); r.cap = g.slice; r.lp_stride = g.lp_stride; r.log_stride = g.log_stride;
+    hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap2, 256), g.by()), dim3(256), 0, ctx->stream, r);
+    LAUNCH_CHECK(ctx);
+    return MIDAS_OK;
+}
+
 int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                      const midas_loop_args& s, int32_t phases) {
     // the grids cover `cap` particles: the capacity, or the caller's upper bound of the live count
     const int64_t cap = (s.grid_n > 0 && s.grid_n < s.cap) ? s.grid_n : s.cap;
-    const unsigned nbcap = (unsigned)ceil_div(cap, SCAN_BLOCK);
+    LoopGrid g;
+    g.cap = cap;
+#ifdef MIDAS_ANNEAL_CLOCKS
+    g.clocks = s.ctl_d_dev;
+#endif
     int rc;
     hipStream_t st = ctx->stream;
     LoopWeightsArgs wa{};
@@ -1323,24 +1394,9 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
             pa.sp.stamps = nullptr;  // scored densely just above
             if ((rc = launch_particle_update(ctx, t6, t3, pa))) return rc;
         }
-        LoopBlockResults br;
-        if ((rc = carve_block_results(ctx, nbcap, br))) return rc;
-        hipLaunchKernelGGL(k_loop_xe, dim3(nbcap), dim3(256), 0, st, (const int32_t*)s.ctl_i_dev, (const double*)s.scores_dev,
-                           (const int32_t*)s.nn_idx_dev, (const uint8_t*)s.valid_dev, s.softmax, s.unit_weights, s.x_dev, s.e_dev, br.bsum, br.bmax,
-                           br.bmin, br.bkept, br.bnan, (int32_t)(cap < (1 << 30) ? cap : (1 << 30)), cb->K,
-#ifdef MIDAS_ANNEAL_CLOCKS
-                           s.ctl_d_dev
-#else
-                           (double*)nullptr
-#endif
-                           );
-        fill_loop_weights(wa, s, br, (int32_t)(cap < (1 << 30) ? cap : (1 << 30)), nbcap, pa.gt16 != nullptr);
-        // the weights at the head of the cluster-moment launch when that launch follows in this call with nothing in between
-        // (DBSCAN reads the re-projected poses: frames that cluster keep the launch of their own)
         static const bool merge_env = !(getenv("MIDAS_LOOP_MERGE") && atoi(getenv("MIDAS_LOOP_MERGE")) == 0);
-        weights_merged = merge_env && (phases & MIDAS_LOOP_ANNEAL) && !(phases & MIDAS_LOOP_DBSCAN);
-        if (!weights_merged) hipLaunchKernelGGL(k_loop_weights, dim3(nbcap), dim3(256), 0, st, wa);
-        LAUNCH_CHECK(ctx);
+        weights_merged = merge_env && loop_weights_mergeable(phases);
+        if ((rc = loop_weights_phase(ctx, s, g, cb->K, pa.gt16 != nullptr, weights_merged, wa))) return rc;
     }
     if (phases & MIDAS_LOOP_DBSCAN) {
         if ((rc = launch_dbscan(ctx, cap, s.ctl_i_dev + LOOP_I_N, s.poses_prop_dev, s.eps, -1, s.labels_dev,
@@ -1348,55 +1404,36 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
             return rc;
     }
     if (phases & MIDAS_LOOP_ANNEAL) {
-        void *part, *cen, *sd, *cnt, *rot;
-        if ((rc = midas_scratch(ctx, LOOP_MAX_CLUSTERS * 10 * sizeof(double), &rot))) return rc;
-        if ((rc = midas_scratch(ctx, (size_t)ceil_div(cap, 256) * LOOP_MAX_CLUSTERS * 36 * sizeof(double), &part))) return rc;
-        if ((rc = midas_scratch(ctx, LOOP_MAX_CLUSTERS * 16 * sizeof(float), &cen))) return rc;
-        if ((rc = midas_scratch(ctx, LOOP_MAX_CLUSTERS * 3 * sizeof(float), &sd))) return rc;
-        if ((rc = midas_scratch(ctx, LOOP_MAX_CLUSTERS * sizeof(int64_t), &cnt))) return rc;
+        LoopMoments m;
+        if ((rc = loop_cluster_phase(ctx, s, g, weights_merged ? &wa : nullptr, m))) return rc;
         SelectScratch ss;
         if ((rc = select_scratch(ctx, cap, ss))) return rc;
-        if ((rc = launch_loop_cluster(ctx, cap, s.ctl_i_dev, s.poses_prop_dev, s.weights_dev, s.labels_dev, (double*)part, (float*)cen,
-                                      (float*)sd, (int64_t*)cnt, (double*)rot, weights_merged ? &wa : nullptr)))
-            return rc;
         if (s.anneal_frozen) {
             // live count == floor == the count annealing started from: the rule (particle_filter.py:421-446) cannot remove (needs
             // |n - floor| > 0) or duplicate (needs k + n <= init) - the decision's bookkeeping runs (cluster rows, variance), the ten
             // launches of the selection, which would each find mode 0 and leave, do not (45 us of a 118 us frame at N = 100k)
-            hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
-                               (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)rot, 1);
+            hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
+                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot, 1);
             LAUNCH_CHECK(ctx);
         } else if (s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU) {  // the reference's CPU tie choices (topk_aten.hip); the decision as always
-            hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
-                               (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)rot);
+            hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
+                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot);
             if ((rc = launch_topk_aten(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, nullptr))) return rc;
         } else if (s.anneal_small && cap <= LOOP_SMALL_MAX) {
-            hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
-                               (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor, (const double*)s.weights_dev, s.src_dev,
-                               (const double*)rot);
+            hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
+                               (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor,
+                               (const double*)s.weights_dev, s.src_dev, (const double*)m.rot);
             LAUNCH_CHECK(ctx);
         } else {
-            hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
-                               (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)rot);
+            hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
+                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot);
             if ((rc = launch_select(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, ss))) return rc;
         }
     }
     if (phases & MIDAS_LOOP_RESAMPLE) {
         // the annealed set may be a third larger than the particle set the bound was given for
         const int64_t cap2 = cap + cap / 3 + 1 < s.cap ? cap + cap / 3 + 1 : s.cap;
-        const unsigned nb2 = (unsigned)ceil_div(cap2, SCAN_BLOCK);
-        void *lp, *bt, *bn;
-        if ((rc = midas_scratch(ctx, ((size_t)cap2 + SCAN_CHUNK) * sizeof(double), &lp))) return rc;  // (the resample reads whole chunks)
-        if ((rc = midas_scratch(ctx, (size_t)nb2 * sizeof(double), &bt))) return rc;
-        if ((rc = midas_scratch(ctx, (size_t)nb2 * sizeof(int32_t), &bn))) return rc;
-        hipLaunchKernelGGL(k_loop_scan, dim3(nb2), dim3(256), 0, st, (const int32_t*)s.ctl_i_dev, (const double*)s.x_dev,
-                           (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)lp, (double*)bt,
-                           (int32_t*)bn);
-        LoopResampleArgs r;
-        fill_loop_resample(r, s, lp, bt, bn);
-        r.cap2 = (int32_t)(cap2 < (1 << 30) ? cap2 : (1 << 30));
-        hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap2, 256)), dim3(256), 0, st, r);
-        LAUNCH_CHECK(ctx);
+        if ((rc = loop_resample_phase(ctx, s, g, cap2))) return rc;
     }
     return MIDAS_OK;
 }
@@ -1411,8 +1448,9 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                            const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride) {
     const int64_t cap = s.cap;
-    const size_t Bz = (size_t)B;
-    const unsigned nbcap = (unsigned)ceil_div(cap, SCAN_BLOCK), by = (unsigned)B;
+    LoopGrid g;
+    g.cap = cap; g.B = B; g.slice = (int32_t)cap; g.log_stride = log_stride;
+    g.lp_stride = (int32_t)(cap + SCAN_CHUNK);  // (the resample reads whole chunks)
     int rc;
     hipStream_t st = ctx->stream;
     LoopWeightsArgs wa{};
@@ -1423,15 +1461,8 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
                              (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
         pa.n_live = s.ctl_i_dev + LOOP_I_N;
         if ((rc = launch_front_small_batch(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, B))) return rc;
-        LoopBlockResults br;
-        if ((rc = carve_block_results(ctx, Bz * nbcap, br))) return rc;
-        hipLaunchKernelGGL(k_loop_xe, dim3(nbcap, by), dim3(256), 0, st, (const int32_t*)s.ctl_i_dev, (const double*)s.scores_dev,
-                           (const int32_t*)s.nn_idx_dev, (const uint8_t*)s.valid_dev, s.softmax, s.unit_weights, s.x_dev, s.e_dev, br.bsum, br.bmax,
-                           br.bmin, br.bkept, br.bnan, (int32_t)cap, cb->K, (double*)nullptr);
-        fill_loop_weights(wa, s, br, (int32_t)cap, nbcap, pa.gt16 != nullptr);
-        weights_merged = (phases & MIDAS_LOOP_ANNEAL) && !(phases & MIDAS_LOOP_DBSCAN);  // (as launch_loop_step: DBSCAN reads the re-projected poses)
-        if (!weights_merged) hipLaunchKernelGGL(k_loop_weights, dim3(nbcap, by), dim3(256), 0, st, wa);
-        LAUNCH_CHECK(ctx);
+        weights_merged = loop_weights_mergeable(phases);
+        if ((rc = loop_weights_phase(ctx, s, g, cb->K, pa.gt16 != nullptr, weights_merged, wa))) return rc;
     }
     if (phases & MIDAS_LOOP_DBSCAN) {
         // one trajectory after the other on the stream, each on its slices; the passes take the same scratch (one set of cell tables)
@@ -1445,43 +1476,22 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
         }
     }
     if (phases & MIDAS_LOOP_ANNEAL) {
-        void *part, *cen, *sd, *cnt, *rot;
-        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 10 * sizeof(double), &rot))) return rc;
-        if ((rc = midas_scratch(ctx, Bz * (size_t)ceil_div(cap, 256) * LOOP_MAX_CLUSTERS * 36 * sizeof(double), &part))) return rc;
-        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 16 * sizeof(float), &cen))) return rc;
-        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * 3 * sizeof(float), &sd))) return rc;
-        if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * sizeof(int64_t), &cnt))) return rc;
-        if ((rc = launch_loop_cluster(ctx, cap, s.ctl_i_dev, s.poses_prop_dev, s.weights_dev, s.labels_dev, (double*)part, (float*)cen,
-                                      (float*)sd, (int64_t*)cnt, (double*)rot, weights_merged ? &wa : nullptr, B)))
-            return rc;
+        LoopMoments m;
+        if ((rc = loop_cluster_phase(ctx, s, g, weights_merged ? &wa : nullptr, m))) return rc;
         if (s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU) {  // the decision alone per trajectory, then B walks side by side
-            hipLaunchKernelGGL(k_loop_decide, dim3(2, by), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen, (const float*)sd,
-                               (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, (uint32_t*)nullptr, (int32_t*)nullptr, s.floor,
-                               (const double*)rot);
+            hipLaunchKernelGGL(k_loop_decide, dim3(2, g.by()), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
+                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, (uint32_t*)nullptr, (int32_t*)nullptr, s.floor,
+                               (const double*)m.rot);
             if ((rc = launch_topk_aten(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, nullptr, B))) return rc;
         } else {
-            hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, by), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)cen,
-                               (const float*)sd, (const int64_t*)cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor,
-                               (const double*)s.weights_dev, s.src_dev, (const double*)rot, (int32_t)cap);
+            hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, g.by()), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
+                               (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor,
+                               (const double*)s.weights_dev, s.src_dev, (const double*)m.rot, (int32_t)cap);
         }
         LAUNCH_CHECK(ctx);
     }
-    if (phases & MIDAS_LOOP_RESAMPLE) {
-        const unsigned nb2 = nbcap;  // (the annealed set never exceeds the capacity)
-        const int64_t lp_stride = cap + SCAN_CHUNK;  // (the resample reads whole chunks)
-        void *lp, *bt, *bn;
-        if ((rc = midas_scratch(ctx, Bz * (size_t)lp_stride * sizeof(double), &lp))) return rc;
-        if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(double), &bt))) return rc;
-        if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(int32_t), &bn))) return rc;
-        hipLaunchKernelGGL(k_loop_scan, dim3(nb2, by), dim3(256), 0, st, (const int32_t*)s.ctl_i_dev, (const double*)s.x_dev,
-                           (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)lp, (double*)bt,
-                           (int32_t*)bn, (int32_t)cap, (int32_t)lp_stride);
-        LoopResampleArgs r;
-        fill_loop_resample(r, s, lp, bt, bn);  // (u_dev: NULL, or (B, cap) through midas_loop_step_batch_draws)
-        r.cap2 = (int32_t)cap; r.cap = (int32_t)cap; r.lp_stride = (int32_t)lp_stride; r.log_stride = log_stride;
-        hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, st, r);
-        LAUNCH_CHECK(ctx);
-    }
+    if (phases & MIDAS_LOOP_RESAMPLE)
+        if ((rc = loop_resample_phase(ctx, s, g, cap))) return rc;  // (the annealed set never exceeds the capacity)
     return MIDAS_OK;
 }
 

@@ -510,6 +510,27 @@ struct StepTailArgs {
     int64_t score_stride = 0;  // K: scores are (batch, K)
     int64_t tstride = 0;       // pipelined batch: doubles between two trajectories' table blocks (tables_of layout per trajectory)
 };
+// The fields the eager step and the pipelined flush fill alike from their arguments (midas_step_args and midas_lazy_flush_args
+// name them the same), as fill_particle_update does for the front; every other field of `ta` is the caller's.
+template <class TailFrameArgs>
+inline void fill_step_tail(StepTailArgs& ta, const TailFrameArgs& s) {
+    ta.N = s.N;
+    ta.softmax = s.softmax;
+    ta.weights = s.weights_dev;
+    ta.status = s.status_dev;
+    ta.mode = s.resample_mode;
+    ta.u = s.u_dev;
+    ta.u32 = s.u32;
+    ta.seed = s.seed;
+    ta.step = s.step;
+    ta.ridx = s.ridx_dev;
+    ta.poses_prop = s.poses_prop_dev;
+    ta.poses_out = s.poses_out_dev;
+    ta.weights_out = s.weights_out_dev;
+    ta.nn_idx = s.nn_idx_dev;
+    ta.hint_out = s.hint_out_dev;
+    ta.rmse_out = s.rmse_dev;
+}
 // the deferred tail on explicit tables (what k_tail_a2 writes and k_tail_b2 / the lazy front read)
 struct TailTables {
     double *e, *x_raw, *lp, *lp_raw, *gend, *gend_raw;       // [N] x4, [ceil(N/16)] x2
@@ -520,7 +541,7 @@ struct TailTables {
 int launch_tail_a2(midas_ctx* ctx, int64_t N, const double* scores, const int32_t* nn_idx, const uint8_t* valid,
                    int32_t softmax, const TailTables& tb, int32_t* status, int batch = 1, int64_t score_stride = 0,
                    bool padded_tables = false, const double* part_rmse = nullptr, double* rmse_out = nullptr, int64_t tstride = 0,
-                   const ScorePredict* predict = nullptr);  // padded: per-slot tables hold a multiple of 16 values (tables_of, api.hip)
+                   const ScorePredict* predict = nullptr);  // padded: per-slot tables hold a multiple of 16 values (tables_of, api_entry.hpp)
 int launch_predict_seed(midas_ctx* ctx, int64_t N, const int32_t* idx, const ScorePredict& pr);
 int launch_shard_tail_a(midas_ctx* ctx, int64_t N, const double* scores, const int32_t* nn_idx, const uint8_t* valid,
                         int32_t softmax, const TailTables& tb, double* r1, int32_t* status, const double* part_rmse = nullptr,

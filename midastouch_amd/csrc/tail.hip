@@ -403,7 +403,7 @@ int launch_shard_tail_a(midas_ctx* ctx, int64_t N, const double* scores, const i
     const ScorePredict* list = predict && predict->stamps && predict->list ? predict : nullptr;
     if ((part_rmse || list) && N < SCAN_CHUNK)
         return midas_set_error(ctx, MIDAS_ERR_INVALID, "shard tail", "rmse sums / prediction list in the tail need the direct tail kernel (N >= 16)");
-    if (N >= SCAN_CHUNK) {  // the shard's per-slot tables are padded (shard_tables_of, api.hip)
+    if (N >= SCAN_CHUNK) {  // the shard's per-slot tables are padded (shard_tables_of, api_shard.hip)
         TailTables t = tb;
         t.bsum_e = r1; t.btot = r1 + nb; t.btot_raw = r1 + 2 * nb; t.bmax = r1 + 3 * nb; t.bmin = r1 + 4 * nb;
         if (tail_grouped_ok(ctx, N, nn_idx, valid, t, predict_blocks(list)))

@@ -530,3 +530,61 @@ def test_loop_engine_tiny_particle_sets(dev, oracle, N0):
         _compare_frame(eng.frame_view(), ref, t, t % 3 == 0)
         poses, labels = ref["poses"], ref["labels"]
     assert int(eng.ctl_i[14].item()) == 0  # no limit / bound error flagged
+
+
+def test_loop_entries_reject_malformed_arguments(dev):
+    """midas_loop_step, midas_loop_step_batch and midas_loop_step_batch_draws share one argument check: each malformed call
+    returns MIDAS_ERR_INVALID with nothing enqueued, and midas_last_error names the condition that failed."""
+    import ctypes as C
+    from midastouch_amd import _lib
+    ctx = _lib.context(dev)
+    lib, none = ctx.lib, C.c_void_p()
+    # every array of a 16-particle frame: zeroed device memory 16 KB apart (a live count of 0), though no call here gets to a launch
+    buf = torch.zeros(1 << 20, dtype=torch.uint8, device=dev)
+    pointers = [name for name, kind in _lib.LoopArgs._fields_ if kind is C.c_void_p]
+
+    def frame(**changes):
+        a = _lib.LoopArgs()
+        for i, name in enumerate(pointers):
+            setattr(a, name, buf.data_ptr() + 16384 * (i + 1))
+        a.tn = a.rot = a.u = a.log = a.host_mirror = a.telemetry = a.gt16 = a.part_rmse = None  # device draws, no log, no rmse
+        a.cap, a.eps, a.floor, a.softmax, a.score_epoch = 16, 1e-2, 8, 1, 1
+        a.resample_mode, a.topk_ties = _lib.RESAMPLE_MULTINOMIAL, _lib.TOPK_TIES_INDEX
+        for name, value in changes.items():
+            setattr(a, name, value)
+        return a
+
+    single = lambda a, ph: lib.midas_loop_step(ctx.h, none, none, none, C.byref(a), ph)
+    batch = lambda a, ph: lib.midas_loop_step_batch(ctx.h, none, none, none, C.byref(a), ph, 2, _lib.LOOP_LOG_DOUBLES)
+    draws = lambda a, ph: lib.midas_loop_step_batch_draws(ctx.h, none, none, none, C.byref(a), ph, 2, _lib.LOOP_LOG_DOUBLES)
+    tail = _lib.LOOP_ANNEAL | _lib.LOOP_RESAMPLE  # phases that take no codebook: every case below is rejected on its own fault
+
+    def rejected(entry, a, phases, names):
+        assert entry(a, phases) == -1  # MIDAS_ERR_INVALID
+        text = lib.midas_last_error(ctx.h).decode()
+        assert text.startswith("invalid argument: ") and names in text, text
+
+    all_null = _lib.LoopArgs()
+    all_null.cap, all_null.eps = 16, 1e-2
+    only_ctl = frame(**{name: None for name in pointers if name not in ("ctl_i", "ctl_d")})
+    for entry in (single, batch, draws):
+        rejected(entry, all_null, tail, "s.ctl_i_dev && s.ctl_d_dev")
+        rejected(entry, only_ctl, tail, "s.poses_dev && s.poses_prop_dev")
+        a = frame()
+        rejected(entry, frame(poses_prop=a.poses), tail, "s.poses_dev != s.poses_prop_dev")
+        rejected(entry, frame(), 0, "phases != 0")
+        rejected(entry, frame(), 16, "(phases & ~15) == 0")
+        rejected(entry, frame(resample_mode=2), tail, "s.resample_mode == MIDAS_RESAMPLE_MULTINOMIAL")
+        rejected(entry, frame(resample_mode=-1), _lib.LOOP_RESAMPLE, "s.resample_mode == MIDAS_RESAMPLE_MULTINOMIAL")
+        rejected(entry, frame(), _lib.LOOP_FRONT, "cb && tree6 && tree3")
+    for entry in (batch, draws):
+        rejected(entry, frame(cap=_lib.LOOP_BATCH_MAX_CAP + 1), tail, "s.cap <= MIDAS_LOOP_BATCH_MAX_CAP")
+        rejected(entry, frame(grid_n=8), tail, "s.grid_n == 0")
+        rejected(entry, frame(anneal_frozen=1), tail, "s.anneal_frozen == 0")
+    host = frame()
+    rejected(batch, frame(tn=host.poses, rot=host.poses_prop), tail, "s.tn_dev == nullptr && s.rot_dev == nullptr && s.u_dev == nullptr")
+    rejected(batch, frame(u=host.x), tail, "s.u_dev == nullptr")
+    rejected(batch, frame(topk_ties=_lib.TOPK_TIES_ATEN_CPU), tail, "s.topk_ties == MIDAS_TOPK_TIES_INDEX")
+    rejected(draws, frame(tn=host.poses), tail, "(s.tn_dev == nullptr) == (s.rot_dev == nullptr)")
+    rejected(draws, frame(topk_ties=2), tail, "s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU")
+    assert lib.midas_sync(ctx.h) == 0
