@@ -890,7 +890,12 @@ int midas_tail_resample(midas_ctx* ctx, const midas_tail_resample_args* args);
                                 * MIDAS_LOOP_MAX_CLUSTERS - 1 clusters (decide / DBSCAN), bit 2: live count above the launches' bound (particles were
                                 * not processed), bit 5: DBSCAN saw non-finite translations or more than 2^21 cells per axis, bit 6: a
                                 * cloud wider than 128 cells per axis with more than 2^20 particles (bits 5 / 6: labels undefined), bit 7: anneal_frozen was
-                                * set and the annealing rule wanted to act (the set was left as it was: not the reference's) */
+                                * set and the annealing rule wanted to act (the set was left as it was: not the reference's), bit 8: the
+                                * resample's cdf status disagrees with ctl_i[NDRAW] (stream_draws: the caller's stream drew, or skipped,
+                                * what the reference's did not) */
+#define MIDAS_LOOP_I_NDRAW 15  /* stream_draws: uniforms the reference's resampler draws on this frame - NSET when the resample's cdf
+                                * status is 0, else 0: on all-zero or NaN weights it returns its input before it draws
+                                * (modules/particle_filter.py:237-241) and torch's generator does not move */
 /* ctl_d (16 x float64) */
 #define MIDAS_LOOP_D_S 0        /* softmax denominator (1 when raw) */
 #define MIDAS_LOOP_D_VARPREV 1  /* particle_var (float32 value) */
@@ -954,13 +959,20 @@ typedef struct midas_loop_args {
                                     * kernel; the fast radix select).  MIDAS_TOPK_TIES_ATEN_CPU (1): the members - and for duplicates
                                     * the order - ATen's CPU kernel picks (std::partial_sort when k * 64 <= n, else std::nth_element +
                                     * std::sort, walked move for move by one wave: topk_aten.hip), i.e. what the reference keeps when it
-                                    * runs on the CPU under a fixed seed (modules/particle_filter.py:433-441) */
+                                    * runs on the CPU under a fixed seed (modules/particle_filter.py:433-441).  In this mode the frame's
+                                    * `var` is torch.mean(cluster_stds) in the order ATen's CPU sum adds (not the running sum of the
+                                    * other mode), of spreads taken in two passes about the float32 centre (0 where a cluster's
+                                    * members coincide; the closed form on the moments leaves ~1e-9 there) */
     int32_t anneal_frozen;         /* 1: the caller states that annealing cannot change the set - the live count equals `floor` AND the
                                     * count annealing started from (modules/particle_filter.py:421-446: a removal needs |n - floor| > 0,
                                     * a duplication k + n <= init_particles; both stay impossible once they are).  The ANNEAL phase then
                                     * runs its decision only (cluster rows, variance: two small workgroups) and none of the selection's
                                     * launches; the decision checks the statement and raises ctl_i[ERR] bit 7 if it finds work to do. */
-    int32_t pad2_;
+    int32_t stream_draws;          /* 1: the frame's uniforms (u_dev) come from a stream that has to stay the reference's, drawn between
+                                    * this call and the one that holds RESAMPLE.  A call without RESAMPLE then ends by writing
+                                    * ctl_i[NDRAW] - the status of the annealed set's CDF as the resample will compute it (the scan's
+                                    * block totals, one more small launch) - for the caller's counted draw; the RESAMPLE call checks its
+                                    * own status against the word (ctl_i[ERR] bit 8).  0: neither (Philox frames: the launches as ever) */
 } midas_loop_args;
 int midas_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                     const midas_loop_args* args, int32_t phases);
@@ -997,7 +1009,7 @@ int midas_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_
  *                    ctl_i[MODE, K, NSET]) by the kernel midas_loop_step runs for it, then B one-wave walks of ATen's algorithm side
  *                    by side, the other kernels of that path with the trajectory as grid.y.
  * `phases` may be a subset: a seeded frame is FRONT | DBSCAN | ANNEAL, then - once the uniforms are drawn for the annealed counts
- * (midas_mt19937_draws_counted_batch on ctl_i[b][MIDAS_LOOP_I_NSET]) - RESAMPLE.  With NULL draws and ties by index the call is
+ * (midas_mt19937_draws_counted_batch on ctl_i[b][MIDAS_LOOP_I_NDRAW], written per trajectory under stream_draws) - RESAMPLE.  With NULL draws and ties by index the call is
  * midas_loop_step_batch; with these draws trajectory b holds the bits of midas_loop_step on it alone with the same draws. */
 int midas_loop_step_batch_draws(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                                 const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);

@@ -202,7 +202,7 @@ class LoopArgs(C.Structure):
         ("unit_weights", C.c_int32), ("telemetry", C.c_void_p),
         ("score_stamps", C.c_void_p), ("score_epoch", C.c_uint32),
         ("host_mirror", C.c_void_p), ("grid_n", C.c_int64), ("anneal_small", C.c_int32), ("topk_ties", C.c_int32),
-        ("anneal_frozen", C.c_int32), ("pad2_", C.c_int32),
+        ("anneal_frozen", C.c_int32), ("stream_draws", C.c_int32),
     ]
 
 
@@ -213,7 +213,8 @@ TOPK_TIES_INDEX, TOPK_TIES_ATEN_CPU = 0, 1  # whom annealing's torch.topk takes 
 LOOP_MAX_CLUSTERS, LOOP_LOG_DOUBLES = 64, 168
 LOOP_BATCH_MAX_CAP = 16384  # MIDAS_LOOP_BATCH_MAX_CAP: particles per trajectory midas_loop_step_batch takes
 (LOOP_I_N, LOOP_I_NSET, LOOP_I_MODE, LOOP_I_K, LOOP_I_INIT, LOOP_I_VARSET, LOOP_I_KEPT, LOOP_I_DRIFT, LOOP_I_STATUS,
- LOOP_I_RAW, LOOP_I_NCL, LOOP_I_NPRES, LOOP_I_FRAME, LOOP_I_NAN, LOOP_I_ERR) = range(15)
+ LOOP_I_RAW, LOOP_I_NCL, LOOP_I_NPRES, LOOP_I_FRAME, LOOP_I_NAN, LOOP_I_ERR, LOOP_I_NDRAW) = range(16)
+LOOP_ERR_NDRAW = 256  # ctl_i[ERR] bit 8: the resample's status disagrees with ctl_i[NDRAW]
 (LOOP_D_S, LOOP_D_VARPREV, LOOP_D_VAR, LOOP_D_RMSE_T, LOOP_D_RMSE_R, LOOP_D_XMAX, LOOP_D_XMIN, LOOP_D_TOTAL) = range(8)
 
 # name -> (restype, argtypes); must list every symbol include/midas_hip.h declares

@@ -177,7 +177,8 @@ class BatchLoopEngine:
         """Trajectory b draws as a process of the reference under torch.manual_seed(seeds[b]) (or continues the torch.Generator
         seeds[b]): `torch.normal(0, mul * sig_t, (n_b, 3))`, `torch.normal(0, mul * sig_r, (n_b, 3))` with n_b ITS live count
         (add_noise_to_odom, particle_filter.py:326-335) and, behind annealing, n_set_b float64 uniforms (the resampler's
-        torch.multinomial, :245), all counts read on the device (midas_mt19937_draws_counted_batch); ties of annealing's top-k follow
+        torch.multinomial, :245) - none for a row whose weights are all zero or hold a NaN on that frame, where the resampler returns
+        before it draws (:237-241; ctl_i[b][LOOP_I_NDRAW]) - all counts read on the device (midas_mt19937_draws_counted_batch); ties of annealing's top-k follow
         ATen's CPU kernel (`topk_ties` becomes "aten_cpu").  Returns the TorchCpuStreams (manual_seed / from_host / to_host per
         row).  seeds=None: back to Philox draws and ties by index.
         The generator runs on the engine's stream; its scratch and the walk's are reserved here, so no frame allocates.  A live
@@ -274,12 +275,16 @@ class BatchLoopEngine:
             st.draws_counted_async([("normal", 0.0, a.std_t, self.ctl_i, _lib.LOOP_I_N, 3, self.cap),
                                     ("normal", 0.0, a.std_r, self.ctl_i, _lib.LOOP_I_N, 3, self.cap)], outs=[self._tn, self._rot], status=status)
             a.tn, a.rot, a.u = _ptr(self._tn), _ptr(self._rot), _ptr(self._u)
+            a.stream_draws = 1
             try:
                 call(self.ctx.lib.midas_loop_step_batch_draws, phases & ~_lib.LOOP_RESAMPLE)
-                st.draws_counted_async([("rand64", self.ctl_i, _lib.LOOP_I_NSET, self.cap)], outs=[self._u], status=status)
+                # every row's NDRAW, not NSET: a row whose weights are all zero or hold a NaN draws nothing on this frame, as the
+                # reference's resampler (particle_filter.py:237-241) - its stream stays where it is, the other rows' move on
+                st.draws_counted_async([("rand64", self.ctl_i, _lib.LOOP_I_NDRAW, self.cap)], outs=[self._u], status=status)
                 call(self.ctx.lib.midas_loop_step_batch_draws, _lib.LOOP_RESAMPLE)
             finally:
                 a.tn = a.rot = a.u = None
+                a.stream_draws = 0
         elif self._topk_ties == "aten_cpu":
             call(self.ctx.lib.midas_loop_step_batch_draws, phases)  # (Philox draws, the ATen tie rule)
         else:

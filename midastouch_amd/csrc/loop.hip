@@ -18,6 +18,8 @@
 //             k_loop_sort_chunks / k_loop_sort_rank (the duplicates in topk's output order: weight descending, index ascending)
 //   RESAMPLE  k_loop_scan (blocked prefix sums of (e * valid)[src]) -> k_loop_resample (n_set draws, exact inverse
 //             search on cdf_i = (BP_b + lp_i) / total, gathers through src)
+//   A frame whose uniforms come from a caller's stream (stream_draws) is split in front of RESAMPLE; its first call ends with
+//   k_loop_scan -> k_loop_ndraw: ctl_i[NDRAW], the uniforms the reference's resampler draws - none on all-zero or NaN weights.
 //
 // Spec (oracle/oracle.py OracleLoop): identical to midas_filter_step where the two overlap; ties of the top-k selection go
 // to the smaller index (torch's CUDA rule), or - midas_loop_args.topk_ties = MIDAS_TOPK_TIES_ATEN_CPU, the mode that replays a
@@ -206,13 +208,52 @@ __global__ __launch_bounds__(256) void k_loop_weights(LoopWeightsArgs a) {
 }
 
 // ---- ANNEAL ---------------------------------------------------------------------------------------------------------
-// One workgroup: the clusters present (labels ascending) -> compact rows, var = float32 running sum of their stds / count
-// (torch.mean(cluster_stds), filter.py:189), then particle_filter.annealing's rule (:413-447) in the float32 arithmetic torch
+// torch.sum of n < 512 contiguous float32 values in the order ATen's CPU kernel adds them (SumKernel.cpp, the AVX2 build: 8 lanes):
+// whole vectors into four interleaved vector accumulators (row_sum, ilp 4; below the cascade's first carry), leftover vectors into
+// the first, the four added 0 + 1 + 2 + 3; then the scalar tail in order, then the 8 lanes in order.  Fewer than 8 values: the same
+// row_sum on scalars.  A running sum differs from it in the last bit from 6 values - two clusters - on (oracle.aten_sum_f32).
+MD float aten_sum_f32(const float* __restrict__ x, int n) {
+    constexpr int V = 8, ILP = 4;
+    const int vs = n / V;
+    if (vs == 0) {
+        float a[ILP] = {0.f, 0.f, 0.f, 0.f};
+        const int g = n / ILP;
+        for (int i = 0; i < g; ++i)
+#pragma unroll
+            for (int k = 0; k < ILP; ++k) a[k] = a[k] + x[i * ILP + k];
+        for (int i = g * ILP; i < n; ++i) a[0] = a[0] + x[i];
+        return ((a[0] + a[1]) + a[2]) + a[3];
+    }
+    float acc[ILP][V];
+#pragma unroll
+    for (int k = 0; k < ILP; ++k)
+#pragma unroll
+        for (int l = 0; l < V; ++l) acc[k][l] = 0.f;
+    const int g = vs / ILP;
+    for (int i = 0; i < g; ++i)
+#pragma unroll
+        for (int k = 0; k < ILP; ++k)
+#pragma unroll
+            for (int l = 0; l < V; ++l) acc[k][l] = acc[k][l] + x[(i * ILP + k) * V + l];
+    for (int i = g * ILP; i < vs; ++i)
+#pragma unroll
+        for (int l = 0; l < V; ++l) acc[0][l] = acc[0][l] + x[i * V + l];
+    float fin = 0.f;
+    for (int j = vs * V; j < n; ++j) fin = fin + x[j];
+#pragma unroll
+    for (int l = 0; l < V; ++l) fin = fin + (((acc[0][l] + acc[1][l]) + acc[2][l]) + acc[3][l]);
+    return fin;
+}
+
+// One workgroup: the clusters present (labels ascending) -> compact rows, var = float32 sum of their stds / count
+// (torch.mean(cluster_stds), filter.py:189; a running sum, or ATen's order: loop_decide), then particle_filter.annealing's rule (:413-447) in the float32 arithmetic torch
 // uses for `var / self.particle_var`, `1.0 - ratio` and `* N`.  Also clears the select histograms.
 // (one thread) -> {mode, k}
+// aten_order: var as torch.mean adds it on the CPU (the reference's own bits: with MIDAS_TOPK_TIES_ATEN_CPU, the mode that replays
+// a CPU run), else the running sum (ties by index - torch's CUDA rule, whose reduction order is not modelled).
 MD void loop_decide(int32_t* __restrict__ ctl_i, double* __restrict__ ctl_d, const float* __restrict__ centers_all,
                     const float* __restrict__ stds_all, const int64_t* __restrict__ counts_all, float* __restrict__ centers_out,
-                    float* __restrict__ stds_out, int32_t floor_n, int& mode_out, int& k_out) {
+                    float* __restrict__ stds_out, int32_t floor_n, int& mode_out, int& k_out, bool aten_order = false) {
     const int32_t n = ctl_i[LOOP_I_N];
     int C = ctl_i[LOOP_I_NCL] + 1;
     if (C > LOOP_MAX_CLUSTERS) { C = LOOP_MAX_CLUSTERS; ctl_i[LOOP_I_ERR] |= 1; }
@@ -230,6 +271,7 @@ MD void loop_decide(int32_t* __restrict__ ctl_i, double* __restrict__ ctl_d, con
         }
         ++np;
     }
+    if (aten_order) sum = aten_sum_f32(stds_out, 3 * np);  // (the compact rows this thread has just written)
     const float var = sum / (float)(3 * np);
     ctl_i[LOOP_I_NPRES] = np;
     ctl_d[LOOP_D_VAR] = (double)var;
@@ -284,7 +326,7 @@ __global__ __launch_bounds__(256) void k_loop_decide(int32_t* __restrict__ ctl_i
                                                      const int64_t* __restrict__ counts_all, float* __restrict__ centers_out,
                                                      float* __restrict__ stds_out, uint32_t* __restrict__ hist,
                                                      int32_t* __restrict__ sel_state, int32_t floor_n, const double* __restrict__ rot,
-                                                     int32_t frozen = 0) {
+                                                     int32_t frozen = 0, int32_t aten_order = 0) {
     if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch_draws): LOOP_MAX_CLUSTERS cluster rows each, no select state
         const int64_t b = blockIdx.y;
         ctl_i += b * LOOP_CTL_I; ctl_d += b * LOOP_CTL_D;
@@ -296,7 +338,7 @@ __global__ __launch_bounds__(256) void k_loop_decide(int32_t* __restrict__ ctl_i
     if (!hist) {  // the decision alone (the batch's ATen walk: no radix select follows)
         if (t != 0) return;
         int mode, k;
-        loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k);
+        loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k, aten_order != 0);
         return;
     }
     for (int i = t; i < SEL_PASSES * SEL_BINS; i += 256) hist[i] = 0u;
@@ -304,13 +346,75 @@ __global__ __launch_bounds__(256) void k_loop_decide(int32_t* __restrict__ ctl_i
     __syncthreads();
     if (t != 0) return;
     int mode, k;
-    loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k);
+    loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k, aten_order != 0);
     if (frozen && mode) {  // the caller said annealing cannot act and no selection was launched: the set stays, the frame says so
         ctl_i[LOOP_I_ERR] |= 128;
         ctl_i[LOOP_I_MODE] = 0; ctl_i[LOOP_I_K] = 0; ctl_i[LOOP_I_NSET] = ctl_i[LOOP_I_N];
         k = 0;
     }
     sel_state[0] = 0; sel_state[1] = 0; sel_state[2] = k;  // pass 0: empty prefix, rank k
+}
+
+// MIDAS_TOPK_TIES_ATEN_CPU (a replay of the reference's bits): the clusters' spreads once more, as the two-pass form of the spec -
+// sqrt(sum w (t - m)^2 / sum w) about the float32 centre m k_loop_cluster_finish wrote, differences first - in place of the closed
+// form on the moments (cluster_close), which cancels: where the members of a cluster coincide (a drifted frame puts every particle
+// on a codebook pose) the spread is 0 and the closed form leaves ~1e-9, enough to move var by one float32 step.  Workgroup c takes
+// label c - 1: its threads walk the particles with stride 256, the partial sums meet in a fixed tree.  Weights: the float32 values,
+// or 1 when isclose(max - min, 0) (particle_filter.py:161-167), as cluster_close decides it.
+__global__ __launch_bounds__(256) void k_loop_std_two_pass(const int32_t* __restrict__ ctl_i, const float* __restrict__ poses,
+                                                           const double* __restrict__ w64, const int32_t* __restrict__ labels,
+                                                           const float* __restrict__ centers, float* __restrict__ stds,
+                                                           const int64_t* __restrict__ counts, int64_t cap) {
+    __shared__ double s_r[4][256];
+    __shared__ float s_x[2][256];
+    if (blockIdx.y) {  // a batch of trajectories: `cap` particles and LOOP_MAX_CLUSTERS cluster rows each
+        const int64_t b = blockIdx.y, o = b * cap;
+        ctl_i += b * LOOP_CTL_I; poses += o * 16; w64 += o; labels += o;
+        centers += b * LOOP_MAX_CLUSTERS * 16; stds += b * LOOP_MAX_CLUSTERS * 3; counts += b * LOOP_MAX_CLUSTERS;
+    }
+    const int c = blockIdx.x, t = threadIdx.x;
+    int C = ctl_i[LOOP_I_NCL] + 1;
+    C = C > LOOP_MAX_CLUSTERS ? LOOP_MAX_CLUSTERS : C;
+    if (c >= C || counts[c] == 0) return;  // (uniform over the workgroup)
+    int64_t n = ctl_i[LOOP_I_N];
+    n = n < cap ? n : cap;
+    const int32_t lab = c - 1;
+    float wmax = -INFINITY, wmin = INFINITY;
+    for (int64_t i = t; i < n; i += 256) {
+        if (labels[i] != lab) continue;
+        const float w = (float)w64[i];
+        wmax = w > wmax ? w : wmax;
+        wmin = w < wmin ? w : wmin;
+    }
+    s_x[0][t] = wmax; s_x[1][t] = wmin;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) {
+            s_x[0][t] = s_x[0][t + h] > s_x[0][t] ? s_x[0][t + h] : s_x[0][t];
+            s_x[1][t] = s_x[1][t + h] < s_x[1][t] ? s_x[1][t + h] : s_x[1][t];
+        }
+        __syncthreads();
+    }
+    const bool flat = __builtin_fabsf(s_x[0][0] - s_x[1][0]) <= 1e-8f;
+    const double m0 = (double)centers[c * 16 + 3], m1 = (double)centers[c * 16 + 7], m2 = (double)centers[c * 16 + 11];
+    double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int64_t i = t; i < n; i += 256) {
+        if (labels[i] != lab) continue;
+        const double w = flat ? 1.0 : (double)(float)w64[i];
+        const double d0 = (double)poses[i * 16 + 3] - m0, d1 = (double)poses[i * 16 + 7] - m1, d2 = (double)poses[i * 16 + 11] - m2;
+        sw = sw + w;
+        s0 = s0 + (d0 * d0) * w; s1 = s1 + (d1 * d1) * w; s2 = s2 + (d2 * d2) * w;
+    }
+    s_r[0][t] = sw; s_r[1][t] = s0; s_r[2][t] = s1; s_r[3][t] = s2;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s_r[k][t] = s_r[k][t] + s_r[k][t + h];
+        }
+        __syncthreads();
+    }
+    if (t < 3) stds[c * 3 + t] = (float)__builtin_sqrt(s_r[1 + t][0] / s_r[0][0]);
 }
 
 // the selection key of particle i: ascending for a removal (k smallest weights), complemented for a duplication (k largest)
@@ -964,6 +1068,51 @@ __global__ __launch_bounds__(256) void k_loop_scan(const int32_t* __restrict__ c
     if (t == 0) { btot[blk] = W; bnan[blk] = f; }
 }
 
+// The status of the annealed set's CDF from the scan's block results, by a 256-thread workgroup (thread t brings block t's total and
+// NaN flag; nb <= LAZY_MAX_BLOCKS blocks are alive, the launch was sized for nb_cap): the block totals added one after the other in
+// block order - s_bp[b] = the total in front of block b, s_bp[nb] the CDF's - then 2 for a NaN (any block's flag, or the total), 1
+// for a total of zero, else 0.  k_loop_resample resamples by it; k_loop_ndraw tells a caller's stream by it, ahead of the resample,
+// whether the reference's resampler draws on this frame.
+MD int loop_cdf_status(double bt_t, int bn_t, int nb, int nb_cap, double* __restrict__ s_bp, int* __restrict__ s_flag) {
+    const int t = threadIdx.x;
+    const int nbl = nb < nb_cap ? nb : nb_cap;  // (more alive than the launch was sized for: flagged elsewhere; stay inside the arrays)
+    if (t < nbl) s_bp[t + 1] = bt_t;
+    if (t == 0) *s_flag = 0;
+    __syncthreads();
+    if (t < nbl && bn_t) *s_flag = 1;
+    if (t == 0) {
+        double acc = 0.0;
+        s_bp[0] = 0.0;
+        for (int b = 0; b < nb; ++b) { const double w = s_bp[b + 1]; acc = acc + w; s_bp[b + 1] = acc; }
+    }
+    __syncthreads();
+    const double total = s_bp[nb];
+    return (*s_flag || total != total) ? 2 : (total == 0.0 ? 1 : 0);
+}
+
+// ctl_i[NDRAW] = the uniforms the reference's resampler draws on this frame: n_set, or 0 where it returns its input before drawing
+// (all-zero or NaN weights, particle_filter.py:237-241) - from the block results of a k_loop_scan over the annealed set, launched
+// with the resample's bound cap2.  One workgroup a trajectory (blockIdx.y), behind the frame's phases up to ANNEAL and in front of
+// the caller's counted draw (midas_loop_args.stream_draws).
+__global__ __launch_bounds__(256) void k_loop_ndraw(int32_t* __restrict__ ctl_i, const double* __restrict__ btot,
+                                                    const int32_t* __restrict__ bnan, int32_t cap2) {
+    __shared__ double s_bp[LAZY_MAX_BLOCKS + 1];
+    __shared__ int s_flag;
+    const int nb_cap = (int)(((int64_t)cap2 + SCAN_BLOCK - 1) / SCAN_BLOCK);
+    if (blockIdx.y) {
+        const int64_t b = blockIdx.y;
+        ctl_i += b * LOOP_CTL_I; btot += b * nb_cap; bnan += b * nb_cap;
+    }
+    const int t = threadIdx.x;
+    const int tb = t < nb_cap ? t : nb_cap - 1;
+    const double bt_t = btot[tb];
+    const int bn_t = bnan[tb];
+    const int64_t n2 = ctl_i[LOOP_I_NSET];
+    const int nb = (int)((n2 + SCAN_BLOCK - 1) / SCAN_BLOCK);
+    const int status = loop_cdf_status(bt_t, bn_t, nb < LAZY_MAX_BLOCKS ? nb : LAZY_MAX_BLOCKS, nb_cap, s_bp, &s_flag);
+    if (t == 0) ctl_i[LOOP_I_NDRAW] = status ? 0 : (int32_t)n2;
+}
+
 struct LoopResampleArgs {
     int32_t* ctl_i;
     double* ctl_d;
@@ -993,6 +1142,7 @@ struct LoopResampleArgs {
     // between two trajectories' tables, doubles between their log rows
     int32_t cap = 0, lp_stride = 0;
     int64_t log_stride = 0;
+    int32_t check_ndraw = 0;  // midas_loop_args.stream_draws: the frame's status against ctl_i[NDRAW]
 };
 
 // n_set draws over cdf_i = (BP_b + lp_i) / total (last slot 1): lower bound (multinomial) / upper bound (systematic) by
@@ -1069,19 +1219,8 @@ __global__ __launch_bounds__(256) void k_loop_resample(LoopResampleArgs a) {
             if (c < (int)nch) s_ce[c] = stride * c + stride - 1 < n2 ? ce[k] : a.lp[n2 - 1];
         }
     }
-    const int nbl = nb < nb_cap ? nb : nb_cap;  // (more alive than the launch was sized for: flagged elsewhere; stay inside the arrays)
-    if (t < nbl) s_bp[t + 1] = bt_t;
-    if (t == 0) s_flag = 0;
-    __syncthreads();
-    if (t < nbl && bn_t) s_flag = 1;
-    if (t == 0) {
-        double acc = 0.0;
-        s_bp[0] = 0.0;
-        for (int b = 0; b < nb; ++b) { const double w = s_bp[b + 1]; acc = acc + w; s_bp[b + 1] = acc; }
-    }
-    __syncthreads();
+    const int status = loop_cdf_status(bt_t, bn_t, nb, nb_cap, s_bp, &s_flag);
     const double total = s_bp[nb];
-    const int status = (s_flag || total != total) ? 2 : (total == 0.0 ? 1 : 0);
     RCK(17);
     if (i < n2) {
         int64_t pick = i;
@@ -1153,6 +1292,8 @@ __global__ __launch_bounds__(256) void k_loop_resample(LoopResampleArgs a) {
         const int32_t n = a.ctl_i[LOOP_I_N];
         a.ctl_i[LOOP_I_STATUS] = status;
         a.ctl_d[LOOP_D_TOTAL] = total;
+        // the caller's stream drew ctl_i[NDRAW] uniforms for this frame: what k_loop_ndraw said must be what happens here
+        if (a.check_ndraw && a.ctl_i[LOOP_I_NDRAW] != (status ? 0 : (int32_t)n2)) a.ctl_i[LOOP_I_ERR] |= 256;
         if (a.log) {
             double* L = a.log;
             L[0] = (double)a.ctl_i[LOOP_I_FRAME]; L[1] = (double)n; L[2] = (double)n2;
@@ -1347,22 +1488,50 @@ static int loop_cluster_phase(midas_ctx* ctx, const midas_loop_args& s, const Lo
                                merged, g.B);
 }
 
-// RESAMPLE over the cap2 slots a trajectory the annealed set may take
-static int loop_resample_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t cap2) {
+// the scan of the cap2 slots a trajectory's annealed set may take: its prefix values and block results, in scratch
+struct LoopScan { void *lp, *bt, *bn; };
+static int loop_scan_launch(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t cap2, LoopScan& sc) {
     const size_t Bz = (size_t)g.B;
     const unsigned nb2 = (unsigned)ceil_div(cap2, SCAN_BLOCK);
-    void *lp, *bt, *bn;
     int rc;
-    if ((rc = midas_scratch(ctx, Bz * ((size_t)cap2 + SCAN_CHUNK) * sizeof(double), &lp))) return rc;  // (the resample reads whole chunks)
-    if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(double), &bt))) return rc;
-    if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(int32_t), &bn))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * ((size_t)cap2 + SCAN_CHUNK) * sizeof(double), &sc.lp))) return rc;  // (the resample reads whole chunks)
+    if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(double), &sc.bt))) return rc;
+    if ((rc = midas_scratch(ctx, Bz * nb2 * sizeof(int32_t), &sc.bn))) return rc;
     hipLaunchKernelGGL(k_loop_scan, dim3(nb2, g.by()), dim3(256), 0, ctx->stream, (const int32_t*)s.ctl_i_dev, (const double*)s.x_dev,
-                       (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)lp, (double*)bt, (int32_t*)bn,
-                       g.slice, g.lp_stride);
+                       (const double*)s.e_dev, (const uint8_t*)s.valid_dev, (const int32_t*)s.src_dev, (double*)sc.lp, (double*)sc.bt,
+                       (int32_t*)sc.bn, g.slice, g.lp_stride);
+    return MIDAS_OK;
+}
+
+// ANNEAL under the ATen tie rule: the spreads in the two-pass form, behind the moments and in front of the decision
+static void loop_std_two_pass(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopMoments& m) {
+    hipLaunchKernelGGL(k_loop_std_two_pass, dim3(LOOP_MAX_CLUSTERS, g.by()), dim3(256), 0, ctx->stream, (const int32_t*)s.ctl_i_dev,
+                       (const float*)s.poses_prop_dev, (const double*)s.weights_dev, (const int32_t*)s.labels_dev, (const float*)m.cen, m.sd,
+                       (const int64_t*)m.cnt, (int64_t)s.cap);
+}
+
+// RESAMPLE over the cap2 slots a trajectory the annealed set may take
+static int loop_resample_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t cap2) {
+    LoopScan sc;
+    if (int rc = loop_scan_launch(ctx, s, g, cap2, sc)) return rc;
     LoopResampleArgs r;
-    fill_loop_resample(r, s, lp, bt, bn);  // (a batch's u_dev: NULL, or (B, cap) through midas_loop_step_batch_draws)
+    fill_loop_resample(r, s, sc.lp, sc.bt, sc.bn);  // (a batch's u_dev: NULL, or (B, cap) through midas_loop_step_batch_draws)
     r.cap2 = loop_bound(cap2); r.cap = g.slice; r.lp_stride = g.lp_stride; r.log_stride = g.log_stride;
+    r.check_ndraw = s.stream_draws;
     hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap2, 256), g.by()), dim3(256), 0, ctx->stream, r);
+    LAUNCH_CHECK(ctx);
+    return MIDAS_OK;
+}
+
+// stream_draws, a call that ends in front of the resample: the resample's scan (the caller's draw in between takes the scratch,
+// so the resample scans again) and ctl_i[NDRAW] from its block results.  The two launches may be sized by different bounds cap2
+// (the resample-only call of a single engine carries no bound of the live count); block b's total does not depend on cap2 and
+// both kernels read the ceil(n_set / SCAN_BLOCK) totals that are alive, so the status is the same.
+static int loop_ndraw_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t cap2) {
+    LoopScan sc;
+    if (int rc = loop_scan_launch(ctx, s, g, cap2, sc)) return rc;
+    hipLaunchKernelGGL(k_loop_ndraw, dim3(1, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, (const double*)sc.bt, (const int32_t*)sc.bn,
+                       loop_bound(cap2));
     LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }
@@ -1406,6 +1575,8 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
     if (phases & MIDAS_LOOP_ANNEAL) {
         LoopMoments m;
         if ((rc = loop_cluster_phase(ctx, s, g, weights_merged ? &wa : nullptr, m))) return rc;
+        const int32_t aten = s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU;
+        if (aten) loop_std_two_pass(ctx, s, g, m);
         SelectScratch ss;
         if ((rc = select_scratch(ctx, cap, ss))) return rc;
         if (s.anneal_frozen) {
@@ -1413,11 +1584,11 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
             // |n - floor| > 0) or duplicate (needs k + n <= init) - the decision's bookkeeping runs (cluster rows, variance), the ten
             // launches of the selection, which would each find mode 0 and leave, do not (45 us of a 118 us frame at N = 100k)
             hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
-                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot, 1);
+                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot, 1, aten);
             LAUNCH_CHECK(ctx);
         } else if (s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU) {  // the reference's CPU tie choices (topk_aten.hip); the decision as always
             hipLaunchKernelGGL(k_loop_decide, dim3(2), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
-                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot);
+                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot, 0, 1);
             if ((rc = launch_topk_aten(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, nullptr))) return rc;
         } else if (s.anneal_small && cap <= LOOP_SMALL_MAX) {
             hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
@@ -1430,10 +1601,12 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
             if ((rc = launch_select(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, ss))) return rc;
         }
     }
+    // the annealed set may be a third larger than the particle set the bound was given for
+    const int64_t cap2 = cap + cap / 3 + 1 < s.cap ? cap + cap / 3 + 1 : s.cap;
     if (phases & MIDAS_LOOP_RESAMPLE) {
-        // the annealed set may be a third larger than the particle set the bound was given for
-        const int64_t cap2 = cap + cap / 3 + 1 < s.cap ? cap + cap / 3 + 1 : s.cap;
         if ((rc = loop_resample_phase(ctx, s, g, cap2))) return rc;
+    } else if (s.stream_draws) {
+        if ((rc = loop_ndraw_phase(ctx, s, g, cap2))) return rc;
     }
     return MIDAS_OK;
 }
@@ -1479,9 +1652,10 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
         LoopMoments m;
         if ((rc = loop_cluster_phase(ctx, s, g, weights_merged ? &wa : nullptr, m))) return rc;
         if (s.topk_ties == MIDAS_TOPK_TIES_ATEN_CPU) {  // the decision alone per trajectory, then B walks side by side
+            loop_std_two_pass(ctx, s, g, m);
             hipLaunchKernelGGL(k_loop_decide, dim3(2, g.by()), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
                                (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, (uint32_t*)nullptr, (int32_t*)nullptr, s.floor,
-                               (const double*)m.rot);
+                               (const double*)m.rot, 0, 1);
             if ((rc = launch_topk_aten(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, nullptr, B))) return rc;
         } else {
             hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, g.by()), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
@@ -1490,8 +1664,11 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
         }
         LAUNCH_CHECK(ctx);
     }
-    if (phases & MIDAS_LOOP_RESAMPLE)
+    if (phases & MIDAS_LOOP_RESAMPLE) {
         if ((rc = loop_resample_phase(ctx, s, g, cap))) return rc;  // (the annealed set never exceeds the capacity)
+    } else if (s.stream_draws) {
+        if ((rc = loop_ndraw_phase(ctx, s, g, cap))) return rc;
+    }
     return MIDAS_OK;
 }
 

@@ -191,7 +191,7 @@ enum : int {
     LOOP_I_INIT = MIDAS_LOOP_I_INIT, LOOP_I_VARSET = MIDAS_LOOP_I_VARSET, LOOP_I_KEPT = MIDAS_LOOP_I_KEPT,
     LOOP_I_DRIFT = MIDAS_LOOP_I_DRIFT, LOOP_I_STATUS = MIDAS_LOOP_I_STATUS, LOOP_I_RAW = MIDAS_LOOP_I_RAW,
     LOOP_I_NCL = MIDAS_LOOP_I_NCL, LOOP_I_NPRES = MIDAS_LOOP_I_NPRES, LOOP_I_FRAME = MIDAS_LOOP_I_FRAME,
-    LOOP_I_NAN = MIDAS_LOOP_I_NAN, LOOP_I_ERR = MIDAS_LOOP_I_ERR,
+    LOOP_I_NAN = MIDAS_LOOP_I_NAN, LOOP_I_ERR = MIDAS_LOOP_I_ERR, LOOP_I_NDRAW = MIDAS_LOOP_I_NDRAW,
     LOOP_D_S = MIDAS_LOOP_D_S, LOOP_D_VARPREV = MIDAS_LOOP_D_VARPREV, LOOP_D_VAR = MIDAS_LOOP_D_VAR,
     LOOP_D_RMSE_T = MIDAS_LOOP_D_RMSE_T, LOOP_D_RMSE_R = MIDAS_LOOP_D_RMSE_R, LOOP_D_XMAX = MIDAS_LOOP_D_XMAX,
     LOOP_D_XMIN = MIDAS_LOOP_D_XMIN, LOOP_D_TOTAL = MIDAS_LOOP_D_TOTAL,

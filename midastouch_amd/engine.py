@@ -489,6 +489,9 @@ class PipelinedFilterEngine(_FoldedResample, FilterEngine):
         motion=True: the motion noise comes from the stream too - `torch.normal(0, sig_t, (N, 3))`, `torch.normal(0, sig_r, (N, 3))`
         in front of the resampler's uniforms, the reference's order (:326-335, :245) - i.e. EVERY draw of a frame is the one a
         seeded run of the reference takes, generated on the device (unit normals a frame ahead, scaled where they are used).
+        The stream draws N uniforms EVERY frame, a frame ahead of the status they are used under: the reference's resampler draws
+        none on a frame whose weights are all zero or hold a NaN (:237-241), so behind such a guard frame this stream is no longer
+        the reference's (LoopEngine.seed_torch_stream skips the draw there).
         seed=None: back to Philox."""
         from .torch_rng import TorchCpuStream
         self.torch_stream = None if seed is None else TorchCpuStream(seed, self.device)
@@ -639,6 +642,9 @@ class BatchFilterEngine(_Engine):
         error.  One walk of the generators per frame; the context's scratch for it is reserved here.  `pieces` (TorchCpuStreams'):
         0 by default - the jump costs B x pieces x 39 workgroups of 78 KB LDS, and at c5 (B = 64) it takes 0.42 ms where the 64
         sequential walks, side by side, take 37 us (the mt19937 paragraph).
+        The streams draw N uniforms EVERY frame, a frame ahead of the status they are used under: the reference's resampler draws
+        none on a frame whose weights are all zero or hold a NaN (:237-241), so behind such a guard frame a row's stream is no longer
+        the reference's (BatchLoopEngine.seed_torch_streams skips the draw there, per row).
         After a run, `torch_streams.to_host(b, g)` hands stream b back to a host generator."""
         self._unit_noise = None  # (tn, rot, event): unit normals of the NEXT frame (the pipelined engine draws them a frame ahead)
         if seeds is None:

@@ -206,9 +206,13 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
                     kw["rot"] = torch.normal(mean=pf.motion_noise["mu"], std=pf.motion_noise["sig_r"], size=(n, 3))
                 else:
                     kw["tn"], kw["rot"] = torch.zeros((n, 3)), torch.zeros((n, 3))
-                eng.step(odom, seq.codes[idx], phases=_lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL, **kw)
-                n_set = int(eng.ctl_i[_lib.LOOP_I_NSET].item())
-                eng.step(None, None, u=torch.rand(n_set, dtype=torch.float64), phases=_lib.LOOP_RESAMPLE)  # multinomial's stream (:245)
+                eng.step(odom, seq.codes[idx], phases=_lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL, stream_draws=True, **kw)
+                # multinomial's stream (:245) - which the resampler does not touch when the weights are all zero or hold a NaN
+                # (:237-241): the device says how many uniforms this frame draws (NDRAW: n_set or 0)
+                ci = eng.ctl_i.cpu()
+                n_set, n_draw = int(ci[_lib.LOOP_I_NSET]), int(ci[_lib.LOOP_I_NDRAW])
+                u = torch.rand(n_draw, dtype=torch.float64) if n_draw else torch.zeros(n_set, dtype=torch.float64)  # (unused)
+                eng.step(None, None, u=u, phases=_lib.LOOP_RESAMPLE, stream_draws=True)
             elif draws == "seeded":
                 # the same draws, sized on the device: nothing is read back (frames seen while prev_idx == 0 do not call motionModel)
                 stream_to(True)

@@ -208,7 +208,8 @@ class LoopEngine:
         """Every draw of a frame from the device replica of torch's CPU generator under torch.manual_seed(seed) (torch_rng.py),
         in the reference's order and with the reference's sizes: `torch.normal(0, mul * sig_t, (n, 3))`, `torch.normal(0, mul *
         sig_r, (n, 3))` with n the live count (add_noise_to_odom, particle_filter.py:326-335) and, behind annealing, n_set float64
-        uniforms (the resampler's torch.multinomial, :245).  Both counts are read on the device (midas_mt19937_draws_counted): a
+        uniforms (the resampler's torch.multinomial, :245) - none on a frame whose weights are all zero or hold a NaN, where the
+        resampler returns before it draws (:237-241; ctl_i[LOOP_I_NDRAW]).  The counts are read on the device (midas_mt19937_draws_counted): a
         step() without tn / rot / u enqueues the whole frame and reads nothing back.  A run that also draws on the host (init_filter)
         hands the stream over with the returned TorchCpuStream's from_host() / to_host().  seed=None: back to Philox.
         The generator runs on the engine's stream, in front of the kernels that read its numbers; its scratch at the engine's
@@ -234,7 +235,7 @@ class LoopEngine:
 
     def _seeded_step(self, odom, code, gt, u32, multiplier, dbscan, std_override, unit_weights, motion_draws):
         """One frame with the stream's draws: the motion noise sized by the live count, the frame up to annealing, the uniforms sized
-        by the annealed count, the resample - four enqueues, the counts never leave the device."""
+        by the annealed count (or none: NDRAW), the resample - four enqueues, the counts never leave the device."""
         st, ci = self.torch_stream, self.ctl_i
         if self._pending_phases:
             raise MidasError("a seeded frame is enqueued whole: finish the frame in progress first")
@@ -252,26 +253,34 @@ class LoopEngine:
         else:
             tn = rot = self._no_noise
         self._enqueue(odom, code, gt, tn, rot, None, u32, multiplier, dbscan, _lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL,
-                      std_override, unit_weights, bound=b)
-        st.draws_counted_async([("rand64", ci, _lib.LOOP_I_NSET, min(self.cap, b + b // 3))], outs=[self._u], status=status)
-        self._enqueue(None, None, None, None, None, self._u, u32, multiplier, dbscan, _lib.LOOP_RESAMPLE, std_override, unit_weights)
+                      std_override, unit_weights, bound=b, stream_draws=True)
+        # NDRAW, not NSET: the resampler returns its input before it draws when the weights are all zero or hold a NaN
+        # (particle_filter.py:237-241) - the stream must not move on such a frame (a zero count consumes nothing)
+        st.draws_counted_async([("rand64", ci, _lib.LOOP_I_NDRAW, min(self.cap, b + b // 3))], outs=[self._u], status=status)
+        self._enqueue(None, None, None, None, None, self._u, u32, multiplier, dbscan, _lib.LOOP_RESAMPLE, std_override, unit_weights,
+                      stream_draws=True)
 
     # ---- one frame ------------------------------------------------------------------------------------------------
     def step(self, odom, code, gt=None, tn=None, rot=None, u=None, u32=-1.0, multiplier: float = 1.0, dbscan=None,
-             phases: int = None, std_override=None, unit_weights: bool = False, motion_draws: bool = True):
+             phases: int = None, std_override=None, unit_weights: bool = False, motion_draws: bool = True, stream_draws: bool = False):
         """Enqueues one frame (or the given phases of it).  dbscan: None = on every `cluster_every`-th frame (count % 50 ==
         0, filter.py:182), True / False to force.  Host draws tn / rot (n, 3) and u (>= n_set,) as in FilterEngine.step.
         With seed_torch_stream the draws are the stream's and the engine splits the frame itself: tn / rot / u / phases are then an
         error; motion_draws=False draws no motion noise and propagates with zeros (the frames the reference starts from, where it
-        does not call motionModel)."""
+        does not call motionModel).
+        stream_draws: the host splits the frame in front of RESAMPLE to draw `u` from a stream that has to stay the reference's - set
+        on both calls: the first then leaves in ctl_i[LOOP_I_NDRAW] how many uniforms the reference's resampler draws on this frame
+        (n_set, or 0 where it returns its input before drawing: all-zero or NaN weights), the second checks itself against it."""
         if self.torch_stream is None:
-            return self._enqueue(odom, code, gt, tn, rot, u, u32, multiplier, dbscan, phases, std_override, unit_weights)
+            return self._enqueue(odom, code, gt, tn, rot, u, u32, multiplier, dbscan, phases, std_override, unit_weights,
+                                 stream_draws=stream_draws)
         if tn is not None or rot is not None or u is not None or phases is not None:
             raise MidasError("seed_torch_stream: the stream draws tn, rot and u and the engine splits the frame - passing them would "
                              "desynchronise the stream from the reference's")
         self._seeded_step(odom, code, gt, u32, multiplier, dbscan, std_override, unit_weights, motion_draws)
 
-    def _enqueue(self, odom, code, gt, tn, rot, u, u32, multiplier, dbscan, phases, std_override, unit_weights, bound: int = None):
+    def _enqueue(self, odom, code, gt, tn, rot, u, u32, multiplier, dbscan, phases, std_override, unit_weights, bound: int = None,
+                 stream_draws: bool = False):
         """bound: the frame's _count_bound() when the caller has taken it already; tn / rot are then the engine's own capacity-sized
         buffers (tn[3 i + j] for particle i, as the kernels index them)."""
         d = self.device
@@ -321,6 +330,7 @@ class LoopEngine:
         a.anneal_small = int(self._grid_n <= 16384)
         a.anneal_frozen = int(self._frozen())
         a.topk_ties = self.topk_ties
+        a.stream_draws = int(bool(stream_draws))
         a.telemetry = _ptr(self.telemetry)
         if self.sparse_scores and phases & _lib.LOOP_FRONT:
             a.score_stamps, a.score_epoch = _ptr(self._stamps), advance_epoch(self)
@@ -378,6 +388,9 @@ def log_records(rows, first: int, last: int, mt=None, strict: bool = True, who: 
         if err & 128:
             fatal.append(f"{who}frame {f}: the engine stated that annealing could not act (live count == floor == init_particles) and the "
                          "rule wanted to: the set was left as it was")
+        if err & _lib.LOOP_ERR_NDRAW:
+            fatal.append(f"{who}frame {f}: the resample's status disagrees with the count its stream's uniforms were drawn by "
+                         "(ctl_i[NDRAW]): the stream is no longer the reference's")
         bits = int(mt[f % log_frames]) if mt is not None else 0
         if bits:
             why = [w for b, w in ((_lib.MT_STATUS_COUNT_RANGE, "a count exceeded the bound its draw was sized for"),

@@ -384,11 +384,51 @@ def dbscan(points, eps: float = 1e-2, min_samples: int = 1):
     return labels, int(ncl)
 
 
-def cluster_var(stds):
-    """`torch.mean(cluster_stds)` (filter/filter.py:189) of the float32 (C,3) spreads as the spec states it: float32
-    running sum in row-major order divided by the float32 count."""
+def aten_sum_f32(values):
+    """`torch.sum` of a contiguous float32 array of fewer than 512 values as ATen's CPU kernel adds it (SumKernel.cpp, the AVX2
+    build every x86 host runs: 8 lanes): whole vectors go to four interleaved vector accumulators (`row_sum`, ilp 4; the
+    cascade's first level holds 16 rows, so nothing is carried over below 8 * 4 * 16 values), leftover vectors to the first
+    accumulator, the four are added 0 + 1 + 2 + 3; then the scalar tail in order, then the 8 lanes in order.  Fewer than 8
+    values: the same `row_sum` on scalars.  A plain running sum differs from this in the last bit from 6 values on."""
+    x = np.asarray(values, dtype=np.float32).ravel()
+    n, V, ILP = x.shape[0], 8, 4
+    assert n < V * ILP * 16, "the cascade's carries are not restated"
+
+    def row_sum(rows, zero):
+        acc = [zero.copy() for _ in range(ILP)]
+        g = len(rows) // ILP
+        for i in range(g):
+            for k in range(ILP):
+                acc[k] = (acc[k] + rows[ILP * i + k]).astype(np.float32)
+        for i in range(ILP * g, len(rows)):
+            acc[0] = (acc[0] + rows[i]).astype(np.float32)
+        for k in range(1, ILP):
+            acc[0] = (acc[0] + acc[k]).astype(np.float32)
+        return acc[0]
+
+    if n < V:
+        return np.float32(row_sum([x[i:i + 1] for i in range(n)], np.zeros(1, np.float32))[0])
+    vs = n // V
+    lanes = row_sum([x[V * i:V * i + V] for i in range(vs)], np.zeros(V, np.float32))
     s = np.float32(0.0)
+    for v in x[vs * V:]:
+        s = np.float32(s + v)
+    for v in lanes:
+        s = np.float32(s + v)
+    return s
+
+
+def cluster_var(stds, order: str = "running"):
+    """`torch.mean(cluster_stds)` (filter/filter.py:189) of the float32 (C,3) spreads: a float32 sum divided by the float32 count.
+    order "running": the values added one after the other, row-major (the spec of the loop with ties by index - torch's CUDA rule,
+    whose reduction order is not modelled).  order "aten_cpu": ATen's CPU sum in ITS order (aten_sum_f32) - what the reference
+    computes on the CPU, the spec of a replay (ties="aten_cpu"); the two differ in the last bit in about four frames of ten once
+    two clusters are present."""
+    assert order in ("running", "index", "aten_cpu")
     flat = np.asarray(stds, dtype=np.float32).ravel()
+    if order == "aten_cpu":
+        return np.float32(aten_sum_f32(flat) / np.float32(flat.shape[0]))
+    s = np.float32(0.0)
     for v in flat:
         s = np.float32(s + v)
     return np.float32(s / np.float32(flat.shape[0]))
@@ -477,7 +517,8 @@ class OracleLoop:
     (:190) - as one `step()` over a particle set whose size changes from frame to frame.  The spec of the device loop
     engine (midas_loop_step): same arithmetic as OracleFilter.step plus
       labels   = dbscan(translations, eps, N // 5) on frames with count % 50 == 0, carried through the resample otherwise;
-      var      = cluster_var(stds of the clusters present), annealing on it (Annealer; ties in the top-k by index);
+      var      = cluster_var(stds of the clusters present; added in ATen's CPU order with ties="aten_cpu"), annealing on it
+                 (Annealer; ties in the top-k by index, or ATen's);
       resample = N' draws over the blocked CDF of (e * mask)[keep], N' = size of the annealed set; the weights that
                  travel on are e / S * mask with S the blocked sum of e over the N particles BEFORE annealing."""
 
@@ -492,7 +533,7 @@ class OracleLoop:
     def step(self, poses, labels, odom, code, tn, rot_deg, u=None, gt=None, mode="weighted_random", u32=None,
              keep_override=None, draws=None):
         """`u`: uniforms for the N' draws (only the first N' are used) or `draws(N')` -> uniforms, called once N' is known
-        (the reference draws them after annealing).  keep_override: teacher-forced annealed index list (tests of tie frames)."""
+        (the reference draws them after annealing) and only when the resampler draws at all (CDF status 0).  keep_override: teacher-forced annealed index list (tests of tie frames)."""
         f, out = self.f, {}
         N = poses.shape[0]
         p1 = propagate(poses, odom, tn, rot_deg)
@@ -513,7 +554,7 @@ class OracleLoop:
             if self.count % self.cluster_every == 0:
                 labels = dbscan(p1[:, :3, 3], self.eps, N // 5)[0]
             uniq, centers, stds = cluster_centers(p1, w, labels)
-            var = cluster_var(stds)
+            var = cluster_var(stds, self.annealer.ties)
             keep = self.annealer.step(w, var, self.floor) if keep_override is None else np.asarray(keep_override)
             if keep_override is not None:  # keep the annealer's state in step with the forced decision
                 self.annealer.step(w, var, self.floor)
@@ -523,12 +564,16 @@ class OracleLoop:
         out["keep"] = keep.astype(np.int32)
         n2 = keep.shape[0]
         em = (e * mask)[keep]
-        if u is None and draws is not None:
-            u = draws(n2)
-        ridx, status = resample_indices(em, mode, u=None if u is None else np.asarray(u)[:n2], u32=u32)
+        # the resampler returns its input BEFORE it draws when the weights are all zero or hold a NaN (particle_filter.py:237-241):
+        # the status first, `draws` - a stream - is asked for nothing on such a frame
+        status = cdf(em)[1]
         out["status"] = status
         if status:
             ridx = np.arange(n2, dtype=np.int32)
+        else:
+            if u is None and draws is not None:
+                u = draws(n2)
+            ridx = resample_indices(em, mode, u=None if u is None else np.asarray(u)[:n2], u32=u32)[0]
         src = keep[ridx]
         out.update(ridx=ridx.astype(np.int32), src=src.astype(np.int32), poses=p1[src], weights_res=w[src],
                    nn_idx_res=idx[src], labels=np.asarray(labels)[src], N=n2)
@@ -554,9 +599,10 @@ class OracleFilter:
         return nn6(R3_SE3(poses), self.cb_feat)[0]
 
     def step(self, poses, odom, code, tn, rot_deg, u=None, mode="weighted_random", u32=None, softmax=True, scores=None,
-             prop_override=None):
+             prop_override=None, draws=None):
         """Returns dict with every intermediate the parity tests compare.  prop_override: continue from these propagated
-        poses instead of the step's own (teacher forcing against a trace of the reference)."""
+        poses instead of the step's own (teacher forcing against a trace of the reference).  `u`: the N uniforms, or
+        `draws(N)` -> uniforms, called only when the resampler draws (CDF status 0)."""
         out = {}
         p1 = propagate(poses, odom, tn, rot_deg) if prop_override is None else _f32(prop_override)
         out["poses_prop"] = p1
@@ -580,12 +626,15 @@ class OracleFilter:
         w = w_pre * mask
         out["weights"] = w
         out["drifted"] = bool(mask.sum() == 0)
-        ridx, status = resample_indices(e * mask, mode, u=u, u32=u32)
+        # the status first: all-zero or NaN weights go on unresampled and `draws`, a stream, is asked for nothing (particle_filter.py:237-241)
+        status = cdf(e * mask)[1]
         out["status"] = status
         if status:
             out["ridx"] = np.arange(len(w), dtype=np.int32)
         else:
-            out["ridx"] = ridx
+            if u is None and draws is not None:
+                u = draws(len(w))
+            out["ridx"] = resample_indices(e * mask, mode, u=u, u32=u32)[0]
         out["poses"] = p1[out["ridx"]]
         out["weights_res"] = w[out["ridx"]]
         out["nn_idx_res"] = idx[out["ridx"]]

@@ -40,3 +40,19 @@ def g2b_cases(g):
         for mode in ("weighted_random", "low_var"):
             yield (ci, w, mode, int(g[f"c{ci}_{mode}_seed"]), str(g[f"c{ci}_{mode}_sha"]), g[f"c{ci}_{mode}_head"],
                    g[f"c{ci}_{mode}_tail"])
+
+
+def guard_trace_inputs(g, trace):
+    """The operands the G14 traces were made from (tools/gen_guard_trace.py): codebook, odometry with the jump off the mesh at the
+    shift frame ("loop", "fixed"; "plain": the trajectory as it is), codes with the NaN entry of the `fixed` trace, ground truth."""
+    from midastouch_amd.synthetic import make_codebook, make_trajectory
+    cb = make_codebook(K=int(g["K"]), D=int(g["D"]), seed=int(g["cb_seed"]), mesh_points=20000)
+    assert sha(cb.embeddings.astype(np.float32)) == str(g["cb_sha"])
+    traj = make_trajectory(cb, T=int(g["T"]) + 1, seed=int(g["traj_seed"]))
+    odoms, codes = traj.odoms.copy(), traj.codes.copy()
+    assert trace in ("loop", "fixed", "plain")
+    if trace != "plain":
+        odoms[int(g["shift_frame"])][:3, 3] += np.float32(g["shift"])
+    if trace == "fixed":
+        codes[int(g["nan_frame"])][int(g["nan_at"])] = np.nan
+    return cb, odoms, codes, traj.gt_poses

@@ -37,9 +37,10 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert lib.midas_strerror(0) == b"ok" and lib.midas_strerror(-1) == b"invalid argument"
 
 
-@pytest.mark.parametrize("cname,mirror", [("midas_step_args", "StepArgs"), ("midas_lazy_args", "LazyArgs")])
+@pytest.mark.parametrize("cname,mirror", [("midas_step_args", "StepArgs"), ("midas_lazy_args", "LazyArgs"),
+                                          ("midas_loop_args", "LoopArgs")])
 def test_args_structs_match_header(cname, mirror):
-    """Field order of the ctypes mirrors of midas_step_args / midas_lazy_args follows the header."""
+    """Field order of the ctypes mirrors of midas_step_args / midas_lazy_args / midas_loop_args follows the header."""
     from midastouch_amd import _lib
     text = open(os.path.join(REPO, "include", "midas_hip.h")).read()
     body = text[text.index("typedef struct %s {" % cname):text.index("} %s;" % cname)]
@@ -56,6 +57,17 @@ def test_args_structs_match_header(cname, mirror):
     got = [f[0] for f in getattr(_lib, mirror)._fields_]
     norm = [f.replace("_dev", "") for f in fields]
     assert norm == got
+
+
+def test_loop_control_words_match_header():
+    """The control-block indices of _lib (LOOP_I_*) are the header's MIDAS_LOOP_I_*, NDRAW (the uniforms a stream-drawn frame
+    consumes) included, and fit the 32-word block."""
+    from midastouch_amd import _lib
+    text = open(os.path.join(REPO, "include", "midas_hip.h")).read()
+    words = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define MIDAS_LOOP_I_([A-Z]+) (\d+)", text)}
+    assert words["NDRAW"] == 15 and len(set(words.values())) == len(words) == 16 and max(words.values()) < 32
+    for name, idx in words.items():
+        assert getattr(_lib, "LOOP_I_" + name) == idx, name
 
 
 def test_guide_layout_query_needs_no_device():

@@ -69,9 +69,10 @@ def test_small_sizes_every_k(dev, oracle, kind):
                 _check(dev, oracle, w, mode, k)
 
 
-@pytest.mark.parametrize("kind", ["random", "shared", "few", "nan"])
+@pytest.mark.parametrize("kind", ["random", "shared", "few", "equal", "nan"])
 @pytest.mark.parametrize("n", [1000, 4096, 20000, 100000])
 def test_filter_sizes(dev, oracle, kind, n):
+    """("equal": one value everywhere - the top-k of a frame whose particles were all pruned, every weight 0.)"""
     torch.set_num_threads(1)
     rng = np.random.default_rng(n)
     w = _weights(rng, n, kind)

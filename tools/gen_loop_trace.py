@@ -98,7 +98,7 @@ def run(pfm, cluster: bool, name: str, init_ratio: float):
                 digest(out, f"dbscan_{t}", labels.astype(np.int32))
             uniq, centers, stds = orc.cluster_centers(prop, w_pruned, labels)
             var = torch.mean(torch.tensor(stds))                       # filter.py:189
-            assert np.float32(var.item()) == orc.cluster_var(stds), "torch.mean differs from the spec's float32 sum"
+            assert np.float32(var.item()) == orc.cluster_var(stds, "aten_cpu"), "torch.mean differs from the restatement of ATen's sum"
             out[f"cl_labels_{t}"], out[f"cl_poses_{t}"], out[f"cl_stds_{t}"] = uniq.astype(np.int32), centers, stds
             out[f"var_{t}"] = np.float32(var.item())
             shadow.particle_var = copy.copy(pf.particle_var)
