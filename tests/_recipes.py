@@ -56,3 +56,150 @@ def guard_trace_inputs(g, trace):
     if trace == "fixed":
         codes[int(g["nan_frame"])][int(g["nan_at"])] = np.nan
     return cb, odoms, codes, traj.gt_poses
+
+
+# rmse_r of a kernel against the oracle: both feed bit-identical x = (tr - 1) / 2 to acosf, so only acosf itself (device
+# ocml: 4 ulp, the OpenCL bound; glibc: 1 ulp) and the product and the square after it (about 1 ulp a side) can differ -
+# under 7 * 2^-23 = 8.3e-7 per term, and an RMS of terms each off by at most eps is off by at most eps ("rmse").
+RMSE_R_REL = 2e-6
+RMSE_T_REL = 1e-9
+
+
+def rmse_rel_dev(got, ref) -> float:
+    """|got - ref| / |ref| of one rmse value; 0 where both are the same zero or both NaN, inf where only the class differs."""
+    got, ref = float(got), float(ref)
+    if np.isnan(got) or np.isnan(ref):
+        return 0.0 if np.isnan(got) and np.isnan(ref) else float("inf")
+    if got == ref:
+        return 0.0
+    return abs(got - ref) / abs(ref) if ref != 0.0 else float("inf")
+
+
+def assert_rmse(got2, ref2, what="") -> float:
+    """(rmse_t, rmse_r) of a kernel against the oracle's: column 0 within 1e-9 relative, column 1 within RMSE_R_REL, no
+    absolute slack (an exact 0 must be an exact 0), NaN equal to NaN.  -> the rotation column's relative deviation."""
+    got2 = np.asarray(got2.detach().cpu().numpy() if hasattr(got2, "detach") else got2, dtype=np.float64).reshape(-1)
+    ref2 = np.asarray(ref2, dtype=np.float64).reshape(-1)
+    assert got2.shape == (2,) and ref2.shape == (2,), (got2.shape, ref2.shape)
+    dt, dr = rmse_rel_dev(got2[0], ref2[0]), rmse_rel_dev(got2[1], ref2[1])
+    assert dt <= RMSE_T_REL, f"{what}: rmse_t {got2[0]!r} vs oracle {ref2[0]!r} (rel {dt:.3g})"
+    assert dr <= RMSE_R_REL, f"{what}: rmse_r {got2[1]!r} vs oracle {ref2[1]!r} (rel {dr:.3g})"
+    return dr
+
+
+# ---- rmse inputs shared by tests/test_oracle_math.py (CPU) and tests/test_gpu_rmse.py ------------------------------------------
+RMSE_CLOUDS = ("band5", "band20", "noise0.5", "noise3")
+# rmse_r against the float64 geodesic angle (derivations: tests/test_oracle_math.py::test_rmse_clouds_vs_float64)
+RMSE_R_REL_F64 = {"band5": 1e-5, "band20": 1e-5, "noise0.5": 1e-4, "noise3": 1e-4}
+RMSE_T_REL_F64 = 1e-8
+
+
+def _pose(R, t):
+    P = np.zeros(R.shape[:-2] + (4, 4), dtype=np.float32)
+    P[..., :3, :3], P[..., :3, 3], P[..., 3, 3] = R, t, 1.0
+    return P
+
+
+def rmse_cloud(kind: str, n: int, seed: int = 0):
+    """-> (poses (n,4,4) float32, gt (4,4) float32): a random gt and n particles turned away from it by an angle uniform in
+    [5, 175] / [20, 160] degrees about a random axis ("band5", "band20"), or by zyx Euler noise of 0.5 / 3 degrees per axis
+    ("noise0.5", "noise3": the motion model's regime), 2 mm of translation noise.  The gt depends on (kind, seed) only: the
+    clouds of one kind at every size stand around the same pose."""
+    from scipy.spatial.transform import Rotation
+    rng = np.random.default_rng([seed, 2000, RMSE_CLOUDS.index(kind)])
+    Rgt = Rotation.from_rotvec(_unit(rng, 1)[0] * rng.uniform(0.3, 3.0)).as_matrix()
+    tgt = rng.uniform(-0.1, 0.1, 3)
+    if n != 2000:  # (2000 particles: the stream goes on, the cloud of tests/test_oracle_math.py)
+        rng = np.random.default_rng([seed, n, RMSE_CLOUDS.index(kind), 1])
+    if kind.startswith("band"):
+        lo = float(kind[4:])
+        Rd = Rotation.from_rotvec(_unit(rng, n) * np.deg2rad(rng.uniform(lo, 180.0 - lo, (n, 1)))).as_matrix()
+    else:
+        Rd = Rotation.from_euler("zyx", rng.normal(0.0, float(kind[5:]), (n, 3)), degrees=True).as_matrix()
+    return _pose(Rgt @ Rd, tgt + rng.normal(0.0, 2e-3, (n, 3))), _pose(Rgt, tgt)
+
+
+def _unit(rng, n):
+    a = rng.standard_normal((n, 3))
+    return a / np.linalg.norm(a, axis=1, keepdims=True)
+
+
+def rmse_ref64(poses, gt, angles=False):
+    """(rmse_t, rmse_r) - with angles=True, (rmse_t, rmse_r, the terms' angles in degrees) - from the float32 inputs widened to float64: R_d = R_gt R_n^T, the geodesic angle
+    atan2(|vee(R_d - R_d^T)| / 2, (tr R_d - 1) / 2) in degrees (well conditioned at every angle, unlike acos), the float64 norm."""
+    P, G = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4), np.asarray(gt, dtype=np.float64)
+    Rd = G[None, :3, :3] @ P[:, :3, :3].transpose(0, 2, 1)
+    A = Rd - Rd.transpose(0, 2, 1)
+    s = 0.5 * np.sqrt(A[:, 2, 1] ** 2 + A[:, 0, 2] ** 2 + A[:, 1, 0] ** 2)
+    c = 0.5 * (np.trace(Rd, axis1=1, axis2=2) - 1.0)
+    th = np.degrees(np.arctan2(s, c))
+    e2 = ((G[None, :3, 3] - P[:, :3, 3]) ** 2).sum(axis=1)
+    return (float(np.sqrt(e2.mean())), float(np.sqrt((th ** 2).mean()))) + ((th,) if angles else ())
+
+
+def rmse_edge_terms(seed: int = 0):
+    """-> [(name, pose (4,4), gt (4,4))]: the single terms at which the rotation formula changes class (about 200): pose equal
+    to gt; gt turned by exactly pi and by pi -+ 1e-3 about the frame axes and random ones; rotation rows of gt scaled by
+    1 +- 2^-20 (x = (tr - 1) / 2 above 1: NaN, hence 0; just below 1); a zero rotation block (120 degrees); a NaN or an Inf in a
+    rotation or a translation entry of the pose or of gt."""
+    from scipy.spatial.transform import Rotation
+    rng = np.random.default_rng([seed, 77])
+    eye = _pose(np.eye(3), np.zeros(3))
+    gts = [eye] + [_pose(Rotation.from_rotvec(_unit(rng, 1)[0] * rng.uniform(0.2, 3.0)).as_matrix(), rng.uniform(-0.1, 0.1, 3))
+                   for _ in range(7)]
+    axes = list(np.eye(3)) + list(_unit(rng, 5))
+    out = []
+    for g, G in enumerate(gts):
+        shifted = G.copy()
+        shifted[:3, 3] += np.float32(1e-3)
+        out.append((f"same g{g}", G.copy(), G))
+        out.append((f"same rotation g{g}", shifted, G))
+        for a, ax in enumerate(axes):
+            for d in (0.0, -1e-3, 1e-3):
+                P = shifted.copy()
+                P[:3, :3] = G[:3, :3].astype(np.float64) @ Rotation.from_rotvec(ax * (np.pi + d)).as_matrix()
+                out.append((f"pi{d:+g} axis{a} g{g}", P, G))
+        for s in (2.0 ** -20, -(2.0 ** -20)):
+            Gs = G.copy()
+            Gs[:3, :3] *= np.float32(1.0 + s)
+            out.append((f"rows scaled 1{s:+.3g} g{g}", shifted, Gs))
+        Z = shifted.copy()
+        Z[:3, :3] = 0.0
+        out.append((f"zero rotation g{g}", Z, G))
+        turned = shifted.copy()  # 30 degrees away: a term that stays finite where only the translation is spoilt
+        turned[:3, :3] = G[:3, :3].astype(np.float64) @ Rotation.from_rotvec(axes[3 + g % 5] * np.deg2rad(30.0)).as_matrix()
+        out.append((f"30 degrees g{g}", turned, G))
+        for val, vn in ((np.nan, "nan"), (np.inf, "inf"), (-np.inf, "-inf")):
+            for where, (i, j) in (("rotation", (int(rng.integers(3)), int(rng.integers(3)))), ("translation", (int(rng.integers(3)), 3))):
+                if g < 4 or vn == "nan":
+                    P = turned.copy()
+                    P[i, j] = val
+                    out.append((f"{vn} in the pose's {where} g{g}", P, G))
+                if g < 2:
+                    Gb = G.copy()
+                    Gb[i, j] = val
+                    out.append((f"{vn} in gt's {where} g{g}", turned, Gb))
+    return out
+
+
+def rmse_mixed_cloud(n: int, seed: int = 0, nan_translation_last: bool = False):
+    """A "noise0.5" cloud of n particles with edge terms at lane 0, lane 63, the first lane of the last (partial) wave and the very
+    last particle, and next to them: NaN-to-0 terms beside finite ones, a 180 degree term, an exact-zero term, a 120 degree one.
+    nan_translation_last: the last particle's translation holds a NaN instead (rmse_t NaN, the rotation column as before)."""
+    from scipy.spatial.transform import Rotation
+    poses, gt = rmse_cloud("noise0.5", n, seed + 100)
+    last_wave = (n - 1) // 64 * 64
+    R = gt[:3, :3].astype(np.float64)
+    poses[0, :3, :3] = gt[:3, :3] * np.float32(1.0 + 2.0 ** -20)             # x > 1: NaN, hence 0
+    poses[1, 0, 1] = np.inf                                                  # Inf in the trace: NaN, hence 0
+    poses[62, :3, :3] = 0.0                                                  # 120 degrees
+    poses[63, :3, :3] = R @ Rotation.from_rotvec([np.pi, 0.0, 0.0]).as_matrix()   # 180 degrees (or NaN-to-0: x = -1 to an ulp)
+    poses[64, :3, :3] = R @ Rotation.from_rotvec([0.0, np.pi - 1e-3, 0.0]).as_matrix()
+    poses[last_wave] = gt                                                    # the identical pose: an exact zero in both columns
+    if last_wave + 1 < n - 1:
+        poses[last_wave + 1, 2, 2] = np.nan                                  # NaN rotation entry: 0
+    if nan_translation_last:
+        poses[n - 1, 1, 3] = np.nan
+    else:
+        poses[n - 1, 1, 1] = np.nan
+    return poses, gt

@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from _recipes import assert_rmse
+
 N_LOC, K, D, FRAMES = 4096, 1500, 64, 4
 
 
@@ -83,6 +85,7 @@ def test_two_rank_gloo_equals_single_process(tmp_path, oracle, mode, exchange):
             assert p[t - 1]["status"][0] == ref["status"] and p[t - 1]["status"][1] == int(ref["mask"].sum())
         rt, rr = oracle.particle_rmse(ref["poses_prop"], traj.gt_poses[t])
         assert parts[0][t - 1]["rmse"][0] == pytest.approx(rt, rel=1e-9)
+        assert_rmse(parts[0][t - 1]["rmse"], (rt, rr), f"frame {t}")
         assert np.array_equal(parts[0][t - 1]["rmse"], parts[1][t - 1]["rmse"])
         poses = ref["poses"]
 

@@ -38,7 +38,9 @@ def _start(oracle, cb, traj, scale):
 @pytest.mark.parametrize("mode", ["weighted_random", "low_var"])
 def test_config1_exact_size_eager_engine(dev, oracle, world, mode):
     from midastouch_amd.engine import FilterEngine
+    from _recipes import assert_rmse
     cb, traj, scale = world
+    worst = 0.0
     ofl = oracle.OracleFilter(cb.poses, cb.embeddings, cb.mesh_vertices)
     eng = FilterEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N, resample=mode, device=dev)
     poses = cb.poses[ofl.SE3_NN_idx(_start(oracle, cb, traj, scale))]  # t = 0: projection onto the codebook (filter/filter.py:159-160)
@@ -63,10 +65,9 @@ def test_config1_exact_size_eager_engine(dev, oracle, world, mode):
         assert st[0] == ref["status"] and st[1] == int(ref["mask"].sum())
         assert np.array_equal(eng.ridx.cpu().numpy(), ref["ridx"]), f"frame {t}: resample indices"
         assert np.array_equal(eng.poses.cpu().numpy(), ref["poses"]), f"frame {t}: resampled poses"
-        rt, rr = oracle.particle_rmse(ref["poses_prop"], traj.gt_poses[t])
-        rm = eng.rmse.cpu().numpy()
-        assert rm[0] == pytest.approx(rt, rel=1e-9) and rm[1] == pytest.approx(rr, rel=1e-4, abs=0.03)
+        worst = max(worst, assert_rmse(eng.rmse, oracle.particle_rmse(ref["poses_prop"], traj.gt_poses[t]), f"frame {t}"))
         poses = ref["poses"]
+    print(f"rmse_r vs oracle, FilterEngine {mode} N={N}: max rel dev {worst:.3g}")
     assert len(np.unique(eng.ridx.cpu().numpy())) < N
 
 

@@ -72,7 +72,8 @@ def test_config2_full_size(dev, oracle, variant):
     0 against the spec exponential (in _check_frame), <= 2 per frame and <= 3 in all against libm's."""
     from midastouch_amd import engine as E
     from midastouch_amd.synthetic import make_codebook, make_trajectory, wide_start
-    N, K, D, seed = 100_000, 50_000, 512, 4000
+    from _recipes import assert_rmse
+    N, K, D, seed, worst = 100_000, 50_000, 512, 4000, 0.0
     cb = make_codebook("004_sugar_box", K=K, D=D, seed=1001)
     traj = make_trajectory(cb, T=8, seed=2001)
     eng = getattr(E, "PipelinedFilterEngine" if variant == "run" else variant)(cb.poses, cb.embeddings, cb.mesh_vertices, N, seed=seed, device=dev)
@@ -96,8 +97,8 @@ def test_config2_full_size(dev, oracle, variant):
             if prev is not None:
                 _check_propagate(oracle, prev, eng.poses_prop.cpu().numpy(), traj.odoms[last], N, seed, last - 1)
             total += _check_frame(eng, oracle, cb, traj.codes[last], seed, last - 1)
-            rt, _ = oracle.particle_rmse(eng.poses_prop.cpu().numpy(), traj.gt_poses[last])
-            assert float(log[-1, 0]) == pytest.approx(rt, rel=1e-9) and float(eng.rmse[0]) == pytest.approx(rt, rel=1e-9)
+            ref2 = oracle.particle_rmse(eng.poses_prop.cpu().numpy(), traj.gt_poses[last])
+            worst = max(worst, assert_rmse(log[-1, :2], ref2, f"log, frame {last}"), assert_rmse(eng.rmse, ref2, f"frame {last}"))
         assert eng.step_count == 6
     else:
         for t in range(1, 7):
@@ -105,8 +106,8 @@ def test_config2_full_size(dev, oracle, variant):
             eng.step(od[t], co[t], gt=gt[t])
             _check_propagate(oracle, prev, eng.poses_prop.cpu().numpy(), traj.odoms[t], N, seed, t - 1)
             total += _check_frame(eng, oracle, cb, traj.codes[t], seed, t - 1)
-            rt, _ = oracle.particle_rmse(eng.poses_prop.cpu().numpy(), traj.gt_poses[t])
-            assert float(eng.rmse[0]) == pytest.approx(rt, rel=1e-9)
+            worst = max(worst, assert_rmse(eng.rmse, oracle.particle_rmse(eng.poses_prop.cpu().numpy(), traj.gt_poses[t]), f"frame {t}"))
+    print(f"rmse_r vs oracle, c2 {variant} N={N}: max rel dev {worst:.3g}")
     assert total <= 3
     tele = eng.telemetry.cpu().numpy()
     assert tele[0] >= 0 and tele[1] >= 0
@@ -117,7 +118,8 @@ def test_config3_one_million_particles(dev, oracle, engine):
     """c3 on one GPU: N = 1 M particles, 50k x 512 codebook (what each of 8 GPUs holds replicated)."""
     from midastouch_amd import engine as E
     from midastouch_amd.synthetic import make_codebook, make_trajectory
-    N, K, D, seed = 1_000_000, 50_000, 512, 4000
+    from _recipes import assert_rmse
+    N, K, D, seed, worst = 1_000_000, 50_000, 512, 4000, 0.0
     cb = make_codebook("035_power_drill", K=K, D=D, seed=1003)
     traj = make_trajectory(cb, T=6, seed=2003)
     eng = getattr(E, engine)(cb.poses, cb.embeddings, cb.mesh_vertices, N, seed=seed, device=dev)
@@ -127,8 +129,8 @@ def test_config3_one_million_particles(dev, oracle, engine):
     for t in range(1, 4):
         eng.step(torch.as_tensor(traj.odoms[t]), torch.as_tensor(traj.codes[t]), gt=torch.as_tensor(traj.gt_poses[t]))
         total += _check_frame(eng, oracle, cb, traj.codes[t], seed, t - 1)
-        rt, _ = oracle.particle_rmse(eng.poses_prop.cpu().numpy(), traj.gt_poses[t])
-        assert float(eng.rmse[0]) == pytest.approx(rt, rel=1e-9)
+        worst = max(worst, assert_rmse(eng.rmse, oracle.particle_rmse(eng.poses_prop.cpu().numpy(), traj.gt_poses[t]), f"frame {t}"))
+    print(f"rmse_r vs oracle, c3 {engine} N={N}: max rel dev {worst:.3g}")
     assert total <= 3
 
 
@@ -264,7 +266,8 @@ def test_config5_batch_full_size(dev, oracle, engine):
     Philox keys (b N + n): NN indices, prune masks, resample indices and poses exact, weights 1e-12, rmse."""
     from midastouch_amd import engine as E
     from midastouch_amd.synthetic import make_codebook, make_trajectory
-    B, N, K, D, seed = 64, 10_000, 50_000, 512, 4200
+    from _recipes import assert_rmse
+    B, N, K, D, seed, worst = 64, 10_000, 50_000, 512, 4200, 0.0
     cb = make_codebook("cotter-pin", K=K, D=D, seed=1005)
     trajs = [make_trajectory(cb, T=6, seed=2200 + b) for b in range(8)]
     ofl = oracle.OracleFilter(cb.poses, cb.embeddings, cb.mesh_vertices)
@@ -299,9 +302,9 @@ def test_config5_batch_full_size(dev, oracle, engine):
             assert np.array_equal(eng.poses[b].cpu().numpy(), ref["poses"]), (t, b)
             st = eng.status[b].cpu().numpy()
             assert st[0] == ref["status"] and st[1] == int(ref["mask"].sum())
-            rt, _ = oracle.particle_rmse(ref["poses_prop"], tr.gt_poses[t])
-            assert eng.rmse[b, 0].item() == pytest.approx(rt, rel=1e-9)
+            worst = max(worst, assert_rmse(eng.rmse[b], oracle.particle_rmse(ref["poses_prop"], tr.gt_poses[t]), f"frame {t} b {b}"))
             poses[b] = ref["poses"]
+    print(f"rmse_r vs oracle, c5 {engine} B={B} N={N}: max rel dev {worst:.3g}")
     # every trajectory, size-independent properties: resample indices inside the trajectory, kept counts consistent
     ridx = eng.ridx.cpu().numpy()
     assert ridx.shape == (B, N) and ridx.min() >= 0 and ridx.max() < N

@@ -317,14 +317,17 @@ def test_gather_rows(dev, ops):
 
 
 def test_rmse(dev, ops, oracle, golden):
-    g = golden("g6_rmse")
+    from _recipes import assert_rmse
+    g, worst = golden("g6_rmse"), 0.0
     for tag in ("small", "wide", "one", "same"):
         out = ops.rmse(T(g[f"{tag}_poses"], dev), T(g[f"{tag}_gt"], dev)).cpu().numpy()
         rt, rr = oracle.particle_rmse(g[f"{tag}_poses"], g[f"{tag}_gt"])
         assert out[0] == pytest.approx(rt, rel=1e-12)
-        assert out[1] == pytest.approx(rr, rel=1e-5, abs=0.03)
+        worst = max(worst, assert_rmse(out, (rt, rr), tag))
         assert out[0] == pytest.approx(float(g[f"{tag}_rmse_t"]), rel=1e-5, abs=1e-9)
+        # against the reference's golden the margin stays: torch's matmul orders the trace differently, and acos near 1 amplifies it
         assert out[1] == pytest.approx(float(g[f"{tag}_rmse_r"]), rel=1e-4, abs=0.03)
+    print(f"rmse_r vs oracle, ops.rmse on the g6 cases: max rel dev {worst:.3g}")
 
 
 def test_check_poses(dev, ops):

@@ -28,7 +28,8 @@ def _setup(N, K, D, seed):
 @pytest.mark.parametrize("read_every", [1, 4, 100])
 def test_pipelined_parity_device_draws(dev, oracle, mode, read_every):
     from midastouch_amd.engine import PipelinedFilterEngine
-    N, K, D = 9000, 3000, 256   # three summation blocks, ragged
+    from _recipes import assert_rmse
+    N, K, D, worst = 9000, 3000, 256, 0.0   # three summation blocks, ragged
     cb, traj = _setup(N, K, D, 7)
     ofl = oracle.OracleFilter(cb.poses, cb.embeddings, cb.mesh_vertices)
     eng = PipelinedFilterEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N, seed=4400, resample=mode, device=dev)
@@ -62,10 +63,10 @@ def test_pipelined_parity_device_draws(dev, oracle, mode, read_every):
             assert np.array_equal(eng.hint.cpu().numpy(), ref["nn_idx_res"])
             st = eng.status.cpu().numpy()
             assert st[0] == ref["status"] and st[1] == int(ref["mask"].sum())
-            rt, rr = oracle.particle_rmse(ref["poses_prop"], traj.gt_poses[t])
-            rm = eng.rmse.cpu().numpy()
-            assert rm[0] == pytest.approx(rt, rel=1e-9) and rm[1] == pytest.approx(rr, rel=1e-4, abs=0.03)
+        # (the frame's own statistic: there without a materialisation, so every frame is checked whatever read_every is)
+        worst = max(worst, assert_rmse(eng.rmse, oracle.particle_rmse(ref["poses_prop"], traj.gt_poses[t]), f"frame {t}"))
         poses, prev = ref["poses"], ref
+    print(f"rmse_r vs oracle, PipelinedFilterEngine {mode} N={N}: max rel dev {worst:.3g}")
     assert np.array_equal(eng.poses.cpu().numpy(), poses)  # final materialisation
 
 

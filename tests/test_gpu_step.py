@@ -51,7 +51,8 @@ def _compare_step(eng, ref, t, check_rmse=None):
 def test_step_parity_host_draws(dev, oracle, mode):
     """Parity mode: torch CPU mt19937 draws in the reference's order (tn, rot, then the uniforms)."""
     from midastouch_amd.engine import FilterEngine
-    N, K, D = 2000, 5000, 256
+    from _recipes import assert_rmse
+    N, K, D, worst = 2000, 5000, 256, 0.0
     cb, traj, scale = _setup(N, K, D)
     ofl = oracle.OracleFilter(cb.poses, cb.embeddings, cb.mesh_vertices)
     eng = FilterEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N, resample=mode, device=dev)
@@ -76,10 +77,9 @@ def test_step_parity_host_draws(dev, oracle, mode):
                  gt=torch.as_tensor(traj.gt_poses[t]).to(dev), tn=tn.to(dev), rot=rot.to(dev),
                  u=None if u is None else u.to(dev), u32=u32)
         _compare_step(eng, ref, t)
-        rt, rr = oracle.particle_rmse(ref["poses_prop"], traj.gt_poses[t])
-        rm = eng.rmse.cpu().numpy()
-        assert rm[0] == pytest.approx(rt, rel=1e-9) and rm[1] == pytest.approx(rr, rel=1e-4, abs=0.03)
+        worst = max(worst, assert_rmse(eng.rmse, oracle.particle_rmse(ref["poses_prop"], traj.gt_poses[t]), f"frame {t}"))
         poses = ref["poses"]
+    print(f"rmse_r vs oracle, FilterEngine {mode} N={N}: max rel dev {worst:.3g}")
     assert len(np.unique(eng.ridx.cpu().numpy())) < N  # resampling actually concentrated the particles
 
 
@@ -282,7 +282,8 @@ def test_batch_engine_matches_oracle_per_trajectory(dev, oracle, dense, monkeypa
     """BASELINE config 5 shape (B trajectories per frame): each trajectory of the batch equals the oracle run with
     the matrix-core scores and the Philox streams keyed by b*N + n - indices exact, weights 1e-12."""
     from midastouch_amd.engine import BatchFilterEngine
-    B, N, K, D = 5, 1024, 3000, 256
+    from _recipes import assert_rmse
+    B, N, K, D, worst = 5, 1024, 3000, 256, 0.0
     cb, traj, scale = _setup(N, K, D, seed=4, obj="cotter-pin")
     from midastouch_amd.synthetic import make_trajectory
     trajs = [make_trajectory(cb, T=8, seed=2100 + b) for b in range(B)]
@@ -310,9 +311,9 @@ def test_batch_engine_matches_oracle_per_trajectory(dev, oracle, dense, monkeypa
             assert np.array_equal(eng.poses[b].cpu().numpy(), ref["poses"]), (t, b)
             st = eng.status[b].cpu().numpy()
             assert st[0] == ref["status"] and st[1] == int(ref["mask"].sum())
-            rt, rr = oracle.particle_rmse(ref["poses_prop"], trajs[b].gt_poses[t])
-            assert eng.rmse[b, 0].item() == pytest.approx(rt, rel=1e-9)
+            worst = max(worst, assert_rmse(eng.rmse[b], oracle.particle_rmse(ref["poses_prop"], trajs[b].gt_poses[t]), f"frame {t} b {b}"))
             poses[b] = ref["poses"]
+    print(f"rmse_r vs oracle, BatchFilterEngine dense={dense} B={B} N={N}: max rel dev {worst:.3g}")
 
 
 @pytest.mark.parametrize("mode", ["weighted_random", "low_var"])

@@ -77,6 +77,8 @@ def test_oracle_filter_step_vs_g10b_trace64(golden, oracle):
         _check_digest(g, f"ridx_{t}", r["ridx"])
         rt, rr = oracle.particle_rmse(r["poses_prop"], traj.gt_poses[t])
         assert rt == pytest.approx(float(g[f"rmse_{t}"][0]), rel=1e-5)
+        # (golden of the reference: torch's trace order, amplified by acos near 1 - hence the 0.03 deg)
+        assert rr == pytest.approx(float(g[f"rmse_{t}"][1]), rel=1e-4, abs=0.03)
         poses = r["poses"]
 
 
@@ -181,8 +183,9 @@ def test_oracle_filter_vs_g14_guard_trace_one_stream(golden, oracle):
             seen.append((t, r["status"]))
         # filter.py:176-179: a set that drifted as a whole goes on from the codebook poses nearest to it
         prop = cb.poses[r["nn_idx"]] if r["drifted"] else r["poses_prop"]
-        rt, _ = oracle.particle_rmse(r["poses_prop"], gts[t])
+        rt, rr = oracle.particle_rmse(r["poses_prop"], gts[t])
         assert rt == pytest.approx(float(g[f"fixed_rmse_{t}"][0]), rel=1e-5)
+        assert rr == pytest.approx(float(g[f"fixed_rmse_{t}"][1]), rel=1e-4, abs=0.03)  # (golden: torch's trace order)
         poses = prop[r["ridx"]]
     assert seen == [(int(g["shift_frame"]), 1), (int(g["nan_frame"]), 2)]
     assert np.array_equal(_rand64(8), g["fixed_tail_u"])

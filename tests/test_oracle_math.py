@@ -1,7 +1,9 @@
 """Independent pins for the oracle pieces whose reference implementation is third-party and absent
 from the checkout (theseus SO3.log_map, pynanoflann KD-tree) - checked against scipy - and for the
-self-contained float32 elementary functions of the arithmetic spec.  CPU-only."""
+self-contained float32 elementary functions of the arithmetic spec; the rotation term of the rmse against a float64
+geodesic angle and, term by term at its edges, against the reference's formula restated in torch.  CPU-only."""
 import numpy as np
+import pytest
 from scipy.spatial import cKDTree
 from scipy.spatial.transform import Rotation
 
@@ -167,3 +169,165 @@ def test_oracle_knn6_matches_ckdtree(oracle):
     assert np.array_equal(idx[:, 0], oracle.nn6(q, pts)[0])
     i2, _ = oracle.knn6(np.zeros((1, 6), np.float32), np.zeros((4, 6), np.float32), 3)  # all tied: index order
     assert i2.tolist() == [[0, 1, 2]]
+
+
+# ---- rmse: the rotation column ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["band5", "band20", "noise0.5", "noise3"])
+def test_rmse_clouds_vs_float64(oracle, kind):
+    """mo_rmse (the float32 trace by an fma chain, acosf, modules/particle_filter.py:485-493) against the float64 geodesic angle
+    of the same float32 inputs, N = 2000 on a random gt.
+    Band clouds (angles uniform in [5, 175] / [20, 160] degrees): six roundings of 2^-24 on a trace of magnitude <= 3 give
+    dx <~ 5e-7, d(theta) <= dx / sin 5 deg = 6e-6 rad = 3.3e-4 deg on terms >= 5 deg, at most 3.3e-6 relative on an RMS near
+    100 deg: rel 1e-5 (measured 1.3e-8, 1.2e-8).  Noise clouds (0.5 and 3 degrees per axis): rel 1e-4 (measured 4.3e-5,
+    5.2e-7).  For small angles rmse^2 = 2 mean(1 - x), so an error dx of the argument moves the RMS by dx / rmse_rad^2 relative:
+    at 3 deg noise (rmse 5.3 deg) even the worst case dx = 5.4e-7 stays at 6.3e-5.  At 0.5 deg noise (rmse 0.875 deg, rmse_rad^2 =
+    2.3e-4) the per-term roundings, about 5e-8 each way, average out over 2000 terms (4e-4 / sqrt(2000)), but a part of dx is
+    COMMON to all particles of one gt - the float32 gt is orthonormal only to 6e-8 and acos, unlike atan2, passes that on at
+    first order: 1e-8 of it is 4.3e-5.  Over other draws of gt the same cloud measures 5e-6 .. 1.5e-4, so the 1e-4 is a statement
+    about this seeded gt, not about the formula; what the formula guarantees there is dx / rmse_rad^2 = 2.3e-3.  No cloud below
+    0.5 deg: at 0.05 deg the float32 formula itself is 1.6e-3 off the float64 angle, which is the reference's behaviour and
+    nothing to assert against.
+    rmse_t: float32 differences (exact or within 2^-24 of the difference) and an fma chain of three terms against the float64
+    norm: under 4 * 2^-24 = 2.4e-7 per term on e^2, unbiased, so 2.4e-7 / (2 sqrt(2000)) = 2.7e-9 on the RMS of 2000: rel 1e-8
+    (measured <= 1.3e-9)."""
+    from _recipes import RMSE_R_REL_F64, RMSE_T_REL_F64, rmse_cloud, rmse_ref64
+    poses, gt = rmse_cloud(kind, 2000)
+    rt, rr = oracle.particle_rmse(poses, gt)
+    ft, fr = rmse_ref64(poses, gt)
+    print(f"{kind}: rmse_r {rr:.9g} (float64 {fr:.9g}, rel {abs(rr - fr) / fr:.3g}), rmse_t rel {abs(rt - ft) / ft:.3g}")
+    assert rr == pytest.approx(fr, rel=RMSE_R_REL_F64[kind], abs=0)
+    assert rt == pytest.approx(ft, rel=RMSE_T_REL_F64, abs=0)
+    lo = {"band5": 90.0, "band20": 90.0, "noise0.5": 0.8, "noise3": 4.5}[kind]
+    assert lo < fr < 1.25 * lo  # the cloud is the regime it names
+
+
+def _fmaf(a, b, c):
+    """fl32(a * b + c) of float32 operands, one rounding: the product is exact in float64, the sum is rounded to odd there
+    (TwoSum tells on which side the exact sum lies), and 53 bits rounded to odd round to 24 as the exact value does."""
+    p, c = float(a) * float(b), float(c)
+    s = p + c
+    if np.isfinite(s):
+        t = s - p
+        e = (p - (s - t)) + (c - t)
+        if e != 0.0 and np.float64(s).view(np.int64) & 1 == 0:
+            s = np.nextafter(s, np.inf if e > 0 else -np.inf)
+    return np.float32(s)
+
+
+def _trace_fma_chain(P, G):
+    """tr(R_gt R_n^T) = sum_ij Rgt_ij Rn_ij in float32, each row by one product and two fused multiply-adds, rows added in order
+    (the arithmetic spec of the trace: DESIGN.md, rmse)."""
+    tr = np.float32(0.0)
+    with np.errstate(all="ignore"):
+        for i in range(3):
+            acc = np.float32(G[i, 0]) * np.float32(P[i, 0])
+            acc = _fmaf(G[i, 1], P[i, 1], acc)
+            acc = _fmaf(G[i, 2], P[i, 2], acc)
+            tr = np.float32(tr + acc)
+    return tr
+
+
+def _reference_formula(poses, gt, spec_trace=False):
+    """particle_rmse as the reference states it, on torch CPU float32: trace of R_gt R_n^T, acos, rad2deg, nan_to_num, the two
+    wraps, the means.  spec_trace: the trace in the spec's order instead of torch.matmul's.  -> (rmse_t, rmse_r, acos argument)."""
+    import torch
+    Pn, Gn = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4), np.asarray(gt, dtype=np.float32)
+    P, G = torch.as_tensor(Pn), torch.as_tensor(Gn)[None]
+    if spec_trace:
+        tr = torch.as_tensor(np.array([_trace_fma_chain(p, Gn) for p in Pn], dtype=np.float32))
+    else:
+        Rd = torch.matmul(G[:, :3, :3], P[:, :3, :3].transpose(1, 2))
+        tr = Rd[:, 0, 0] + Rd[:, 1, 1] + Rd[:, 2, 2]
+    x = (tr - 1.0) * 0.5
+    ang = torch.nan_to_num(torch.rad2deg(torch.acos(x)))
+    ang = torch.where(ang > 180.0, ang - 360.0, ang)
+    ang = torch.where(ang < -180.0, ang + 360.0, ang)
+    e_t = torch.linalg.norm(G[:, :3, 3] - P[:, :3, 3], dim=1)
+    return float(torch.sqrt(torch.mean(e_t ** 2))), float(torch.sqrt(torch.mean(ang ** 2))), x.double().numpy()
+
+
+def _cls(v):
+    return "nan" if np.isnan(v) else "inf" if np.isinf(v) else "zero" if v == 0 else "finite"
+
+
+def test_rmse_edge_terms_vs_reference_formula(oracle):
+    """Every edge term as an N = 1 call (rmse_r = |angle|, rmse_t = |e|) against the reference's formula restated in torch:
+    acos, rad2deg, nan_to_num, the two wraps, the means.  Same class (NaN / Inf / zero / finite), and finite angles >= 1 degree
+    within rel 1e-5 (torch's acos and glibc's acosf, 1 ulp each, the product with 57.29...: 3 * 2^-23).
+    That bound is on the formula BEHIND the trace, so the restatement takes the trace in the spec's order (a float32 fma chain,
+    emulated exactly): at pi and pi -+ 1e-3 one ulp of the acos argument moves the angle by 3.4e-3 .. 2e-2 degrees, 2e-5 .. 1e-4
+    relative, and decides NaN against 179.98 at x = -1, so against torch.matmul's order (37 of these terms differ by an ulp or
+    two in x) no 1e-5 can hold.  test_rmse_edge_terms_vs_torch_matmul is that comparison, with the tolerance conditioning gives."""
+    from _recipes import rmse_edge_terms
+    terms = rmse_edge_terms()
+    assert len(terms) >= 200
+    seen, worst = set(), 0.0
+    for name, P, G in terms:
+        rt, rr = oracle.particle_rmse(P[None], G)
+        ft, fr, x = _reference_formula(P[None], G, spec_trace=True)
+        assert _cls(rt) == _cls(ft) and _cls(rr) == _cls(fr), (name, rt, ft, rr, fr)
+        seen.add(f"{_cls(rt)}/{_cls(rr)}")
+        if _cls(ft) == "finite":
+            assert rt == pytest.approx(ft, rel=1e-6), name
+        if _cls(fr) == "finite" and fr >= 1.0:
+            assert rr == pytest.approx(fr, rel=1e-5, abs=0), (name, rr, fr)
+            worst = max(worst, abs(rr - fr) / fr)
+    print(f"{len(terms)} edge terms, classes (rmse_t/rmse_r) {sorted(seen)}, largest rel deviation of a finite term {worst:.3g}")
+    assert {"zero/zero", "finite/zero", "finite/finite", "nan/finite", "inf/finite"} <= seen
+
+
+def test_rmse_edge_terms_vs_torch_matmul(oracle):
+    """The same terms against the reference's formula with torch.matmul's own trace.  The two sides round the trace in different
+    orders, so their acos arguments differ by a few 2^-24 (dx = 4 * 2^-24 allowed).  Within dx of +-1 the class itself is
+    open - NaN-to-0 on one side of 1, a finite angle on the other - and each side is held to "0, or within acos(1 - 2 dx) of
+    the boundary angle"; elsewhere classes agree and finite angles >= 1 degree agree within max(1e-5 theta, dx / sin theta)."""
+    from _recipes import rmse_edge_terms
+    dx = 4 * 2.0 ** -24
+    lim = np.degrees(np.arccos(1.0 - 2 * dx)) * 1.001
+    boundary = 0
+    for name, P, G in rmse_edge_terms():
+        rt, rr = oracle.particle_rmse(P[None], G)
+        ft, fr, x = _reference_formula(P[None], G)
+        assert _cls(rt) == _cls(ft), name
+        if np.isfinite(x[0]) and abs(abs(x[0]) - 1.0) <= dx:
+            ok = (lambda v: v == 0 or v <= lim) if x[0] > 0 else (lambda v: v == 0 or 180.0 - v <= lim)
+            assert ok(rr) and ok(fr), (name, rr, fr, x[0])
+            boundary += 1
+            continue
+        assert _cls(rr) == _cls(fr), (name, rr, fr)
+        if _cls(rr) == "finite" and fr >= 1.0:
+            assert abs(rr - fr) <= max(1e-5 * fr, np.degrees(dx / np.sin(np.radians(fr)))), (name, rr, fr)
+    assert boundary >= 20
+
+
+def test_rmse_named_edges(oracle):
+    """The values the edge rules give, stated outright: the identical pose 0 / 0; a zero rotation block 120 degrees; a turn by
+    pi about a frame axis from the identity 180 exactly; rows scaled by 1 + 2^-20: x > 1, NaN, hence 0; by 1 - 2^-20: a small
+    finite angle (acos(1 - 1.5 * 2^-20) = 0.0969 degrees); NaN rotation entry: term 0; NaN translation entry: rmse_t NaN and
+    the rotation term untouched; mixed clouds: the NaN-to-0 terms count as zeros in the mean, they are not dropped."""
+    from _recipes import rmse_cloud, rmse_mixed_cloud
+    eye = np.eye(4, dtype=np.float32)
+    assert oracle.particle_rmse(eye[None], eye) == (0.0, 0.0)
+    Z = eye.copy(); Z[:3, :3] = 0
+    assert oracle.particle_rmse(Z[None], eye)[1] == pytest.approx(120.0, rel=1e-6)
+    for d in ([1, -1, -1], [-1, 1, -1], [-1, -1, 1]):
+        P = eye.copy(); P[:3, :3] = np.diag(d)
+        assert oracle.particle_rmse(P[None], eye)[1] == pytest.approx(180.0, rel=1e-6)
+    G = eye.copy(); G[:3, :3] *= np.float32(1 + 2.0 ** -20)
+    assert oracle.particle_rmse(eye[None], G)[1] == 0.0
+    G = eye.copy(); G[:3, :3] *= np.float32(1 - 2.0 ** -20)
+    assert oracle.particle_rmse(eye[None], G)[1] == pytest.approx(np.degrees(np.arccos(1 - 1.5 * 2.0 ** -20)), rel=1e-3)
+    P = eye.copy(); P[1, 2] = np.nan
+    assert oracle.particle_rmse(P[None], eye) == (0.0, 0.0)
+    P = Z.copy(); P[0, 3] = np.nan
+    rt, rr = oracle.particle_rmse(P[None], eye)
+    assert np.isnan(rt) and rr == pytest.approx(120.0, rel=1e-6)
+    # a NaN-to-0 term among n - 1 ordinary ones: sqrt(sum of the others / n)
+    poses, gt = rmse_cloud("noise0.5", 257, 5)
+    full = oracle.particle_rmse(poses, gt)[1]
+    t0 = oracle.particle_rmse(poses[:1], gt)[1]
+    poses[0, 0, 0] = np.nan
+    assert oracle.particle_rmse(poses, gt)[1] == pytest.approx(np.sqrt((full ** 2 * 257 - t0 ** 2) / 257), rel=1e-12)
+    for n in (257, 4097):
+        a, b = oracle.particle_rmse(*rmse_mixed_cloud(n)), oracle.particle_rmse(*rmse_mixed_cloud(n, nan_translation_last=True))
+        assert np.isfinite(a[0]) and np.isnan(b[0]) and a[1] == b[1] and a[1] > 1.0
