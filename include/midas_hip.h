@@ -993,7 +993,8 @@ int midas_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* 
  * draws (tn_dev, rot_dev, u_dev NULL); topk_ties == MIDAS_TOPK_TIES_INDEX; grid_n == 0 and anneal_frozen == 0; a float32 codebook
  * with sparse scoring (score_stamps_dev and a non-zero score_epoch, D in {128, 256, 512, 1024}); 1 <= B <= 65535.
  * Within that regime there is one path: args->anneal_small and the MIDAS_LOOP_MERGE / MIDAS_FRONT_SMALL switches, which choose
- * between bit-identical paths of midas_loop_step, are not consulted here. */
+ * between bit-identical paths of midas_loop_step, are not consulted here.  Sets beyond MIDAS_LOOP_BATCH_MAX_CAP - the reference's
+ * own 50 000 - go through midas_loop_step_batch_wide below; this entry keeps its bound. */
 #define MIDAS_LOOP_BATCH_MAX_CAP 16384
 int midas_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                           const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);
@@ -1013,6 +1014,23 @@ int midas_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_
  * midas_loop_step_batch; with these draws trajectory b holds the bits of midas_loop_step on it alone with the same draws. */
 int midas_loop_step_batch_draws(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                                 const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);
+/* midas_loop_step_batch for wide sets - the sizes the reference itself runs (config/expt/ycb.yaml: num_particles 50000; annealing
+ * floors of 10 000) and this project's headline 100 000 - B loop bodies of filter/filter.py:150-190 with annealing's selection
+ * (particle_filter.py:405-447) at any of them.  Arguments and layout are midas_loop_step_batch's: every array (B, ...) contiguous with
+ * `cap` as the per-trajectory extent, trajectory b keyed (seed + b, step), frame for frame the bits of midas_loop_step on it alone.
+ * The regime - anything else is MIDAS_ERR_INVALID with nothing enqueued: cap <= MIDAS_LOOP_BATCH_WIDE_MAX_CAP (32 summation blocks
+ * of 4096) and B * cap <= 2^24; device draws (tn_dev, rot_dev, u_dev NULL); topk_ties == MIDAS_TOPK_TIES_INDEX; grid_n == 0 and
+ * anneal_frozen == 0; a float32 codebook with sparse scoring; 1 <= B <= 65535; any subset of phases.
+ * Beyond MIDAS_LOOP_BATCH_MAX_CAP one trajectory's keys no longer fit the one workgroup of the small-set selection: every trajectory's
+ * decision and midas_loop_step's radix selection (six digit passes, compaction, the duplicates' sort) run with the trajectory as
+ * grid.y on per-trajectory histograms, state, block counts and pair buffers - the decision and the selection's ten launches once for the batch, their boundaries the
+ * grid-wide syncs between the passes - and the front is the small-set kernel over ceil(cap / 64) waves a trajectory.  The grids
+ * cover the capacity on every frame (no per-frame bound), the B DBSCAN passes follow each other as in midas_loop_step_batch.
+ * For cap <= MIDAS_LOOP_BATCH_MAX_CAP the call is midas_loop_step_batch: the same launches, the same bits.
+ * Seeded streams and the ATen tie rule at these sizes: not yet (midas_loop_step_batch_draws keeps its bound). */
+#define MIDAS_LOOP_BATCH_WIDE_MAX_CAP 131072
+int midas_loop_step_batch_wide(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                               const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);
 /* cluster_particles(method="euclidean") alone (particle_filter.py:208-217): labels_dev[i] = DBSCAN label of pose i's
  * translation, eps as given, min_samples < 0 -> N / 5.  Exact float64 predicate |dx|^2 <= eps^2, clusters numbered by their
  * first core point, border points to the smallest adjacent cluster - what sklearn's DBSCAN returns.  Any extent (dense cell grid

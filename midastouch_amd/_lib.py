@@ -212,6 +212,7 @@ MT19937_HIST_WORDS = 20560  # MIDAS_MT19937_HIST_WORDS
 TOPK_TIES_INDEX, TOPK_TIES_ATEN_CPU = 0, 1  # whom annealing's torch.topk takes inside a tie (include/midas_hip.h)
 LOOP_MAX_CLUSTERS, LOOP_LOG_DOUBLES = 64, 168
 LOOP_BATCH_MAX_CAP = 16384  # MIDAS_LOOP_BATCH_MAX_CAP: particles per trajectory midas_loop_step_batch takes
+LOOP_BATCH_WIDE_MAX_CAP = 131072  # MIDAS_LOOP_BATCH_WIDE_MAX_CAP: particles per trajectory midas_loop_step_batch_wide takes
 (LOOP_I_N, LOOP_I_NSET, LOOP_I_MODE, LOOP_I_K, LOOP_I_INIT, LOOP_I_VARSET, LOOP_I_KEPT, LOOP_I_DRIFT, LOOP_I_STATUS,
  LOOP_I_RAW, LOOP_I_NCL, LOOP_I_NPRES, LOOP_I_FRAME, LOOP_I_NAN, LOOP_I_ERR, LOOP_I_NDRAW) = range(16)
 LOOP_ERR_NDRAW = 256  # ctl_i[ERR] bit 8: the resample's status disagrees with ctl_i[NDRAW]
@@ -287,6 +288,7 @@ SIGNATURES = {
     "midas_loop_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32]),
     "midas_loop_step_batch": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64]),
     "midas_loop_step_batch_draws": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64]),
+    "midas_loop_step_batch_wide": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64]),
     "midas_dbscan": (C.c_int, [_P, _I64, _P, _D, _I64, _P, _P]),
     "midas_dbscan_points": (C.c_int, [_P, _I64, C.c_int32, _P, _D, _I64, _P, _P]),
     "midas_anneal_select": (C.c_int, [_P, _I64, _P, _I32, _I64, _P]),

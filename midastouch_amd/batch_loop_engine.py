@@ -7,8 +7,8 @@ block, its own labels, cluster rows and log ring - and the kernels of the small-
 Trajectory b draws from the Philox streams keyed (seed + b, frame): frame for frame it holds the bits of a LoopEngine built with
 seed + b and stepped with row b of the operands.
 
-The regime is the small set: at most 16 384 particles per trajectory (`_lib.LOOP_BATCH_MAX_CAP`), a float32 codebook scored
-sparsely.  Larger sets and sharding stay with LoopEngine and the sharded engine.  DBSCAN frames run the single pass once per
+The regime is the small set: at most 16 384 particles per trajectory (`_lib.LOOP_BATCH_MAX_CAP`; `wide=True`, below: 131 072), a
+float32 codebook scored sparsely.  Sharding stays with the sharded engine.  DBSCAN frames run the single pass once per
 trajectory, one after the other on the stream, on one shared set of cell tables.
 
 Seeded runs: `seed_torch_streams(seeds)` makes trajectory b a process of the reference under `torch.manual_seed(seeds[b])` - its
@@ -17,6 +17,14 @@ the live and annealed counts in ITS control block, and ties of annealing's `torc
 (`topk_ties = "aten_cpu"`, settable on its own too).  Row b then holds, frame for frame, the bits of a LoopEngine built with
 `topk_ties="aten_cpu"` and `seed_torch_stream(seeds[b])` - the reference's particles - through `midas_loop_step_batch_draws`; a frame
 is four enqueues and reads nothing back.
+
+Wide sets: `BatchLoopEngine(..., wide=True)` holds up to 131 072 particles per trajectory (`_lib.LOOP_BATCH_WIDE_MAX_CAP`, with
+B x capacity <= 2^24) - the reference's own `num_particles: 50000` (config/expt/ycb.yaml) and the headline's 100 000 - through
+`midas_loop_step_batch_wide`: beyond 16 384 annealing's selection is LoopEngine's radix select with the trajectory as grid.y, on
+per-trajectory state reserved at construction.  Row b holds the bits of a LoopEngine built with seed + b as before; up to 16 384 a
+wide engine runs the launches of a plain one.  Open follow-up: `seed_torch_streams` and `topk_ties = "aten_cpu"` raise on a wide
+engine - the one-wave walk of ATen's top-k takes 1.4 - 11 ms at 100 000 particles per trajectory, which a batch frame cannot carry;
+seeded replays at these sizes stay with LoopEngine.
 """
 from __future__ import annotations
 
@@ -33,11 +41,17 @@ from .loop_engine import ALL_PHASES, log_records
 class BatchLoopEngine:
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, batch: int, num_particles: int, *, sig_t=2e-4, sig_r=0.5,
                  pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2,
-                 cluster: bool = True, cluster_every: int = 50, log_frames: int = 4096, device=None):
+                 cluster: bool = True, cluster_every: int = 50, log_frames: int = 4096, device=None, wide: bool = False):
         self.B, self.cap = B, cap = int(batch), int(num_particles)
+        self.wide = bool(wide)
         if B < 1 or B > 65535:
             raise MidasError("BatchLoopEngine holds 1 .. 65535 trajectories")
-        if cap < 1 or cap > _lib.LOOP_BATCH_MAX_CAP:
+        if self.wide:
+            if cap < 1 or cap > _lib.LOOP_BATCH_WIDE_MAX_CAP:
+                raise MidasError(f"a wide BatchLoopEngine holds 1 .. {_lib.LOOP_BATCH_WIDE_MAX_CAP} particles per trajectory (larger sets: LoopEngine)")
+            if B * cap > 1 << 24:
+                raise MidasError(f"a wide BatchLoopEngine holds at most 2^24 particles in all, not {B} x {cap}")
+        elif cap < 1 or cap > _lib.LOOP_BATCH_MAX_CAP:
             raise MidasError(f"BatchLoopEngine holds 1 .. {_lib.LOOP_BATCH_MAX_CAP} particles per trajectory (larger sets: LoopEngine)")
         self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3 = codebook_index(
             cb_poses, cb_embeddings, mesh_vertices, device)
@@ -86,7 +100,8 @@ class BatchLoopEngine:
         self.torch_streams = None  # seed_torch_streams
         # The scratch every phase combination of a batch frame asks for, reserved now so that no frame allocates: per trajectory the
         # hand-over records of the front (32 B a particle), the block results, the cluster-moment partials (64 x 36 doubles per 256
-        # particles) and cluster rows, the resample's prefix values; once, DBSCAN's cell tables (84 MB + 41 B a particle).
+        # particles) and cluster rows, the resample's prefix values, a wide engine's select state; once, DBSCAN's cell tables (84 MB +
+        # 41 B a particle).
         per_traj = self._per_traj()
         self._scratch = (128 << 20) + 256 * cap + B * per_traj + 64 * 256
         self.ctx.call("midas_scratch_reserve", self._scratch)
@@ -99,6 +114,8 @@ class BatchLoopEngine:
 
     @topk_ties.setter
     def topk_ties(self, rule):
+        if rule == "aten_cpu" and self.wide:
+            raise MidasError("a wide BatchLoopEngine breaks ties by index: the ATen tie rule beyond 16 384 particles stays with LoopEngine")
         self._args.topk_ties = {"index": _lib.TOPK_TIES_INDEX, "aten_cpu": _lib.TOPK_TIES_ATEN_CPU}[rule]
         if rule == "aten_cpu":  # the walk's queue, stopper lists, marks and block counts per trajectory, beside the frame's own
             cap = self.cap
@@ -109,7 +126,12 @@ class BatchLoopEngine:
     def _per_traj(self):
         cap = self.cap
         nb, nb256 = (cap + 4095) // 4096, (cap + 255) // 256
-        return 32 * cap + 32 * nb + 8 * 64 * 10 + 8 * 36 * 64 * nb256 + 4 * 64 * 16 + 4 * 64 * 3 + 8 * 64 + 8 * (cap + 16) + 12 * nb
+        frame = 32 * cap + 32 * nb + 8 * 64 * 10 + 8 * 36 * 64 * nb256 + 4 * 64 * 16 + 4 * 64 * 3 + 8 * 64 + 8 * (cap + 16) + 12 * nb
+        if self.wide and cap > _lib.LOOP_BATCH_MAX_CAP:
+            # the radix selection per trajectory (loop.hip select_scratch): 6 x 2048 histogram words, 32 state words, two block counts
+            # a summation block, and cap / 3 + 1 (key, index) pairs twice - selected, then sorted
+            frame += 4 * 6 * 2048 + 4 * 32 + 2 * 4 * nb + 2 * (8 + 4) * (cap // 3 + 1)
+        return frame
 
     # ---- state ----------------------------------------------------------------------------------------------------
     def set_particles(self, poses, labels=None, reset_annealing: bool = True):
@@ -188,6 +210,8 @@ class BatchLoopEngine:
             self.torch_streams = None
             self.topk_ties = "index"
             return None
+        if self.wide:
+            raise MidasError("a wide BatchLoopEngine draws from Philox: seeded torch streams beyond 16 384 particles stay with LoopEngine")
         seeds = list(seeds)
         if len(seeds) != self.B:
             raise MidasError(f"{len(seeds)} seeds for a batch of {self.B} trajectories")
@@ -287,6 +311,8 @@ class BatchLoopEngine:
                 a.stream_draws = 0
         elif self._topk_ties == "aten_cpu":
             call(self.ctx.lib.midas_loop_step_batch_draws, phases)  # (Philox draws, the ATen tie rule)
+        elif self.wide:
+            call(self.ctx.lib.midas_loop_step_batch_wide, phases)
         else:
             call(self.ctx.lib.midas_loop_step_batch, phases)
         self._labels_prev = self._labels

@@ -1,5 +1,6 @@
 // api_loop.hip - the loop engine's entry points: the whole loop body on a variable-size particle set, for one trajectory
-// (midas_loop_step) and for B per launch (midas_loop_step_batch, midas_loop_step_batch_draws).  One argument check for the three.
+// (midas_loop_step) and for B per launch (midas_loop_step_batch, midas_loop_step_batch_draws, midas_loop_step_batch_wide).  One
+// argument check for the four.
 #include "api_entry.hpp"
 
 using namespace midas;
@@ -7,7 +8,8 @@ using namespace midas;
 // single: any capacity the blocked scan takes, a bound below it (grid_n), any draws, any selection.
 // batch: the small-set regime with device draws and ties by index; batch_draws: that regime with host draws and either tie rule
 // (include/midas_hip.h).
-enum class LoopRegime { single, batch, batch_draws };
+// batch_wide: batch's draws and tie rule for up to MIDAS_LOOP_BATCH_WIDE_MAX_CAP particles a trajectory, B * cap <= 2^24.
+enum class LoopRegime { single, batch, batch_draws, batch_wide };
 
 static int loop_args_check(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                            const midas_loop_args* args, int32_t phases, LoopRegime regime, int32_t B = 1, int64_t log_stride = 0) {
@@ -16,7 +18,9 @@ static int loop_args_check(midas_ctx* ctx, const midas_codebook* cb, const midas
     const bool batch = regime != LoopRegime::single;
     MIDAS_REQUIRE(ctx, B >= 1 && B <= 65535);
     MIDAS_REQUIRE(ctx, s.cap > 0 && s.ctl_i_dev && s.ctl_d_dev);
-    if (batch)
+    if (regime == LoopRegime::batch_wide)
+        MIDAS_REQUIRE(ctx, s.cap <= MIDAS_LOOP_BATCH_WIDE_MAX_CAP && (int64_t)B * s.cap <= ((int64_t)1 << 24));
+    else if (batch)
         MIDAS_REQUIRE(ctx, s.cap <= MIDAS_LOOP_BATCH_MAX_CAP);
     else
         MIDAS_REQUIRE(ctx, ceil_div(s.cap, SCAN_BLOCK) <= LAZY_MAX_BLOCKS);
@@ -25,7 +29,7 @@ static int loop_args_check(midas_ctx* ctx, const midas_codebook* cb, const midas
                            s.labels_dev != s.labels_out_dev && s.src_dev && s.ridx_dev && s.scores_dev && s.cluster_poses_dev &&
                            s.cluster_stds_dev);
     MIDAS_REQUIRE(ctx, (uintptr_t)s.poses_dev % 16 == 0 && (uintptr_t)s.poses_prop_dev % 16 == 0);
-    if (regime == LoopRegime::batch) {
+    if (regime == LoopRegime::batch || regime == LoopRegime::batch_wide) {
         MIDAS_REQUIRE(ctx, s.tn_dev == nullptr && s.rot_dev == nullptr && s.u_dev == nullptr);
         MIDAS_REQUIRE(ctx, s.topk_ties == MIDAS_TOPK_TIES_INDEX);
     } else if (regime == LoopRegime::batch_draws) {
@@ -73,6 +77,13 @@ MIDAS_EXPORT int midas_loop_step_batch_draws(midas_ctx* ctx, const midas_codeboo
     MIDAS_ENTER(ctx);
     if (int rc = loop_args_check(ctx, cb, tree6, tree3, args, phases, LoopRegime::batch_draws, B, log_stride)) return rc;
     return launch_loop_step_batch(ctx, cb, tree6, tree3, *args, phases, B, log_stride);
+}
+
+MIDAS_EXPORT int midas_loop_step_batch_wide(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
+                                            const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride) {
+    MIDAS_ENTER(ctx);
+    if (int rc = loop_args_check(ctx, cb, tree6, tree3, args, phases, LoopRegime::batch_wide, B, log_stride)) return rc;
+    return launch_loop_step_batch(ctx, cb, tree6, tree3, *args, phases, B, log_stride, true);
 }
 
 }  // extern "C"

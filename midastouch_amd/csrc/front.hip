@@ -429,9 +429,11 @@ int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t
 }
 
 int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a_in,
-                             const midas_codebook* cb, const double* code, double* scores, int32_t B) {
+                             const midas_codebook* cb, const double* code, double* scores, int32_t B, bool wide) {
     ParticleUpdateArgs a = a_in;
-    if (!(a.n_live && a.N > 0 && a.N <= 16384 && a.sp.stamps && !a.rs.enabled && cb->dtype == MIDAS_F32 &&
+    // wide (midas_loop_step_batch_wide): the same kernel over the ceil(N / 64) waves of a larger capacity - a wave indexes the hand-over
+    // records, the per-wave rmse partials and every (B, ...) array in 64 bits, and k_loop_weights sums any number of partials
+    if (!(a.n_live && a.N > 0 && (a.N <= 16384 || (wide && a.N <= MIDAS_LOOP_BATCH_WIDE_MAX_CAP)) && a.sp.stamps && !a.rs.enabled && cb->dtype == MIDAS_F32 &&
           (cb->D == 512 || cb->D == 256 || cb->D == 128 || cb->D == 1024) && (uintptr_t)cb->emb % 16 == 0 && (uintptr_t)code % 16 == 0))
         return midas_set_error(ctx, MIDAS_ERR_INVALID, "launch_front_small_batch", "no small-set front for these arguments");
     a.scores = nullptr;  // deferred: k_loop_xe gathers the scores

@@ -39,6 +39,7 @@ namespace midas {
 constexpr int SEL_PASSES = 6;
 constexpr int SEL_BINS = 2048;
 constexpr int SORT_CHUNK = 2048;  // (key, index) pairs sorted per workgroup in LDS
+constexpr int SEL_HIST_WORDS = SEL_PASSES * SEL_BINS, SEL_STATE_WORDS = 4 * (SEL_PASSES + 2);  // one trajectory's select state
 __device__ const int kSelShift[SEL_PASSES] = {53, 42, 31, 20, 9, 0};
 __device__ const int kSelWidth[SEL_PASSES] = {11, 11, 11, 11, 11, 9};
 
@@ -327,11 +328,12 @@ __global__ __launch_bounds__(256) void k_loop_decide(int32_t* __restrict__ ctl_i
                                                      float* __restrict__ stds_out, uint32_t* __restrict__ hist,
                                                      int32_t* __restrict__ sel_state, int32_t floor_n, const double* __restrict__ rot,
                                                      int32_t frozen = 0, int32_t aten_order = 0) {
-    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch_draws): LOOP_MAX_CLUSTERS cluster rows each, no select state
-        const int64_t b = blockIdx.y;
+    if (blockIdx.y) {  // a batch of trajectories: LOOP_MAX_CLUSTERS cluster rows each; no select state (midas_loop_step_batch_draws'
+        const int64_t b = blockIdx.y;  // ATen walk), or every trajectory's own histograms and state (midas_loop_step_batch_wide)
         ctl_i += b * LOOP_CTL_I; ctl_d += b * LOOP_CTL_D;
         centers_all += b * LOOP_MAX_CLUSTERS * 16; stds_all += b * LOOP_MAX_CLUSTERS * 3; counts_all += b * LOOP_MAX_CLUSTERS;
         centers_out += b * LOOP_MAX_CLUSTERS * 16; stds_out += b * LOOP_MAX_CLUSTERS * 3; rot += b * LOOP_MAX_CLUSTERS * 10;
+        if (hist) { hist += b * SEL_HIST_WORDS; sel_state += b * SEL_STATE_WORDS; }
     }
     if (blockIdx.x == 1) { loop_rotations(ctl_i, counts_all, rot, centers_out); return; }
     const int t = threadIdx.x;
@@ -341,8 +343,8 @@ __global__ __launch_bounds__(256) void k_loop_decide(int32_t* __restrict__ ctl_i
         loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k, aten_order != 0);
         return;
     }
-    for (int i = t; i < SEL_PASSES * SEL_BINS; i += 256) hist[i] = 0u;
-    for (int i = t; i < 4 * (SEL_PASSES + 2); i += 256) sel_state[i] = 0;
+    for (int i = t; i < SEL_HIST_WORDS; i += 256) hist[i] = 0u;
+    for (int i = t; i < SEL_STATE_WORDS; i += 256) sel_state[i] = 0;
     __syncthreads();
     if (t != 0) return;
     int mode, k;
@@ -472,9 +474,13 @@ MD void select_advance(const uint32_t* __restrict__ hist, int32_t* __restrict__ 
 // pass P of the radix select: histogram of digit P over the particles whose key starts with the prefix found so far
 template <int P>
 __global__ __launch_bounds__(256) void k_loop_select(const int32_t* __restrict__ ctl_i, const double* __restrict__ w,
-                                                     uint32_t* __restrict__ hist, int32_t* __restrict__ state) {
+                                                     uint32_t* __restrict__ hist, int32_t* __restrict__ state, int32_t cap = 0) {
     __shared__ uint32_t s_h[SEL_BINS];
     __shared__ int s_scan[8];
+    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch_wide): `cap` weights, its own histograms and state each
+        const int64_t b = blockIdx.y;
+        ctl_i += b * LOOP_CTL_I; w += b * cap; hist += b * SEL_HIST_WORDS; state += b * SEL_STATE_WORDS;
+    }
     const int mode = ctl_i[LOOP_I_MODE];
     if (!mode) return;
     const int64_t n = ctl_i[LOOP_I_N];
@@ -506,9 +512,13 @@ __global__ __launch_bounds__(256) void k_loop_select(const int32_t* __restrict__
 // per 4096-slot block: particles whose key is below the threshold key, and equal to it
 __global__ __launch_bounds__(256) void k_loop_compact_count(const int32_t* __restrict__ ctl_i, const double* __restrict__ w,
                                                             const uint32_t* __restrict__ hist, int32_t* __restrict__ state,
-                                                            int32_t* __restrict__ c_less, int32_t* __restrict__ c_eq) {
+                                                            int32_t* __restrict__ c_less, int32_t* __restrict__ c_eq, int32_t cap = 0) {
     __shared__ int s_scan[8];
     __shared__ int s_a[4], s_b[4];
+    if (blockIdx.y) {  // a batch of trajectories: `cap` weights, a launch's block counts, its own histograms and state each
+        const int64_t b = blockIdx.y, ob = b * gridDim.x;
+        ctl_i += b * LOOP_CTL_I; w += b * cap; hist += b * SEL_HIST_WORDS; state += b * SEL_STATE_WORDS; c_less += ob; c_eq += ob;
+    }
     const int mode = ctl_i[LOOP_I_MODE];
     if (!mode) return;
     const int64_t n = ctl_i[LOOP_I_N];
@@ -545,9 +555,14 @@ __global__ __launch_bounds__(256) void k_loop_compact_count(const int32_t* __res
 __global__ __launch_bounds__(256) void k_loop_compact(const int32_t* __restrict__ ctl_i, const double* __restrict__ w,
                                                       const int32_t* __restrict__ state, const int32_t* __restrict__ c_less,
                                                       const int32_t* __restrict__ c_eq, int32_t* __restrict__ src,
-                                                      uint64_t* __restrict__ sel_key, int32_t* __restrict__ sel_idx) {
+                                                      uint64_t* __restrict__ sel_key, int32_t* __restrict__ sel_idx, int32_t cap = 0,
+                                                      int32_t ksel = 0) {
     __shared__ int s_l[LAZY_MAX_BLOCKS], s_e[LAZY_MAX_BLOCKS];
     __shared__ int s_wl[4], s_we[4];
+    if (blockIdx.y) {  // a batch of trajectories: `cap` weights and sources, `ksel` pairs, a launch's block counts, its own state each
+        const int64_t b = blockIdx.y, o = b * cap, ob = b * gridDim.x, ok = b * ksel;
+        ctl_i += b * LOOP_CTL_I; w += o; src += o; state += b * SEL_STATE_WORDS; c_less += ob; c_eq += ob; sel_key += ok; sel_idx += ok;
+    }
     const int mode = ctl_i[LOOP_I_MODE];
     const int64_t n = ctl_i[LOOP_I_N];
     const int blk = blockIdx.x, t = threadIdx.x;
@@ -615,9 +630,13 @@ MD bool pair_less(uint64_t ka, int32_t ia, uint64_t kb, int32_t ib) { return ka 
 
 __global__ __launch_bounds__(1024) void k_loop_sort_chunks(const int32_t* __restrict__ ctl_i, const uint64_t* __restrict__ key_in,
                                                           const int32_t* __restrict__ idx_in, uint64_t* __restrict__ key_out,
-                                                          int32_t* __restrict__ idx_out) {
+                                                          int32_t* __restrict__ idx_out, int32_t ksel = 0) {
     __shared__ uint64_t s_k[SORT_CHUNK];
     __shared__ int32_t s_i[SORT_CHUNK];
+    if (blockIdx.y) {  // a batch of trajectories: `ksel` pairs in and out each
+        const int64_t b = blockIdx.y, ok = b * ksel;
+        ctl_i += b * LOOP_CTL_I; key_in += ok; idx_in += ok; key_out += ok; idx_out += ok;
+    }
     if (ctl_i[LOOP_I_MODE] != 2) return;
     const int k = ctl_i[LOOP_I_K];
     const int c0 = blockIdx.x * SORT_CHUNK;
@@ -649,7 +668,12 @@ __global__ __launch_bounds__(1024) void k_loop_sort_chunks(const int32_t* __rest
 // ... then every pair finds its rank: its place in its own chunk plus, by binary search, the pairs of every other chunk
 // that precede it (all pairs are distinct).  src[n + rank] = index.
 __global__ __launch_bounds__(256) void k_loop_sort_rank(const int32_t* __restrict__ ctl_i, const uint64_t* __restrict__ key_s,
-                                                        const int32_t* __restrict__ idx_s, int32_t* __restrict__ src) {
+                                                        const int32_t* __restrict__ idx_s, int32_t* __restrict__ src, int32_t cap = 0,
+                                                        int32_t ksel = 0) {
+    if (blockIdx.y) {  // a batch of trajectories: `ksel` sorted pairs and `cap` sources each
+        const int64_t b = blockIdx.y, ok = b * ksel;
+        ctl_i += b * LOOP_CTL_I; key_s += ok; idx_s += ok; src += b * cap;
+    }
     if (ctl_i[LOOP_I_MODE] != 2) return;
     const int k = ctl_i[LOOP_I_K];
     const int64_t n = ctl_i[LOOP_I_N];
@@ -679,6 +703,7 @@ __global__ __launch_bounds__(256) void k_loop_sort_rank(const int32_t* __restric
 // thread in registers, LDS histograms, the k duplicates sorted in LDS - with identical results.
 constexpr int LOOP_SMALL_MAX = 16384, LOOP_SMALL_PAIRS = 8192;
 static_assert(LOOP_SMALL_MAX == MIDAS_LOOP_BATCH_MAX_CAP, "midas_loop_step_batch runs this regime's kernels");
+static_assert((MIDAS_LOOP_BATCH_WIDE_MAX_CAP + SCAN_BLOCK - 1) / SCAN_BLOCK <= LAZY_MAX_BLOCKS, "k_loop_compact stages a trajectory's block counts in LDS");
 
 // exclusive prefix over the 1024 threads of (a, b); totals returned in ta / tb.  s_w: 32 ints of LDS.
 MD void small_scan2(int a, int b, int& ea, int& eb, int& ta, int& tb, int* s_w) {
@@ -1334,16 +1359,18 @@ struct SelectScratch {
     size_t ksel;
 };
 
-static int select_scratch(midas_ctx* ctx, int64_t cap, SelectScratch& ss) {
+// B trajectories: every array (B, ...) contiguous - SEL_HIST_WORDS, SEL_STATE_WORDS, the block counts of a launch over `cap`, ksel pairs
+static int select_scratch(midas_ctx* ctx, int64_t cap, SelectScratch& ss, int32_t B = 1) {
     const unsigned nbcap = (unsigned)ceil_div(cap, SCAN_BLOCK);
+    const size_t Bz = (size_t)B;
     ss.ksel = (size_t)cap / 3 + 1;
     void* p;
     int rc;
-#define SEL_SCRATCH(field, type, count)                                           \
-    if ((rc = midas_scratch(ctx, (size_t)(count) * sizeof(type), &p))) return rc; \
+#define SEL_SCRATCH(field, type, count)                                                \
+    if ((rc = midas_scratch(ctx, Bz * (size_t)(count) * sizeof(type), &p))) return rc; \
     ss.field = (type*)p
-    SEL_SCRATCH(hist, uint32_t, SEL_PASSES * SEL_BINS);
-    SEL_SCRATCH(state, int32_t, 4 * (SEL_PASSES + 2));
+    SEL_SCRATCH(hist, uint32_t, SEL_HIST_WORDS);
+    SEL_SCRATCH(state, int32_t, SEL_STATE_WORDS);
     SEL_SCRATCH(c_less, int32_t, nbcap);
     SEL_SCRATCH(c_eq, int32_t, nbcap);
     SEL_SCRATCH(sel_key, uint64_t, ss.ksel);
@@ -1354,24 +1381,29 @@ static int select_scratch(midas_ctx* ctx, int64_t cap, SelectScratch& ss) {
     return MIDAS_OK;
 }
 
-// ctl_i[N, MODE, K] and the cleared histograms / pass-0 state are in place: select, compact, order the duplicates
-static int launch_select(midas_ctx* ctx, int64_t cap, const int32_t* ci, const double* w, int32_t* src, const SelectScratch& ss) {
+// ctl_i[N, MODE, K] and the cleared histograms / pass-0 state are in place: select, compact, order the duplicates.
+// B trajectories (midas_loop_step_batch_wide): the same ten launches with the trajectory as grid.y - ctl_i (B, 32), w and src (B, cap),
+// the scratch of select_scratch(.., B); the launch boundaries stay the grid-wide syncs between the digit passes, one set for the batch.
+// A trajectory whose MODE is 0 leaves every launch at its head but k_loop_compact, which writes its identity.
+static int launch_select(midas_ctx* ctx, int64_t cap, const int32_t* ci, const double* w, int32_t* src, const SelectScratch& ss,
+                         int32_t B = 1) {
     hipStream_t st = ctx->stream;
-    const unsigned nbcap = (unsigned)ceil_div(cap, SCAN_BLOCK);
-    hipLaunchKernelGGL(k_loop_select<0>, dim3(nbcap), dim3(256), 0, st, ci, w, ss.hist, ss.state);
-    hipLaunchKernelGGL(k_loop_select<1>, dim3(nbcap), dim3(256), 0, st, ci, w, ss.hist, ss.state);
-    hipLaunchKernelGGL(k_loop_select<2>, dim3(nbcap), dim3(256), 0, st, ci, w, ss.hist, ss.state);
-    hipLaunchKernelGGL(k_loop_select<3>, dim3(nbcap), dim3(256), 0, st, ci, w, ss.hist, ss.state);
-    hipLaunchKernelGGL(k_loop_select<4>, dim3(nbcap), dim3(256), 0, st, ci, w, ss.hist, ss.state);
-    hipLaunchKernelGGL(k_loop_select<5>, dim3(nbcap), dim3(256), 0, st, ci, w, ss.hist, ss.state);
-    hipLaunchKernelGGL(k_loop_compact_count, dim3(nbcap), dim3(256), 0, st, ci, w, (const uint32_t*)ss.hist, ss.state, ss.c_less,
-                       ss.c_eq);
-    hipLaunchKernelGGL(k_loop_compact, dim3(nbcap), dim3(256), 0, st, ci, w, (const int32_t*)ss.state, (const int32_t*)ss.c_less,
-                       (const int32_t*)ss.c_eq, src, ss.sel_key, ss.sel_idx);
-    hipLaunchKernelGGL(k_loop_sort_chunks, dim3((unsigned)ceil_div((int64_t)ss.ksel, SORT_CHUNK)), dim3(1024), 0, st, ci,
-                       (const uint64_t*)ss.sel_key, (const int32_t*)ss.sel_idx, ss.srt_key, ss.srt_idx);
-    hipLaunchKernelGGL(k_loop_sort_rank, dim3((unsigned)ceil_div((int64_t)ss.ksel, 256)), dim3(256), 0, st, ci,
-                       (const uint64_t*)ss.srt_key, (const int32_t*)ss.srt_idx, src);
+    const unsigned nbcap = (unsigned)ceil_div(cap, SCAN_BLOCK), by = (unsigned)B;
+    const int32_t slice = B > 1 ? (int32_t)cap : 0, ksel = (int32_t)ss.ksel;  // (read by trajectories behind the first only)
+    hipLaunchKernelGGL(k_loop_select<0>, dim3(nbcap, by), dim3(256), 0, st, ci, w, ss.hist, ss.state, slice);
+    hipLaunchKernelGGL(k_loop_select<1>, dim3(nbcap, by), dim3(256), 0, st, ci, w, ss.hist, ss.state, slice);
+    hipLaunchKernelGGL(k_loop_select<2>, dim3(nbcap, by), dim3(256), 0, st, ci, w, ss.hist, ss.state, slice);
+    hipLaunchKernelGGL(k_loop_select<3>, dim3(nbcap, by), dim3(256), 0, st, ci, w, ss.hist, ss.state, slice);
+    hipLaunchKernelGGL(k_loop_select<4>, dim3(nbcap, by), dim3(256), 0, st, ci, w, ss.hist, ss.state, slice);
+    hipLaunchKernelGGL(k_loop_select<5>, dim3(nbcap, by), dim3(256), 0, st, ci, w, ss.hist, ss.state, slice);
+    hipLaunchKernelGGL(k_loop_compact_count, dim3(nbcap, by), dim3(256), 0, st, ci, w, (const uint32_t*)ss.hist, ss.state, ss.c_less,
+                       ss.c_eq, slice);
+    hipLaunchKernelGGL(k_loop_compact, dim3(nbcap, by), dim3(256), 0, st, ci, w, (const int32_t*)ss.state, (const int32_t*)ss.c_less,
+                       (const int32_t*)ss.c_eq, src, ss.sel_key, ss.sel_idx, slice, ksel);
+    hipLaunchKernelGGL(k_loop_sort_chunks, dim3((unsigned)ceil_div((int64_t)ss.ksel, SORT_CHUNK), by), dim3(1024), 0, st, ci,
+                       (const uint64_t*)ss.sel_key, (const int32_t*)ss.sel_idx, ss.srt_key, ss.srt_idx, ksel);
+    hipLaunchKernelGGL(k_loop_sort_rank, dim3((unsigned)ceil_div((int64_t)ss.ksel, 256), by), dim3(256), 0, st, ci,
+                       (const uint64_t*)ss.srt_key, (const int32_t*)ss.srt_idx, src, slice, ksel);
     LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }
@@ -1618,9 +1650,13 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 // (the decision by k_loop_decide per trajectory and launch_topk_aten's B walks in place of k_loop_anneal_small).  One path each: the
 // single call's `anneal_small` field and its MIDAS_LOOP_MERGE / MIDAS_FRONT_SMALL switches (which pick between bit-identical
 // paths there) are not consulted - k_front_small, the merged weights launch and k_loop_anneal_small always run.
+// wide (midas_loop_step_batch_wide, cap <= MIDAS_LOOP_BATCH_WIDE_MAX_CAP, device draws and ties by index): a capacity beyond
+// LOOP_SMALL_MAX takes k_front_small over as many waves as it has, and - one trajectory's keys no longer fit one workgroup - the
+// single call's decision and radix selection with the trajectory as grid.y (launch_select).  Up to LOOP_SMALL_MAX the launches above.
 int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
-                           const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride) {
+                           const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride, bool wide) {
     const int64_t cap = s.cap;
+    const bool large = wide && cap > LOOP_SMALL_MAX;
     LoopGrid g;
     g.cap = cap; g.B = B; g.slice = (int32_t)cap; g.log_stride = log_stride;
     g.lp_stride = (int32_t)(cap + SCAN_CHUNK);  // (the resample reads whole chunks)
@@ -1633,7 +1669,7 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
         fill_particle_update(pa, s, t6, t3, cap, s.poses_dev, s.hint_dev, s.valid_dev, s.score_stamps_dev,
                              (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
         pa.n_live = s.ctl_i_dev + LOOP_I_N;
-        if ((rc = launch_front_small_batch(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, B))) return rc;
+        if ((rc = launch_front_small_batch(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, B, large))) return rc;
         weights_merged = loop_weights_mergeable(phases);
         if ((rc = loop_weights_phase(ctx, s, g, cb->K, pa.gt16 != nullptr, weights_merged, wa))) return rc;
     }
@@ -1657,6 +1693,12 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
                                (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, (uint32_t*)nullptr, (int32_t*)nullptr, s.floor,
                                (const double*)m.rot, 0, 1);
             if ((rc = launch_topk_aten(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, nullptr, B))) return rc;
+        } else if (large) {  // every trajectory's decision clears its own histograms and state, then the selection's launches once
+            SelectScratch ss;
+            if ((rc = select_scratch(ctx, cap, ss, B))) return rc;
+            hipLaunchKernelGGL(k_loop_decide, dim3(2, g.by()), dim3(256), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen, (const float*)m.sd,
+                               (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, ss.hist, ss.state, s.floor, (const double*)m.rot);
+            if ((rc = launch_select(ctx, cap, s.ctl_i_dev, s.weights_dev, s.src_dev, ss, B))) return rc;
         } else {
             hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, g.by()), dim3(1024), 0, st, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
                                (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, s.floor,

@@ -381,9 +381,10 @@ int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t
                        const midas_codebook* cb, const double* code, double* scores, bool* launched);
 int launch_particle_update(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a);
 // the loop step's small-set front (k_front_small) for B trajectories with their live counts (midas_loop_step_batch): a.N = the
-// capacity, a.n_live = trajectory 0's count, LOOP_CTL_I entries apart
+// capacity (up to 16 384; wide, midas_loop_step_batch_wide: up to MIDAS_LOOP_BATCH_WIDE_MAX_CAP), a.n_live = trajectory 0's count,
+// LOOP_CTL_I entries apart
 int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a,
-                             const midas_codebook* cb, const double* code, double* scores, int32_t B);
+                             const midas_codebook* cb, const double* code, double* scores, int32_t B, bool wide = false);
 // One launch of a front as launch_frame_front hands it to the units that hold the kernels, and the form of k_frame_front it asks
 // for (the template's LAZY, FW, SCR, PREF, STATS: front_wave.hpp).  A family's launcher launches the form if it is one of its own
 // and says whether it was.
@@ -602,7 +603,8 @@ int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const
 int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                      const midas_loop_args& a, int32_t phases);
 int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
-                           const midas_loop_args& a, int32_t phases, int32_t B, int64_t log_stride);
+                           const midas_loop_args& a, int32_t phases, int32_t B, int64_t log_stride,
+                           bool wide = false);  // midas_loop_step_batch_wide: capacities beyond the small-set regime
 // src[0 .. n_set): the annealed particle set as indices - mode 1: the N particles minus the k of smallest weight, in
 // order; mode 2: all N followed by the k of largest weight, best first; ties to the smaller index
 int launch_anneal_select(midas_ctx* ctx, int64_t N, const double* w, int32_t mode, int64_t k, int32_t ties, int32_t* src, int32_t* info);

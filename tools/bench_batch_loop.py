@@ -12,6 +12,8 @@ One JSON line per engine form with each figure's median over the repeats and [mi
   batch_loop_seeded   BatchLoopEngine.seed_torch_streams (midas_loop_step_batch_draws, the draws sized on the device per trajectory)
   single_loop_seeded  one LoopEngine(topk_ties="aten_cpu").seed_torch_stream on trajectory 0 - B x its frame is what the sweep cost before
   batch_loop          the Philox batch frame (orientation: the seeded batch frame should sit near it plus one seeded single frame)
+--wide: BatchLoopEngine(wide=True) (midas_loop_step_batch_wide: sets beyond 16 384 particles per trajectory, e.g. 16 50000) against B single
+  LoopEngine frames; --floor=N: annealing's floor (default 1000).  The fixed-N form is left out.
 --profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch), no timing."""
 import json
 import os
@@ -28,9 +30,14 @@ from midastouch_amd.loop_engine import LoopEngine
 from midastouch_amd.synthetic import make_codebook, make_trajectory, wide_start
 
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
-profile, seeded = "--profile" in sys.argv, "--seeded" in sys.argv
+profile, seeded, wide = "--profile" in sys.argv, "--seeded" in sys.argv, "--wide" in sys.argv
 B, N0, K, T, R = (int(argv[i]) if len(argv) > i else d for i, d in enumerate((64, 10000, 50000, 300, 3)))
 D, FLOOR, EVERY, SEED = 512, 1000, 50, 4000
+if wide and seeded:
+    sys.exit("bench_batch_loop.py: --wide and --seeded exclude each other (a wide BatchLoopEngine draws from Philox: seed_torch_streams raises on it)")
+for a in sys.argv[1:]:
+    if a.startswith("--floor="):
+        FLOOR = int(a.split("=", 1)[1])
 dev = torch.device("cuda", 0)
 cb = make_codebook(K=K, D=D, seed=1000)
 trajs = [make_trajectory(cb, T=T + 1, seed=2000 + b) for b in range(B)]
@@ -66,7 +73,7 @@ def over_repeats(rows):
 
 
 def run_batch(seeds=None):
-    eng = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, **kw)
+    eng = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, **kw, **({"wide": True} if wide else {}))
     if seeds is not None:
         eng.seed_torch_streams(seeds)
     eng.set_particles(starts)
@@ -108,9 +115,11 @@ if profile:
     torch.cuda.synchronize()
     sys.exit(0)
 
-head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R}
+head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R, **({"wide": True} if wide else {})}
 out = {}
 forms = (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed))
+if wide:
+    forms = forms[:2]
 if seeded:
     forms = (("batch_loop_seeded", run_batch_seeded), ("single_loop_seeded", run_single_seeded), ("batch_loop", run_batch))
 for name, run in forms:
