@@ -973,6 +973,9 @@ typedef struct midas_loop_args {
                                     * ctl_i[NDRAW] - the status of the annealed set's CDF as the resample will compute it (the scan's
                                     * block totals, one more small launch) - for the caller's counted draw; the RESAMPLE call checks its
                                     * own status against the word (ctl_i[ERR] bit 8).  0: neither (Philox frames: the launches as ever) */
+    int32_t dbscan_batched;        /* midas_loop_step_batch, _draws and _wide: 1 = the DBSCAN phase clusters all B trajectories in one
+                                    * set of launches (midas_dbscan_batch's pass; B * cap <= MIDAS_DBSCAN_BATCH_MAX_POINTS, the same
+                                    * labels); 0 = midas_loop_step's pass once per trajectory.  midas_loop_step takes 0 only */
 } midas_loop_args;
 int midas_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                     const midas_loop_args* args, int32_t phases);
@@ -986,7 +989,8 @@ int midas_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* 
  * trajectory 0's row of this frame, trajectory b's lies b * log_stride doubles behind it; host_mirror is NULL or 2 B ints;
  * cb_poses and the scalars are shared.  `phases` as in midas_loop_step; a frame's DBSCAN flag applies to every trajectory.
  * The kernels run with the trajectory as grid.y and every trajectory reads its own live and annealed counts; the DBSCAN phase
- * runs midas_loop_step's pass once per trajectory, one after the other on the stream, on one shared set of cell tables.
+ * runs midas_loop_step's pass once per trajectory, one after the other on the stream, on one shared set of cell tables - or, with
+ * args->dbscan_batched = 1 (B * cap <= MIDAS_DBSCAN_BATCH_MAX_POINTS), midas_dbscan_batch's one pass over all of them: the same labels.
  * Trajectory b draws from the Philox streams keyed (seed + b, step) with slot keys from 0: frame for frame the bits of
  * midas_loop_step on trajectory b alone with seed + b.
  * The small-set regime only - anything else is MIDAS_ERR_INVALID with nothing enqueued: cap <= MIDAS_LOOP_BATCH_MAX_CAP; device
@@ -1025,7 +1029,7 @@ int midas_loop_step_batch_draws(midas_ctx* ctx, const midas_codebook* cb, const 
  * decision and midas_loop_step's radix selection (six digit passes, compaction, the duplicates' sort) run with the trajectory as
  * grid.y on per-trajectory histograms, state, block counts and pair buffers - the decision and the selection's ten launches once for the batch, their boundaries the
  * grid-wide syncs between the passes - and the front is the small-set kernel over ceil(cap / 64) waves a trajectory.  The grids
- * cover the capacity on every frame (no per-frame bound), the B DBSCAN passes follow each other as in midas_loop_step_batch.
+ * cover the capacity on every frame (no per-frame bound), the DBSCAN phase is midas_loop_step_batch's (dbscan_batched included).
  * For cap <= MIDAS_LOOP_BATCH_MAX_CAP the call is midas_loop_step_batch: the same launches, the same bits.
  * Seeded streams and the ATen tie rule at these sizes: not yet (midas_loop_step_batch_draws keeps its bound). */
 #define MIDAS_LOOP_BATCH_WIDE_MAX_CAP 131072
@@ -1039,6 +1043,20 @@ int midas_loop_step_batch_wide(midas_ctx* ctx, const midas_codebook* cb, const m
  * than 128 cells per axis with more than 2^20 points (the hash table of occupied cells holds 2^21 slots): labels undefined}. */
 int midas_dbscan(midas_ctx* ctx, int64_t N, const float* poses_dev, double eps, int64_t min_samples, int32_t* labels_dev,
                  int32_t* ncl_dev);
+/* cluster_particles(method="euclidean") (particle_filter.py:208-217, called from filter/filter.py:182-183 on every 50th frame) for
+ * B particle sets in ONE set of launches: row b of labels_dev holds exactly midas_dbscan's labels of row b alone (sklearn's: clusters
+ * numbered by their first core point, a border point to the smallest adjacent cluster).  poses_dev (B, cap, 16); n_dev NULL (every
+ * row holds cap points) or row b's live count at n_dev[b * n_stride] (clamped to cap; 0 allowed); min_samples < 0 -> n_b / 5 per
+ * row; labels_dev (B, cap), slots beyond n_b not written; info_dev (B, 2) out, row b = {number of clusters, flags} as midas_dbscan's
+ * ncl_dev: 2 = more than max_clusters clusters (max_clusters in 1 .. MIDAS_LOOP_MAX_CLUSTERS - 1; 0 = any number), 32 = non-finite
+ * coordinates / more than 2^21 cells per axis - per row: a bad row never changes another row's labels.
+ * The rows share midas_dbscan's 2^21-slot cell tables: row b owns the slots [b S, (b + 1) S), S = floor(2^21 / B) - a dense grid there
+ * when it has at most 128 cells per axis and S cells in all, else a hash table of its occupied cells (load <= 1/2 since cap <= S / 2:
+ * flag 64 cannot occur).  Hence the bound: MIDAS_ERR_INVALID before any launch for B < 1, B > 65535, cap < 1 and
+ * B * cap > MIDAS_DBSCAN_BATCH_MAX_POINTS. */
+#define MIDAS_DBSCAN_BATCH_MAX_POINTS 1048576
+int midas_dbscan_batch(midas_ctx* ctx, int32_t B, int64_t cap, const int32_t* n_dev, int64_t n_stride, const float* poses_dev, double eps,
+                       int64_t min_samples, int32_t* labels_dev, int32_t* info_dev, int32_t max_clusters);
 /* cluster_particles(method="logmap") (particle_filter.py:218-223): DBSCAN of N points of `dim` (2 .. 6) float64 coordinates
  * (row-major) - the 6-d SE(3) logarithms there -, all pairs, the same predicate and numbering as midas_dbscan (sklearn's
  * labels).  min_samples < 0 -> N / 5.  info_dev: 2 x int32 out {number of clusters, spread steps taken (-1: not settled)}.

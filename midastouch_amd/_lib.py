@@ -202,7 +202,7 @@ class LoopArgs(C.Structure):
         ("unit_weights", C.c_int32), ("telemetry", C.c_void_p),
         ("score_stamps", C.c_void_p), ("score_epoch", C.c_uint32),
         ("host_mirror", C.c_void_p), ("grid_n", C.c_int64), ("anneal_small", C.c_int32), ("topk_ties", C.c_int32),
-        ("anneal_frozen", C.c_int32), ("stream_draws", C.c_int32),
+        ("anneal_frozen", C.c_int32), ("stream_draws", C.c_int32), ("dbscan_batched", C.c_int32),
     ]
 
 
@@ -213,6 +213,7 @@ TOPK_TIES_INDEX, TOPK_TIES_ATEN_CPU = 0, 1  # whom annealing's torch.topk takes 
 LOOP_MAX_CLUSTERS, LOOP_LOG_DOUBLES = 64, 168
 LOOP_BATCH_MAX_CAP = 16384  # MIDAS_LOOP_BATCH_MAX_CAP: particles per trajectory midas_loop_step_batch takes
 LOOP_BATCH_WIDE_MAX_CAP = 131072  # MIDAS_LOOP_BATCH_WIDE_MAX_CAP: particles per trajectory midas_loop_step_batch_wide takes
+DBSCAN_BATCH_MAX_POINTS = 1 << 20  # MIDAS_DBSCAN_BATCH_MAX_POINTS: B * cap of midas_dbscan_batch and of a batch frame's one DBSCAN pass
 (LOOP_I_N, LOOP_I_NSET, LOOP_I_MODE, LOOP_I_K, LOOP_I_INIT, LOOP_I_VARSET, LOOP_I_KEPT, LOOP_I_DRIFT, LOOP_I_STATUS,
  LOOP_I_RAW, LOOP_I_NCL, LOOP_I_NPRES, LOOP_I_FRAME, LOOP_I_NAN, LOOP_I_ERR, LOOP_I_NDRAW) = range(16)
 LOOP_ERR_NDRAW = 256  # ctl_i[ERR] bit 8: the resample's status disagrees with ctl_i[NDRAW]
@@ -290,6 +291,7 @@ SIGNATURES = {
     "midas_loop_step_batch_draws": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64]),
     "midas_loop_step_batch_wide": (C.c_int, [_P, _P, _P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64]),
     "midas_dbscan": (C.c_int, [_P, _I64, _P, _D, _I64, _P, _P]),
+    "midas_dbscan_batch": (C.c_int, [_P, _I32, _I64, _P, _I64, _P, _D, _I64, _P, _P, _I32]),
     "midas_dbscan_points": (C.c_int, [_P, _I64, C.c_int32, _P, _D, _I64, _P, _P]),
     "midas_anneal_select": (C.c_int, [_P, _I64, _P, _I32, _I64, _P]),
     "midas_anneal_select_ties": (C.c_int, [_P, _I64, _P, _I32, _I64, _I32, _P, _P]),

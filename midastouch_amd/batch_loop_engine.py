@@ -8,8 +8,10 @@ Trajectory b draws from the Philox streams keyed (seed + b, frame): frame for fr
 seed + b and stepped with row b of the operands.
 
 The regime is the small set: at most 16 384 particles per trajectory (`_lib.LOOP_BATCH_MAX_CAP`; `wide=True`, below: 131 072), a
-float32 codebook scored sparsely.  Sharding stays with the sharded engine.  DBSCAN frames run the single pass once per
-trajectory, one after the other on the stream, on one shared set of cell tables.
+float32 codebook scored sparsely.  Sharding stays with the sharded engine.  A DBSCAN frame clusters all B trajectories in ONE pass
+(`midas_dbscan_batch`'s launches: every trajectory in its own region of the one set of cell tables, the same labels as its own pass)
+whenever B x capacity <= 2^20 (`_lib.DBSCAN_BATCH_MAX_POINTS`); beyond that - or with `batched_dbscan=False` - it runs the single
+pass once per trajectory, one after the other on the stream.  Plain, seeded and wide engines alike.
 
 Seeded runs: `seed_torch_streams(seeds)` makes trajectory b a process of the reference under `torch.manual_seed(seeds[b])` - its
 motion noise and its resampler's uniforms come from a device replica of torch's CPU generator (torch_rng.TorchCpuStreams), sized by
@@ -41,11 +43,17 @@ from .loop_engine import ALL_PHASES, log_records
 class BatchLoopEngine:
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, batch: int, num_particles: int, *, sig_t=2e-4, sig_r=0.5,
                  pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2,
-                 cluster: bool = True, cluster_every: int = 50, log_frames: int = 4096, device=None, wide: bool = False):
+                 cluster: bool = True, cluster_every: int = 50, log_frames: int = 4096, device=None, wide: bool = False,
+                 batched_dbscan=None):
         self.B, self.cap = B, cap = int(batch), int(num_particles)
         self.wide = bool(wide)
         if B < 1 or B > 65535:
             raise MidasError("BatchLoopEngine holds 1 .. 65535 trajectories")
+        # one DBSCAN pass for the batch (None: whenever its cell tables hold the batch) or one per trajectory
+        if batched_dbscan and B * cap > _lib.DBSCAN_BATCH_MAX_POINTS:
+            raise MidasError(f"batched_dbscan=True holds at most DBSCAN_BATCH_MAX_POINTS = {_lib.DBSCAN_BATCH_MAX_POINTS} particles in all, "
+                             f"not {B} x {cap} (None or False: one pass per trajectory there)")
+        self.batched_dbscan = B * cap <= _lib.DBSCAN_BATCH_MAX_POINTS if batched_dbscan is None else bool(batched_dbscan)
         if self.wide:
             if cap < 1 or cap > _lib.LOOP_BATCH_WIDE_MAX_CAP:
                 raise MidasError(f"a wide BatchLoopEngine holds 1 .. {_lib.LOOP_BATCH_WIDE_MAX_CAP} particles per trajectory (larger sets: LoopEngine)")
@@ -96,14 +104,16 @@ class BatchLoopEngine:
         a.floor, a.eps = self.floor, self.eps
         a.telemetry, a.score_stamps = _ptr(self.telemetry), _ptr(self._stamps)
         a.topk_ties = _lib.TOPK_TIES_INDEX
+        a.dbscan_batched = int(self.batched_dbscan)
         self._topk_ties = "index"
         self.torch_streams = None  # seed_torch_streams
         # The scratch every phase combination of a batch frame asks for, reserved now so that no frame allocates: per trajectory the
         # hand-over records of the front (32 B a particle), the block results, the cluster-moment partials (64 x 36 doubles per 256
         # particles) and cluster rows, the resample's prefix values, a wide engine's select state; once, DBSCAN's cell tables (84 MB +
-        # 41 B a particle).
+        # 41 B a particle) - the batched pass: the same tables, 41 B for every particle of the batch, and per trajectory its record, root
+        # list and bounds partials.
         per_traj = self._per_traj()
-        self._scratch = (128 << 20) + 256 * cap + B * per_traj + 64 * 256
+        self._scratch = (128 << 20) + 256 * cap + B * per_traj + (64 + 32 * self.batched_dbscan) * 256
         self.ctx.call("midas_scratch_reserve", self._scratch)
 
     # whom annealing's torch.topk takes inside a tie: "index" (torch's CUDA rule, the radix select: midas_loop_step_batch as ever) or
@@ -131,6 +141,10 @@ class BatchLoopEngine:
             # the radix selection per trajectory (loop.hip select_scratch): 6 x 2048 histogram words, 32 state words, two block counts
             # a summation block, and cap / 3 + 1 (key, index) pairs twice - selected, then sorted
             frame += 4 * 6 * 2048 + 4 * 32 + 2 * 4 * nb + 2 * (8 + 4) * (cap // 3 + 1)
+        if self.batched_dbscan:
+            # dbscan.hip launch_dbscan_batch: cell, sorted position, point, core flag, parent, worklist, cell list and rank per particle;
+            # a record (96 B), 64 roots and up to 64 x 6 bounds partials per trajectory
+            frame += 41 * cap + 96 + 4 * 64 + 24 * min(nb256, 64)
         return frame
 
     # ---- state ----------------------------------------------------------------------------------------------------

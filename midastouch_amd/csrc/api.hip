@@ -565,6 +565,16 @@ MIDAS_EXPORT int midas_dbscan(midas_ctx* ctx, int64_t N, const float* poses_dev,
     return launch_dbscan(ctx, N, nullptr, poses_dev, eps, min_samples, labels_dev, ncl_dev, ncl_dev + 1, 0);
 }
 
+MIDAS_EXPORT int midas_dbscan_batch(midas_ctx* ctx, int32_t B, int64_t cap, const int32_t* n_dev, int64_t n_stride, const float* poses_dev,
+                                    double eps, int64_t min_samples, int32_t* labels_dev, int32_t* info_dev, int32_t max_clusters) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, B >= 1 && B <= 65535 && cap >= 1 && (int64_t)B * cap <= MIDAS_DBSCAN_BATCH_MAX_POINTS);
+    MIDAS_REQUIRE(ctx, poses_dev && labels_dev && info_dev && eps > 0.0 && (n_dev == nullptr || n_stride >= 1));
+    MIDAS_REQUIRE(ctx, max_clusters >= 0 && max_clusters < MIDAS_LOOP_MAX_CLUSTERS);
+    MIDAS_HIP_CHECK(ctx, hipMemsetAsync(info_dev, 0, (size_t)B * 2 * sizeof(int32_t), ctx->stream));
+    return launch_dbscan_batch(ctx, B, cap, n_dev, n_stride, poses_dev, eps, min_samples, labels_dev, info_dev, info_dev + 1, 2, max_clusters);
+}
+
 MIDAS_EXPORT int midas_dbscan_points(midas_ctx* ctx, int64_t N, int32_t dim, const double* points_dev, double eps, int64_t min_samples,
                                      int32_t* labels_dev, int32_t* info_dev) {
     MIDAS_ENTER(ctx);

@@ -51,6 +51,9 @@ static int loop_args_check(midas_ctx* ctx, const midas_codebook* cb, const midas
         }
     }
     if (phases & MIDAS_LOOP_DBSCAN) MIDAS_REQUIRE(ctx, s.eps > 0.0);
+    // one DBSCAN pass for the batch: the batch entries only, within the cell tables' bound (a call without the phase does not look)
+    MIDAS_REQUIRE(ctx, s.dbscan_batched == 0 || s.dbscan_batched == 1);
+    if (s.dbscan_batched) MIDAS_REQUIRE(ctx, batch && (int64_t)B * s.cap <= MIDAS_DBSCAN_BATCH_MAX_POINTS);
     if (phases & MIDAS_LOOP_RESAMPLE)
         MIDAS_REQUIRE(ctx, s.resample_mode == MIDAS_RESAMPLE_MULTINOMIAL || s.resample_mode == MIDAS_RESAMPLE_SYSTEMATIC);
     return MIDAS_OK;

@@ -23,6 +23,15 @@
 //     extent limit short of 2^21 cells per axis; round 3 fell back to the host's sklearn there;
 //   * any number of clusters: up to 62 are ranked in LDS, more by a prefix sum over the root flags (midas_dbscan; the loop
 //     step keeps its 62-cluster arrays - min_samples = N / 5 allows about five).
+//   * B clouds in one set of launches (midas_dbscan_batch, the batch loop engines' DBSCAN frame; filter/filter.py:182-183 for B
+//     trajectories): the same kernels' bodies on another layout.  Row b owns the slots [b S, (b + 1) S), S = floor(2^21 / B), of the
+//     one set of cell tables - a dense grid there (at most 128 cells per axis and S in all) or a hash table of its occupied cells
+//     inside the region (range reduction of the mixed key to S, probing wraps within it; B cap <= 2^20 keeps the load at or below
+//     one half).  Every row has its own record (DbRow); particles are numbered b cap + i, the sorted order is one array over all
+//     rows (row b from the exclusive prefix of the live counts on), the worklist and the core-cell list are shared.  Kernels over
+//     particles, and the per-row scans and ranking, run with the row as grid.y; kernels over sorted positions run over
+//     [0, sum n_b) and find their row through the cell id (c / S).  The bodies are templates over the argument record (DbArgs /
+//     DbBatchArgs): the single form's kernels are the instantiations they always were.
 // Predicate (sklearn's KD-tree on float64 copies): ((dx*dx) + dy*dy) + dz*dz <= eps*eps, accumulated in that order.
 // Pinned by fixture G9 (labels written by the reference's own cluster_particles) through the oracle's O(N^2) restatement.
 #include <cmath>
@@ -91,13 +100,62 @@ __device__ __forceinline__ int64_t db_n(const DbArgs& a) {
     return n < a.N ? n : a.N;
 }
 
-__global__ __launch_bounds__(256) void k_db_bounds(DbArgs a) {
+// ---- the batched form's layout (midas_dbscan_batch) ----------------------------------------------------------------------
+struct DbRow : DbGrid {  // one per row, written by k_dbb_setup; ncells: the slots of its region it uses (dense: dx dy dz, hashed: S)
+    int32_t base;        // first slot of the row's region of the cell tables
+    int32_t S;           // slots of a region
+    int32_t off;         // exclusive prefix of the live counts: the row's first sorted position
+    int32_t row;
+};
+struct DbBatchArgs : DbArgs {  // N: capacity of a row; the arrays by particle hold B N entries, particle (b, i) at b N + i; `grid`: the
+                               // record of the whole batch (n = sum of the live counts, nwork, ncore_cells)
+    DbRow* rows;               // [B]
+    int32_t B, S;
+    int64_t n_stride;          // row b's live count: n_dev[b n_stride]
+    int64_t out_stride;        // row b's results: ncl_out[b out_stride], err_out[b out_stride]
+};
+// What the shared bodies ask the argument record: the single form answers with constants (its code is what it was).
+// row of a launch that has the row as grid.y
+__device__ __forceinline__ constexpr int64_t db_yrow(const DbArgs&) { return 0; }
+__device__ __forceinline__ int64_t db_yrow(const DbBatchArgs&) { return (int64_t)blockIdx.y; }
+__device__ __forceinline__ const DbGrid& db_ygrid(const DbArgs& a) { return *a.grid; }
+__device__ __forceinline__ const DbRow& db_ygrid(const DbBatchArgs& a) { return a.rows[blockIdx.y]; }
+__device__ __forceinline__ constexpr int64_t db_particle(const DbArgs&, int64_t i) { return i; }  // index of the y-row's particle i
+__device__ __forceinline__ int64_t db_particle(const DbBatchArgs& a, int64_t i) { return (int64_t)blockIdx.y * a.N + i; }
+__device__ __forceinline__ constexpr int64_t db_out_stride(const DbArgs&) { return 0; }
+__device__ __forceinline__ int64_t db_out_stride(const DbBatchArgs& a) { return a.out_stride; }
+__device__ __forceinline__ int64_t db_n(const DbBatchArgs& a) {
+    if (!a.n_dev) return a.N;
+    const int64_t n = a.n_dev[(int64_t)blockIdx.y * a.n_stride];
+    return n < 0 ? 0 : (n < a.N ? n : a.N);
+}
+// first slot and first sorted position of a row
+__device__ __forceinline__ constexpr int db_base(const DbGrid&) { return 0; }
+__device__ __forceinline__ int db_base(const DbRow& g) { return g.base; }
+__device__ __forceinline__ constexpr int db_off(const DbGrid&) { return 0; }
+__device__ __forceinline__ int db_off(const DbRow& g) { return g.off; }
+// the record of the row that owns cell c (gl: the launch's own copy of *a.grid); _wave: c is the same in every lane
+__device__ __forceinline__ const DbGrid& db_row_of(const DbArgs&, const DbGrid& gl, int) { return gl; }
+__device__ __forceinline__ DbRow db_row_of(const DbBatchArgs& a, const DbGrid&, int c) { return a.rows[(unsigned)c / (unsigned)a.S]; }
+__device__ __forceinline__ const DbGrid& db_row_of_wave(const DbArgs&, const DbGrid& gl, int) { return gl; }
+__device__ __forceinline__ DbRow db_row_of_wave(const DbBatchArgs& a, const DbGrid&, int c) {
+    return a.rows[(unsigned)__builtin_amdgcn_readfirstlane(c) / (unsigned)a.S];
+}
+// the record and the root list of the row that owns particle `orig`
+__device__ __forceinline__ DbGrid* db_row_of_particle(const DbArgs& a, int32_t) { return a.grid; }
+__device__ __forceinline__ DbGrid* db_row_of_particle(const DbBatchArgs& a, int32_t orig) { return &a.rows[orig / (int32_t)a.N]; }
+__device__ __forceinline__ int32_t* db_roots_of_particle(const DbArgs& a, int32_t) { return a.roots; }
+__device__ __forceinline__ int32_t* db_roots_of_particle(const DbBatchArgs& a, int32_t orig) { return a.roots + (size_t)(orig / (int32_t)a.N) * (DB_MAXROOTS + 1); }
+
+// (the kernels below are shared by the two forms: k_db_x<DbArgs> and k_db_x<DbBatchArgs>)
+template <class A>
+__global__ __launch_bounds__(256) void k_db_bounds(A a) {
     __shared__ float s[6][4];
     const int64_t n = db_n(a);
     const int t = threadIdx.x;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
-        const float* P = a.poses + i * 16;
+        const float* P = a.poses + db_particle(a, i) * 16;
         const float c[3] = {P[3], P[7], P[11]};
 #pragma unroll
         for (int d = 0; d < 3; ++d) { lo[d] = c[d] < lo[d] ? c[d] : lo[d]; hi[d] = c[d] > hi[d] ? c[d] : hi[d]; }
@@ -116,26 +174,23 @@ __global__ __launch_bounds__(256) void k_db_bounds(DbArgs a) {
     if (t < 6) {
         float v = s[t][0];
         for (int w = 1; w < 4; ++w) v = t < 3 ? (s[t][w] < v ? s[t][w] : v) : (s[t][w] > v ? s[t][w] : v);
-        a.part[blockIdx.x * 6 + t] = v;
+        a.part[(db_yrow(a) * gridDim.x + blockIdx.x) * 6 + t] = v;
     }
 }
 
-__global__ __launch_bounds__(64) void k_db_setup(DbArgs a, int nblocks) {
-    if (threadIdx.x != 0) return;
-    const int64_t n = db_n(a);
+// the cloud's extent from the bounds partials -> origin, cell side and cells per axis; hashed: some axis has more than DB_MAXDIM cells
+__device__ __forceinline__ void db_setup_dims(const float* part, int nblocks, int64_t n, double eps, DbGrid& g, int* dims, int& err, int& hashed) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int b = 0; b < nblocks; ++b)
         for (int d = 0; d < 3; ++d) {
-            const float x = a.part[b * 6 + d], y = a.part[b * 6 + 3 + d];
+            const float x = part[b * 6 + d], y = part[b * 6 + 3 + d];
             lo[d] = x < lo[d] ? x : lo[d];
             hi[d] = y > hi[d] ? y : hi[d];
         }
-    DbGrid g;
-    g.h = a.eps * DB_CELL;
+    g.h = eps * DB_CELL;
     g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2];
-    int dims[3];
-    int err = 0;
-    int hashed = 0;
+    err = 0;
+    hashed = 0;
     for (int d = 0; d < 3; ++d) {
         const double ext = (double)hi[d] - (double)lo[d];
         double c = n > 0 ? floor(ext / g.h) + 1.0 : 1.0;
@@ -144,6 +199,15 @@ __global__ __launch_bounds__(64) void k_db_setup(DbArgs a, int nblocks) {
         if (c > (double)(1 << DB_HASH_BITS)) { c = (double)(1 << DB_HASH_BITS); err |= 1; }  // (6 km at eps = 1e-2, or infinite coordinates)
         dims[d] = (int)c;
     }
+}
+
+__global__ __launch_bounds__(64) void k_db_setup(DbArgs a, int nblocks) {
+    if (threadIdx.x != 0) return;
+    const int64_t n = db_n(a);
+    DbGrid g;
+    int dims[3];
+    int err, hashed;
+    db_setup_dims(a.part, nblocks, n, a.eps, g, dims, err, hashed);
     if (hashed && n > DB_MAXCELLS / 2) { hashed = 0; err |= 2; }  // the table is sized for a load of one half (err 2: a wide cloud of more than 2^20 points)
     if (!hashed)
         for (int d = 0; d < 3; ++d)
@@ -158,6 +222,45 @@ __global__ __launch_bounds__(64) void k_db_setup(DbArgs a, int nblocks) {
     g.nwork = 0;
     g.ncore_cells = 0;
     *a.grid = g;
+}
+
+// Batched: one wave per row.  The lanes add up the live counts of the rows before it (its first sorted position); lane 0 writes the
+// row's record - dense when the cloud has at most DB_MAXDIM cells per axis and no more cells than the region has slots, hashed
+// otherwise (never beyond a load of one half: 2 N <= S) - and the last row's the record of the whole batch.
+__global__ __launch_bounds__(64) void k_dbb_setup(DbBatchArgs a, int nblocks) {
+    const int b = blockIdx.y;
+    const int64_t n = db_n(a);
+    int64_t before = 0;
+    for (int r = threadIdx.x; r < b; r += 64) {
+        int64_t m = a.N;
+        if (a.n_dev) { m = a.n_dev[(int64_t)r * a.n_stride]; m = m < 0 ? 0 : (m < a.N ? m : a.N); }
+        before += m;
+    }
+    int off = (int)before;  // (B N <= 2^20)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o);
+    if (threadIdx.x != 0) return;
+    DbRow g;
+    int dims[3];
+    int err, hashed;
+    db_setup_dims(a.part + (size_t)b * nblocks * 6, nblocks, n, a.eps, g, dims, err, hashed);
+    if (!hashed && (int64_t)dims[0] * dims[1] * dims[2] > (int64_t)a.S) hashed = 1;
+    g.dx = dims[0]; g.dy = dims[1]; g.dz = dims[2];
+    g.ncells = hashed ? a.S : g.dx * g.dy * g.dz;
+    g.hashed = hashed;
+    g.n = (int32_t)n;
+    g.ms = a.min_samples < 0 ? (int32_t)(n / 5) : (int32_t)a.min_samples;
+    g.nroots = 0;
+    g.err = err;
+    g.nwork = 0;
+    g.ncore_cells = 0;
+    g.base = b * a.S; g.S = a.S; g.off = off; g.row = b;
+    a.rows[b] = g;
+    if (b == a.B - 1) {
+        DbGrid all = g;  // (only n and the two list counters are read)
+        all.n = off + (int32_t)n;
+        *a.grid = all;
+    }
 }
 
 // float32 <-> uint32 keys whose unsigned order is the floats' order (atomicMin / atomicMax on bounds)
@@ -204,13 +307,22 @@ __device__ __forceinline__ void db_cell_coords(const DbGrid& g, float x, float y
 __device__ __forceinline__ unsigned long long db_key64(int cx, int cy, int cz) {
     return (unsigned long long)cx | ((unsigned long long)cy << DB_HASH_BITS) | ((unsigned long long)cz << (2 * DB_HASH_BITS));
 }
-__device__ __forceinline__ unsigned db_hash(unsigned long long k) {
+__device__ __forceinline__ unsigned long long db_mix(unsigned long long k) {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k & (unsigned)(DB_MAXCELLS - 1);
+    return k;
 }
+// the slot a key probes first and the slot probed after s: over the whole table, or (batched) inside the row's region - the upper
+// half of the mixed key times S, shifted down (S is no power of two in general), and probing wraps at the region's end
+__device__ __forceinline__ unsigned db_slot_first(const DbGrid&, unsigned long long key) { return (unsigned)db_mix(key) & (unsigned)(DB_MAXCELLS - 1); }
+__device__ __forceinline__ unsigned db_slot_next(const DbGrid&, unsigned s) { return (s + 1) & (unsigned)(DB_MAXCELLS - 1); }
+__device__ __forceinline__ unsigned db_slot_first(const DbRow& g, unsigned long long key) {
+    return (unsigned)g.base + (unsigned)(((db_mix(key) >> 32) * (unsigned long long)(unsigned)g.S) >> 32);
+}
+__device__ __forceinline__ unsigned db_slot_next(const DbRow& g, unsigned s) { return s + 1 == (unsigned)(g.base + g.S) ? (unsigned)g.base : s + 1; }
 // slot of the cell with this key, inserted if absent (k_db_count only)
-__device__ __forceinline__ int db_hash_insert(unsigned long long* hkeys, unsigned long long key) {
-    unsigned s = db_hash(key);
+template <class G>
+__device__ __forceinline__ int db_hash_insert(const G& g, unsigned long long* hkeys, unsigned long long key) {
+    unsigned s = db_slot_first(g, key);
     while (true) {
         const unsigned long long cur = __hip_atomic_load(&hkeys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (cur == key) return (int)s;
@@ -218,17 +330,18 @@ __device__ __forceinline__ int db_hash_insert(unsigned long long* hkeys, unsigne
             const unsigned long long old = atomicCAS(&hkeys[s], DB_EMPTY, key);
             if (old == DB_EMPTY || old == key) return (int)s;
         }
-        s = (s + 1) & (unsigned)(DB_MAXCELLS - 1);
+        s = db_slot_next(g, s);
     }
 }
 // slot of the cell with this key or -1 (after k_db_count: the table is read-only)
-__device__ __forceinline__ int db_hash_find(const unsigned long long* hkeys, unsigned long long key) {
-    unsigned s = db_hash(key);
+template <class G>
+__device__ __forceinline__ int db_hash_find(const G& g, const unsigned long long* hkeys, unsigned long long key) {
+    unsigned s = db_slot_first(g, key);
     while (true) {
         const unsigned long long cur = hkeys[s];
         if (cur == key) return (int)s;
         if (cur == DB_EMPTY) return -1;
-        s = (s + 1) & (unsigned)(DB_MAXCELLS - 1);
+        s = db_slot_next(g, s);
     }
 }
 
@@ -277,36 +390,48 @@ __global__ __launch_bounds__(256) void k_db_hclear(DbArgs a) {
     if (!a.grid->hashed) return;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < DB_MAXCELLS; i += (int64_t)gridDim.x * 256) a.hkeys[i] = DB_EMPTY;
 }
+// batched: the regions of the hashed rows only
+__global__ __launch_bounds__(256) void k_dbb_hclear(DbBatchArgs a) {
+    const DbRow* g = &a.rows[blockIdx.y];
+    if (!g->hashed) return;
+    const int base = g->base;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.S; i += gridDim.x * 256) a.hkeys[base + i] = DB_EMPTY;
+}
 
-__global__ __launch_bounds__(256) void k_db_count(DbArgs a) {
-    const DbGrid g = *a.grid;
+template <class A>
+__global__ __launch_bounds__(256) void k_db_count(A a) {
+    const auto g = db_ygrid(a);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool in = i < g.n;
     int c = 0;
     if (in) {
-        const float* P = a.poses + i * 16;
+        const float* P = a.poses + db_particle(a, i) * 16;
         int cx, cy, cz;
         db_cell_coords(g, P[3], P[7], P[11], cx, cy, cz);
-        c = g.hashed ? db_hash_insert(a.hkeys, db_key64(cx, cy, cz)) : (cz * g.dy + cy) * g.dx + cx;
-        a.cid[i] = c;
+        c = g.hashed ? db_hash_insert(g, a.hkeys, db_key64(cx, cy, cz)) : db_base(g) + (cz * g.dy + cy) * g.dx + cx;
+        a.cid[db_particle(a, i)] = c;
     }
     (void)db_cell_fetch_inc(a.cell_count, c, in);
 }
 
-// exclusive scan of the cell populations (one workgroup); the counters become the scatter cursors
-__global__ __launch_bounds__(1024) void k_db_scan(DbArgs a) {
+// exclusive scan of the cell populations (one workgroup); the counters become the scatter cursors.  Batched: one workgroup per
+// row over the slots the row uses (a dense row's dx dy dz, a hashed row's region), from the row's first sorted position on; the
+// closing entry behind its last used slot is the next row's first where the region is full (both store the same value)
+template <class A>
+__global__ __launch_bounds__(1024) void k_db_scan(A a) {
     __shared__ int s_w[16];
     __shared__ int s_carry;
-    const DbGrid g = *a.grid;
+    const auto g = db_ygrid(a);
     const int t = threadIdx.x;
-    if (t == 0) s_carry = 0;
+    const int c0 = db_base(g);
+    if (t == 0) s_carry = db_off(g);
     __syncthreads();
     for (int base = 0; base < g.ncells; base += 1024 * 8) {
         int v[8], mine = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int c = base + t * 8 + j;
-            v[j] = c < g.ncells ? a.cell_count[c] : 0;
+            v[j] = c < g.ncells ? a.cell_count[c0 + c] : 0;
             mine += v[j];
         }
         int incl = mine;
@@ -322,8 +447,8 @@ __global__ __launch_bounds__(1024) void k_db_scan(DbArgs a) {
         int run = before;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int c = base + t * 8 + j;
-            if (c < g.ncells) {
+            const int c = c0 + base + t * 8 + j;
+            if (c - c0 < g.ncells) {
                 a.cell_start[c] = run; a.cell_count[c] = run; a.cell_rep[c] = 0x7fffffff; a.cell_num[c] = -1;
 #pragma unroll
                 for (int d = 0; d < 3; ++d) { a.cell_box[(size_t)d * DB_MAXCELLS + c] = 0xFFFFFFFFu; a.cell_box[(size_t)(3 + d) * DB_MAXCELLS + c] = 0u; }
@@ -334,20 +459,21 @@ __global__ __launch_bounds__(1024) void k_db_scan(DbArgs a) {
         if (t == 1023) s_carry = run;
         __syncthreads();
     }
-    if (t == 0) a.cell_start[g.ncells] = s_carry;
+    if (t == 0) a.cell_start[c0 + g.ncells] = s_carry;
 }
 
-__global__ __launch_bounds__(256) void k_db_scatter(DbArgs a) {
-    const DbGrid g = *a.grid;
+template <class A>
+__global__ __launch_bounds__(256) void k_db_scatter(A a) {
+    const auto g = db_ygrid(a);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool in = i < g.n;
-    const int c = in ? a.cid[i] : 0;
+    const int c = in ? a.cid[db_particle(a, i)] : 0;
     const int p = db_cell_fetch_inc(a.cell_count, c, in);
     float x = 0.f, y = 0.f, z = 0.f;
     if (in) {
-        const float* P = a.poses + i * 16;
+        const float* P = a.poses + db_particle(a, i) * 16;
         x = P[3]; y = P[7]; z = P[11];
-        a.s_orig[p] = (int32_t)i;
+        a.s_orig[p] = (int32_t)db_particle(a, i);
         a.s_pt[p] = make_float4(x, y, z, __int_as_float(c));
     }
     // tight bounds of the cell's points: the lanes of a wave that share a cell reduce first (one atomic per cell and bound)
@@ -393,15 +519,17 @@ __device__ __forceinline__ bool db_within(const float4& p, const float4& q, doub
 }
 
 // walks the 5 x 5 x 5 cells around cell c (own cell included when `own`); f(cell) returns true to stop
-template <typename F>
-__device__ __forceinline__ void db_for_cells(const DbGrid& g, const unsigned long long* __restrict__ hkeys, int c, bool own, F f) {
+// (cell indices are slots of the tables: a dense row's local index sits behind its region's base)
+template <class G, typename F>
+__device__ __forceinline__ void db_for_cells(const G& g, const unsigned long long* __restrict__ hkeys, int c, bool own, F f) {
     int cx, cy, cz;
     if (g.hashed) {
         const unsigned long long k = hkeys[c];
         const unsigned m = (1u << DB_HASH_BITS) - 1u;
         cx = (int)((unsigned)k & m); cy = (int)((unsigned)(k >> DB_HASH_BITS) & m); cz = (int)((unsigned)(k >> (2 * DB_HASH_BITS)) & m);
     } else {
-        cx = c % g.dx; cy = (c / g.dx) % g.dy; cz = c / (g.dx * g.dy);
+        const int cl = c - db_base(g);
+        cx = cl % g.dx; cy = (cl / g.dx) % g.dy; cz = cl / (g.dx * g.dy);
     }
     for (int z = cz - 2 < 0 ? 0 : cz - 2; z <= (cz + 2 >= g.dz ? g.dz - 1 : cz + 2); ++z)
         for (int y = cy - 2 < 0 ? 0 : cy - 2; y <= (cy + 2 >= g.dy ? g.dy - 1 : cy + 2); ++y)
@@ -409,9 +537,9 @@ __device__ __forceinline__ void db_for_cells(const DbGrid& g, const unsigned lon
                 int c2;
                 if (g.hashed) {
                     if (x == cx && y == cy && z == cz) c2 = c;
-                    else if ((c2 = db_hash_find(hkeys, db_key64(x, y, z))) < 0) continue;  // nobody lives there
+                    else if ((c2 = db_hash_find(g, hkeys, db_key64(x, y, z))) < 0) continue;  // nobody lives there
                 } else {
-                    c2 = (z * g.dy + y) * g.dx + x;
+                    c2 = db_base(g) + (z * g.dy + y) * g.dx + x;
                 }
                 if (c2 == c && !own) continue;
                 if (f(c2)) return;
@@ -422,38 +550,44 @@ __device__ __forceinline__ void db_for_cells(const DbGrid& g, const unsigned lon
 // kernels that give a point a whole wave used to walk the 125 cells one after the other with every lane doing the same box
 // test - 125 dependent look-ups a point.  nbr = 25 (z + 2) + 5 (y + 2) + (x + 2) offset index; returns the cell or -1 (outside the
 // grid, nobody lives there, or the centre cell itself unless `own`).
-__device__ __forceinline__ void db_cell_xyz(const DbGrid& g, const unsigned long long* __restrict__ hkeys, int c, int& cx, int& cy, int& cz) {
+template <class G>
+__device__ __forceinline__ void db_cell_xyz(const G& g, const unsigned long long* __restrict__ hkeys, int c, int& cx, int& cy, int& cz) {
     if (g.hashed) {
         const unsigned long long k = hkeys[c];
         const unsigned m = (1u << DB_HASH_BITS) - 1u;
         cx = (int)((unsigned)k & m); cy = (int)((unsigned)(k >> DB_HASH_BITS) & m); cz = (int)((unsigned)(k >> (2 * DB_HASH_BITS)) & m);
     } else {
-        cx = c % g.dx; cy = (c / g.dx) % g.dy; cz = c / (g.dx * g.dy);
+        const int cl = c - db_base(g);
+        cx = cl % g.dx; cy = (cl / g.dx) % g.dy; cz = cl / (g.dx * g.dy);
     }
 }
-__device__ __forceinline__ int db_neighbour_cell(const DbGrid& g, const unsigned long long* __restrict__ hkeys, int c, int cx, int cy, int cz,
+template <class G>
+__device__ __forceinline__ int db_neighbour_cell(const G& g, const unsigned long long* __restrict__ hkeys, int c, int cx, int cy, int cz,
                                                  int nbr, bool own) {
     if (nbr >= 125) return -1;
     const int x = cx + nbr % 5 - 2, y = cy + (nbr / 5) % 5 - 2, z = cz + nbr / 25 - 2;
     if (x < 0 || y < 0 || z < 0 || x >= g.dx || y >= g.dy || z >= g.dz) return -1;
     if (nbr == 62) return own ? c : -1;  // the centre
-    if (g.hashed) return db_hash_find(hkeys, db_key64(x, y, z));
-    return (z * g.dy + y) * g.dx + x;
+    if (g.hashed) return db_hash_find(g, hkeys, db_key64(x, y, z));
+    return db_base(g) + (z * g.dy + y) * g.dx + x;
 }
 
 // core <=> at least min_samples points within eps (itself included).  Pass 1, one thread per point, decides what needs no
 // distance: the own cell alone reaches min_samples (all of it is within eps), or the 125 cells together cannot.  The rest
 // goes to a worklist.
-__global__ __launch_bounds__(256) void k_db_core(DbArgs a) {
+// (Batched: p runs over the sorted positions of all rows, the point's row comes with its cell; the worklist is one for all rows.)
+template <class A>
+__global__ __launch_bounds__(256) void k_db_core(A a) {
     DbGrid* gp = a.grid;
-    const DbGrid g = *gp;
+    const DbGrid gl = *gp;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool in = p < g.n;
+    const bool in = p < gl.n;
     int c = 0, state = 0;  // 1 core, 0 not core, 2 undecided
     int32_t orig = 0;
     if (in) {
         const float4 me = a.s_pt[p];
         c = __float_as_int(me.w);
+        const auto& g = db_row_of(a, gl, c);
         const int cnt = a.cell_start[c + 1] - a.cell_start[c];
         state = cnt >= g.ms ? 1 : 0;
         if (!state) {
@@ -482,14 +616,16 @@ __global__ __launch_bounds__(256) void k_db_core(DbArgs a) {
 // cells are scanned, 64 candidates at a time, and the count stops as soon as min_samples is reached OR can no longer be reached
 // (round 5 walked the 125 cells one by one, every lane the same box test, and counted a point that could not become core to
 // the end: 1 - 2 ms of the DBSCAN frame at N = 100k).
-__global__ __launch_bounds__(256) void k_db_core_count(DbArgs a) {
-    const DbGrid g = *a.grid;
+template <class A>
+__global__ __launch_bounds__(256) void k_db_core_count(A a) {
+    const DbGrid gl = *a.grid;
     const int lane = threadIdx.x & 63;
     const int wave = (int)((blockIdx.x * 256 + threadIdx.x) >> 6), nwaves = (int)((gridDim.x * 256) >> 6);
-    for (int wi = wave; wi < g.nwork; wi += nwaves) {
+    for (int wi = wave; wi < gl.nwork; wi += nwaves) {
         const int32_t p = a.work[wi];
         const float4 me = a.s_pt[p];
         const int c = __float_as_int(me.w);
+        const auto& g = db_row_of_wave(a, gl, c);
         int cx, cy, cz;
         db_cell_xyz(g, a.hkeys, c, cx, cy, cz);
         int cnt = a.cell_start[c + 1] - a.cell_start[c];  // the own cell: all of it within eps
@@ -566,9 +702,10 @@ __device__ __forceinline__ void db_union(int32_t* parent, int32_t x, int32_t y) 
 }
 
 // the core points of a cell are a clique: hang each under the cell's representative
-__global__ __launch_bounds__(256) void k_db_clique(DbArgs a) {
+template <class A>
+__global__ __launch_bounds__(256) void k_db_clique(A a) {
     DbGrid* gp = a.grid;
-    const DbGrid g = *gp;
+    const DbGrid g = *gp;  // (batched: the record of the whole batch - the sorted positions and the cell list are shared)
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= g.n || !a.s_core[p]) return;
     const int c = __float_as_int(a.s_pt[p].w);
@@ -591,12 +728,14 @@ __device__ __forceinline__ void db_cell_box(const DbArgs& a, int c, double* lo, 
         hi[d] = (double)db_unkey(a.cell_box[(size_t)(3 + d) * DB_MAXCELLS + c]);
     }
 }
-__global__ __launch_bounds__(256) void k_db_link(DbArgs a) {
-    const DbGrid g = *a.grid;
+template <class A>
+__global__ __launch_bounds__(256) void k_db_link(A a) {
+    const DbGrid gl = *a.grid;
     const int lane = threadIdx.x & 63;
     const int wave = (int)((blockIdx.x * 256 + threadIdx.x) >> 6), nwaves = (int)((gridDim.x * 256) >> 6);
-    for (int ci = wave; ci < g.ncore_cells; ci += nwaves) {
+    for (int ci = wave; ci < gl.ncore_cells; ci += nwaves) {
         const int c = a.core_cells[ci];
+        const auto& g = db_row_of_wave(a, gl, c);
         const int32_t rep = a.cell_rep[c];
         const int b1 = a.cell_start[c], e1 = a.cell_start[c + 1];
         double lo1[3], hi1[3];
@@ -649,9 +788,9 @@ __global__ __launch_bounds__(256) void k_db_link(DbArgs a) {
 
 // flatten; the roots (a cluster's first core point in index order) are collected (the first DB_MAXROOTS in a list for the LDS
 // ranking; all of them as flags by particle index for the general ranking)
-__global__ __launch_bounds__(256) void k_db_roots(DbArgs a) {
-    DbGrid* gp = a.grid;
-    const DbGrid g = *gp;
+template <class A>
+__global__ __launch_bounds__(256) void k_db_roots(A a) {
+    const DbGrid g = *a.grid;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= g.n) return;
     const int32_t orig = a.s_orig[p];
@@ -660,8 +799,8 @@ __global__ __launch_bounds__(256) void k_db_roots(DbArgs a) {
         const int32_t r = db_find(a.parent, orig);
         a.parent[orig] = r;  // the unions are complete: values only ever move towards the root, a plain store is safe
         if (r == orig) {
-            const int slot = atomicAdd(&gp->nroots, 1);
-            if (slot < DB_MAXROOTS) a.roots[slot] = orig;
+            const int slot = atomicAdd(&db_row_of_particle(a, orig)->nroots, 1);  // (a root list and a count per row)
+            if (slot < DB_MAXROOTS) db_roots_of_particle(a, orig)[slot] = orig;
             flag = 1;
         }
     }
@@ -670,10 +809,12 @@ __global__ __launch_bounds__(256) void k_db_roots(DbArgs a) {
 
 // more clusters than the LDS ranking holds: rank[i] := number of roots among the particles before i (one workgroup; a no-op
 // otherwise)
-__global__ __launch_bounds__(1024) void k_db_rank(DbArgs a) {
+template <class A>
+__global__ __launch_bounds__(1024) void k_db_rank(A a) {
     __shared__ int s_w[16];
     __shared__ int s_carry;
-    const DbGrid g = *a.grid;
+    const auto g = db_ygrid(a);
+    int32_t* rank = a.rank + db_yrow(a) * a.N;  // (batched: one workgroup per row over the row's particles)
     if (g.nroots <= DB_MAXROOTS || (a.max_clusters > 0 && a.max_clusters <= DB_MAXROOTS)) return;
     const int t = threadIdx.x;
     if (t == 0) s_carry = 0;
@@ -683,7 +824,7 @@ __global__ __launch_bounds__(1024) void k_db_rank(DbArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int i = base + t * 8 + j;
-            v[j] = i < g.n ? a.rank[i] : 0;
+            v[j] = i < g.n ? rank[i] : 0;
             mine += v[j];
         }
         int incl = mine;
@@ -699,7 +840,7 @@ __global__ __launch_bounds__(1024) void k_db_rank(DbArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int i = base + t * 8 + j;
-            if (i < g.n) a.rank[i] = run;
+            if (i < g.n) rank[i] = run;
             run += v[j];
         }
         __syncthreads();
@@ -709,10 +850,13 @@ __global__ __launch_bounds__(1024) void k_db_rank(DbArgs a) {
 }
 
 // cluster number of a root = its rank among the roots; per cell the number of its core points' cluster
-__global__ __launch_bounds__(256) void k_db_number(DbArgs a) {
+// (Batched: the row as grid.y, over the row's own sorted positions; the prefix ranks count from the row's first particle, so
+// rank[root] is the number within the row.)
+template <class A>
+__global__ __launch_bounds__(256) void k_db_number(A a) {
     __shared__ int32_t s_roots[DB_MAXROOTS + 1];
-    DbGrid* gp = a.grid;
-    const DbGrid g = *gp;
+    const auto g = db_ygrid(a);
+    const int32_t* roots = a.roots + db_yrow(a) * (DB_MAXROOTS + 1);
     int nr = g.nroots;
     // general = ranked through the prefix sum; otherwise the first DB_MAXROOTS roots are ranked here and the clusters beyond
     // that limit (the loop step's arrays) stay unnumbered
@@ -721,17 +865,17 @@ __global__ __launch_bounds__(256) void k_db_number(DbArgs a) {
     nr = over ? DB_MAXROOTS : nr;
     const int t = threadIdx.x;
     if (!general && t < nr) {  // rank sort of the few roots
-        const int32_t v = a.roots[t];
+        const int32_t v = roots[t];
         int rank = 0;
-        for (int j = 0; j < nr; ++j) rank += a.roots[j] < v ? 1 : 0;
+        for (int j = 0; j < nr; ++j) rank += roots[j] < v ? 1 : 0;
         s_roots[rank] = v;
     }
     __syncthreads();
     if (blockIdx.x == 0 && t == 0) {
-        *a.ncl_out = nr;
-        if (a.err_out && (over || g.err)) *a.err_out |= (over ? 2 : 0) | (g.err & 1 ? 32 : 0) | (g.err & 2 ? 64 : 0);  // cluster limit | extent / non-finite | hash capacity
+        a.ncl_out[db_yrow(a) * db_out_stride(a)] = nr;
+        if (a.err_out && (over || g.err)) a.err_out[db_yrow(a) * db_out_stride(a)] |= (over ? 2 : 0) | (g.err & 1 ? 32 : 0) | (g.err & 2 ? 64 : 0);  // cluster limit | extent / non-finite | hash capacity
     }
-    for (int64_t p = (int64_t)blockIdx.x * 256 + t; p < g.n; p += (int64_t)gridDim.x * 256) {
+    for (int64_t p = db_off(g) + (int64_t)blockIdx.x * 256 + t; p < db_off(g) + g.n; p += (int64_t)gridDim.x * 256) {
         if (!a.s_core[p]) continue;
         const int32_t orig = a.s_orig[p];
         const int32_t r = db_find(a.parent, orig);
@@ -750,14 +894,16 @@ __global__ __launch_bounds__(256) void k_db_number(DbArgs a) {
 // within eps (the own cell always is) offers its cluster number outright - the wave's minimum over those is the answer unless a
 // CUT cell holds a smaller number, and only those cut cells are scanned, 64 candidates at a time, any hit ends the cell.
 // (Round 3: a thread per point, 4.5 ms at N = 100k; round 4: a wave per point walking the cells one by one, 1.0 ms; now 0.2.)
-__global__ __launch_bounds__(256) void k_db_border(DbArgs a) {
-    const DbGrid g = *a.grid;
+template <class A>
+__global__ __launch_bounds__(256) void k_db_border(A a) {
+    const DbGrid gl = *a.grid;
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * 256) >> 6;
-    for (int64_t p = wave; p < g.n; p += nwaves) {
+    for (int64_t p = wave; p < gl.n; p += nwaves) {
         if (a.s_core[p]) continue;
         const float4 me = a.s_pt[p];
         const int c = __float_as_int(me.w);
+        const auto& g = db_row_of_wave(a, gl, c);
         int cx, cy, cz;
         db_cell_xyz(g, a.hkeys, c, cx, cy, cz);
         int best = 0x7fffffff;
@@ -840,20 +986,76 @@ int launch_dbscan(midas_ctx* ctx, int64_t cap, const int32_t* n_dev, const float
 #undef DB_SCRATCH
     const unsigned gp = (unsigned)ceil_div(cap, 256);
     MIDAS_HIP_CHECK(ctx, hipMemsetAsync(a.cell_count, 0, (size_t)DB_MAXCELLS * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_db_bounds, dim3(nbb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_bounds<DbArgs>, dim3(nbb), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_db_setup, dim3(1), dim3(64), 0, st, a, nbb);
     hipLaunchKernelGGL(k_db_hclear, dim3(1024), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_count, dim3(gp), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_scan, dim3(1), dim3(1024), 0, st, a);
-    hipLaunchKernelGGL(k_db_scatter, dim3(gp), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_core, dim3(gp), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_core_count, dim3(gp < 2048 ? gp : 2048), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_clique, dim3(gp), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_link, dim3(gp < 2048 ? gp : 2048), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_roots, dim3(gp), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_rank, dim3(1), dim3(1024), 0, st, a);
-    hipLaunchKernelGGL(k_db_number, dim3(gp < 1024 ? gp : 1024), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_db_border, dim3(gp), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_count<DbArgs>, dim3(gp), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_scan<DbArgs>, dim3(1), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(k_db_scatter<DbArgs>, dim3(gp), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_core<DbArgs>, dim3(gp), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_core_count<DbArgs>, dim3(gp < 2048 ? gp : 2048), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_clique<DbArgs>, dim3(gp), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_link<DbArgs>, dim3(gp < 2048 ? gp : 2048), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_roots<DbArgs>, dim3(gp), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_rank<DbArgs>, dim3(1), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(k_db_number<DbArgs>, dim3(gp < 1024 ? gp : 1024), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_border<DbArgs>, dim3(gp), dim3(256), 0, st, a);
+    DB_LAUNCH_CHECK(ctx);
+    return MIDAS_OK;
+}
+
+// B clouds, one set of launches (see the head of this file).  B >= 1, cap >= 1, B * cap <= MIDAS_DBSCAN_BATCH_MAX_POINTS: the
+// entry points check.
+int launch_dbscan_batch(midas_ctx* ctx, int32_t B, int64_t cap, const int32_t* n_dev, int64_t n_stride, const float* poses, double eps,
+                        int64_t min_samples, int32_t* labels_out, int32_t* ncl_out, int32_t* err_out, int64_t out_stride, int32_t max_clusters) {
+    hipStream_t st = ctx->stream;
+    DbBatchArgs a;
+    a.N = cap; a.n_dev = n_dev; a.poses = poses; a.eps = eps; a.r2 = eps * eps; a.min_samples = min_samples;
+    a.labels = labels_out; a.ncl_out = ncl_out; a.err_out = err_out; a.max_clusters = max_clusters;
+    a.B = B; a.S = DB_MAXCELLS / B; a.n_stride = n_stride; a.out_stride = out_stride;
+    const int64_t total = (int64_t)B * cap;
+    const int nbb = (int)(ceil_div(cap, 256) < 64 ? ceil_div(cap, 256) : 64);  // bounds partials a row
+    int rc;
+    void* p;
+#define DB_SCRATCH(field, type, count)                                        \
+    if ((rc = midas_scratch(ctx, (size_t)(count) * sizeof(type), &p))) return rc; \
+    a.field = (type*)p
+    DB_SCRATCH(grid, DbGrid, 1);
+    DB_SCRATCH(rows, DbRow, B);
+    DB_SCRATCH(part, float, (size_t)B * nbb * 6);
+    DB_SCRATCH(cell_count, int32_t, DB_MAXCELLS);
+    DB_SCRATCH(cell_start, int32_t, DB_MAXCELLS + 1);
+    DB_SCRATCH(cell_rep, int32_t, DB_MAXCELLS);
+    DB_SCRATCH(cell_num, int32_t, DB_MAXCELLS);
+    DB_SCRATCH(cell_box, uint32_t, 6 * (size_t)DB_MAXCELLS);
+    DB_SCRATCH(cid, int32_t, total);
+    DB_SCRATCH(s_orig, int32_t, total);
+    DB_SCRATCH(s_pt, float4, total);
+    DB_SCRATCH(s_core, uint8_t, total);
+    DB_SCRATCH(parent, int32_t, total);
+    DB_SCRATCH(roots, int32_t, (size_t)B * (DB_MAXROOTS + 1));
+    DB_SCRATCH(work, int32_t, total);
+    DB_SCRATCH(core_cells, int32_t, total);
+    DB_SCRATCH(hkeys, unsigned long long, DB_MAXCELLS);
+    DB_SCRATCH(rank, int32_t, total + 1);
+#undef DB_SCRATCH
+    const unsigned gp = (unsigned)ceil_div(cap, 256), gs = (unsigned)ceil_div(total, 256);  // blocks over a row / over all sorted positions
+    const unsigned gh = (unsigned)(ceil_div(a.S, 1024) < 64 ? ceil_div(a.S, 1024) : 64);
+    MIDAS_HIP_CHECK(ctx, hipMemsetAsync(a.cell_count, 0, (size_t)DB_MAXCELLS * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_db_bounds<DbBatchArgs>, dim3(nbb, B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_dbb_setup, dim3(1, B), dim3(64), 0, st, a, nbb);
+    hipLaunchKernelGGL(k_dbb_hclear, dim3(gh, B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_count<DbBatchArgs>, dim3(gp, B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_scan<DbBatchArgs>, dim3(1, B), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(k_db_scatter<DbBatchArgs>, dim3(gp, B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_core<DbBatchArgs>, dim3(gs), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_core_count<DbBatchArgs>, dim3(gs < 2048 ? gs : 2048), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_clique<DbBatchArgs>, dim3(gs), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_link<DbBatchArgs>, dim3(gs < 2048 ? gs : 2048), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_roots<DbBatchArgs>, dim3(gs), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_rank<DbBatchArgs>, dim3(1, B), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(k_db_number<DbBatchArgs>, dim3(gp < 64 ? gp : 64, B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_db_border<DbBatchArgs>, dim3(gs), dim3(256), 0, st, a);
     DB_LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }

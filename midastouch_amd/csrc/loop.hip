@@ -1673,7 +1673,12 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
         weights_merged = loop_weights_mergeable(phases);
         if ((rc = loop_weights_phase(ctx, s, g, cb->K, pa.gt16 != nullptr, weights_merged, wa))) return rc;
     }
-    if (phases & MIDAS_LOOP_DBSCAN) {
+    if ((phases & MIDAS_LOOP_DBSCAN) && s.dbscan_batched) {
+        // all trajectories in one set of launches, each in its own region of the cell tables (dbscan.hip): the labels of the passes below
+        if ((rc = launch_dbscan_batch(ctx, B, cap, s.ctl_i_dev + LOOP_I_N, LOOP_CTL_I, s.poses_prop_dev, s.eps, -1, s.labels_dev,
+                                      s.ctl_i_dev + LOOP_I_NCL, s.ctl_i_dev + LOOP_I_ERR, LOOP_CTL_I, LOOP_MAX_CLUSTERS - 1)))
+            return rc;
+    } else if (phases & MIDAS_LOOP_DBSCAN) {
         // one trajectory after the other on the stream, each on its slices; the passes take the same scratch (one set of cell tables)
         const midas_scratch_pos pos = midas_scratch_mark(ctx);
         for (int32_t b = 0; b < B; ++b) {

@@ -615,6 +615,11 @@ int launch_topk_aten(midas_ctx* ctx, int64_t cap, const int32_t* ci, const doubl
 int launch_dbscan_points(midas_ctx* ctx, int64_t N, int32_t dim, const double* pts, double eps, int64_t min_samples, int32_t* labels, int32_t* info);
 int launch_dbscan(midas_ctx* ctx, int64_t cap, const int32_t* n_dev, const float* poses, double eps, int64_t min_samples,
                   int32_t* labels_out, int32_t* ncl_out, int32_t* err_out, int32_t max_clusters);  // max_clusters 0: any number
+// the same for B clouds in one set of launches (B * cap <= MIDAS_DBSCAN_BATCH_MAX_POINTS): poses (B, cap, 16), labels_out (B, cap),
+// row b's count at n_dev[b * n_stride] (n_dev null: cap), its cluster count at ncl_out[b * out_stride], its flags ORed into
+// err_out[b * out_stride]
+int launch_dbscan_batch(midas_ctx* ctx, int32_t B, int64_t cap, const int32_t* n_dev, int64_t n_stride, const float* poses, double eps,
+                        int64_t min_samples, int32_t* labels_out, int32_t* ncl_out, int32_t* err_out, int64_t out_stride, int32_t max_clusters);
 
 // mt19937.hip - torch's CPU generator stream on the device
 int launch_mt_seed(midas_ctx* ctx, uint64_t seed, uint32_t* state);

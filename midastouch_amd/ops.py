@@ -334,6 +334,37 @@ def dbscan(poses: torch.Tensor, eps: float = 1e-2, min_samples: int = -1):
     return labels, info
 
 
+def dbscan_batch(poses: torch.Tensor, counts=None, eps: float = 1e-2, min_samples: int = -1, max_clusters: int = 0, out=None):
+    """cluster_particles(method="euclidean") labels (particle_filter.py:208-217) of B particle sets in one set of launches
+    (midas_dbscan_batch): poses (B, N, 4, 4); counts None (every row holds N points) or B live counts (int tensor or sequence,
+    0 .. N each); min_samples < 0 -> n_b // 5 per row; max_clusters 0 = any number, 1 .. 62 = a row with more reports flag 2.
+    Returns (labels int32 (B, N), info int32 (B, 2) = per row [clusters, flags]); row b holds `dbscan(poses[b, :n_b])`'s labels,
+    slots beyond n_b are left as they are (-1 in a fresh tensor; `out`: a (B, N) int32 tensor of the caller's to write into).
+    B * N is bounded by `_lib.DBSCAN_BATCH_MAX_POINTS` (the rows share one set of cell tables)."""
+    if poses.dim() != 4 or tuple(poses.shape[2:]) != (4, 4):
+        raise MidasError(f"expected (B,N,4,4) poses, got {tuple(poses.shape)}")
+    B, N = int(poses.shape[0]), int(poses.shape[1])
+    if B < 1 or N < 1:
+        raise MidasError(f"dbscan_batch needs at least one row and one slot, got {B} x {N}")
+    if B * N > _lib.DBSCAN_BATCH_MAX_POINTS:
+        raise MidasError(f"dbscan_batch holds at most DBSCAN_BATCH_MAX_POINTS = {_lib.DBSCAN_BATCH_MAX_POINTS} points in all, not {B} x {N} "
+                         "(cluster the rows one by one with dbscan)")
+    ctx = _ctx(poses)
+    if poses.dtype != torch.float32 or not poses.is_contiguous():
+        poses = poses.float().contiguous()
+    if counts is not None:
+        counts = torch.as_tensor(counts).to(poses.device, torch.int32).contiguous().reshape(-1)
+        if counts.numel() != B:
+            raise MidasError(f"{counts.numel()} counts for {B} rows")
+    if out is None:
+        out = torch.full((B, N), -1, dtype=torch.int32, device=poses.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (B, N) or not out.is_contiguous() or out.device != poses.device:
+        raise MidasError(f"out must be a contiguous ({B},{N}) int32 tensor on {poses.device}")
+    info = torch.zeros((B, 2), dtype=torch.int32, device=poses.device)
+    ctx.call("midas_dbscan_batch", B, N, _ptr(counts), 1, _ptr(poses), float(eps), int(min_samples), _ptr(out), _ptr(info), int(max_clusters))
+    return out, info
+
+
 def dbscan_points(points: torch.Tensor, eps: float = 1e-2, min_samples: int = -1):
     """DBSCAN labels of N points in 2 .. 6 dimensions (cluster_particles(method="logmap"), particle_filter.py:218-223: the
     6-d SE(3) logarithms), all pairs on the device in float64 - sklearn's predicate and numbering.

@@ -14,6 +14,8 @@ One JSON line per engine form with each figure's median over the repeats and [mi
   batch_loop          the Philox batch frame (orientation: the seeded batch frame should sit near it plus one seeded single frame)
 --wide: BatchLoopEngine(wide=True) (midas_loop_step_batch_wide: sets beyond 16 384 particles per trajectory, e.g. 16 50000) against B single
   LoopEngine frames; --floor=N: annealing's floor (default 1000).  The fixed-N form is left out.
+--dbscan serial|batched: the batch engine's DBSCAN frame as B passes one after the other (batched_dbscan=False) or as the one batched pass
+  (batched_dbscan=True; B x N0 <= 2^20); default: the engine's own choice (batched whenever it fits).
 --profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch), no timing."""
 import json
 import os
@@ -29,7 +31,17 @@ from midastouch_amd.engine import PipelinedBatchFilterEngine
 from midastouch_amd.loop_engine import LoopEngine
 from midastouch_amd.synthetic import make_codebook, make_trajectory, wide_start
 
-argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+DBSCAN = None  # BatchLoopEngine(batched_dbscan=...): None = the engine's choice
+args = sys.argv[1:]
+if "--dbscan" in args:  # `--dbscan VALUE`: taken out with its value, so that the value is no positional argument
+    i = args.index("--dbscan")
+    args[i:i + 2] = ["--dbscan=" + (args[i + 1] if i + 1 < len(args) else "")]
+for a in args:
+    if a.startswith("--dbscan="):
+        if a.split("=", 1)[1] not in ("serial", "batched"):
+            sys.exit("bench_batch_loop.py: --dbscan serial|batched")
+        DBSCAN = a.split("=", 1)[1] == "batched"
+argv = [a for a in args if not a.startswith("--")]
 profile, seeded, wide = "--profile" in sys.argv, "--seeded" in sys.argv, "--wide" in sys.argv
 B, N0, K, T, R = (int(argv[i]) if len(argv) > i else d for i, d in enumerate((64, 10000, 50000, 300, 3)))
 D, FLOOR, EVERY, SEED = 512, 1000, 50, 4000
@@ -73,7 +85,7 @@ def over_repeats(rows):
 
 
 def run_batch(seeds=None):
-    eng = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, **kw, **({"wide": True} if wide else {}))
+    eng = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, batched_dbscan=DBSCAN, **kw, **({"wide": True} if wide else {}))
     if seeds is not None:
         eng.seed_torch_streams(seeds)
     eng.set_particles(starts)
@@ -115,7 +127,8 @@ if profile:
     torch.cuda.synchronize()
     sys.exit(0)
 
-head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R, **({"wide": True} if wide else {})}
+head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R, **({"wide": True} if wide else {}),
+        **({} if DBSCAN is None else {"dbscan": "batched" if DBSCAN else "serial"})}
 out = {}
 forms = (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed))
 if wide:
