@@ -310,7 +310,9 @@ int midas_rmse(midas_ctx* ctx, int64_t N, const float* poses_dev, const float* g
  * unit quaternions, centre translation = weighted mean; std = sqrt(sum w (t - centre)^2 / sum w) per axis.
  * weights: float64 (weights64_dev) or float32 (weights32_dev), exactly one non-NULL.  centers_dev: C x 16 float32,
  * stds_dev: C x 3 float32, counts_dev: NULL or C int64 (members per label; a label nobody carries gives NaN rows).
- * 1 <= C <= 64. */
+ * 1 <= C <= 65535; up to 64 clusters a workgroup skips those none of its particles carries, beyond that every workgroup sums
+ * every cluster (C x ceil(N / 256) x 288 bytes of scratch: many GB at the limit with a large N - the call then returns the
+ * out-of-memory error). */
 int midas_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses_dev, const double* weights64_dev,
                           const float* weights32_dev, const int64_t* labels_dev, int32_t C, const int64_t* label_values_dev,
                           float* centers_dev, float* stds_dev, int64_t* counts_dev);

@@ -88,7 +88,9 @@ MD void cluster_close(const double* s_m, float* out, float* sd, int64_t* count, 
     }
     // torch.isclose(max - min, 0): |d| <= atol (1e-8), in the float32 arithmetic of the reference
     const float d = (float)s_m[M_WMAX] - (float)s_m[M_WMIN];
-    const bool flat = __builtin_fabsf(d) <= 1e-8f;
+    // The extrema let a NaN weight lose unless it comes first (cluster.hip, cluster_finish_body), where the reference's max and
+    // min propagate it and isclose(NaN, 0) is false: a NaN sum w (a NaN weight anywhere among the members) is never flat.
+    const bool flat = __builtin_fabsf(d) <= 1e-8f && s_m[M_SW] == s_m[M_SW];
     const int oq = flat ? M_QQ1 : M_QQW, ot = flat ? M_T1 : M_TW, ott = flat ? M_TT1 : M_TTW;
     const double sw = flat ? s_m[M_CNT] : s_m[M_SW];
     double A10[10];

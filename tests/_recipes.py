@@ -203,3 +203,423 @@ def rmse_mixed_cloud(n: int, seed: int = 0, nan_translation_last: bool = False):
     else:
         poses[n - 1, 1, 1] = np.nan
     return poses, gt
+
+
+# ---- cluster centres: a reference that is not the oracle's twin, the derived bounds, the input sets -----------------------------
+# (tests/test_cluster_reference.py on the CPU, tests/test_gpu_cluster_pin.py and tests/test_gpu_cluster_finishers.py on the GPU)
+U64 = 2.0 ** -53   # unit roundoff of float64
+U32 = 2.0 ** -24   # unit roundoff of float32
+ROT_GAP_ASSERTED = 1e-3    # eigen gap from which the rotation is compared entry by entry
+ROT_GAP_ARBITRARY = 1e-9   # eigen gap below which any method's rotation is arbitrary: finite and orthonormal is all that is asked
+ROT_TOL = 2.0 ** -23       # two float32 roundings of an entry in [-1, 1]
+
+
+def shepperd_branch(poses):
+    """The branch of the kernel's quaternion extraction (cluster.hip, quat_of) every pose takes, from the float32 entries widened
+    to float64: 0 `tr > 0`, 1 `r00` the largest diagonal entry, 2 `r11 > r22`, 3 the rest."""
+    R = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)[:, :3, :3].astype(np.float64)
+    r00, r11, r22 = R[:, 0, 0], R[:, 1, 1], R[:, 2, 2]
+    tr = r00 + r11 + r22
+    return np.where(tr > 0.0, 0, np.where((r00 > r11) & (r00 > r22), 1, np.where(r11 > r22, 2, 3)))
+
+
+def quat_shepperd64(poses):
+    """Shepperd's extraction in float64 with the kernel's branch rule, (n, 4) as x, y, z, w with w >= 0, normalised - the yardstick of
+    the one- and two-member clusters, where the float32 matrix is the whole input and two extractions of a matrix that is
+    orthonormal only to 6e-8 may differ by as much."""
+    R = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)[:, :3, :3].astype(np.float64)
+    br = shepperd_branch(poses)
+    q = np.zeros((R.shape[0], 4))
+    for n in range(R.shape[0]):
+        r = R[n]
+        if br[n] == 0:
+            s = np.sqrt(r[0, 0] + r[1, 1] + r[2, 2] + 1.0) * 2.0
+            q[n] = ((r[2, 1] - r[1, 2]) / s, (r[0, 2] - r[2, 0]) / s, (r[1, 0] - r[0, 1]) / s, 0.25 * s)
+        elif br[n] == 1:
+            s = np.sqrt(1.0 + r[0, 0] - r[1, 1] - r[2, 2]) * 2.0
+            q[n] = (0.25 * s, (r[0, 1] + r[1, 0]) / s, (r[0, 2] + r[2, 0]) / s, (r[2, 1] - r[1, 2]) / s)
+        elif br[n] == 2:
+            s = np.sqrt(1.0 + r[1, 1] - r[0, 0] - r[2, 2]) * 2.0
+            q[n] = ((r[0, 1] + r[1, 0]) / s, 0.25 * s, (r[1, 2] + r[2, 1]) / s, (r[0, 2] - r[2, 0]) / s)
+        else:
+            s = np.sqrt(1.0 + r[2, 2] - r[0, 0] - r[1, 1]) * 2.0
+            q[n] = ((r[0, 2] + r[2, 0]) / s, (r[1, 2] + r[2, 1]) / s, 0.25 * s, (r[1, 0] - r[0, 1]) / s)
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    q[q[:, 3] < 0] *= -1.0
+    return q
+
+
+def cluster_reference(poses, w, labels, label_values=None):
+    """The cluster centres of particle_filter.get_cluster_centers(method="quat_avg") per label value (default: the sorted unique
+    labels) from the float32 poses and the float32-rounded weights exactly as given - not the oracle's arithmetic restated:
+      * the flatten rule abs(float32(max - min)) <= 1e-8 (every weight then counts 1); a NaN weight is never flat and makes the
+        cluster's rotation, translation and spread NaN (the reference's max, min and sums propagate it);
+      * quaternions as the oracle takes them (scipy, qw >= 0) - clusters of ONE OR TWO members take quat_shepperd64 instead;
+      * the moment matrix and every translation sum by math.fsum (exactly rounded sums of the float64 products);
+      * the rotation from numpy.linalg.eigh; the float32 centre; the spread in two passes around that float32 centre.
+    -> a list of dicts, one per label value: center (4,4) f32, std (3,) f32, var (3,) float64 (the two-pass variance), mean64 (3,),
+    gap (lambda_1 - lambda_2; inf for a NaN or empty cluster), tmax (max abs(t) of the members), count, flat, nan.  An empty
+    cluster: NaN everywhere, count 0, as midas_cluster_centers reports it."""
+    import math
+
+    from scipy.spatial.transform import Rotation
+    P = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)
+    w32 = np.asarray(w).astype(np.float32).reshape(-1)
+    labels = np.asarray(labels).reshape(-1)
+    values = np.unique(labels) if label_values is None else np.asarray(label_values).reshape(-1)
+    out = []
+    for lab in values:
+        sel = labels == lab
+        n = int(sel.sum())
+        rec = dict(label=int(lab), count=n, flat=False, nan=False, gap=float("inf"), tmax=0.0,
+                   center=np.full((4, 4), np.nan, dtype=np.float32), std=np.full(3, np.nan, dtype=np.float32),
+                   var=np.full(3, np.nan), mean64=np.full(3, np.nan))
+        out.append(rec)
+        if n == 0:
+            continue
+        tp, tw = P[sel].astype(np.float64), w32[sel]
+        t = tp[:, :3, 3]
+        rec["tmax"] = float(np.abs(t).max())
+        rec["center"][3] = (0.0, 0.0, 0.0, 1.0)
+        if np.isnan(tw).any():
+            rec["nan"] = True
+            continue
+        rec["flat"] = bool(abs(np.float32(tw.max() - tw.min())) <= 1e-8)
+        tw = np.ones(n) if rec["flat"] else tw.astype(np.float64)
+        sw = math.fsum(tw)
+        if n <= 2:
+            q = quat_shepperd64(P[sel])
+        else:
+            q = Rotation.from_matrix(tp[:, :3, :3]).as_quat()
+            q[q[:, 3] < 0] *= -1.0
+        M = np.zeros((4, 4))
+        for i in range(4):
+            for j in range(i, 4):
+                M[i, j] = M[j, i] = math.fsum(tw * (q[:, i] * q[:, j])) / sw
+        if np.isfinite(M).all():
+            evals, evecs = np.linalg.eigh(M)  # ascending
+            rec["gap"] = float(evals[3] - evals[2])
+            aq = evecs[:, 3] if evecs[3, 3] >= 0 else -evecs[:, 3]
+            rec["center"][:3, :3] = Rotation.from_quat(aq).as_matrix()
+        mean = np.array([math.fsum(tw * t[:, k]) for k in range(3)]) / sw
+        rec["mean64"] = mean
+        rec["center"][:3, 3] = mean  # (rounded to float32 here)
+        d = t - rec["center"][:3, 3].astype(np.float64)
+        rec["var"] = np.array([math.fsum(tw * (d[:, k] * d[:, k])) for k in range(3)]) / sw
+        rec["std"] = np.sqrt(rec["var"]).astype(np.float32)
+    return out
+
+
+def spread_kappa(nblocks: int) -> int:
+    return 4 * (int(nblocks) + 12) + 4
+
+
+def assert_cluster(got_c, got_s, ref, nblocks, tag="", log=None):
+    """Centres (C,4,4) and spreads (C,3) of a device form against cluster_reference's records `ref`, with bounds that follow from
+    the arithmetic (nblocks = the 256-particle workgroups whose partials the finisher adds up).  The effective weights - 1 where the
+    set is flattened - must be >= 0: with weights of mixed sign neither the spread bound nor the rotation applies (the moment matrix
+    is then not positive semi-definite, which top_eigvec4's trace test assumes):
+
+    Translation.  The kernel's mean is a float64 quotient of two sums whose error (see below) is far under a float32 ulp, rounded
+    once to float32: within ONE float32 ulp of float32(the exactly summed mean); exact equality is counted.
+
+    Spread (weights >= 0).  sd = sqrt(var) with var = (S2 - 2 m S1 + m^2 S0) / S0 from the one-pass moments S2 = sum w t^2,
+    S1 = sum w t, S0 = sum w and the float32 centre m, in float64 (u = 2^-53).  Every moment is a sum taken through six butterfly
+    levels, three additions over the waves and a chain over the blocks - at most nblocks + 8 additions deep - of terms that carry
+    at most two product roundings (w t is exact: 24 + 24 bits): each moment is within (nblocks + 10) u of the sum of its terms'
+    magnitudes, and with weights >= 0 the three terms of the closed form are bounded by S0 T^2, 2 S0 T^2 and S0 T^2 with
+    T = max abs(t): 4 (nblocks + 10) u S0 T^2 in all.  The closed form adds three products (m S1, m m, (m m) S0), two additions
+    and the division on the same magnitudes: under 4 * 2 + 4 more.  Hence |var - var_ref| <= E = kappa u T^2 with
+    kappa = 4 (nblocks + 12) + 4, and |sd - sd_ref| = |var - var_ref| / (sd + sd_ref), bounded here by E / (sd_ref + sqrt(E))
+    - the collapsed set, sd_ref = 0, may report up to sqrt(E) - plus one float32 rounding on either side, 2^-23 sd_ref.
+    No slack beyond that: a case outside it means the kernel or this derivation is wrong.
+
+    Rotation.  Eigen gap >= 1e-3: every entry within 2^-23 of the reference's float32 entry (two float32 roundings; the float64
+    eigenvector error, about 1e-13 / gap, is far below).  Gap < 1e-9: any answer is arbitrary - finite and orthonormal
+    (abs(R R^T - I) < 1e-6) is all that is asked.  In between nothing but finiteness.
+
+    NaN and empty clusters: NaN where the reference is NaN (the bottom row of a cluster with members stays 0 0 0 1).
+    -> dict of what was seen: t_ulp (largest translation deviation in ulps), t_exact / t_total, sd_frac (largest deviation as a
+    fraction of its bound), sd_equal / sd_total (float32 spreads equal to the reference's), kappa_ratio (largest
+    abs(sd^2 - var_ref) / (u T^2) - the measured counterpart of kappa - after taking off 2^-22 var_ref, what rounding sd to
+    float32 can account for; kappa_ratio_collapsed: over the sets with var_ref = 0 alone, where nothing is taken off), rot_dev
+    (largest entry deviation among the asserted clusters), rot_checked, rot_arbitrary."""
+    got_c = np.asarray(got_c.detach().cpu().numpy() if hasattr(got_c, "detach") else got_c, dtype=np.float32).reshape(-1, 4, 4)
+    got_s = np.asarray(got_s.detach().cpu().numpy() if hasattr(got_s, "detach") else got_s, dtype=np.float32).reshape(-1, 3)
+    assert got_c.shape[0] == len(ref) and got_s.shape[0] == len(ref), (tag, got_c.shape, got_s.shape, len(ref))
+    seen = dict(t_ulp=0.0, t_exact=0, t_total=0, sd_frac=0.0, sd_equal=0, sd_total=0, kappa_ratio=0.0, kappa_ratio_collapsed=0.0,
+                rot_dev=0.0, rot_checked=0, rot_arbitrary=0)
+    kappa = spread_kappa(nblocks)
+    for i, r in enumerate(ref):
+        what = f"{tag}: cluster {i} (label {r['label']}, {r['count']} members)"
+        c, s = got_c[i], got_s[i]
+        if r["count"] == 0 or r["nan"]:
+            assert np.isnan(s).all() and np.isnan(c[:3]).all(), f"{what}: expected NaN, got {c} {s}"
+            if r["count"] == 0:
+                assert np.isnan(c[3]).all(), what
+            else:
+                assert np.array_equal(c[3], np.float32([0, 0, 0, 1])), what
+            continue
+        assert np.isfinite(c).all() and np.isfinite(s).all(), f"{what}: not finite: {c} {s}"
+        assert np.array_equal(c[3], np.float32([0, 0, 0, 1])), what
+        # translation
+        rt = r["center"][:3, 3]
+        ulp = np.spacing(np.abs(rt))
+        dev = np.abs(c[:3, 3].astype(np.float64) - rt.astype(np.float64)) / ulp.astype(np.float64)
+        seen["t_ulp"] = max(seen["t_ulp"], float(dev.max()))
+        seen["t_exact"] += int((c[:3, 3] == rt).sum())
+        seen["t_total"] += 3
+        assert dev.max() <= 1.0, f"{what}: translation {c[:3, 3]!r} vs {rt!r} ({dev.max():.3g} ulp)"
+        # spread
+        T2 = r["tmax"] ** 2
+        E = kappa * U64 * T2
+        rs = r["std"].astype(np.float64)
+        bound = 2.0 ** -23 * rs + (E / (rs + np.sqrt(E)) if E > 0.0 else 0.0)
+        d = np.abs(s.astype(np.float64) - rs)
+        frac = np.where(d == 0.0, 0.0, d / np.where(bound > 0.0, bound, 1e-300))
+        seen["sd_frac"] = max(seen["sd_frac"], float(frac.max()))
+        seen["sd_equal"] += int((s == r["std"]).sum())
+        seen["sd_total"] += 3
+        if T2 > 0.0:
+            ratio = np.maximum(np.abs(s.astype(np.float64) ** 2 - r["var"]) - 2.0 ** -22 * r["var"], 0.0) / (U64 * T2)
+            seen["kappa_ratio"] = max(seen["kappa_ratio"], float(ratio.max()))
+            if (r["var"] == 0.0).all():
+                seen["kappa_ratio_collapsed"] = max(seen["kappa_ratio_collapsed"], float(ratio.max()))
+        assert (d <= bound).all(), (f"{what}: spread {s!r} vs {r['std']!r}: off by {d} where kappa = {kappa}, max|t| = {r['tmax']:.3g} "
+                                    f"allow {bound}")
+        # rotation
+        R = c[:3, :3].astype(np.float64)
+        if r["gap"] >= ROT_GAP_ASSERTED:
+            dr = float(np.abs(R - r["center"][:3, :3].astype(np.float64)).max())
+            seen["rot_dev"] = max(seen["rot_dev"], dr)
+            seen["rot_checked"] += 1
+            assert dr <= ROT_TOL, f"{what}: rotation off by {dr:.3g} (gap {r['gap']:.3g})\n{c[:3, :3]}\n{r['center'][:3, :3]}"
+        elif r["gap"] < ROT_GAP_ARBITRARY:
+            seen["rot_arbitrary"] += 1
+            assert np.abs(R @ R.T - np.eye(3)).max() < 1e-6, f"{what}: degenerate mean (gap {r['gap']:.3g}) is not a rotation:\n{R}"
+    if log is not None:
+        for k, v in seen.items():
+            log[k] = (log.get(k, 0) + v) if isinstance(v, int) else max(log.get(k, 0.0), v)
+    return seen
+
+
+# ---- the input sets.  cluster_set(name) -> dict(poses (N,4,4) f32, w (N,) float64 or float32, labels (N,) i64, label_values (C,) i64,
+# oracle: whether oracle.cluster_centers applies (no NaN weight, weights >= 0 with a positive sum, label_values its sorted unique
+# labels or a permutation with extras), nonneg: weights >= 0).  Names are "group/parameters"; everything is drawn from the name.
+CL_SIZES = (1, 2, 63, 64, 65, 255, 256, 257, 4097, 32768, 32769, 65537)
+CL_COUNTS = (1, 2, 9, 130, 1000)
+CL_AXES = {"x": (1.0, 0.0, 0.0), "y": (0.0, 1.0, 0.0), "z": (0.0, 0.0, 1.0), "xy": (2.0 ** -0.5, 2.0 ** -0.5, 0.0)}
+CL_PI_ANGLES = {"pi-1e-3": np.pi - 1e-3, "pi-0.05": np.pi - 0.05, "pi": np.pi}
+CL_ROT_SPREADS = (0.01, 0.14, 0.5, 1.0, 2.0)
+CL_DISTS = (0.05, 0.5, 1.0, 10.0)
+CL_SIGMAS = (2e-3, 2e-4, 2e-5, 2e-6, 2e-7, 0.0)
+CL_WKINDS = ("random", "flat", "peaky")
+CL_ENV_SEEDS = 4
+CL_FLATTEN = ("1e-8", "above", "below", "zero", "signed_zero", "all_zero", "below_f32")
+CL_NAN_AT = ("first", "last", "block2")
+CL_FIN_N = 24577  # 97 blocks; cut at multiples of 4096 into two and three slices
+# the other finishers' sets, as the rows of one ops.pose_estimate call each ("neg", "zerosum": bit equality of the forms only)
+CL_FIN_ROWS = [[f"fin/far/{CL_FIN_N}", f"fin/collapsed/{CL_FIN_N}", f"fin/uniform/{CL_FIN_N}"],
+               [f"fin/pi_x/{CL_FIN_N}", f"fin/pi_y/{CL_FIN_N}", f"fin/pi_z/{CL_FIN_N}"],
+               [f"fin/pi_xy/{CL_FIN_N}", f"fin/neg/{CL_FIN_N}", f"fin/zerosum/{CL_FIN_N}"],
+               ["size/32769", "fin/collapsed/32769", "fin/uniform/32769"]]  # 129 blocks: the second staging chunk
+
+
+def _name_seed(name):
+    return list(hashlib.sha256(name.encode()).digest()[:8])
+
+
+def _weights(rng, n, kind):
+    if kind == "random":
+        w = rng.uniform(0.0, 1.0, n)
+    elif kind == "flat":
+        return np.full(n, 1.0 / n)
+    elif kind == "peaky":
+        w = rng.uniform(0.0, 1.0, n) ** 12
+    else:
+        raise ValueError(kind)
+    return w / w.sum()
+
+
+def _cloud(rng, n, Rc, rot_sigma, tc, sigma_t):
+    """n float32 poses: rotation Rc turned by a rotation vector of rot_sigma per axis, translation tc + sigma_t noise."""
+    from scipy.spatial.transform import Rotation
+    R = (Rc * Rotation.from_rotvec(rot_sigma * rng.standard_normal((n, 3)))).as_matrix() if rot_sigma else np.tile(Rc.as_matrix(), (n, 1, 1))
+    return _pose(R, np.asarray(tc) + sigma_t * rng.standard_normal((n, 3)))
+
+
+def _one(poses, w, **kw):
+    n = poses.shape[0]
+    return dict(dict(poses=poses, w=w, labels=np.zeros(n, dtype=np.int64), label_values=np.zeros(1, dtype=np.int64), oracle=True, nonneg=True), **kw)
+
+
+def cluster_set(name: str):
+    from scipy.spatial.transform import Rotation
+    rng = np.random.default_rng(_name_seed(name))
+    rnd_rot = lambda: Rotation.from_rotvec(_unit(rng, 1)[0] * rng.uniform(0.3, 2.5))  # noqa: E731
+    group, _, arg = name.partition("/")
+    if group == "size":       # one cluster of N particles
+        n = int(arg)
+        return _one(_cloud(rng, n, rnd_rot(), 0.14, (0.05, -0.03, 0.08), 2e-3), _weights(rng, n, "random"))
+    if group == "count":      # C clusters over 4096 particles, labels drawn at random: at C = 1000 most clusters have no member
+        C, n = int(arg), 4096  # in most workgroups, some have one or two members and some none at all
+        labels = rng.integers(0, C, n).astype(np.int64)
+        poses = np.empty((n, 4, 4), dtype=np.float32)
+        for c in range(C):
+            m = labels == c
+            poses[m] = _cloud(rng, int(m.sum()), rnd_rot(), 0.1, rng.uniform(-0.1, 0.1, 3), 2e-3)
+        return dict(poses=poses, w=_weights(rng, n, "random"), labels=labels, label_values=np.arange(C, dtype=np.int64), oracle=True, nonneg=True)
+    if group == "labels":
+        n = 4096
+        if arg == "neg_t":    # every translation negative in every coordinate, three clusters in contiguous runs: most workgroups
+            labels = np.sort(rng.integers(0, 3, n)).astype(np.int64)  # skip two of them (the signed zeros of the skipped partials)
+            vals = np.arange(3, dtype=np.int64)
+        elif arg == "wide":   # label values -1, 0 and 2^40
+            vals = np.array([1 << 40, -1, 0], dtype=np.int64)
+            labels = vals[rng.integers(0, 3, n)]
+        else:
+            labels = rng.integers(0, 9, n).astype(np.int64)
+            vals = rng.permutation(9).astype(np.int64)             # "unsorted"
+            if arg == "missing":                                    # a value nobody carries in the middle
+                vals = np.concatenate([vals[:4], [77], vals[4:]]).astype(np.int64)
+            elif arg != "unsorted":
+                raise ValueError(name)
+        poses = np.empty((n, 4, 4), dtype=np.float32)
+        for v in np.unique(labels):
+            m = labels == v
+            tc = -rng.uniform(0.2, 0.5, 3) if arg == "neg_t" else rng.uniform(-0.1, 0.1, 3)
+            poses[m] = _cloud(rng, int(m.sum()), rnd_rot(), 0.1, tc, 2e-3)
+        if arg == "neg_t":
+            assert (poses[:, :3, 3] < 0).all()
+        return dict(poses=poses, w=_weights(rng, n, "random"), labels=labels, label_values=vals, oracle=True, nonneg=True)
+    if group == "pi":         # centres a half turn (nearly, exactly) about an axis, 0.05 rad around them: Shepperd's other branches
+        ax, ang = arg.split("/")
+        n = 1000
+        return _one(_cloud(rng, n, Rotation.from_rotvec(np.array(CL_AXES[ax]) * CL_PI_ANGLES[ang]), 0.05, (0.04, 0.02, -0.07), 2e-3),
+                    _weights(rng, n, "random"))
+    if group == "straddle":   # 120 degrees about random axes, +- a few degrees: tr = 1 + 2 cos(angle) on both sides of 0
+        n = 1000
+        R = Rotation.from_rotvec(_unit(rng, n) * (2.0 * np.pi / 3.0 + 0.05 * rng.standard_normal((n, 1)))).as_matrix()
+        return _one(_pose(R, np.array((0.04, 0.02, -0.07)) + 2e-3 * rng.standard_normal((n, 3))), _weights(rng, n, "random"))
+    if group == "gap":
+        n = 2000
+        tc = (0.04, 0.02, -0.07)
+        if arg.startswith("spread"):
+            return _one(_cloud(rng, n, rnd_rot(), float(arg[6:]), tc, 2e-3), _weights(rng, n, "random"))
+        if arg == "uniform":
+            R = Rotation.random(n, random_state=int(rng.integers(1 << 31))).as_matrix()
+            return _one(_pose(R, np.asarray(tc) + 2e-3 * rng.standard_normal((n, 3))), _weights(rng, n, "random"))
+        if arg == "two_groups":  # two tight groups 170 degrees apart, 0.6 / 0.4 of the weight
+            Ra = rnd_rot()
+            Rb = Ra * Rotation.from_rotvec(_unit(rng, 1)[0] * np.deg2rad(170.0))
+            P = np.concatenate([_cloud(rng, n // 2, Ra, 0.01, tc, 2e-3), _cloud(rng, n // 2, Rb, 0.01, tc, 2e-3)])
+            w = np.concatenate([0.6 * _weights(rng, n // 2, "random"), 0.4 * _weights(rng, n // 2, "random")])
+            return _one(P, w)
+        if arg == "degenerate":  # two rotations a half turn apart, equal weights: lambda_1 = lambda_2 exactly
+            R = np.stack([np.eye(3), np.diag([1.0, -1.0, -1.0])])
+            return _one(_pose(R, np.array([tc, tc]) + np.array([[1e-3, 0, 0], [-1e-3, 0, 0]])), np.array([0.5, 0.5]))
+        if arg == "single":
+            return _one(_cloud(rng, 1, rnd_rot(), 0.0, tc, 0.0), np.array([1.0]))
+        if arg == "one_weight":  # the whole weight on one particle
+            w = np.zeros(500)
+            w[137] = 1.0
+            return _one(_cloud(rng, 500, rnd_rot(), 0.14, tc, 2e-3), w)
+        raise ValueError(name)
+    if group in ("env", "fin"):  # a cluster `dist` metres from the origin, translation noise sigma (0: collapsed onto ONE pose)
+        if group == "env":
+            dist, sigma, kind, _seed = arg.split("/")
+            n, rot = 1000, None
+        else:                    # the other finishers' sets: fin/<regime>/<N>
+            regime, n = arg.split("/")
+            n, kind = int(n), "random"
+            dist, sigma, rot = {"far": ("1.0", "0.0002", None), "collapsed": ("1.0", "0.0", None), "uniform": ("0.05", "0.002", "uniform"),
+                                "neg": ("0.05", "0.002", None), "zerosum": ("0.05", "0.002", None)}.get(regime, ("0.05", "0.002", regime))
+        dist, sigma = float(dist), float(sigma)
+        tc = dist * np.array([0.6, -0.64, 0.48])  # a unit vector, no coordinate 0
+        if rot is None:
+            P = _cloud(rng, n, rnd_rot(), 0.05 if sigma else 0.0, tc, sigma)
+        elif rot == "uniform":
+            P = _pose(Rotation.random(n, random_state=int(rng.integers(1 << 31))).as_matrix(), tc + sigma * rng.standard_normal((n, 3)))
+        else:                    # "pi_x" ..: centred on the exact half turn
+            P = _cloud(rng, n, Rotation.from_rotvec(np.array(CL_AXES[rot[3:]]) * np.pi), 0.05, tc, sigma)
+        if group == "fin" and regime == "neg":  # weights of mixed sign: no reference applies, the forms agree bit for bit
+            return _one(P, rng.uniform(-1.0, 1.0, n), oracle=False, nonneg=False, reference=False)
+        if group == "fin" and regime == "zerosum":
+            # pairs +a, -a with a in {0.5, 1, 2, 3} (an odd last particle weighs 0): not flat, and the float32 weights add up to
+            # exactly 0 in any order - cluster_close divides every moment by sw == 0.  No reference: the forms agree bit for bit.
+            a = np.repeat(rng.choice([0.5, 1.0, 2.0, 3.0], n // 2), 2) * np.tile([1.0, -1.0], n // 2)
+            w = np.concatenate([a, np.zeros(n - a.shape[0])])
+            assert w.astype(np.float32).sum(dtype=np.float64) == 0.0 and w.max() - w.min() > 1.0
+            return _one(P, w, oracle=False, nonneg=False, reference=False)
+        return _one(P, _weights(rng, n, kind))
+    if group == "flatten":    # float32 weights at the flatten rule's boundary, 1000 particles (four workgroups)
+        n = 1000
+        P = _cloud(rng, n, rnd_rot(), 0.14, (0.05, -0.03, 0.08), 2e-3)
+        d = np.float32(1e-8)
+        pick = rng.integers(0, 2, n).astype(np.float32)
+        pick[:2] = (0.0, 1.0)
+        if arg == "1e-8":
+            w = pick * d
+        elif arg == "above":
+            w = pick * np.nextafter(d, np.float32(1.0))
+        elif arg == "below":
+            w = pick * np.nextafter(d, np.float32(0.0))
+        elif arg == "zero":
+            w = np.full(n, 0.37, dtype=np.float32)
+        elif arg == "signed_zero":
+            w = np.where(pick > 0, np.float32(-0.0), np.float32(0.0)).astype(np.float32)
+        elif arg == "all_zero":
+            w = np.zeros(n, dtype=np.float32)
+        elif arg == "below_f32":  # float64 weights that differ only below float32 resolution
+            w = 0.37 + 1e-12 * rng.uniform(0.0, 1.0, n)
+            assert w.max() > w.min() and np.float32(w.max()) == np.float32(w.min())
+        else:
+            raise ValueError(name)
+        return _one(P, w)
+    if group == "nan":        # two clusters; cluster 0's weights all equal but for one NaN; arg: where ("none": the NaN-free twin)
+        n = 1000
+        labels = (np.arange(n) % 2).astype(np.int64)
+        labels[[0, 600, n - 1]] = 0
+        P = np.empty((n, 4, 4), dtype=np.float32)
+        for c in range(2):
+            m = labels == c
+            P[m] = _cloud(rng, int(m.sum()), rnd_rot(), 0.1, rng.uniform(-0.1, 0.1, 3), 2e-3)
+        w = np.where(labels == 0, 0.37, rng.uniform(0.0, 1.0, n))
+        return dict(poses=P, w=w, labels=labels, label_values=np.arange(2, dtype=np.int64), oracle=True, nonneg=True)
+    raise ValueError(name)
+
+
+def cluster_nan_set(where: str):
+    """The "nan" set with a NaN weight in cluster 0 at particle 0 ("first"), the last particle ("last") or particle 600, in the third
+    workgroup ("block2").  The poses, labels and every other weight are the NaN-free set's."""
+    s = dict(cluster_set("nan/twin"))
+    w = s["w"].copy()
+    w[{"first": 0, "last": -1, "block2": 600}[where]] = np.nan
+    return dict(s, w=w, oracle=False)
+
+
+def cluster_set_names(envelope_seeds: int = CL_ENV_SEEDS):
+    """Every set of tests/test_gpu_cluster_pin.py, by group, and ("fin") the sets of tests/test_gpu_cluster_finishers.py to which a
+    reference with weights >= 0 applies."""
+    return {
+        "size": [f"size/{n}" for n in CL_SIZES],
+        "count": [f"count/{c}" for c in CL_COUNTS],
+        "labels": ["labels/unsorted", "labels/missing", "labels/wide", "labels/neg_t"],
+        "shepperd": [f"pi/{ax}/{ang}" for ax in CL_AXES for ang in CL_PI_ANGLES] + ["straddle/0"],
+        "gap": [f"gap/spread{s}" for s in CL_ROT_SPREADS] + ["gap/uniform", "gap/two_groups", "gap/degenerate", "gap/single", "gap/one_weight"],
+        "env": [f"env/{d}/{s}/{k}/{i}" for d in CL_DISTS for s in CL_SIGMAS for k in CL_WKINDS for i in range(envelope_seeds)],
+        "flatten": [f"flatten/{a}" for a in CL_FLATTEN],
+        "nan": ["nan/twin"],
+        "fin": sorted({n for row in CL_FIN_ROWS for n in row if n.startswith("fin/") and n.split("/")[1] not in ("neg", "zerosum")}),
+    }
+
+
+_CL_REF_CACHE = {}
+
+
+def cluster_set_reference(name: str):
+    """(the set, cluster_reference's records of it) - computed once per process and shared; nobody writes into either."""
+    if name not in _CL_REF_CACHE:
+        s = cluster_set(name)
+        _CL_REF_CACHE[name] = (s, cluster_reference(s["poses"], s["w"], s["labels"], s["label_values"]))
+    return _CL_REF_CACHE[name]

@@ -4,6 +4,7 @@ import pytest
 import torch
 from scipy.spatial.transform import Rotation
 
+from _recipes import assert_cluster, cluster_reference
 from oracle import oracle as orc
 
 
@@ -61,6 +62,8 @@ def test_kernel_matches_oracle(n_per, wdtype):
     assert cnt.cpu().tolist() == [int((labels == u).sum()) for u in uniq]
     assert np.abs(c.cpu().numpy() - ref_c).max() < 2e-6
     np.testing.assert_allclose(s.cpu().numpy(), ref_s, rtol=2e-4, atol=1e-9)
+    # the derived bounds against the exactly summed reference (tests/_recipes.py): an ulp on the translation, 2^-23 on the rotation
+    assert_cluster(c, s, cluster_reference(poses, w, labels, uniq), -(-len(labels) // 256), f"n_per {n_per}")
     # same call twice: bit-identical (fixed summation order, no atomics)
     c2, s2, _ = ops.cluster_centers(torch.as_tensor(poses).to(dev), torch.as_tensor(w).to(dev), torch.as_tensor(labels).to(dev),
                                     torch.as_tensor(uniq).to(dev))
@@ -80,6 +83,7 @@ def test_class_surface_and_empty_label():
     assert cp.shape == (2, 4, 4) and cs.shape == (2, 3) and cp.dtype == torch.float32
     assert np.abs(cp.cpu().numpy() - ref_c).max() < 2e-6
     np.testing.assert_allclose(cs.cpu().numpy(), ref_s, rtol=2e-4, atol=1e-9)
+    assert_cluster(cp, cs, cluster_reference(poses, w, labels, uniq), -(-len(labels) // 256), "class surface")
     c, s, cnt = ops.cluster_centers(parts.poses, parts.weights, parts.labels, torch.tensor([-1, 1, 7], device=dev))
     assert cnt.cpu().tolist() == [400, 800, 0]
     assert torch.isnan(c[2]).all() and torch.isnan(s[2]).all() and not torch.isnan(c[:2]).any()

@@ -44,6 +44,7 @@ def _same(a, b):
 # ---- 1, 5: the plain batched call ---------------------------------------------------------------------
 @pytest.mark.parametrize("N", [1, 255, 256, 4097, 30_011])
 def test_batched_call_matches_single_calls_and_oracle(dev, oracle, N):
+    from _recipes import assert_cluster, cluster_reference
     from midastouch_amd import ops
     from test_cluster_centers import _clustered
     B = 5
@@ -74,6 +75,7 @@ def test_batched_call_matches_single_calls_and_oracle(dev, oracle, N):
         assert np.isfinite(ref_c).all() and np.isfinite(ref_s).all(), (N, b)
         assert np.abs(c[b].cpu().numpy() - ref_c[0]).max() < 2e-6, (N, b)
         np.testing.assert_allclose(s[b].cpu().numpy(), ref_s[0], rtol=2e-4, atol=1e-9)
+        assert_cluster(c[b][None], s[b][None], cluster_reference(poses[b], weights[b], np.zeros(N, dtype=np.int64)), -(-N // 256), f"N {N}, row {b}")
     # the same call twice: the same bits (fixed summation order, no atomics)
     c2, s2 = ops.pose_estimate(P, W)
     assert _same(c, c2) and _same(s, s2)
