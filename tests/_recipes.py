@@ -623,3 +623,115 @@ def cluster_set_reference(name: str):
         s = cluster_set(name)
         _CL_REF_CACHE[name] = (s, cluster_reference(s["poses"], s["w"], s["labels"], s["label_values"]))
     return _CL_REF_CACHE[name]
+
+
+# ---- the resample search: the plain reference and draws that land ON the CDF --------------------------------------------------
+# (tests/test_resample_reference.py on the CPU, tests/test_gpu_resample_pin.py on the GPU; DESIGN.md, "resample search")
+U_MAX = 1.0 - 2.0 ** -53   # the largest draw of a 53-bit uniform
+RS_KINDS = ("on", "below", "above", "ends")
+RS_SIZES = (1, 2, 15, 16, 17, 255, 256, 257, 4095, 4096, 4097, 8193)
+
+
+def expected_slots(cdf, u, upper):
+    """The rule every search claims, by numpy: the lower bound (first slot whose entry is >= u: torch.multinomial), or the upper bound
+    (first slot whose entry is > u: the reference's `sampleLocs[c] < weightsSum[i]` loop); a draw beyond the last entry takes N - 1."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    return np.minimum(np.searchsorted(cdf, np.asarray(u, dtype=np.float64), "right" if upper else "left"), cdf.shape[0] - 1).astype(np.int32)
+
+
+def systematic_locs(M, u32):
+    """The low-variance sampler's locations restated (modules/particle_filter.py:254-261): float32 offset, float64 grid, fmod 1."""
+    off = np.float32(u32) / np.float32(M)
+    return np.fmod(np.arange(M, dtype=np.float64) / float(M) + np.float64(off), 1.0)
+
+
+def tie_share(cdf, u):
+    """Fraction of the draws that EQUAL a CDF entry."""
+    u = np.asarray(u, dtype=np.float64)
+    return float(np.isin(u, np.asarray(cdf, dtype=np.float64)).mean()) if u.size else 0.0
+
+
+def structural_slots(cdf, guide_unit=4):
+    """The slots at which a search changes table, line or path: the ends of the 16-slot chunks, the 256-slot groups and the
+    4096-slot blocks with the slot before and after each; the guide-unit ends (units of 4, which contain those of 8 and 16: any
+    layout midas_lazy_guide_layout reports); the first and the last valid slot (an entry above its predecessor); both ends of every
+    flat run; slot 0, N - 2 and N - 1."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    N = cdf.shape[0]
+    pick = [np.array([0, N - 2, N - 1])]
+    for step in (16, 256, 4096):
+        e = np.arange(step - 1, N, step)
+        pick += [e - 1, e, e + 1]
+    pick.append(np.arange(guide_unit - 1, N, guide_unit))
+    rises = np.flatnonzero(np.diff(np.concatenate([[0.0], cdf])) != 0.0)   # slots that carry weight
+    if rises.size:
+        pick.append(rises[[0, -1]])
+    same = np.diff(cdf) == 0.0                                             # slot i + 1 repeats slot i
+    starts = np.flatnonzero(same & ~np.concatenate([[False], same[:-1]]))
+    stops = np.flatnonzero(same & ~np.concatenate([same[1:], [False]])) + 1
+    pick += [starts, stops]
+    s = np.unique(np.concatenate(pick))
+    return s[(s >= 0) & (s < N)]
+
+
+def crafted_draws(cdf, kind, rng, M=None, guide_unit=4):
+    """M (default N) float64 draws in [0, 1) made from the CDF's own entries, in an `rng` order:
+      "on"     every distinct entry itself; with more distinct entries than draws the entries of structural_slots first, then an
+               rng sample of the rest;
+      "below", "above"  nextafter of the same entries towards 0 and towards 1;
+      "ends"   0, 2^-53, 1 - 2^-53, cdf[N - 2] and its two neighbours, the midpoints of the first and of the last interval.
+    A value >= 1 (the last entry is 1) becomes 1 - 2^-53.  "below" leaves out the entry 0.0 (a run of pruned particles at the start:
+    nothing lies below it).  Spare draws - a frame that lost nine particles in ten has a tenth as many distinct entries as draws -
+    come from rng: three in four an entry drawn again (the same treatment), one in four a plain rng.random()."""
+    cdf = np.asarray(cdf, dtype=np.float64)
+    N = cdf.shape[0]
+    M = N if M is None else int(M)
+    if kind == "ends":
+        distinct = np.unique(cdf)
+        vals = [0.0, 2.0 ** -53, U_MAX]
+        if N >= 2:
+            vals += [cdf[N - 2], np.nextafter(cdf[N - 2], 0.0), np.nextafter(cdf[N - 2], 1.0)]
+        pos = distinct[distinct > 0.0]
+        vals += [0.5 * pos[0], 0.5 * ((distinct[-2] if distinct.size > 1 else 0.0) + distinct[-1])]
+        vals = np.array(vals)
+    elif kind in ("on", "below", "above"):
+        first = np.unique(cdf[structural_slots(cdf, guide_unit)])
+        rest = np.setdiff1d(np.unique(cdf), first)
+        if first.size > M:
+            first = rng.choice(first, M, replace=False)
+        rest = rng.choice(rest, min(rest.size, M - first.size), replace=False)
+        vals = np.concatenate([first, rest])
+        if kind == "below":
+            vals = vals[vals > 0.0]
+        if vals.size and vals.size < M:
+            vals = np.concatenate([vals, rng.choice(vals, 3 * (M - vals.size) // 4)])
+        if kind == "below":
+            vals = np.nextafter(vals, 0.0)
+        elif kind == "above":
+            vals = np.nextafter(vals, 1.0)
+    else:
+        raise ValueError(kind)
+    vals = vals[:M]
+    u = np.concatenate([vals, rng.random(M - vals.shape[0])])
+    u = np.where(u >= 1.0, U_MAX, u)
+    assert u.shape == (M,) and (u >= 0.0).all() and (u < 1.0).all()
+    return np.ascontiguousarray(u[rng.permutation(M)])
+
+
+def tie_weights(N, pruned):
+    """The masks of the tie frames: raw weights of exactly 1.0 (or -1.0) * mask.  pruned: "all" valid, every other particle
+    ("half"), the second half, the first half, the last particle alone, or the first k particles ("lead<k>")."""
+    m = np.ones(N, dtype=bool)
+    if pruned == "half":
+        m[1::2] = False
+    elif pruned == "second":
+        m[N // 2:] = False
+    elif pruned == "first":
+        m[: N // 2] = False
+    elif pruned == "last":
+        m[N - 1] = False
+    elif pruned.startswith("lead"):
+        m[: int(pruned[4:])] = False
+    elif pruned != "all":
+        raise ValueError(pruned)
+    return m
