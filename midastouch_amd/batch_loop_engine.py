@@ -138,7 +138,7 @@ class BatchLoopEngine:
         nb, nb256 = (cap + 4095) // 4096, (cap + 255) // 256
         frame = 32 * cap + 32 * nb + 8 * 64 * 10 + 8 * 36 * 64 * nb256 + 4 * 64 * 16 + 4 * 64 * 3 + 8 * 64 + 8 * (cap + 16) + 12 * nb
         if self.wide and cap > _lib.LOOP_BATCH_MAX_CAP:
-            # the radix selection per trajectory (loop.hip select_scratch): 6 x 2048 histogram words, 32 state words, two block counts
+            # the radix selection per trajectory (anneal.hip select_scratch): 6 x 2048 histogram words, 32 state words, two block counts
             # a summation block, and cap / 3 + 1 (key, index) pairs twice - selected, then sorted
             frame += 4 * 6 * 2048 + 4 * 32 + 2 * 4 * nb + 2 * (8 + 4) * (cap // 3 + 1)
         if self.batched_dbscan:

@@ -1,6 +1,6 @@
 // cluster_rot.hpp - the rotation part of a cluster centre (Markley's quaternion mean, modules/pose.py:112-147): the
 // eigenvector of the largest eigenvalue of sum w q q^T / sum w by repeated squaring in float64, written as a rotation matrix.
-// Shared by cluster.hip (midas_cluster_centers) and loop.hip (the loop step computes it beside the annealing).
+// Shared by cluster.hip (midas_cluster_centers) and anneal_decide.hpp (the loop step computes it beside the annealing: loop_rotations).
 #pragma once
 #include "midas_internal.hpp"
 

@@ -1,6 +1,6 @@
 // loop_weights.hpp - the weights of a loop frame from k_loop_xe's block results: S = blocks summed in order, the isclose guard,
 // w = (e or x) / S * valid, every particle back onto its codebook pose when all of them were pruned (filter.py:176-179), and -
-// first workgroup - the control block and the rmse (particle_filter.py:449-470).  Shared by k_loop_weights (loop.hip) and by
+// first workgroup - the control block and the rmse (particle_filter.py:449-470).  Shared by k_loop_weights (loop_weights.hip) and by
 // k_loop_weights_moments (cluster.hip: the same work at the head of the cluster-moment launch, one launch less per frame).
 // Every function is called by all 256 threads of the workgroup.
 #pragma once

@@ -150,6 +150,8 @@ int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* deta
         if (_e != hipSuccess) return midas_set_error((ctx), MIDAS_ERR_HIP, #expr, hipGetErrorString(_e)); \
     } while (0)
 
+#define LAUNCH_CHECK(ctx) MIDAS_HIP_CHECK(ctx, hipGetLastError())
+
 #define MIDAS_REQUIRE(ctx, cond)                                                       \
     do {                                                                               \
         if (!(cond)) return midas_set_error((ctx), MIDAS_ERR_INVALID, #cond, "invalid argument"); \
@@ -165,9 +167,10 @@ int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* deta
         return (int)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&kernel));     \
     }
 #define MIDAS_WARM_DECL(name) int warm_##name();
-// (warm_particles also loads the units cut out of particles.hip - tree, front, front_folded, front_batch - and warm_resample those
-// cut out of resample.hip - tail, shard_route: their warm functions are declared and chained in particles.hip and resample.hip,
-// so midas_ctx_create's list of units stays as it is)
+// (warm_particles also loads the units cut out of particles.hip - tree, front, front_folded, front_batch -, warm_resample those
+// cut out of resample.hip - tail, shard_route - and warm_loop the phases of a loop frame - loop_weights, anneal, anneal_small,
+// loop_resample: their warm functions are declared and chained in particles.hip, resample.hip and loop.hip, so midas_ctx_create's
+// list of units stays as it is)
 namespace midas {
 MIDAS_WARM_DECL(score) MIDAS_WARM_DECL(particles) MIDAS_WARM_DECL(resample) MIDAS_WARM_DECL(cluster) MIDAS_WARM_DECL(topn)
 MIDAS_WARM_DECL(selfsim) MIDAS_WARM_DECL(loop) MIDAS_WARM_DECL(dbscan) MIDAS_WARM_DECL(dbscan_nd) MIDAS_WARM_DECL(index_build)
@@ -596,7 +599,7 @@ int launch_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* 
 struct LoopWeightsArgs;  // loop_weights.hpp
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop.hip)
+                        const LoopWeightsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop_weights.hip)
                         int32_t B = 1);  // trajectories (grid.y): every array (B, ...) contiguous, the scratch ones included
 
 // loop.hip / dbscan.hip - the reference's whole loop body on a variable-size particle set (midas_loop_step)
@@ -605,6 +608,47 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                            const midas_loop_args& a, int32_t phases, int32_t B, int64_t log_stride,
                            bool wide = false);  // midas_loop_step_batch_wide: capacities beyond the small-set regime
+
+// The phases of a loop frame, what launch_loop_step and launch_loop_step_batch launch alike: each is the host launcher of the unit
+// that holds its kernels.  What they are launched over - the single call: one trajectory, the slice strides 0 (the kernels' defaults).
+struct LoopGrid {
+    int64_t cap;               // particles of a trajectory the grids cover
+    int32_t B = 1;             // trajectories = the grid's y: every array - the caller's and the scratch - (B, ...) contiguous
+    int32_t slice = 0;         // a batch: particles between two trajectories' slices of the (B, ...) arrays,
+    int32_t lp_stride = 0;     //          prefix values between their tables,
+    int64_t log_stride = 0;    //          doubles between their log rows
+    double* clocks = nullptr;  // MIDAS_ANNEAL_CLOCKS (the single call): k_loop_xe's phase clocks
+    unsigned nbcap() const { return (unsigned)ceil_div(cap, SCAN_BLOCK); }
+    unsigned by() const { return (unsigned)B; }
+    bool batch() const { return slice != 0; }
+};
+inline int32_t loop_bound(int64_t n) { return (int32_t)(n < (1 << 30) ? n : (1 << 30)); }  // a particle bound as the kernels take it
+// loop_weights.hip - FRONT, second half: k_loop_xe, then the weights - launched, or (merged) left in `wa` for the cluster-moment launch
+bool loop_weights_mergeable(int32_t phases);
+int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t K, bool rmse, bool merged, LoopWeightsArgs& wa);
+// anneal.hip - ANNEAL behind the clusters' moments (loop_cluster_phase, loop.hip): the decision and the annealed set as an index list
+struct LoopMoments { float *cen, *sd; int64_t* cnt; double* rot; };
+enum class LoopAnneal {
+    frozen,     // the caller said annealing cannot act: the decision's bookkeeping alone
+    aten_walk,  // the decision, then ATen's CPU tie choices (topk_aten.hip)
+    small,      // sets up to LOOP_SMALL_MAX (anneal_decide.hpp): decision and selection by one workgroup (anneal_small.hip)
+    select      // the decision, then the radix select's ten launches
+};
+inline LoopAnneal loop_anneal_regime(bool frozen, bool aten, bool small) {
+    return frozen ? LoopAnneal::frozen : aten ? LoopAnneal::aten_walk : small ? LoopAnneal::small : LoopAnneal::select;
+}
+int loop_anneal_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopMoments& m, LoopAnneal regime);
+// anneal_small.hip - the decision alone, for the regimes of anneal.hip (hist / sel_state: the select state it clears, or null)
+int launch_loop_decide(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopMoments& m, uint32_t* hist,
+                       int32_t* sel_state, int32_t frozen, int32_t aten_order);
+// the single-workgroup annealing of B trajectories: with the decision from the moments m (a second workgroup
+// writes the centres' rotations), or - m null - on a plan the host left in ctl_i (launch_anneal_select)
+int launch_anneal_small(midas_ctx* ctx, const LoopGrid& g, int32_t* ctl_i, double* ctl_d, const LoopMoments* m, float* centers_out,
+                        float* stds_out, int32_t floor_n, const double* w, int32_t* src);
+// loop_resample.hip - RESAMPLE over the cap2 slots a trajectory the annealed set may take; stream_draws, a call that ends in front of
+// it: ctl_i[NDRAW]
+int loop_resample_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t cap2);
+int loop_ndraw_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t cap2);
 // src[0 .. n_set): the annealed particle set as indices - mode 1: the N particles minus the k of smallest weight, in
 // order; mode 2: all N followed by the k of largest weight, best first; ties to the smaller index
 int launch_anneal_select(midas_ctx* ctx, int64_t N, const double* w, int32_t mode, int64_t k, int32_t ties, int32_t* src, int32_t* info);

@@ -71,6 +71,11 @@ MD double block_total(const double* v, double* s_gtot) {
     return W;
 }
 
+// Where slot i of a 4096-slot block sits in LDS when the slots are read and written slot-per-lane in memory and summed in the
+// chunk-per-thread view (k_loop_xe, k_loop_scan): i + i / 16 - thread t's chunk starts at 17 t, the chunk reads are spread over the banks.
+MD int lds_chunk_pos(int i) { return i + (i >> 4); }
+constexpr int LDS_CHUNK_DOUBLES = SCAN_BLOCK + SCAN_BLOCK / 16;
+
 // One 4096-slot block by one 256-thread workgroup, thread t owning the chunk of slots [16 t, 16 t + 16) - the view the
 // summation spec is written in, so nothing is transposed: x = scores[nn_idx], e = exp(x - 1), e*valid, block sums,
 // block-local prefix, chunk-end and group-end tables, block extrema of x; the raw-score variant only when the block's own

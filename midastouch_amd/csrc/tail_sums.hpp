@@ -6,8 +6,6 @@
 
 namespace midas {
 
-#define LAUNCH_CHECK(ctx) MIDAS_HIP_CHECK(ctx, hipGetLastError())
-
 constexpr int TB_MAX_BLOCKS = 1024;  // 4 M particles (per GPU in the fused step, in total in the sharded step)
 
 MD double wmax(double v) {

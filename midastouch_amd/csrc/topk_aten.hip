@@ -20,14 +20,12 @@
 //     (tests/test_gpu_topk_aten.py builds such inputs with the oracle's adversary).
 //
 // Spec: oracle/aten_topk.c, pinned against torch.topk (tests/test_aten_topk.py).  One wave per call; 0.3 - 5 ms at
-// N = 100k: this is the mode that follows the reference move for move, not the fast one (loop.hip's radix select, ties by index).
+// N = 100k: this is the mode that follows the reference move for move, not the fast one (anneal.hip's radix select, ties by index).
 // A batch of trajectories (midas_loop_step_batch_draws) runs B such waves side by side, one workgroup each, on B queues.
 #include "midas_internal.hpp"
 #include "midas_math.hpp"
 
 namespace midas {
-
-#define LAUNCH_CHECK(ctx) MIDAS_HIP_CHECK(ctx, hipGetLastError())
 
 struct alignas(16) TkPair { double v; int32_t i; int32_t pad; };
 

@@ -15,7 +15,7 @@ torch = pytest.importorskip("torch")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
-# switch -> value that selects the non-default path (front.hip, front_batch.hip, tree.hip, tail.hip, loop.hip, index_build.hip, api.hip)
+# switch -> value that selects the non-default path (front.hip, front_batch.hip, tree.hip, tail.hip, loop.hip, anneal.hip, index_build.hip, api.hip)
 SWITCHES = [
     ("MIDAS_TAIL_GROUPED", "0"),     # step tail: 25 workgroups instead of 391 waves with hand-over records
     ("MIDAS_TB2_TAB", "1"),          # flush: tables in LDS

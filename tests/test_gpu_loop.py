@@ -340,6 +340,41 @@ def test_loop_engine_frozen_annealing_runs_the_decision_only(dev, oracle, N0):
         bad.read_log()
 
 
+def test_loop_engine_frozen_annealing_under_the_aten_tie_rule(dev, oracle):
+    """The frozen decision of the single call with `topk_ties="aten_cpu"`: the spreads in the two-pass form, var added in ATen's
+    order, no selection - the one pairing of annealing regime and tie rule no other test reaches.  300 particles, one DBSCAN frame
+    and two annealing frames behind it, each the oracle's loop body under the same rule and identical to an engine that keeps the
+    launches (the ATen walk finds mode 0 and leaves the identity)."""
+    from midastouch_amd.loop_engine import LoopEngine
+    from midastouch_amd.synthetic import make_codebook, make_trajectory
+    N0, K, D, T, seed = 300, 3000, 256, 3, 4301
+    cb = make_codebook(K=K, D=D, seed=1014, mesh_points=20000)
+    traj = make_trajectory(cb, T=T + 1, seed=2014)
+    rng = np.random.default_rng(5)
+    loop = oracle.OracleLoop(cb.poses, cb.embeddings, cb.mesh_vertices, cluster=True, cluster_every=5, floor=N0, ties="aten_cpu")
+    poses = cb.poses[rng.integers(0, K, N0)]
+    engs = []
+    for allow in (True, False):
+        e = LoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N0, seed=seed, floor=N0, cluster_every=5, topk_ties="aten_cpu", device=dev)
+        e.allow_frozen = allow
+        e.set_particles(torch.as_tensor(poses))
+        assert e._frozen() is allow
+        engs.append(e)
+    labels = np.zeros(N0, dtype=np.int64)
+    for t in range(T):
+        tn, rot = oracle.philox_noise(N0, seed, t, np.float32(2e-4), np.float32(0.5))
+        ref = loop.step(poses, labels, traj.odoms[t + 1], traj.codes[t + 1], tn, rot, gt=traj.gt_poses[t + 1], mode="weighted_random",
+                        draws=lambda n2: oracle.philox_uniform64(n2, seed, t))
+        assert ref["N"] == N0
+        for e in engs:
+            e.step(torch.as_tensor(traj.odoms[t + 1]), torch.as_tensor(traj.codes[t + 1]), gt=torch.as_tensor(traj.gt_poses[t + 1]))
+            _compare_frame(e.frame_view(), ref, t, t % 5 == 0)
+        poses, labels = ref["poses"], ref["labels"]
+    for ra, rb in zip(*[e.read_log() for e in engs]):
+        assert ra["n_after"] == rb["n_after"] == N0 and ra["mode"] == rb["mode"] == 0 and ra["err"] == rb["err"] == 0
+        assert np.array_equal(ra["cluster_poses"], rb["cluster_poses"]) and np.array_equal(ra["cluster_stds"], rb["cluster_stds"])
+
+
 def test_loop_engine_replays_reference_loop_trace(dev, golden, oracle):
     """G13 (the reference's loop body with DBSCAN + annealing, N0 = 4096, 64 frames) with the reference's host draws in
     its order - tn, rot, then, once the annealed size is known, the resampler's uniforms (the frame is split there) - and
