@@ -65,6 +65,11 @@ MD float aten_sum_f32(const float* __restrict__ x, int n) {
     return fin;
 }
 
+// Python's int(x) of a float32 x >= 0 in front of a min(.., cap - 1): the truncation where it fits, `cap` from there on (and for +inf).
+// The reference's int is unbounded, so a product of 2^31 and more - a tiny previous spread - still ends at the cap of its min; a bare
+// (int)x is undefined there.  Every x below cap converts as before; NaN does not get here (neither branch of the rule takes it).
+MD int trunc_capped(float x, int cap) { return x >= (float)cap ? cap : (int)x; }
+
 // One workgroup: the clusters present (labels ascending) -> compact rows, var = float32 sum of their stds / count
 // (torch.mean(cluster_stds), filter.py:189; a running sum, or ATen's order: loop_decide), then particle_filter.annealing's rule (:413-447) in the float32 arithmetic torch
 // uses for `var / self.particle_var`, `1.0 - ratio` and `* N`.  Also clears the select histograms.
@@ -106,13 +111,13 @@ MD void loop_decide(int32_t* __restrict__ ctl_i, double* __restrict__ ctl_d, con
         const float ratio = var / prev;
         ctl_d[LOOP_D_VARPREV] = (double)var;
         if (ratio < 1.0f) {
-            const int a = (int)((1.0f - ratio) * (float)n);
+            const int a = trunc_capped((1.0f - ratio) * (float)n, n / 3 + 1);
             const int b = n - floor_n < 0 ? floor_n - n : n - floor_n;
             k = a < b ? a : b;
             k = k < n / 3 ? k : n / 3;
             mode = k > 0 ? 1 : 0;
         } else if (ratio > 1.0f) {
-            const int a = (int)((ratio - 1.0f) * (float)n);
+            const int a = trunc_capped((ratio - 1.0f) * (float)n, n / 3 + 1);
             k = a < n / 3 ? a : n / 3;
             mode = (k + n > ctl_i[LOOP_I_INIT] || k <= 0) ? 0 : 2;
         }

@@ -735,3 +735,150 @@ def tie_weights(N, pruned):
     elif pruned != "all":
         raise ValueError(pruned)
     return m
+
+
+# ---- the annealing rule: the float32 decision restated, its mutants, inputs at its edges -----------------------------------------
+# (tools/gen_anneal_rule.py writes G15 from these; tests/test_anneal_rule_reference.py on the CPU, tests/test_gpu_anneal_rule.py on
+# the GPU; DESIGN.md, "The annealing rule's arithmetic")
+ANNEAL_MUTANTS = ("f64", "f64_product", "reciprocal")
+ANNEAL_SEARCH_KEEP = 16    # discriminating cases kept per mutant
+ANNEAL_SEPARATE_MIN = 8    # ... of which a recipe must hold at least this many (f64_product: sets of at most 300 particles)
+# the sets of fixture G15 as (var, n, floor, init, main): main sets carry the discriminating search's conditions; the others are the
+# rule's small and one-sided regimes (n < floor: the reference's abs lets it remove; n in 1 .. 4: n // 3 is 0 or 1)
+ANNEAL_FIXTURE_SETS = (
+    (0.0123456, 300, 100, 400, True),   # the cap by n // 3 bites (|n - floor| = 200), room to grow by n // 3 exactly
+    (3.3e-4, 299, 150, 398, True),      # n + n // 3 == init: the largest duplication fills the set to its last slot
+    (0.0123456, 300, 250, 340, False),  # the cap by |n - floor| bites (50 < n // 3), growth stops at 40 < n // 3
+    (0.0123456, 200, 300, 300, False),  # n < floor
+    (3.3e-4, 1, 8, 8, False), (3.3e-4, 2, 8, 8, False), (3.3e-4, 3, 8, 8, False), (3.3e-4, 4, 8, 8, False),
+)
+
+
+def f32_bits(x):
+    return np.asarray(x, dtype=np.float32).view(np.uint32)
+
+
+def f32_from_bits(b):
+    return np.asarray(b, dtype=np.uint32).view(np.float32)
+
+
+def anneal_rule(var, prev, n, floor, init, variant="f32"):
+    """particle_filter.annealing's rule (modules/particle_filter.py:422-447) behind the first-call and var == 0 exits, over an array
+    of previous spreads `prev` (float32): ratio = var / prev; ratio < 1: k = min(int((1 - ratio) * n), |n - floor|, n // 3), remove
+    if k; ratio > 1: k = min(int((ratio - 1) * n), n // 3), duplicate if k and k + n <= init.  `int` is Python's: unbounded, and an
+    OverflowError on an infinite product.  -> (mode, k) int64 arrays: mode 1 remove, 2 duplicate, 0 nothing (k = 0), -1 raises.
+    variant "f32": every operation in float32, as torch evaluates it on 0-dim float32 tensors - THE rule.  The mutants: "f64" all in
+    float64; "f64_product" the float32 ratio, then 1 - ratio and the product in float64; "reciprocal" var * (1 / prev) in float32."""
+    var, prev, n = np.float32(var), np.atleast_1d(np.asarray(prev, dtype=np.float32)), int(n)
+    one, nf = np.float32(1.0), np.float32(n)
+    with np.errstate(all="ignore"):
+        if variant == "f64":
+            ratio = np.float64(var) / prev.astype(np.float64)
+            lo, hi = (1.0 - ratio) * float(n), (ratio - 1.0) * float(n)
+        elif variant == "f64_product":
+            ratio = (var / prev).astype(np.float32)
+            lo, hi = (1.0 - ratio.astype(np.float64)) * float(n), (ratio.astype(np.float64) - 1.0) * float(n)
+        elif variant in ("f32", "reciprocal"):
+            ratio = (var / prev if variant == "f32" else var * (one / prev)).astype(np.float32)
+            lo, hi = (one - ratio) * nf, (ratio - one) * nf
+            assert lo.dtype == np.float32 and hi.dtype == np.float32
+        else:
+            raise ValueError(variant)
+        lo, hi = np.trunc(lo.astype(np.float64)), np.trunc(hi.astype(np.float64))
+        k1 = np.minimum(np.minimum(lo, float(abs(n - int(floor)))), float(n // 3))
+        k2 = np.minimum(hi, float(n // 3))
+        remove, grow = (ratio < 1) & (k1 > 0), (ratio > 1) & (k2 > 0) & (k2 + n <= int(init))
+        raises = (ratio > 1) & np.isinf(hi)
+    mode = np.where(raises, -1, np.where(remove, 1, np.where(grow, 2, 0))).astype(np.int64)
+    k = np.where(mode == 1, k1, np.where(mode == 2, k2, 0.0)).astype(np.int64)
+    return mode, k
+
+
+def _ulp_steps(x, steps):
+    """The float32 values `steps` ulps away from each positive finite x (an array per x, flattened in order)."""
+    b = f32_bits(x).astype(np.int64).reshape(-1, 1) + np.asarray(steps, dtype=np.int64).reshape(1, -1)
+    return f32_from_bits(b.reshape(-1).astype(np.uint32))
+
+
+def _prev_for(var, n, m, sign):
+    """float32(var / float32(1 -+ m / n)): the previous spread at which |1 - ratio| * n stands at the integer m."""
+    return np.float32(np.float64(np.float32(var)) / np.float64(np.float32(1.0 - sign * np.asarray(m, dtype=np.float64) / n)))
+
+
+def recipe_anneal_rule_cases(var, n, floor, init):
+    """The inputs of one annealing decision at the rule's edges, for a frame of mean cluster spread `var` (float32, > 0) over n
+    particles: a list of dicts tag, kind, prev (np.float32: particle_var before the call; inf: the first call), var (np.float32).
+
+    kind "target": for m in {0, 1, 2, n // 7, |n - floor| - 1 .. + 1, n // 3 - 1 .. + 1, init - n - 1 .. + 1} within [0, n) and both
+    signs, prev0 = float32(var / float32(1 -+ m / n)) and its neighbours 1 and 2 ulps either side (m = 0: prev == var, the ratio
+    exactly 1 and one ulp beside it).
+    kind "search": m = 1 .. min(|n - floor|, n // 3) - 1 below 1 and 1 .. min(n // 3, init - n) - 1 above, prev0 and 4 ulps either
+    side, the float32 rule against each of ANNEAL_MUTANTS: the first ANNEAL_SEARCH_KEEP inputs (m ascending, removal first, ulps
+    ascending) on which a mutant decides otherwise.
+    kind "special": prev NaN (nothing, the state becomes var), 1e-12 (the product finite and beyond 2^31), inf (first call).
+    kind "var0": var == 0 on a set prev (the state stays).   kind "out_of_spec": prev == 0, the ratio infinite: the reference raises.
+    Everything is a function of (float32 var, n, floor, init) alone."""
+    var, n, floor, init = np.float32(var), int(n), int(floor), int(init)
+    assert var > 0 and n >= 1
+    gap = abs(n - floor)
+    cases, seen = [], set()
+
+    def add(tag, kind, prev, v=var):
+        key = (int(f32_bits(prev)), int(f32_bits(v)))
+        if key not in seen:
+            seen.add(key)
+            cases.append(dict(tag=tag, kind=kind, prev=np.float32(prev), var=np.float32(v)))
+
+    for tag, p in (("nan", np.nan), ("tiny", 1e-12), ("first", np.inf)):
+        add(tag, "special", np.float32(p))
+    add("var0", "var0", np.float32(2.0) * var, np.float32(0.0))
+    add("prev0", "out_of_spec", np.float32(0.0))
+    targets = sorted({m for m in (0, 1, 2, n // 7, gap - 1, gap, gap + 1, n // 3 - 1, n // 3, n // 3 + 1, init - n - 1, init - n, init - n + 1)
+                      if 0 <= m < n})
+    for m in targets:
+        for sign, sn in ((1, "-"), (-1, "+")):
+            for d, p in zip((0, 1, -1, 2, -2), _ulp_steps(_prev_for(var, n, m, sign), (0, 1, -1, 2, -2))):
+                add(f"m{sn}{m}{d:+d}", "target", p)
+    # the discriminating search
+    ms, sg = [], []
+    for sign, top in ((1, min(gap, n // 3)), (-1, min(n // 3, init - n))):
+        ms += list(range(1, max(top, 1)))
+        sg += [sign] * (max(top, 1) - 1)
+    if ms:
+        order = np.lexsort((np.asarray(sg) < 0, np.asarray(ms)))  # m ascending, removal first
+        ms, sg = np.asarray(ms)[order], np.asarray(sg)[order]
+        steps = np.arange(-4, 5)
+        prevs = _ulp_steps(_prev_for(var, n, ms, sg), steps)
+        rule = anneal_rule(var, prevs, n, floor, init)
+        for mut in ANNEAL_MUTANTS:
+            other = anneal_rule(var, prevs, n, floor, init, mut)
+            for j in np.flatnonzero((rule[0] != other[0]) | (rule[1] != other[1]))[:ANNEAL_SEARCH_KEEP]:
+                add(f"s{'-' if sg[j // 9] > 0 else '+'}{ms[j // 9]}{steps[j % 9]:+d}", "search", prevs[j])
+    return cases
+
+
+def anneal_rule_separations(cases, n, floor, init):
+    """How many of the recipe's cases (var > 0, finite prev) each mutant decides otherwise than the float32 rule."""
+    live = [c for c in cases if c["var"] > 0 and np.isfinite(c["prev"]) and c["prev"] > 0]
+    var = {int(f32_bits(c["var"])) for c in live}
+    assert len(var) == 1  # (one frame's cases)
+    var, prev = f32_from_bits(var.pop())[()], np.array([c["prev"] for c in live], dtype=np.float32)
+    rule = anneal_rule(var, prev, n, floor, init)
+    out = {}
+    for mut in ANNEAL_MUTANTS:
+        other = anneal_rule(var, prev, n, floor, init, mut)
+        out[mut] = int(((rule[0] != other[0]) | (rule[1] != other[1])).sum())
+    return out
+
+
+def assert_anneal_recipe_conditions(cases, n, floor, init, what="", one_sided=False):
+    """The conditions that keep a recipe honest (not measurements): at least ANNEAL_SEPARATE_MIN of its cases separate the float32
+    rule from the float64 rule and from the reciprocal division, and - for sets of at most 300 particles - from the float64 product.
+    one_sided: a set whose floor or init_particles cuts the rule's range on one side to under n // 3 (the regimes beside the main
+    set: |n - floor| or init - n small) has too few integers in reach for the float64 product, which parts from the rule on about
+    eight inputs per hundred integers scanned; the other two conditions hold there as well."""
+    sep = anneal_rule_separations(cases, n, floor, init)
+    assert sep["f64"] >= ANNEAL_SEPARATE_MIN and sep["reciprocal"] >= ANNEAL_SEPARATE_MIN, (what, sep)
+    if n <= 300 and not one_sided:
+        assert sep["f64_product"] >= ANNEAL_SEPARATE_MIN, (what, sep)
+    return sep

@@ -18,6 +18,9 @@ as-is produce the outputs stored here:
   G10 a T-step trace of the filter.py loop body (filter/filter.py:150-190) - written by
       tools/gen_trace_golden.py because it needs the oracle for the two ops the reference
       cannot run here (SO3 log-map, KD-tree).
+  G15 particle_filter.annealing, one decision per case at the edges of its float32 rule
+      (modules/particle_filter.py:413-447) - written by tools/gen_anneal_rule.py from the
+      recipe in tests/_recipes.py, with this file's import_reference, new_pf and marker_poses.
 
 A fixture is data only: inputs + the reference's outputs (+ the RNG draws it consumed).
 Usage:  python tools/gen_goldens.py            (rewrites tests/golden/*.npz)
