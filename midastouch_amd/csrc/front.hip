@@ -12,7 +12,7 @@ namespace midas {
 template <bool STATS>
 __global__ __launch_bounds__(64) void k_particle_update(TreeView<Kd6> t6, TreeView<Kd3> t3, ParticleUpdateArgs a) {
     __shared__ double s_cd[KD_MAX_LEVELS * 64];  // child-distance columns, reused by both searches
-    particle_update_wave<false, false, false, STATS>(t6, t3, a, blockIdx.x, gridDim.x, blockIdx.y, s_cd);
+    particle_update_wave<false, false, false, STATS, false, true>(t6, t3, a, blockIdx.x, gridDim.x, blockIdx.y, s_cd);
 }
 
 int launch_particle_update(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a_in) {
@@ -111,7 +111,7 @@ MD float dpp_f32(float v) { return __uint_as_float(dpp_u32<CTRL>(__float_as_uint
 // lane, with two lanes two; header + 16 records of the vertex list are one round trip either way.
 static_assert(NN_SOLO == 32 && MESH_SOLO == 16, "the group scans fetch 32 / 16 records");
 #ifndef MIDAS_NNP_OCC
-#define MIDAS_NNP_OCC 2  // the two-kernel form only serves small sets now (<= 10 240 particles, the loop step): registers over occupancy
+#define MIDAS_NNP_OCC 2  // the two-kernel form only serves small sets now (launch_frame_front's split_front: a pipelined set of <= 512 particles, a plain one of <= 2048, a live-count set of <= 16 384 - the loop step): registers over occupancy
 #endif
 template <int LPP>
 MD void particle_nn_prune_wg(const TreeView<Kd6>& t6, const TreeView<Kd3>& t3, ParticleUpdateArgs a, const PuFeat* __restrict__ feat) {

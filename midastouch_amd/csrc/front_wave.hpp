@@ -189,7 +189,9 @@ MD int64_t lazy_source(const LazyResample& rs, const double* rs_lds, int64_t n, 
 // STATS (profiling instantiations only, chosen by MIDAS_ABLATE != 0): per-wave phase clocks, scan statistics and the ablation
 // switches; the production instantiations read no clock and test no switch
 // PRES: the presorted form (pre_order / pre_src, batch kernels only) is compiled in; elsewhere the arguments are ignored
-template <bool WT = false, bool SCREEN = false, bool PREF = false, bool STATS = false, bool PRES = false>
+// NANPART: the per-wave extrema of x carry a NaN score on (k_particle_update alone: the one kernel whose partials a guard reads -
+// the eager step's legacy tail, k_tail_a; every other form of the tail gathers the scores itself)
+template <bool WT = false, bool SCREEN = false, bool PREF = false, bool STATS = false, bool PRES = false, bool NANPART = false>
 MD void particle_update_wave(const TreeView<Kd6>& t6, const TreeView<Kd3>& t3, ParticleUpdateArgs a, int64_t wave,
                              int nwaves, int traj, double* s_cd, double* rs_lds = nullptr) {
     const int lane = threadIdx.x & 63;
@@ -418,6 +420,9 @@ MD void particle_update_wave(const TreeView<Kd6>& t6, const TreeView<Kd3>& t3, P
     const double NEG = -INFINITY, POS = INFINITY;
     if (a.scores) {
         double mx = wave_max(live ? x : NEG), mn = wave_min(live ? x : POS);
+        // NaN never wins a comparison: a wave with a NaN score hands on NaN extrema (torch.max / min propagate it), which is where
+        // block_extrema looks for it - the guard is then open and every weight NaN, not the raw scores of a collapsed cloud
+        if (NANPART && __any(live && x != x)) { mx = NAN; mn = NAN; }
         if (lane == 0) { a.part_max[wave] = mx; a.part_min[wave] = mn; }
     }
     if (a.gt16) {

@@ -607,14 +607,17 @@ MO_API void mo_exp_vec(int64_t N, const double* x, double shift, double* out) {
  * weights -> softmax.  get_similarity tail (particle_filter.py:459-468):
  * if |max-min| <= 1e-8 (torch.isclose(.., 0) with default atol) or !softmax -> copy x;
  * else w = mo_exp(x - max) / blocked_sum(mo_exp(x - max)).
+ * torch's max and min propagate NaN and NaN is never close: a NaN at ANY slot makes both extrema
+ * NaN, the softmax applies and every weight is NaN (a plain `>` / `<` scan would keep a NaN only
+ * at x[0] and copy the scores of a collapsed cloud with a NaN elsewhere).
  * returns 1 when softmax was applied.
  */
 MO_API int mo_softmax(int64_t N, const double* x, int softmax, double* w) {
     if (N == 0) return 0;
     double mx = x[0], mn = x[0];
     for (int64_t i = 1; i < N; ++i) {
-        if (x[i] > mx) mx = x[i];
-        if (x[i] < mn) mn = x[i];
+        if (x[i] > mx || isnan(x[i])) mx = x[i];
+        if (x[i] < mn || isnan(x[i])) mn = x[i];
     }
     if (!softmax || fabs(mx - mn) <= 1e-8) {
         if (w != x) memcpy(w, x, (size_t)N * sizeof(double));

@@ -882,3 +882,191 @@ def assert_anneal_recipe_conditions(cases, n, floor, init, what="", one_sided=Fa
     if n <= 300 and not one_sided:
         assert sep["f64_product"] >= ANNEAL_SEPARATE_MIN, (what, sep)
     return sep
+
+
+# ---- the softmax guard: one dissenting slot in a cloud collapsed onto one score ---------------------------------------------------
+# (tools/gen_softmax_guard.py writes G16 from these; tests/test_softmax_guard_reference.py on the CPU, tests/test_gpu_softmax_guard.py
+# on the GPU; DESIGN.md, "The softmax guard's rule")
+GUARD_WIDE = 0.4472135954999579               # 1 / sqrt(5): the cosine of e_0 and the float32 row (1, 2, 0, ...)
+GUARD_BELOW32 = float(np.float32(1e-8))       # 9.99999993922529e-09: the float32 nearest 1e-8 lies BELOW the edge
+GUARD_ABOVE32 = float(np.nextafter(np.float32(1e-8), np.float32(1.0)))   # 1.000000082740371e-08: the next float32, above it
+# kind -> (the dissenter's score beside a base of +0.0, whether get_similarity applies the softmax)
+GUARD_KINDS = {
+    "wide_hi": (GUARD_WIDE, True), "wide_lo": (-GUARD_WIDE, True),
+    "edge": (1e-8, False), "above": (float(np.nextafter(1e-8, 1.0)), True), "below": (float(np.nextafter(1e-8, 0.0)), False),
+    "above32_hi": (GUARD_ABOVE32, True), "above32_lo": (-GUARD_ABOVE32, True),
+    "below32_hi": (GUARD_BELOW32, False), "below32_lo": (-GUARD_BELOW32, False),
+    "signed_zero": (-0.0, False), "nan": (float("nan"), True),
+}
+GUARD_WIDE_KINDS = ("wide_hi", "wide_lo")
+GUARD_EDGE_KINDS = tuple(k for k in GUARD_KINDS if k not in GUARD_WIDE_KINDS)
+# the kinds a float32 codebook row can produce: kind -> the first two entries of the row (the rest 0) under the code e_0
+GUARD_ROWS = {
+    "wide_hi": (1.0, 2.0), "wide_lo": (-1.0, 2.0),
+    "above32_hi": (GUARD_ABOVE32, 1.0), "above32_lo": (-GUARD_ABOVE32, 1.0),
+    "below32_hi": (GUARD_BELOW32, 1.0), "below32_lo": (-GUARD_BELOW32, 1.0),
+    "nan": (float("nan"), 1.0),
+}
+GUARD_N = 12345                               # 3 * 4096 + 57: the last lane of the last group holds one live slot
+GUARD_SLOTS = (0, 3, 63, 64, 255, 256, 1023, 1024, 4095, 4096, 8191, 10114, 12288, 12344)
+GUARD_EDGE_SLOTS = (0, 10114, 12344)
+GUARD_SMALL = (1, 2, 15, 16, 17)
+GUARD_N66 = 65 * 4096 + 57                    # 266 297: 66 blocks, past the one-wave tables
+GUARD_SLOTS66 = (63 * 4096 + 17, 64 * 4096, GUARD_N66 - 1)
+GUARD_N258 = 257 * 4096 + 57                  # 1 052 729: 258 blocks, the second round of the 256-strided block loops
+GUARD_SLOTS258 = (256 * 4096 - 1, 256 * 4096, GUARD_N258 - 1)
+GUARD_K, GUARD_D = 800, 128
+
+
+def recipe_guard_scores(N, kind, slot):
+    """N float64 scores: +0.0 everywhere, x[slot] the dissenter of GUARD_KINDS[kind]."""
+    x = np.zeros(int(N), dtype=np.float64)
+    x[int(slot)] = GUARD_KINDS[kind][0]
+    return x
+
+
+def guard_applied(N, kind):
+    """Whether get_similarity applies the softmax to recipe_guard_scores(N, kind, .): one particle alone is always raw - NaN too,
+    as far as the weights go (max - min of a single NaN is NaN: the softmax of one NaN is NaN as well)."""
+    return bool(GUARD_KINDS[kind][1]) and (int(N) > 1 or kind == "nan")
+
+
+def guard_cases(edge_kinds=GUARD_EDGE_KINDS, big=(GUARD_N66,)):
+    """(N, kind, slot) of the issue's list: GUARD_N at every slot with the wide kinds, its three edge slots with the edge kinds and
+    NaN as well; N in 1, 2, 15, 16, 17 at every slot with every kind; the sizes of `big` at their three slots with every kind."""
+    out = [(GUARD_N, k, s) for s in GUARD_SLOTS for k in GUARD_WIDE_KINDS]
+    out += [(GUARD_N, k, s) for s in GUARD_EDGE_SLOTS for k in edge_kinds]
+    out += [(n, k, s) for n in GUARD_SMALL for s in range(n) for k in GUARD_WIDE_KINDS + tuple(edge_kinds)]
+    for n in big:
+        slots = {GUARD_N66: GUARD_SLOTS66, GUARD_N258: GUARD_SLOTS258}[n]
+        out += [(n, k, s) for s in slots for k in GUARD_WIDE_KINDS + tuple(edge_kinds)]
+    return out
+
+
+def guard_rule_torch(x):
+    """particle_filter.get_similarity's tail (modules/particle_filter.py:459-468) restated on float64 scores: the softmax over dim 0
+    unless isclose(max - min, a zero of the same dtype) with torch's default tolerances.  -> (weights, applied)."""
+    import torch
+    w = torch.as_tensor(np.asarray(x, dtype=np.float64))
+    if w.numel() == 1:       # (.squeeze() of one target: a 0-dim tensor, max == min, returned as it is)
+        return w.numpy().copy(), False
+    close = bool(torch.isclose(w.max() - w.min(), torch.zeros(1, dtype=w.dtype)))
+    if close:
+        return w.numpy().copy(), False
+    return torch.softmax(w, dim=0).numpy(), True
+
+
+def guard_rows(kind, D=GUARD_D):
+    """(base row, dissenting row) float32 (D,): (0, 1, 0, ...) and GUARD_ROWS[kind] - under the code e_0 their cosines are 0 and the
+    kind's value exactly (the norm sqrt(1 + a^2) is 1.0 in float64 for the 1e-8 rows; 1 / sqrt(5) for the wide ones)."""
+    base = np.zeros(D, dtype=np.float32)
+    base[1] = 1.0
+    row = np.zeros(D, dtype=np.float32)
+    row[0], row[1] = GUARD_ROWS[kind]
+    return base, row
+
+
+_GUARD_WORLD = {}
+
+
+def guard_world(d=GUARD_D):
+    """The codebook the guard frames stand on, and per row k the row the pose of k lands on once it is moved 5 m off the surface
+    (`moved`: a pruned particle still takes a nearest entry and its score counts in the guard) - by the oracle, once per process."""
+    if d not in _GUARD_WORLD:
+        from midastouch_amd.synthetic import make_codebook
+        from oracle import oracle
+        cb = make_codebook("004_sugar_box", K=GUARD_K, D=d, seed=1005)
+        off = cb.poses.copy()
+        off[:, :3, 3] += 5.0
+        ofl = oracle.OracleFilter(cb.poses, cb.embeddings, cb.mesh_vertices, pen_max=0.5)
+        assert np.array_equal(ofl.SE3_NN_idx(cb.poses), np.arange(GUARD_K)), "codebook poses that are not their own nearest entry"
+        moved = ofl.SE3_NN_idx(off)
+        dist_on, dist_off = oracle.nn3_dist(cb.poses, ofl.verts), oracle.nn3_dist(off, ofl.verts)
+        assert (dist_on <= 0.5).all() and (dist_off > 0.5).all()
+        _GUARD_WORLD[d] = (cb, moved)
+    return _GUARD_WORLD[d]
+
+
+_GUARD_FRAMES = {}
+
+
+def guard_frame(N, kind, slot, pruned="none", d=GUARD_D, salt=0):
+    """An engine frame whose scores are recipe_guard_scores(N, kind, slot): every codebook row (0, 1, 0, ...) but row k*, the kind's
+    dissenting row; the code e_0; identity odometry, no motion noise, pen_max = 0.5; every particle on a codebook pose, the pruned
+    ones 5 m off the surface.  pruned: "none", "half" (every other particle but the dissenter) or "dissenter" (the dissenting
+    particle alone - it then starts on the pose whose moved copy lands on k*).  What is asserted here, on the CPU: the scores of
+    the two rows are exactly the kind's; nn = the constructed nearest entries (guard_world's `moved` for the pruned) name k* at
+    `slot` and nowhere else.  slot None: the flat twin for a batch row beside dissenting rows - the same codebook, nobody on k*, the
+    code e_1: every particle scores exactly 1.0.  -> a namespace like tie_frame's with nn, mask, x (the scores per particle), kstar."""
+    import types
+    key = (N, kind, slot, pruned, d, salt)
+    if key in _GUARD_FRAMES:
+        return _GUARD_FRAMES[key]
+    from oracle import oracle
+    cb, moved = guard_world(d)
+    K = GUARD_K
+    flat = slot is None
+    assert kind in GUARD_ROWS and (flat or 0 <= slot < N) and pruned in ("none", "half", "dissenter")
+    assert pruned != "dissenter" or (GUARD_KINDS[kind][1] and not flat), "pruning the dissenter of a raw kind leaves every weight zero"
+    mask = np.ones(N, dtype=bool)
+    rng = np.random.default_rng([N, N if flat else slot, salt, 41 + flat])
+    if pruned == "dissenter":
+        mask[slot] = False
+        home = 0
+        kstar = int(moved[home])             # the entry the moved dissenter lands on
+    else:
+        if pruned == "half":
+            mask[rng.random(N) < 0.5] = False
+            mask[0 if flat else slot] = True
+        kstar = int(np.setdiff1d(np.arange(K), moved)[0])   # an entry no moved pose lands on
+        home = kstar
+    others = np.setdiff1d(np.arange(K), [kstar, home])
+    idx = others[rng.integers(0, others.shape[0], N)]
+    if not flat:
+        idx[slot] = home
+    nn = np.where(mask, idx, moved[idx]).astype(np.int32)
+    if flat:
+        assert (nn != kstar).all(), "a flat frame with a particle on the dissenting row"
+    else:
+        assert nn[slot] == kstar and (np.delete(nn, slot) != kstar).all(), "the dissenting row is not the dissenter's alone"
+    base, row = guard_rows(kind, d)
+    emb = np.tile(base, (K, 1))
+    emb[kstar] = row
+    code = np.zeros(d)
+    code[1 if flat else 0] = 1.0
+    sc = oracle.score_codebook(emb, code)
+    val = GUARD_KINDS[kind][0]
+    if flat:
+        assert (np.delete(sc, kstar) == 1.0).all()
+    else:
+        assert np.array_equal(sc[[kstar]], [val], equal_nan=True) and (np.delete(sc, kstar) == 0.0).all() and not np.signbit(np.delete(sc, kstar)).any()
+    start = cb.poses[idx].copy()
+    start[~mask, :3, 3] += 5.0
+    x = sc[nn]
+    assert np.array_equal(x, np.ones(N) if flat else recipe_guard_scores(N, kind, slot), equal_nan=True)
+    fr = types.SimpleNamespace(key=("guard",) + key, N=N, kind=kind, slot=slot, pruned=pruned, emb=emb, code=code, odom=np.eye(4, dtype=np.float32),
+                               start=start, kw=dict(sig_t=0.0, sig_r=0.0, pen_max=0.5, seed=4600), mask=mask, nn=nn, x=x, scores=sc,
+                               kstar=kstar, applied=False if flat else guard_applied(N, kind), d=d, idx=idx)
+    _GUARD_FRAMES[key] = fr
+    return fr
+
+
+def guard_expected(fr, shard=None):
+    """What every engine must report for a guard frame, from its construction and the oracle's arithmetic alone (no nearest-neighbour
+    search: the frame of a million particles is built this way too): e = softmax_numerators(x, shift = 1), S = the blocked sum of e
+    over ALL particles, weights = e / S * mask, the CDF of e * mask and its status.  shard = (ranks, n_loc): the sums as `ranks`
+    ranks of n_loc slots add them - every rank's slots in blocks of their own, +0.0 padded (tests/test_gpu_resample_pin.py)."""
+    from oracle import oracle
+    e, applied = oracle.softmax_numerators(fr.x, True, shift=1.0)
+    assert applied == fr.applied, (fr.key, applied)
+    em = e * fr.mask
+    if shard is None:
+        pad_of, keep = (lambda a: a), slice(None)
+    else:
+        ranks, n_loc = shard
+        pad = (-n_loc) % 4096
+        pad_of = lambda a: np.concatenate([np.concatenate([a[r * n_loc:(r + 1) * n_loc], np.zeros(pad)]) for r in range(ranks)])  # noqa: E731
+        keep = np.concatenate([np.arange(n_loc) + r * (n_loc + pad) for r in range(ranks)])
+    S = oracle.blocked_scan(pad_of(e))[1] if applied else 1.0
+    c, status = oracle.cdf(pad_of(em))
+    return dict(e=e, em=em, applied=applied, weights=e / S * fr.mask, cdf=c[keep], status=status, V=int(fr.mask.sum()), N=fr.N)

@@ -21,6 +21,10 @@ as-is produce the outputs stored here:
   G15 particle_filter.annealing, one decision per case at the edges of its float32 rule
       (modules/particle_filter.py:413-447) - written by tools/gen_anneal_rule.py from the
       recipe in tests/_recipes.py, with this file's import_reference, new_pf and marker_poses.
+  G16 particle_filter.get_similarity on clouds collapsed onto one score with one dissenting
+      particle, at the edges of the isclose guard (modules/particle_filter.py:459-468) - written
+      by tools/gen_softmax_guard.py from the rows in tests/_recipes.py, with this file's
+      import_reference and new_pf.
 
 A fixture is data only: inputs + the reference's outputs (+ the RNG draws it consumed).
 Usage:  python tools/gen_goldens.py            (rewrites tests/golden/*.npz)
