@@ -1070,3 +1070,718 @@ def guard_expected(fr, shard=None):
     S = oracle.blocked_scan(pad_of(e))[1] if applied else 1.0
     c, status = oracle.cdf(pad_of(em))
     return dict(e=e, em=em, applied=applied, weights=e / S * fr.mask, cdf=c[keep], status=status, V=int(fr.mask.sum()), N=fr.N)
+
+
+# ---- DBSCAN at its edges: points on eps, counts at min_samples, single links ------------------------------------------------------
+# (tools/gen_dbscan_edges.py writes G17 from these; tests/test_dbscan_edges_reference.py on the CPU, tests/test_gpu_dbscan_edges.py on
+# the GPU; DESIGN.md, "DBSCAN's rule")
+# Points on an integer lattice scaled by a power of two, x = V 2^-k with |V| < 2^24, and eps = m 2^-k: the coordinates are exact float32
+# values, eps eps is exact in double and every squared distance is an integer times 2^-2k in any arithmetic, any order, fused or not.
+# The predicate is |dV|^2 <= m^2 over integers; the reference is a brute-force DBSCAN on int64 with sklearn's scan order.
+DB_CELL = 0.577            # cell side / eps (csrc/dbscan.hip DB_CELL)
+DB_MAXDIM = 128            # cells per axis of the dense grid
+DB_POPS = (1, 63, 64, 65, 255, 256, 257, 300)   # cell populations: the scans step by 64 (link, border) and by 256 (core count)
+DB_ROUNDING_MUTANTS = ("reversed", "contracted", "f32")
+DB_ROUNDING_MIN = 8        # cases per mutant a recipe must hold
+
+
+def _db_labels(adj, ms):
+    """Labels of sklearn's DBSCAN from the neighbour relation (itself included): clusters numbered by their first core point in index
+    order, a border point takes the smallest number among the clusters whose core points reach it.  -> (labels, clusters, core)."""
+    n = len(adj)
+    core = adj.sum(axis=1) >= ms
+    lab = np.full(n, -1, dtype=np.int64)
+    cadj = adj & core[None, :]
+    ncl = 0
+    for i in range(n):
+        if not core[i] or lab[i] >= 0:
+            continue
+        lab[i] = ncl
+        stack = [i]
+        while stack:
+            j = stack.pop()
+            nb = np.flatnonzero(cadj[j] & (lab < 0))
+            lab[nb] = ncl
+            stack.extend(nb.tolist())
+        ncl += 1
+    if n:
+        big = np.iinfo(np.int64).max
+        cand = np.where(cadj, lab[None, :], big).min(axis=1)
+        border = ~core & (cand < big)
+        lab[border] = cand[border]
+    return lab, ncl, core
+
+
+def db_int_dbscan(V, m2, ms):
+    """Brute-force DBSCAN of the integer points V (N, d): neighbours <=> |dV|^2 <= m2, in int64."""
+    V = np.asarray(V, dtype=np.int64).reshape(len(V), -1)
+    V = V - V.min(axis=0) if len(V) else V
+    sq = (V * V).sum(axis=1)
+    d2 = sq[:, None] + sq[None, :] - 2 * (V @ V.T)
+    return _db_labels(d2 <= m2, ms)
+
+
+def db_f64_d2(X, variant="spec"):
+    """Squared distances of all pairs of the float32 points X (N, 3) as the kernel's predicate adds them up - ((dx dx) + dy dy) + dz dz
+    in double - or as a mutant does: "reversed" (dz first), "contracted" (the chain fused: fma(dz, dz, fma(dy, dy, dx dx))), "f32"."""
+    X = np.asarray(X, dtype=np.float32)
+    if variant == "f32":
+        d = [X[:, None, a] - X[None, :, a] for a in range(3)]
+        return ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]).astype(np.float64)
+    Y = X.astype(np.float64)
+    d = [Y[:, None, a] - Y[None, :, a] for a in range(3)]
+    if variant == "spec":
+        return (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+    if variant == "reversed":
+        return (d[2] * d[2] + d[1] * d[1]) + d[0] * d[0]
+    if variant == "contracted":
+        return _fma(d[2], d[2], _fma(d[1], d[1], d[0] * d[0]))
+    raise ValueError(variant)
+
+
+def _fma(a, b, c):
+    """fma(a, b, c) in double, exactly rounded, through rationals (small arrays only: the rounding sets hold four points)."""
+    from fractions import Fraction
+    a, b, c = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(c, dtype=np.float64))
+    out = np.empty(a.shape, dtype=np.float64)
+    for i in np.ndindex(a.shape):
+        out[i] = float(Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i])))
+    return out
+
+
+def db_f64_dbscan(X, eps, ms, variant="spec"):
+    """The float64 restatement of the kernel's DBSCAN (and, by `variant`, of a mutant's)."""
+    return _db_labels(db_f64_d2(X, variant) <= float(eps) * float(eps), ms)
+
+
+def db_cells(X, eps):
+    """Cell of every point, cells per axis and `hashed`, as k_db_setup and db_cell_coords do: floor((x - min) / (0.577 eps)) on the
+    float32 bounds, in double; hashed when some axis has more than 128 cells."""
+    X64 = np.asarray(X, dtype=np.float32).astype(np.float64)
+    lo, h = X64.min(axis=0), float(eps) * DB_CELL
+    dims = np.floor((X64.max(axis=0) - lo) / h) + 1.0
+    c = np.clip(np.floor((X64 - lo) / h), 0.0, dims - 1.0).astype(np.int64)
+    return c, dims.astype(np.int64), bool((dims > DB_MAXDIM).any())
+
+
+def db_classes(X, eps, i):
+    """The occupied cells as point i's core test and border pass see them: {cell offset: dict(pop, cls, on_min, on_max, single)}, cls
+    "own", "within" (the tight box's far corner is within eps: counted without a distance), "cut" (exact tests), "beyond" (the near
+    corner is beyond eps) or "far" (outside the 5 x 5 x 5 walk); on_min / on_max: the near / far corner lies exactly on eps."""
+    c, _, _ = db_cells(X, eps)
+    X64 = np.asarray(X, dtype=np.float32).astype(np.float64)
+    r2 = float(eps) * float(eps)
+    keys, inv = np.unique(c, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    p, out = X64[i], {}
+    for ci, key in enumerate(keys):
+        pts = X64[inv == ci]
+        off = tuple(int(v) for v in key - c[i])
+        lo, hi = pts.min(axis=0), pts.max(axis=0)
+        gmax = np.maximum(p - lo, hi - p)
+        gmin = np.maximum(np.maximum(lo - p, p - hi), 0.0)
+        mind2 = (gmin[0] * gmin[0] + gmin[1] * gmin[1]) + gmin[2] * gmin[2]
+        maxd2 = (gmax[0] * gmax[0] + gmax[1] * gmax[1]) + gmax[2] * gmax[2]
+        if off == (0, 0, 0):
+            cls = "own"
+        elif max(abs(v) for v in off) > 2:
+            cls = "far"
+        else:
+            cls = "within" if maxd2 <= r2 else ("cut" if mind2 <= r2 else "beyond")
+        out[off] = dict(pop=len(pts), cls=cls, on_min=bool(mind2 == r2), on_max=bool(maxd2 == r2), single=bool((lo == hi).all()))
+    return out
+
+
+def _db_case(name, sites, m, k, off, ms, seed, anchor, markers=False, fifth=False, first=None, dist=3):
+    """A lattice case from `sites` {local integer site: multiplicity} (coincident particles, which resampling produces): the point
+    `anchor`, at least 3 m below every site on every axis, is the grid's origin (it places the lattice on the cell grid); markers: a far point that
+    gives the x axis more than 128 cells (the hashed table); fifth: far padding points, each alone in its cell, bring n // 5 onto ms
+    (ms None: n // 5 as it falls); first: a local site whose copy is moved to index 0 of the shuffled order."""
+    sites = {tuple(int(x) for x in s): int(c) for s, c in sites.items() if c > 0}
+    pts = np.array([s for s, c in sites.items() for _ in range(c)], dtype=np.int64).reshape(-1, 3)
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    a = np.asarray(anchor, dtype=np.int64)
+    assert (a <= lo - dist * m).all(), (name, a, lo)
+    extra = [a]
+    side = int(np.ceil(DB_CELL * m))
+    if markers:
+        extra.append(np.array([a[0] + (DB_MAXDIM + 2) * side, a[1], a[2]]))
+    n = len(pts) + len(extra)
+    if fifth and ms is not None:
+        assert n <= 5 * ms + 4, (name, n, ms)
+        npad = max(5 * ms - n, 0)
+        step, per = m + 1, 8   # more than eps apart: never neighbours, never cell-mates
+        j = np.arange(npad)
+        pad = np.stack([hi[0] + dist * m + step * (j // (per * per)), a[1] + step * (j // per % per), a[2] + step * (j % per)], axis=1)
+        extra += list(pad)
+    V = np.concatenate([pts, np.array(extra, dtype=np.int64).reshape(-1, 3)]) + np.asarray(off, dtype=np.int64)
+    n = len(V)
+    order = np.random.default_rng([17, seed]).permutation(n)
+    if first is not None:
+        f = int(np.flatnonzero((pts == np.asarray(first)).all(axis=1))[0])
+        at = int(np.flatnonzero(order == f)[0])
+        order[[0, at]] = order[[at, 0]]
+    V = V[order]
+    assert np.abs(V).max() < (1 << 24)
+    X = (V.astype(np.float64) * 2.0 ** -k).astype(np.float32)
+    assert np.array_equal(X.astype(np.float64) * 2.0 ** k, V)  # exact float32 values
+    ms = n // 5 if ms is None else int(ms)
+    if fifth:
+        assert n // 5 == ms, (name, n, ms)
+    eps = m * 2.0 ** -k
+    lab, ncl, core = db_int_dbscan(V, m * m, ms)
+    local = V - np.asarray(off, dtype=np.int64)
+    c = dict(name=name, V=V, local=local, k=int(k), m=int(m), off=tuple(int(x) for x in off), ms=ms, eps=eps, X=X, labels=lab, ncl=ncl,
+             core=core, fifth=bool(fifth), hashed=db_cells(X, eps)[2])
+    assert c["hashed"] == bool(markers) or fifth, (name, db_cells(X, eps)[1])
+    return c
+
+
+def _db_site_index(c, site):
+    return np.flatnonzero((c["local"] == np.asarray(site, dtype=np.int64)).all(axis=1))
+
+
+def _db_cube(m, R):
+    g = np.arange(-R, R + 1)
+    S = np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3)
+    return S, (S * S).sum(axis=1)
+
+
+def db_probe(m, k, off, r, pops, delta=0, markers=False, fifth=False, seed=0, own=1, cut_pops=None):
+    """One site p (the local origin, `own` copies) and neighbours placed by class, so that p's neighbour count c is known: with
+    min_samples = c + delta the core set is p's site alone (delta 0: every neighbour is a border point of cluster 0, the decoys are noise)
+    or empty (delta 1: everything is noise) - any dropped or extra candidate flips the whole set.  Around p:
+      corner   a point exactly on eps that is its cell's nearest corner to p, its cell-mate beyond eps (mind2 == r2 < maxd2): two cells
+      cut      per entry P of `pops` a cell of P - 1 copies of a site within eps and one site beyond it (at m^2 + 1 where the cell has one)
+      within   per entry P of `pops` a cell of P copies of one site well within eps
+      decoy    sites at m^2 + 1, alone in their cells
+      on       antipodal pairs exactly on eps, each alone in its cell (the box is the point: maxd2 == r2) - one pair more than there
+               are points beyond eps, so that no site but p sees as many points as p does (no site is within eps of both v and -v).
+    cut_pops: the cut cells' populations where they differ from `pops`; (): the two corner cells are then the only cells the upper bound
+    of p's count can take its last points from - read as "beyond", p is dropped before any distance is looked at."""
+    m2, hl = m * m, DB_CELL * m
+    cutp = tuple(pops if cut_pops is None else cut_pops)
+    a = 3 * m + (m + 2) + np.asarray(r, dtype=np.int64)        # the anchor lies this far below p: _db_case's, the cube reaches m + 2 down
+    S, d2 = _db_cube(m, m + 2)
+    cell = np.floor((S + a) / hl).astype(np.int64)
+    cid = {}
+    for i, key in enumerate(map(tuple, cell)):
+        cid.setdefault(key, []).append(i)
+    own_cell = tuple(np.floor(a / hl).astype(np.int64))
+    used, sites, plan = {own_cell}, {(0, 0, 0): own}, {}
+    outside = 0
+
+    def take(key):
+        used.add(key)
+
+    # corner: v on eps, w = v one step further out on one axis, same cell
+    corners = 0
+    for i in np.flatnonzero(d2 == m2):
+        key = tuple(cell[i])
+        if key in used or corners == 2:
+            continue
+        v = S[i]
+        best = None
+        for ax in range(3):
+            w = v.copy()
+            w[ax] += 1 if v[ax] >= 0 else -1
+            if (np.abs(w) <= m + 2).all() and tuple(np.floor((w + a) / hl).astype(np.int64)) == key:
+                dw = int((w * w).sum())
+                if best is None or dw < best[0]:
+                    best = (dw, w)
+        if best is None:
+            continue
+        sites[tuple(v)] = 1
+        sites[tuple(best[1])] = 1
+        plan[tuple(int(x) - int(y) for x, y in zip(key, own_cell))] = "corner"
+        outside += 1
+        corners += 1
+        take(key)
+    # cut cells, the farthest-reaching first (their box is cut whatever the alignment)
+    cells = sorted((key for key in cid if key not in used), key=lambda key: -max(d2[i] for i in cid[key] if d2[i] <= m2) if any(d2[i] <= m2 for i in cid[key]) else 0)
+    todo = list(cutp)
+    for key in cells:
+        if not todo:
+            break
+        idx = cid[key]
+        ins = [i for i in idx if 0 < d2[i] < m2]
+        outs = [i for i in idx if d2[i] > m2]
+        if not ins or not outs or key in used:
+            continue
+        u = max(ins, key=lambda i: d2[i])
+        w = min(outs, key=lambda i: d2[i])
+        P = todo.pop(0)
+        if P > 1:
+            sites[tuple(S[u])] = P - 1
+            sites[tuple(S[w])] = 1
+            outside += 1
+            plan[tuple(int(x) - int(y) for x, y in zip(key, own_cell))] = "cut"
+        else:
+            sites[tuple(S[u])] = 1   # a population of one: the box is the point
+            plan[tuple(int(x) - int(y) for x, y in zip(key, own_cell))] = "within"
+        take(key)
+    assert not todo, ("cut cells", m, r)
+    # within cells, the nearest first
+    todo = list(pops)
+    for key in sorted((key for key in cid if key not in used), key=lambda key: min(d2[i] for i in cid[key])):
+        if not todo:
+            break
+        u = min(cid[key], key=lambda i: d2[i])
+        if not 0 < d2[u] < m2:
+            continue
+        sites[tuple(S[u])] = todo.pop(0)
+        plan[tuple(int(x) - int(y) for x, y in zip(key, own_cell))] = "within"
+        take(key)
+    assert not todo, ("within cells", m, r)
+    # decoys at m^2 + 1, alone
+    decoys = 0
+    for i in np.flatnonzero(d2 == m2 + 1):
+        key = tuple(cell[i])
+        if key in used or decoys == 3:
+            continue
+        sites[tuple(S[i])] = 1
+        plan[tuple(int(x) - int(y) for x, y in zip(key, own_cell))] = "decoy"
+        outside += 1
+        decoys += 1
+        take(key)
+    assert decoys >= 1
+    # antipodal pairs on eps, alone
+    pairs = 0
+    for i in np.flatnonzero(d2 == m2):
+        v = S[i]
+        if tuple(v) < tuple(-v) or pairs == max(outside + 1, 3):
+            continue
+        k1, k2 = tuple(cell[i]), tuple(np.floor((-v + a) / hl).astype(np.int64))
+        if k1 in used or k2 in used or k1 == k2:
+            continue
+        sites[tuple(v)] = 1
+        sites[tuple(-v)] = 1
+        for key in (k1, k2):
+            plan[tuple(int(x) - int(y) for x, y in zip(key, own_cell))] = "on"
+            take(key)
+        pairs += 1
+    assert pairs >= 3, ("antipodal pairs", pairs, outside)   # (fewer than outside + 1 may do: the conditions below are what counts)
+    cnt = sum(n for s, n in sites.items() if sum(x * x for x in s) <= m2)
+    name = f"probe/m{m}/r{'.'.join(map(str, r))}/off{'.'.join(map(str, off))}/{'hashed' if markers else 'dense'}/{'fifth' if fifth else 'ms'}/own{own}/pops{len(pops)}{'' if cut_pops is None else 'cut' + str(len(cutp))}/c{'+1' if delta else ''}"
+    c = _db_case(name, sites, m, k, off, cnt + delta, seed, -a, markers=markers, fifth=fifth)
+    # --- the conditions, on the case as built
+    ip = _db_site_index(c, (0, 0, 0))
+    assert len(ip) == own
+    loc2 = (c["local"] * c["local"]).sum(axis=1)
+    near = loc2 <= m2
+    assert int(near.sum()) == cnt
+    if delta == 0:
+        assert np.array_equal(np.flatnonzero(c["core"]), ip), name          # the core set is exactly p's site
+        assert c["ncl"] == 1 and (c["labels"][near] == 0).all() and (c["labels"][~near] == -1).all(), name
+    else:
+        assert not c["core"].any() and c["ncl"] == 0 and (c["labels"] == -1).all(), name
+    cls = db_classes(c["X"], c["eps"], int(ip[0]))
+    seen = {}
+    for offc, what in plan.items():
+        got = cls[offc]
+        if what == "corner":
+            assert got["cls"] == "cut" and got["on_min"] and not got["on_max"] and got["pop"] == 2, (name, offc, got)
+        elif what == "cut":
+            assert got["cls"] == "cut" and not got["on_min"], (name, offc, got)
+        elif what == "within":
+            assert got["cls"] == "within" and got["single"] and not got["on_max"], (name, offc, got)
+        elif what == "decoy":
+            assert got["cls"] == "beyond" and got["pop"] == 1, (name, offc, got)
+        elif what == "on":
+            assert got["cls"] == "within" and got["single"] and got["on_max"] and got["pop"] == 1, (name, offc, got)
+        seen[what] = seen.get(what, 0) + 1
+    assert cls[(0, 0, 0)]["cls"] == "own" and cls[(0, 0, 0)]["pop"] == own
+    assert seen["corner"] == 2 and seen.get("cut", 0) + seen["within"] == len(pops) + len(cutp) and seen["on"] == 2 * pairs
+    assert sorted(v["pop"] for o, v in cls.items() if plan.get(o) in ("cut", "within")) == sorted(list(pops) + list(cutp)), name
+    if not cutp and delta == 0:   # the upper bound of p's count without the corner cells falls short of min_samples
+        assert cnt - 2 < c["ms"] == cnt and sum(v["pop"] for v in cls.values() if v["cls"] in ("own", "within", "cut")) == cnt + 2, name
+    c.update(p=int(ip[0]), count=cnt, plan=plan, classes=seen)
+    return c
+
+
+def db_own_cell(m, k, off, r, short, markers=False, seed=0, ms=64):
+    """p's own cell decides: short 0 - the cell holds min_samples points exactly (core by population, no distance at all), decoys at
+    m^2 + 1 around it; short 1 - the cell holds p (ms - 2 copies) and a second site p' (one copy), one short of min_samples, and the
+    missing neighbour is one point exactly on eps of p, alone in its cell and beyond eps of p'.  The core set is p's site; with
+    min_samples one higher it is empty."""
+    m2, hl = m * m, DB_CELL * m
+    out = []
+    for rx in range(int(np.ceil(hl)) + 1):   # the alignment on x that puts p and p' into one cell
+        ax = -(4 * m + 2 + r[0] + rx)
+        if np.floor((0 - ax) / hl) == np.floor((1 - ax) / hl):
+            break
+    anchor = (ax, -(4 * m + 2 + r[1]), -(4 * m + 2 + r[2]))
+    for delta in (0, 1):
+        sites = {}
+        S, d2 = _db_cube(m, m + 2)
+        far = lambda s, o: sum((x - y) ** 2 for x, y in zip(s, o)) > m2  # noqa: E731
+        dec = [tuple(S[i]) for i in np.flatnonzero(d2 == m2 + 1)]
+        dec = [s for s in dec if far(s, (1, 0, 0)) and far(s, (-m, 0, 0))]      # decoys of p that no other site counts
+        for s in dec[::max(len(dec) // 4, 1)][:4]:
+            sites[s] = 1
+        if short:
+            sites[(0, 0, 0)] = ms - 2
+            sites[(1, 0, 0)] = 1
+            sites[(-m, 0, 0)] = 1
+        else:
+            sites[(0, 0, 0)] = ms
+        name = f"own/m{m}/r{'.'.join(map(str, r))}/{'hashed' if markers else 'dense'}/short{short}/c{'+1' if delta else ''}"
+        c = _db_case(name, sites, m, k, off, ms + delta, seed, anchor, markers=markers)
+        ip = _db_site_index(c, (0, 0, 0))
+        cls = db_classes(c["X"], c["eps"], int(ip[0]))
+        assert cls[(0, 0, 0)]["pop"] == ms - short, (name, cls[(0, 0, 0)])
+        if delta == 0:
+            assert np.array_equal(np.flatnonzero(c["core"]), ip) and c["ncl"] == 1, name
+        else:
+            assert not c["core"].any(), name
+        if short:
+            on = [v for o, v in cls.items() if v["on_max"] and v["single"] and v["pop"] == 1]
+            assert len(on) == 1, name
+        c.update(p=int(ip[0]), count=ms)
+        out.append(c)
+    return out
+
+
+def _db_plus_vector(m):
+    """An integer vector of squared length m^2 + 1 whose first component is m (the next lattice point beside (m, 0, 0))."""
+    return (m, 1, 0)
+
+
+def db_bridge(m, k, off, r, on, kind, seed, markers=False, fifth=False, second_first=True):
+    """Two blocks of core points joined by exactly one pair, a - b: exactly on eps (one cluster) or at m^2 + 1 (two).  kind "box": a
+    and b are single-site cells of min_samples copies (the cells' boxes decide the link); "cut": the cell of a holds 65 copies of a and
+    65 of a site one step further from b, the cell of b likewise (the link is found by the exact scan, a point against the other cell's
+    core points); "one": a and b are single particles among 130 of their cells.  second_first: index 0 is a point of b's block, so the
+    geometrically first block is not cluster 0."""
+    # the cell-mates lie diagonally (a2 one step further in x and one up in y, b2 likewise on the other side): the two cells' boxes are
+    # exactly eps apart in BOTH forms - the boxes never decide, the exact scan does - and a - b is the only pair that can be within eps
+    b = (m, 0, 0) if on else _db_plus_vector(m)
+    a2, b2 = (-1, 1, 0), (m + 1, 1 - b[1], 0)
+    pop = {"box": None, "cut": (65, 65), "one": (1, 129)}[kind]
+    ms = 5 if kind == "box" else 100
+    hl = DB_CELL * m
+    side = int(np.ceil(hl))
+    for rx in range(side + 1):      # the alignment on x that puts a with a2, b with b2 and the two pairs apart; on y, 0 with 1
+        lo = -1 - (3 * m + rx)
+        cx = lambda x: int(np.floor((x - lo) / hl))  # noqa: E731
+        if kind == "box" or (cx(0) == cx(-1) and cx(m) == cx(m + 1) and cx(0) != cx(m)):
+            break
+    else:
+        raise AssertionError(("bridge alignment", m))
+    for ry in range(side + 1):
+        loy = -(3 * m + r[1] + ry)
+        if np.floor((0 - loy) / hl) == np.floor((1 - loy) / hl):
+            break
+    if kind == "box":
+        sites = {(0, 0, 0): ms, b: ms}
+    else:
+        sites = {(0, 0, 0): pop[0], a2: pop[1], b: pop[0], b2: pop[1]}
+    name = f"bridge/m{m}/{kind}/{'on' if on else 'plus'}/r{rx}.{r[1]}.{r[2]}/{'hashed' if markers else 'dense'}/{'fifth' if fifth else 'ms'}/s{seed}"
+    c = _db_case(name, sites, m, k, off, None if fifth else ms, seed, (lo, loy, -(3 * m + r[2])), markers=markers, fifth=fifth,
+                 first=(b if second_first else (0, 0, 0)))
+    ia, ib = _db_site_index(c, (0, 0, 0)), _db_site_index(c, b)
+    d = c["local"][ia[0]] - c["local"][ib[0]]
+    assert int((d * d).sum()) == m * m + (0 if on else 1)
+    yz = (c["local"][:, 1] >= 0) & (c["local"][:, 1] <= 1) & (c["local"][:, 2] == 0)
+    blockA = (c["local"][:, 0] <= 0) & (c["local"][:, 0] >= -1) & yz
+    blockB = (c["local"][:, 0] >= m) & (c["local"][:, 0] <= m + 1) & yz
+    assert c["core"][blockA | blockB].all() and int((blockA | blockB).sum()) == sum(sites.values()), name
+    assert c["ncl"] == (1 if on else 2), name
+    if not on:
+        first_block = blockB if second_first else blockA
+        assert (c["labels"][first_block] == 0).all() and (c["labels"][(blockA | blockB) & ~first_block] == 1).all(), name
+    else:
+        assert (c["labels"][blockA | blockB] == 0).all(), name
+    # the pairs of the two blocks within eps: the bridge alone
+    A, B = c["local"][blockA], c["local"][blockB]
+    dd = ((A[:, None, :] - B[None, :, :]) ** 2).sum(axis=2)
+    assert int((dd <= m * m).sum()) == (len(ia) * len(ib) if on else 0), name
+    cells, _, _ = db_cells(c["X"], c["eps"])
+    ca, cb = cells[ia[0]], cells[ib[0]]
+    assert not np.array_equal(ca, cb)
+    if kind != "box":
+        assert (cells[blockA] == ca).all() and (cells[blockB] == cb).all(), name   # 130 points a cell
+        cls = db_classes(c["X"], c["eps"], int(ia[0]))[tuple(int(v) for v in cb - ca)]
+        assert cls["cls"] == "cut" and cls["on_min"] and cls["pop"] == 130, (name, cls)
+    else:
+        cls = db_classes(c["X"], c["eps"], int(ia[0]))[tuple(int(v) for v in cb - ca)]
+        assert cls["single"] and cls["on_max"] == bool(on) and cls["cls"] == ("within" if on else "beyond"), (name, cls)
+    return c
+
+
+def db_border(m, k, off, r, mode, apop, seed, markers=False, fifth=False):
+    """A non-core point x (the local origin).  Cluster 0 reaches it through ONE core point a exactly on eps (mode "on": label 0), or a
+    lies at m^2 + 1 ("plus": label 1, x lies well inside cluster 1, whose core point b shares x's cell and is x's only neighbour of
+    that cluster), or neither reaches it ("none": b is taken away as well, label -1).  apop 1: a is alone in its cell (the box decides);
+    apop P > 1: a is one particle among P of its cell, the others one step beyond eps of x (the exact scan, 64 candidates at a time)."""
+    ms = max(5, -(-(apop + 4 + int(markers)) // 4)) if fifth else 5     # fifth: n // 5 == ms is within the padding's reach
+    a = (-m, 0, 0) if mode == "on" else tuple(-v for v in _db_plus_vector(m))
+    sites = {(0, 0, 0): 1, a: 1}
+    if apop > 1:
+        sites[(a[0] - 1, a[1], a[2])] = apop - 1      # the cell-mates of a: core by their cell's population
+    else:
+        sites[(a[0] - 5 if m >= 5 else a[0] - m, a[1], a[2])] = ms   # what makes a a core point: within eps of a, beyond eps of x
+    if mode != "none":
+        sites[(1, 0, 0)] = 1                           # b, in x's cell
+    sites[(1 + m, 0, 0)] = ms                          # b': exactly on eps of b, beyond eps of x
+    hl = DB_CELL * m
+    for rx in range(int(np.ceil(hl)) + 1):
+        lo = min(s[0] for s in sites) - (3 * m + rx)
+        cx = lambda x: int(np.floor((x - lo) / hl))  # noqa: E731
+        if cx(0) == cx(1) and (apop == 1 or cx(a[0]) == cx(a[0] - 1)) and (apop > 1 or cx(a[0]) != cx(a[0] - 5 if m >= 5 else a[0] - m)):
+            break
+    else:
+        raise AssertionError(("border alignment", m))
+    name = f"border/m{m}/{mode}/apop{apop}/r{rx}.{r[1]}.{r[2]}/{'hashed' if markers else 'dense'}/{'fifth' if fifth else 'ms'}/s{seed}"
+    first = (a[0] - 1, a[1], a[2]) if apop > 1 else (a[0] - 5 if m >= 5 else a[0] - m, a[1], a[2])   # cluster 0 is a's
+    c = _db_case(name, sites, m, k, off, ms, seed, (lo, -(3 * m + 1 + r[1]), -(3 * m + r[2])), markers=markers, fifth=fifth, first=first)
+    ix, ia = int(_db_site_index(c, (0, 0, 0))[0]), int(_db_site_index(c, a)[0])
+    assert not c["core"][ix] and c["core"][ia] and c["labels"][ia] == 0, name
+    want = {"on": 0, "plus": 1, "none": -1}[mode]
+    assert c["labels"][ix] == want, (name, c["labels"][ix])
+    assert c["ncl"] == 2, name
+    cells, _, _ = db_cells(c["X"], c["eps"])
+    cls = db_classes(c["X"], c["eps"], ix)
+    ca = cls[tuple(int(v) for v in cells[ia] - cells[ix])]
+    if mode == "on":
+        assert ca["on_max" if apop == 1 else "on_min"] and ca["pop"] == apop and ca["cls"] == ("within" if apop == 1 else "cut"), (name, ca)
+    else:
+        assert ca["cls"] == "beyond" and ca["pop"] == apop, (name, ca)
+    if mode != "none":
+        ibb = int(_db_site_index(c, (1, 0, 0))[0])
+        assert np.array_equal(cells[ibb], cells[ix]) and c["core"][ibb] and c["labels"][ibb] == 1 and cls[(0, 0, 0)]["pop"] == 2, name
+        # b is x's only neighbour of cluster 1
+        d2 = ((c["local"] - c["local"][ix]) ** 2).sum(axis=1)
+        assert int(((d2 <= m * m) & c["core"] & (c["labels"] == 1)).sum()) == 1, name
+    c.update(x=ix, want=want)
+    return c
+
+
+def db_corner(m, k, off, want, seed=0, markers=False):
+    """Two points whose cells are two apart on every axis of `want` (a tuple of 0 / 2 per axis) and yet within eps: sqrt(3) 0.577 < 1
+    leaves a sliver.  The recipe searches the alignment.  p, q = p + d and a cell-mate q' of q beyond eps of p (q's cell is cut: p's
+    count needs the exact scan of a cell at the rim of the 5 x 5 x 5 walk), and a decoy at m^2 + 1 of p beside q.  Two cases: min_samples
+    2 (p is a core point only through q) and 3 (p is a border point only through q)."""
+    m2, hl = m * m, DB_CELL * m
+    d, dplus = {(2, 2, 2): ((56, 56, 56), (55, 57, 56)), (2, 2, 0): ((72, 65, 0), (72, 65, 1)), (2, 0, 0): ((97, 0, 0), (97, 1, 0))}[tuple(want)]
+    assert m == 97 and sum(x * x for x in d) in (m2, m2 - 1) and sum(x * x for x in dplus) == m2 + 1
+    t = []
+    for ax in range(3):       # p lies t cells-and-a-bit above the anchor: the smallest t that gives the wanted offsets
+        for cand in range(3 * m, 3 * m + 40 * int(hl)):
+            cp, cq, cq1 = (int(np.floor(v / hl)) for v in (cand, cand + d[ax], cand + d[ax] + (1 if ax == 0 else 0)))
+            if cq - cp == want[ax] and cq1 == cq:
+                t.append(cand)
+                break
+        else:
+            raise AssertionError(("corner alignment", want, ax))
+    q1 = (d[0] + 1, d[1], d[2])
+    out = []
+    for ms in (2, 3):
+        name = f"corner/{'.'.join(map(str, want))}/{'hashed' if markers else 'dense'}/ms{ms}"
+        sites = {(0, 0, 0): 1, d: 1, q1: 1, dplus: 1}
+        c = _db_case(name, sites, m, k, off, ms, seed, tuple(-v for v in t), markers=markers)
+        ip, iq = int(_db_site_index(c, (0, 0, 0))[0]), int(_db_site_index(c, d)[0])
+        cells, _, _ = db_cells(c["X"], c["eps"])
+        assert tuple(int(v) for v in cells[iq] - cells[ip]) == tuple(want), (name, cells[iq] - cells[ip])
+        cls = db_classes(c["X"], c["eps"], ip)[tuple(want)]
+        assert cls["cls"] == "cut" and cls["pop"] >= 2, (name, cls)
+        assert c["core"][iq] and c["labels"][ip] == 0 and c["ncl"] == 1, name
+        assert bool(c["core"][ip]) == (ms == 2), name
+        # without q, p is noise
+        keep = np.arange(len(c["V"])) != iq
+        lab = db_int_dbscan(c["V"][keep], m2, ms)[0]
+        assert lab[np.flatnonzero(keep) == ip][0] == -1, name
+        c.update(p=ip)
+        out.append(c)
+    return out
+
+
+def db_rounding_cases(mutant, seed=0, trials=6000):
+    """The float64 predicate's rounding, a separate edge: pairs p, q whose differences carry more than 26 significant bits (p with
+    components of magnitude 2^-30 .. 2^-12, q about eps away along unequal axes - and, for the float32 mutant, also pairs at |x| about
+    0.3), and an eps with fl(eps eps) between the spec's sum ((dx dx) + dy dy) + dz dz and the mutant's.  Each pair is the bridge of a
+    four-point set: p with a cell-mate 0.3 eps behind it, q with one 0.3 eps beyond it, min_samples 2 - every point is a core point by
+    its cell's population, the two cells' boxes are cut and the pair p - q alone decides between one cluster and two.
+    -> DB_ROUNDING_MIN cases on which the spec says "within" and the mutant does not, and as many the other way round."""
+    rng = np.random.default_rng([23, seed, DB_ROUNDING_MUTANTS.index(mutant)])
+    got = {True: [], False: []}
+    for trial in range(trials):
+        if all(len(v) >= DB_ROUNDING_MIN for v in got.values()):
+            break
+        eps0 = 1e-2 * rng.uniform(0.5, 1.5)
+        if mutant == "f32" and trial % 2:
+            p = rng.uniform(-0.3, 0.3, 3)
+        else:
+            p = rng.choice([-1.0, 1.0], 3) * np.ldexp(rng.uniform(1.0, 2.0, 3), -rng.integers(12, 31, 3))
+        u = rng.uniform(0.2, 1.0, 3)
+        u /= np.linalg.norm(u)
+        X = np.stack([p, p - 0.3 * eps0 * u, p + eps0 * u, p + 1.3 * eps0 * u]).astype(np.float32)
+        s, t = db_f64_d2(X[[0, 2]], "spec")[0, 1], db_f64_d2(X[[0, 2]], mutant)[0, 1]
+        if s == t:
+            continue
+        lo, hi = min(s, t), max(s, t)
+        eps = np.sqrt(lo)
+        for _ in range(4):            # fl(eps eps) into [lo, hi)
+            if eps * eps < lo:
+                eps = np.nextafter(eps, np.inf)
+        if not lo <= eps * eps < hi:
+            continue
+        within = bool(s <= eps * eps)
+        if len(got[within]) >= DB_ROUNDING_MIN:
+            continue
+        cells, _, _ = db_cells(X, eps)
+        if not (np.array_equal(cells[0], cells[1]) and np.array_equal(cells[2], cells[3]) and not np.array_equal(cells[0], cells[2])):
+            continue
+        lab, ncl, core = db_f64_dbscan(X, eps, 2)
+        labm, nclm, _ = db_f64_dbscan(X, eps, 2, mutant)
+        assert core.all() and ncl == (1 if within else 2) and nclm == (2 if within else 1), (mutant, trial)
+        for v in DB_ROUNDING_MUTANTS + ("spec",):   # the other three cross pairs are far from the edge in every arithmetic
+            d = db_f64_d2(X, v)
+            assert min(d[0, 3], d[1, 2], d[1, 3]) > 1.5 * eps * eps
+        cls = db_classes(X, eps, 0)[tuple(int(v) for v in cells[2] - cells[0])]
+        assert cls["cls"] == ("cut" if within else "beyond") and cls["pop"] == 2
+        got[within].append(dict(name=f"rounding/{mutant}/{'within' if within else 'beyond'}/{len(got[within])}", X=X, eps=float(eps), ms=2,
+                                labels=lab, ncl=ncl, mutant=mutant, mutant_labels=labm, within=within, fifth=False, hashed=False))
+    assert all(len(v) >= DB_ROUNDING_MIN for v in got.values()), (mutant, {k: len(v) for k, v in got.items()})
+    return got[True] + got[False]
+
+
+def db_rounding_separations(n=1000, seed=0):
+    """Of n near-origin pairs, on how many does an eps exist that separates the spec's sum from each mutant's (the sums differ)."""
+    rng = np.random.default_rng([29, seed])
+    count = {v: 0 for v in DB_ROUNDING_MUTANTS}
+    for _ in range(n):
+        p = rng.choice([-1.0, 1.0], 3) * np.ldexp(rng.uniform(1.0, 2.0, 3), -rng.integers(12, 31, 3))
+        u = rng.uniform(0.2, 1.0, 3)
+        X = np.stack([p, p + 1e-2 * u / np.linalg.norm(u)]).astype(np.float32)
+        s = db_f64_d2(X, "spec")[0, 1]
+        for v in DB_ROUNDING_MUTANTS:
+            count[v] += int(db_f64_d2(X, v)[0, 1] != s)
+    return count
+
+
+DB_TINY_SITES = ((0, 0, 0), (7, 0, 0), (14, 1, 0), (0, 0, 0), (300, 0, 0), (14, 8, 0), (-2, -3, -6), (300, 7, 0), (21, 1, 0))
+
+
+def db_tiny_cases(m=7, k=10, off=(768, -300, 5000)):
+    """n = 1 .. 9 points under min_samples = n // 5, which is 0 or 1: every point is a core point, the clusters are the components of
+    "within eps" (on-eps links, a pair at m^2 + 1, a coincident pair).  n < 5 is out of spec: sklearn refuses min_samples = 0."""
+    out = []
+    for n in range(1, 10):
+        V = np.array(DB_TINY_SITES[:n], dtype=np.int64) + np.asarray(off, dtype=np.int64)
+        X = (V * 2.0 ** -k).astype(np.float32)
+        lab, ncl, core = db_int_dbscan(V, m * m, n // 5)
+        lab1, ncl1, _ = db_int_dbscan(V, m * m, 1)
+        assert core.all() and np.array_equal(lab, lab1) and ncl == ncl1
+        out.append(dict(name=f"tiny/n{n}", V=V, local=V - np.asarray(off), k=k, m=m, off=tuple(off), ms=n // 5, eps=m * 2.0 ** -k, X=X, labels=lab,
+                        ncl=ncl, core=core, fifth=True, hashed=db_cells(X, m * 2.0 ** -k)[2]))
+    assert out[8]["ncl"] == 3 and out[8]["labels"].tolist() == [0, 0, 1, 0, 2, 1, 0, 2, 1]
+    return out
+
+
+DB_POINTS_SIZES = (255, 256, 257, 513)
+
+
+def db_points_case(dim, N, m=7, k=10, seed=0):
+    """A float64 lattice in `dim` dimensions for the all-pairs kernel (midas_dbscan_points; the 256-column tile and its NaN padding at
+    N = 255, 256, 257, 513).  Copies M = 4 a site, min_samples = 2 M:
+      chain 1   12 sites along axis 0, exactly eps apart: an end site has 2 M neighbours (== min_samples, M of them on eps), and the
+                smallest index is a copy of the far end - the cluster's number has to travel the whole chain (more than one spread step)
+      chain 2   3 sites, the first at m^2 + 1 of chain 1's last site: a second cluster
+      border    single points exactly on eps of one chain-1 site, along axis 1 and along the last axis: label 0; a decoy at m^2 + 1: noise
+      filler    far single points, noise
+    Copies of chain 1's end sites stand at the indices 255, 256 and N - 1.  dim != 3: the lattice lies at 2^33 + 5, beyond float32."""
+    M, L = 4, 12
+    e = lambda ax, v=1: tuple(v if i == ax else 0 for i in range(dim))  # noqa: E731
+    add = lambda *vs: tuple(int(sum(x)) for x in zip(*vs))  # noqa: E731
+    pts = []
+    for j in range(L):
+        pts += [e(0, j * m)] * M
+    plus = add(e(0, m), e(1, 1))
+    c2 = add(e(0, (L - 1) * m), plus)
+    for j in range(3):
+        pts += [add(c2, e(0, j * m))] * M
+    pts += [add(e(0, 5 * m), e(1, m)), add(e(0, 3 * m), e(dim - 1, -m)), add(e(0, 7 * m), e(dim - 1, m), e(0 if dim == 2 else dim - 2, 1))]
+    nfill = N - len(pts)
+    assert nfill > 0
+    pts += [add(e(0, 100 * m + 3 * m * j), e(1, -50 * m)) for j in range(nfill)]
+    V = np.array(pts, dtype=np.int64)
+    order = np.random.default_rng([31, dim, N, seed]).permutation(N)
+    pos = {int(v): i for i, v in enumerate(order)}
+
+    def put(at, src):  # the point `src` of the list goes to index `at`
+        i = pos[src]
+        o = int(order[at])
+        order[at], order[i] = src, o
+        pos[src], pos[o] = at, i
+    put(0, (L - 1) * M)                     # a copy of chain 1's far end first
+    put(N - 1, 0)                           # copies of its near end at N - 1 and around the tile boundary
+    for at, src in ((255, 1), (256, 2)):
+        if at < N - 1:
+            put(at, src)
+    V = V[order]
+    off = (1 << 33) + 5 if dim != 3 else 768
+    V = V + off
+    X = V.astype(np.float64) * 2.0 ** -k
+    assert np.array_equal(X * 2.0 ** k, V) and (dim == 3) == bool(np.array_equal(X.astype(np.float32).astype(np.float64), X))
+    ms = 2 * M
+    lab, ncl, core = db_int_dbscan(V, m * m, ms)
+    cnt = (((V[:, None, :] - V[None, :, :]) ** 2).sum(axis=2) <= m * m).sum(axis=1)
+    assert ncl == 2 and int((cnt == ms).sum()) == 4 * M and int(core.sum()) == (L + 3) * M, (dim, N)
+    assert lab[0] == 0 and core[0] and sorted(np.unique(lab).tolist()) == [-1, 0, 1]
+    assert int((~core & (lab == 0)).sum()) == 2 and int((lab == -1).sum()) == nfill + 1
+    # with `<` for `<=` nothing is a core point
+    assert not db_int_dbscan(V, m * m - 1, ms)[2].any()
+    return dict(name=f"points/d{dim}/n{N}", V=V, k=k, m=m, ms=ms, eps=m * 2.0 ** -k, X=X, labels=lab, ncl=ncl, core=core, dim=dim)
+
+
+DB_OFFSETS = ((768, -300, 5000), (-4096, 17, -1), (0, 0, 0))     # lattice offsets, some with negative coordinates
+DB_ALIGN = ((0, 0, 0), (1, 2, 3), (3, 1, 2))                      # shifts of the lattice against the cell grid
+DB_SMALL_POPS = (1, 63, 64, 65)
+_DB_CASES = {}
+
+
+def db_edge_cases():
+    """Every lattice case, the rounding cases and the tiny sets, built once: {name: case}."""
+    if _DB_CASES:
+        return _DB_CASES
+    out = []
+    m, k = 7, 10
+    for hashed in (False, True):
+        for delta in (0, 1):
+            out.append(db_probe(m, k, DB_OFFSETS[0], DB_ALIGN[1], DB_POPS, delta, markers=hashed, seed=1))
+            out.append(db_probe(9, k, DB_OFFSETS[1], DB_ALIGN[2], DB_POPS, delta, markers=hashed, seed=2))
+            for oi, off in enumerate(DB_OFFSETS):
+                for ri, r in enumerate(DB_ALIGN):
+                    out.append(db_probe(m, k, off, r, DB_SMALL_POPS, delta, markers=hashed, seed=10 * oi + ri, own=1 + 2 * ri))
+            for ri in (0, 1):
+                out.append(db_probe(m, k, DB_OFFSETS[ri + 1], DB_ALIGN[ri], DB_SMALL_POPS, delta, markers=hashed, seed=20 + ri, own=2, cut_pops=()))
+            out.append(db_probe(m, k, DB_OFFSETS[0], DB_ALIGN[0], DB_SMALL_POPS, delta, markers=hashed, fifth=True, seed=5))
+            out.append(db_probe(3, 9, DB_OFFSETS[2], DB_ALIGN[0], (1, 63, 64), delta, markers=hashed, fifth=True, seed=6))
+        for short in (0, 1):
+            for ri, r in enumerate(DB_ALIGN[:2]):
+                out += db_own_cell(m, k, DB_OFFSETS[ri], r, short, markers=hashed, seed=ri)
+        for on in (True, False):
+            for kind in ("box", "cut", "one"):
+                for s in range(16 if (kind == "one" and on) else 2):
+                    out.append(db_bridge(m, k, DB_OFFSETS[s % 3], DB_ALIGN[s % 3], on, kind, s, markers=hashed, second_first=s % 4 != 3))
+                out.append(db_bridge(m, k, DB_OFFSETS[1], DB_ALIGN[1], on, kind, 40, markers=hashed, fifth=True))
+        for mode in ("on", "plus", "none"):
+            for apop in (1, 65, 130):
+                for s in range(2):
+                    out.append(db_border(m, k, DB_OFFSETS[(s + apop) % 3], DB_ALIGN[s], mode, apop, s, markers=hashed))
+                out.append(db_border(m, k, DB_OFFSETS[0], DB_ALIGN[2], mode, apop, 50, markers=hashed, fifth=True))
+        for want in ((2, 2, 2), (2, 2, 0), (2, 0, 0)):
+            out += db_corner(97, 13, DB_OFFSETS[0] if not hashed else DB_OFFSETS[1], want, markers=hashed)
+    for mutant in DB_ROUNDING_MUTANTS:
+        out += db_rounding_cases(mutant)
+    out += db_tiny_cases()
+    for c in out:
+        assert c["name"] not in _DB_CASES, c["name"]
+        _DB_CASES[c["name"]] = c
+    return _DB_CASES
+
+
+def db_fixture_cases():
+    """The cases fixture G17 holds: those the reference's cluster_particles can be given - min_samples is n // 5 there, and at least 1."""
+    return [c for c in db_edge_cases().values() if c["fifth"] and c["ms"] >= 1 and "V" in c]

@@ -25,6 +25,10 @@ as-is produce the outputs stored here:
       particle, at the edges of the isclose guard (modules/particle_filter.py:459-468) - written
       by tools/gen_softmax_guard.py from the rows in tests/_recipes.py, with this file's
       import_reference and new_pf.
+  G17 particle_filter.cluster_particles on lattice sets with points exactly on eps, neighbour
+      counts exactly at min_samples, single-pair bridges and on-eps border links
+      (modules/particle_filter.py:208-217) - written by tools/gen_dbscan_edges.py from the
+      recipes in tests/_recipes.py, with this file's import_reference and new_pf.
 
 A fixture is data only: inputs + the reference's outputs (+ the RNG draws it consumed).
 Usage:  python tools/gen_goldens.py            (rewrites tests/golden/*.npz)
