@@ -614,7 +614,7 @@ MD int mesh_list_check(const MeshRec* __restrict__ vlist, int32_t h, const doubl
 // float32 points d~ satisfy |d - d~| <= E + 1.1e-7 d~ with E = 2.5e-7 (|tq_x| + |tq_y| + |tq_z|); the computed squared
 // distance is within 4e-7 (relative) of d~^2.  Hence, with 4e-6 of relative slack on the squares:
 //   d2f <= (thr - E)^2 (1 - 4e-6)  =>  d <= thr  (a sure hit: the exact test d2 <= t2 holds - t2 is thr^2 to 1e-16),
-//   d2f >= (thr + E)^2 (1 + 4e-6)  =>  d >  thr  (a sure miss),
+//   d2f >  (thr + E)^2 (1 + 4e-6)  =>  d >  thr  (a sure miss; strict, for thr = 0 at the origin: see below),
 // and anything between (about one record in 10^5; also NaN) is AMBIGUOUS: the lane returns -2 and the caller decides it
 // with mesh_list_check on the float64 records.  "Provably too far" uses a bound that is never below the exact path's
 // (a later stop is still a correct stop): rho > (thr + |tq - header| (1 + 1e-6)) (1 + 1e-6).  Events in record order,
@@ -652,7 +652,9 @@ MD int mesh_screen_check(const MeshScr* __restrict__ vscr, int32_t h, const floa
 #pragma unroll
         for (int j = 0; j < MESH_BATCH; ++j) {
             const float d = dist2f3(tqf, e[j]);
-            const bool hit = d <= t2lo, miss = d >= t2hi;
+            // (a strict miss: with thr = 0 and a translation of exactly 0, E = 0 and t2hi = 0 - a vertex ON the particle, d2f = 0, is
+            // no miss (0 > 0 is false: kept) and goes to the float64 records; d2f > 0 = t2hi there means v_f != 0, hence v != 0, d > 0)
+            const bool hit = d <= t2lo, miss = d > t2hi;
             stops |= (e[j].rho > limf ? 1u : 0u) << j;
             hits |= (hit ? 1u : 0u) << j;
             amb |= ((hit | miss) ? 0u : 1u) << j;
@@ -711,6 +713,9 @@ MD FieldProbe field_fetch(const MeshField& f, const float* tq, bool live) {
     return pr;
 }
 MD int field_decide(const MeshField& f, const FieldProbe& pr, double thr) {
+    // the rule is !(dist > thr): under a NaN or +inf threshold no distance compares greater - a NaN translation's (dist = +inf)
+    // neither - and every particle is kept, field or no field, before the exact paths (which find no vertex for such a lane) are asked
+    if (!(thr < (double)INFINITY)) return 1;
     if (pr.state == 2 || !(thr >= 0.0)) return -1;
     const float thr_up = __double2float_ru(thr), thr_dn = __double2float_rd(thr);
     if (pr.state == 1) return f.expand > thr_up * 1.00001f ? 0 : -1;  // outside the grown bounding box: farther than `expand` from every vertex

@@ -1785,3 +1785,452 @@ def db_edge_cases():
 def db_fixture_cases():
     """The cases fixture G17 holds: those the reference's cluster_particles can be given - min_samples is n // 5 there, and at least 1."""
     return [c for c in db_edge_cases().values() if c["fifth"] and c["ms"] >= 1 and "V" in c]
+
+
+# ---- the prune at its edges: vertices on the threshold sphere, the edges of the vertex lists ---------------------------------------
+# (tools/gen_prune_edges.py writes G18 from these; tests/test_prune_edges_reference.py on the CPU, tests/test_gpu_prune_edges.py on
+# the GPU; DESIGN.md, "The prune's rule")
+# The rule is invalid = dist_to_nearest_vertex > pen_max in float64 (modules/particle_filter.py:379-403).  The world is an integer
+# lattice with unit u = 2^-16 m: every vertex (float64), every codebook entry's and every particle's translation (float32) is an integer
+# multiple of u below 2^24 in magnitude, so every value is exact in float32, every squared distance an integer times u^2 in any
+# arithmetic, fused or not, in any order, and with thr = m u the predicate is |dV|^2 <= m^2 over int64.  One case = one particle, its
+# own codebook entry (identity rotation) and its own vertices in its own region; regions stand PE_SPACING units apart and every point of
+# a case lies within PE_REACH units of its region's origin, so no case sees another's vertices or entries (asserted from integers).
+PE_K = 16
+PE_U = 2.0 ** -PE_K
+PE_M = 131                 # thr = 131 u = 1.99890 mm, next to the reference's 0.002
+# squared_threshold(131 u) lies one ulp ABOVE (131 u)^2 - as for every m whose significand is below sqrt 2 -, so on that world a vertex
+# exactly on the sphere has d2 < t2 and a `<` for the `<=` of a hit test goes unnoticed.  With a significand of sqrt 2 or more
+# (113 = 1.77 * 64) t2 == (m u)^2 exactly: on the world of 113 u (1.72424 mm) an on-sphere vertex has d2 == t2 at every stage.
+PE_M_STRICT = 113
+PE_MS = (PE_M, PE_M_STRICT)
+PE_SPACING = 4096          # units between the origins of neighbouring regions
+PE_REACH = 600             # a case's entry, particle and vertices lie this close (per axis) to its region's origin
+PE_DELTA = 450             # list-depth, tie and tree cases: the particle stands 450 u from its entry
+PE_LIST = 256              # records of an entry's vertex list (csrc/midas_internal.hpp MESH_M)
+PE_DEPTHS = (1, 8, 9, 16, 17, 32, 33, 80, 81, 144, 145, 256, 257, 300)   # the deciding vertex's rank by distance from the entry
+PE_OFF = (37, -21, 12)     # the particle of an "off its entry" case, from the entry
+PE_FIELD_DISTS = ("0", "1", "m/4", "m/2", "2m", "4m", "far")
+PE_DEGENERATE = (0.0, float("inf"), -1e-3, float("nan"))
+PE_D = 128
+PE_AXES = ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1))
+
+
+def pe_squared_threshold(thr):
+    """csrc/midas_internal.hpp squared_threshold restated: the largest float64 t2 with sqrt(t2) <= thr, so that sqrt(d2) > thr <=>
+    d2 > t2; -1 for a negative or NaN threshold, +inf for +inf."""
+    thr = float(thr)
+    if not thr >= 0.0:
+        return -1.0
+    if np.isinf(thr):
+        return float("inf")
+    t = thr * thr
+    while np.sqrt(t) > thr:
+        t = float(np.nextafter(t, 0.0))
+    while np.sqrt(np.nextafter(t, np.inf)) <= thr:
+        t = float(np.nextafter(t, np.inf))
+    return t
+
+
+def pe_classes(m, off=0):
+    """The direction classes (a, b, c), 0 <= a <= b <= c, with a^2 + b^2 + c^2 = m^2 + off, by enumeration."""
+    import math
+    t, out = m * m + off, []
+    for a in range(m + 2):
+        for b in range(a, m + 2):
+            c2 = t - a * a - b * b
+            if c2 < b * b:
+                break
+            c = math.isqrt(c2)
+            if c * c == c2:
+                out.append((a, b, c))
+    return out
+
+
+def pe_orbit(v):
+    """Every distinct image of v under sign flips and axis permutations, sorted."""
+    import itertools
+    return sorted({tuple(s * x for s, x in zip(sg, p)) for p in itertools.permutations(v) for sg in itertools.product((1, -1), repeat=3)})
+
+
+def _pe_case(name, family, m, P, verts, E=(0, 0, 0), decider=None, tie=False, kind=None):
+    """A case in its region's own coordinates (integers): the entry E, the particle P, its vertices; `decider` the index of the
+    vertex that decides it.  Works out the nearest vertex's squared distance d2 (-1: no vertex of its own), the mask d2 <= m^2, the
+    deciding vertex's rank by distance from the entry (1 = the list's first record; asserted unambiguous unless `tie`) and whether
+    the lists can settle the case at all."""
+    P, E = np.asarray(P, dtype=np.int64), np.asarray(E, dtype=np.int64)
+    V = np.asarray(verts, dtype=np.int64).reshape(-1, 3)
+    assert np.abs(P).max() <= PE_REACH and np.abs(E).max() <= PE_REACH and (not len(V) or np.abs(V).max() <= PE_REACH), name
+    assert len({tuple(v) for v in V}) == len(V), f"{name}: coincident vertices"
+    dP = ((V - P) ** 2).sum(1)
+    rho2 = ((V - E) ** 2).sum(1)
+    d2 = int(dP.min()) if len(V) else -1
+    c = dict(name=name, family=family, kind=kind, m=m, P=P, E=E, V=V, d2=d2, keep=bool(len(V) and d2 <= m * m), rank=0, decider=decider, tie=tie)
+    if decider is not None:
+        below, same = int((rho2 < rho2[decider]).sum()), int((rho2 == rho2[decider]).sum())
+        assert same == (2 if tie else 1), f"{name}: {same} vertices at the deciding vertex's distance from the entry"
+        c["rank"] = below + 1
+        others = np.delete(dP, decider)
+        assert not len(others) or others.min() > m * m + 1, f"{name}: a filler within reach of the particle"
+    return c
+
+
+def pe_sphere_cases(m):
+    """On the sphere: one vertex at |dV|^2 = m^2 (kept), m^2 - 1 (kept) and m^2 + 1 (pruned) in every direction class under sign
+    flips and axis permutations; the particle on its entry and PE_OFF off it (the m^2 cases both ways, the others alternating)."""
+    out = []
+    for off, kind in ((0, "on"), (-1, "in"), (1, "out")):
+        i = 0
+        for cl in pe_classes(m, off):
+            for d in pe_orbit(cl):
+                for delta in (((0, 0, 0), PE_OFF) if off == 0 else ((0, 0, 0),) if i % 2 else (PE_OFF,)):
+                    P = np.array(delta)
+                    c = _pe_case(f"sphere-{kind}-{d[0]}.{d[1]}.{d[2]}-{'on' if delta[0] == 0 else 'off'}", "sphere", m, P, [P + d], decider=0, kind=kind)
+                    assert c["d2"] == m * m + off and c["rank"] == 1
+                    out.append(c)
+                i += 1
+    return out
+
+
+def pe_collinear_cases(m):
+    """Entry, particle and vertex on one line, the vertex on the far side: rho_vertex = delta + d exactly, the tightest case of the
+    triangle-inequality stop.  Along the six axes at d = m - 1, m, m + 1; along every direction class of the sphere at d = m."""
+    out = []
+    for a in PE_AXES:
+        a = np.array(a)
+        for r in (m - 1, m, m + 1):
+            out.append(_pe_case(f"collinear-axis{a.tolist()}-{r}", "collinear", m, 200 * a, [(200 + r) * a], decider=0, kind="on" if r == m else "in" if r < m else "out"))
+            assert out[-1]["d2"] == r * r
+    for cl in pe_classes(m):
+        d = np.array(pe_orbit(cl)[len(pe_orbit(cl)) // 3])
+        out.append(_pe_case(f"collinear-{cl}", "collinear", m, 2 * d, [3 * d], decider=0, kind="on"))
+        assert out[-1]["d2"] == m * m and int((9 * d * d).sum()) == 9 * m * m
+    return out
+
+
+def _pe_depth_vectors(m):
+    """The deciding vertex from the particle, per kind: on the sphere (collinear with the entry: the stop's tightest case),
+    at m^2 - 1 and at m^2 + 1."""
+    v = {"on": (m, 0, 0), "in": pe_classes(m, -1)[-1][::-1], "out": (m, 1, 0)}
+    assert sum(x * x for x in v["in"]) == m * m - 1 and sum(x * x for x in v["out"]) == m * m + 1
+    return v
+
+
+def pe_depth_cases(m):
+    """List depth: the deciding vertex is the j-th by distance from the entry, j in PE_DEPTHS (257 and 300: not in the list - the
+    header's rho must not stop the scan and the tree must find it).  The j - 1 fillers stand on the entry's far side at the radii
+    1 .. j - 1, each at 450 + r > m + 1 from the particle.  Kind "none": the twin with no vertex within reach."""
+    out, vec = [], _pe_depth_vectors(m)
+    P = np.array((PE_DELTA, 0, 0))
+    for j in PE_DEPTHS:
+        fill = [(-r, 0, 0) for r in range(1, j)]
+        for kind in ("on", "in", "out", "none"):
+            if kind == "none":
+                c = _pe_case(f"depth-{j}-none", "depth", m, P, fill, kind=kind)
+                c["rank"] = j
+                assert not c["keep"]
+            else:
+                c = _pe_case(f"depth-{j}-{kind}", "depth", m, P, fill + [P + vec[kind]], decider=j - 1, kind=kind)
+                assert c["rank"] == j and c["keep"] == (kind != "out")
+            out.append(c)
+    return out
+
+
+def pe_tie_cases(m):
+    """Ties at the list's end: 255 fillers, then two vertices equidistant from the entry at ranks 256 / 257, one of them on the
+    particle's sphere and the other on the far side.  Whichever the builder lists, the particle is kept."""
+    out = []
+    for a in PE_AXES:
+        a = np.array(a)
+        fill = [tuple(-r * a) for r in range(1, PE_LIST)]
+        out.append(_pe_case(f"tie-{a.tolist()}", "tie", m, PE_DELTA * a, fill + [tuple(-(PE_DELTA + m) * a), tuple((PE_DELTA + m) * a)], decider=PE_LIST, tie=True, kind="on"))
+    for c in out:   # (255 fillers at the radii 1 .. 255; the far-side twin and the deciding vertex share the ranks 256 and 257)
+        assert len(c["V"]) == PE_LIST + 1 and c["rank"] == PE_LIST and c["keep"] and c["d2"] == m * m
+    return out
+
+
+def pe_tree_cases(m):
+    """Tree edges: 256 fillers exhaust the list, the lone vertex within reach stands axis-aligned BETWEEN entry and particle, so a
+    leaf whose box ends at it has box_dist2 == d2 == m^2 u^2 from the particle; and the same vertex one unit farther (pruned)."""
+    out = []
+    for a in PE_AXES:
+        a = np.array(a)
+        fill = [tuple(-r * a) for r in range(1, PE_LIST + 1)]
+        for r, kind in ((m, "on"), (m + 1, "out")):
+            c = _pe_case(f"tree-{a.tolist()}-{kind}", "tree", m, PE_DELTA * a, fill + [tuple((PE_DELTA - r) * a)], decider=PE_LIST, kind=kind)
+            assert c["rank"] == PE_LIST + 1 and c["d2"] == r * r
+            out.append(c)
+    return out
+
+
+def pe_field_cases(m):
+    """Field-decided: the particle on its entry, its one vertex at 0, 1, m/4, m/2, 2m and 4m units; "far": no vertex of its own (the
+    nearest stands in another region, beyond 20 m units)."""
+    out = []
+    for tag in PE_FIELD_DISTS:
+        for a in PE_AXES[:2]:
+            r = {"0": 0, "1": 1, "m/4": m // 4, "m/2": m // 2, "2m": 2 * m, "4m": 4 * m, "far": None}[tag]
+            V = [] if r is None else [tuple(r * np.array(a))]
+            out.append(_pe_case(f"field-{tag}-{a}", "field", m, (0, 0, 0), V, kind=tag))
+            assert out[-1]["keep"] == (r is not None and r <= m)
+    return out
+
+
+_PE_WORLDS = {}
+
+
+def pe_world(m=PE_M):
+    """Every lattice case of threshold m u as the particles of ONE frame over ONE world.  -> a namespace: cases; per case (= per
+    particle = per codebook entry) keep, d2, rank, the slice of its vertices; entries / parts / verts as int64 lattice coordinates;
+    cb_poses, poses (identity rotations, float32), verts64, emb, code, thr.  Asserts the isolation of the regions, the exactness of
+    every coordinate and, by an exact nearest-neighbour query over the whole world, that each case's nearest vertex is its own."""
+    import types
+    if m in _PE_WORLDS:
+        return _PE_WORLDS[m]
+    from scipy.spatial import cKDTree
+    cases = pe_sphere_cases(m) + pe_collinear_cases(m) + pe_depth_cases(m) + pe_tie_cases(m) + pe_tree_cases(m) + pe_field_cases(m)
+    n = len(cases)
+    assert len({c["name"] for c in cases}) == n
+    g = int(np.ceil(n ** (1.0 / 3.0)))
+    i = np.arange(n)
+    org = (np.stack([i % g, (i // g) % g, i // (g * g)], axis=1) - g // 2).astype(np.int64) * PE_SPACING
+    # the first field case - particle, entry and vertex on one point - takes the region at the world's origin: its translation is
+    # exactly (0, 0, 0), where the float32 screen's slack E vanishes (under thr = 0 its bounds collapse onto d2f = 0)
+    zero, first = int(np.flatnonzero((org == 0).all(1))[0]), [c["family"] == "field" and c["kind"] == "0" for c in cases].index(True)
+    org[[zero, first]] = org[[first, zero]]
+    assert not org[first].any() and not cases[first]["P"].any() and not cases[first]["V"].any()
+    assert PE_SPACING - 2 * PE_REACH > 4 * m + PE_REACH, "points of two regions within 4 m units + PE_REACH"
+    entries = np.stack([c["E"] for c in cases]) + org
+    parts = np.stack([c["P"] for c in cases]) + org
+    at = np.cumsum([0] + [len(c["V"]) for c in cases])
+    verts = np.concatenate([c["V"] + o for c, o in zip(cases, org)])
+    owner = np.repeat(i, np.diff(at))
+    for a in (entries, parts, verts):
+        assert np.abs(a).max() < (1 << 24)
+        f = (a * PE_U).astype(np.float32)
+        assert np.array_equal(f.astype(np.float64) * 2.0 ** PE_K, a.astype(np.float64))
+    # exact queries (integers below 2^24, squared distances below 2^53)
+    vt, et = cKDTree(verts.astype(np.float64)), cKDTree(entries.astype(np.float64))
+    dv, iv = vt.query(parts.astype(np.float64), k=1)
+    de, ie = et.query(parts.astype(np.float64), k=2)
+    assert np.array_equal(ie[:, 0], i) and (de[:, 1] > de[:, 0] + 2 * PE_REACH).all(), "a particle whose nearest entry is not its own"
+    d2 = np.array([c["d2"] for c in cases], dtype=np.int64)
+    got = np.rint(dv * dv).astype(np.int64)
+    has = d2 >= 0
+    assert np.array_equal(got[has], d2[has]) and np.array_equal(owner[iv[has]], i[has]), "a case whose nearest vertex is not its own"
+    assert (got[~has] > (20 * m) ** 2).all(), "a case without vertices within 20 m units of another's"
+    # the entry's list: its own vertices first, every foreign vertex farther than any of its own and beyond the stop's reach
+    own_far = np.array([int(((c["V"] - c["E"]) ** 2).sum(1).max()) if len(c["V"]) else 0 for c in cases])
+    assert ((PE_SPACING - 2 * PE_REACH) ** 2 > own_far).all() and PE_SPACING - 2 * PE_REACH > PE_DELTA + m + 4
+    keep = np.array([c["keep"] for c in cases])
+    assert np.array_equal(keep, has & (d2 <= m * m))
+    ident = np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+    cb_poses, poses = ident.copy(), ident.copy()
+    cb_poses[:, :3, 3] = (entries * PE_U).astype(np.float32)
+    poses[:, :3, 3] = (parts * PE_U).astype(np.float32)
+    rng = np.random.default_rng(1800 + m)
+    emb = rng.standard_normal((n, PE_D)).astype(np.float32)
+    w = types.SimpleNamespace(m=m, thr=m * PE_U, cases=cases, n=n, org=org, entries=entries, parts=parts, verts=verts, owner=owner, at=at,
+                              keep=keep, d2=d2, rank=np.array([c["rank"] for c in cases]), family=np.array([c["family"] for c in cases]),
+                              kind=np.array([str(c["kind"]) for c in cases]), cb_poses=cb_poses, poses=poses,
+                              verts64=verts.astype(np.float64) * PE_U, emb=emb, code=rng.standard_normal(PE_D))
+    nfill = np.diff(at) - np.array([c["decider"] is not None for c in cases]) - (w.family == "tie")
+    # what neither the field nor the lists can settle and the tree must: a deciding vertex within a unit of the sphere behind the
+    # list's end whose header cannot stop - the header's rho is the 257th vertex's distance from the entry: 450 - m or 450 - m - 1 in
+    # the tree family, the 257th filler's 257 u under the 300th vertex, all far below delta + thr; only the 257th vertex at m^2 + 1
+    # on the far side (rho^2 = (450 + m)^2 + 1) is stopped by it.  (The twins with no vertex within reach stand 451 u from their
+    # nearest vertex: the field may decide them - `tree_open` - and without a field the tree does.)
+    w.tree = ((w.rank > PE_LIST) & np.isin(w.kind, ("on", "in"))) | (w.family == "tree") | ((w.family == "depth") & (w.rank == 300) & (w.kind == "out"))
+    w.tree_open = (w.kind == "none") & (nfill >= PE_LIST)
+    w.shallow = (w.kind == "on") & (w.rank <= 16) & (w.rank >= 1) & np.isin(w.family, ("sphere", "collinear", "depth"))
+    _PE_WORLDS[m] = w
+    return w
+
+
+def pe_frames(w):
+    """The frames run over a world, as index lists into its cases: "all"; "small" (at most 512: every case outside the sphere
+    family and every tenth of it - the two-kernel form's side of both engines' limits); "shallow" (only on-sphere cases decided
+    within the first 16 records: nothing may reach the tree)."""
+    i = np.arange(w.n)
+    sph = i[w.family == "sphere"]
+    small = np.sort(np.concatenate([i[w.family != "sphere"], sph[::10]]))
+    small = small if len(small) % 2 == 0 else small[1:]     # (an even count: the sharded step takes no other)
+    assert len(small) <= 512 < 2048 < w.n and w.n % 2 == 0
+    shallow = i[w.shallow]
+    return {"all": i, "small": small, "shallow": shallow[len(shallow) % 2:]}
+
+
+def pe_degenerate_expected(w, thr, poses=None):
+    """~(nn3_dist > thr) by the oracle for a degenerate threshold (0, +inf, negative, NaN) over the world's particles (or `poses`)."""
+    from oracle import oracle
+    d = oracle.nn3_dist(w.poses if poses is None else poses, w.verts64)
+    with np.errstate(invalid="ignore"):
+        return ~(d > thr)
+
+
+def pe_nan_pose():
+    P = np.eye(4, dtype=np.float32)
+    P[0, 3] = np.nan
+    return P
+
+
+def _pe_brute_world(name, m, verts, parts):
+    """A small world decided by brute force over int64: every particle stands on a codebook entry of its own (distinct
+    positions: its nearest entry is itself, at distance 0), the mask is min |dV|^2 <= m^2.  -> a namespace like pe_world's."""
+    import types
+    verts, parts = np.asarray(verts, dtype=np.int64).reshape(-1, 3), np.asarray(parts, dtype=np.int64).reshape(-1, 3)
+    n = len(parts)
+    assert len({tuple(p) for p in parts}) == n and len({tuple(v) for v in verts}) == len(verts) and max(np.abs(verts).max(), np.abs(parts).max()) < (1 << 24)
+    d2 = ((parts[:, None, :] - verts[None, :, :]) ** 2).sum(2).min(1)
+    ident = np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+    ident[:, :3, 3] = (parts * PE_U).astype(np.float32)
+    assert np.array_equal(ident[:, :3, 3].astype(np.float64) * 2.0 ** PE_K, parts.astype(np.float64))
+    rng = np.random.default_rng(1900 + m + len(verts))
+    cb_poses = _pe_with_far_entries(ident)
+    return types.SimpleNamespace(name=name, m=m, thr=m * PE_U, n=n, parts=parts, verts=verts, d2=d2, keep=d2 <= m * m, cb_poses=cb_poses, poses=ident.copy(),
+                                 verts64=verts.astype(np.float64) * PE_U, emb=rng.standard_normal((len(cb_poses), PE_D)).astype(np.float32),
+                                 code=rng.standard_normal(PE_D))
+
+
+PE_FAR_ENTRIES = 600
+
+
+def _pe_with_far_entries(poses):
+    """The small worlds' codebooks: an entry per particle, then PE_FAR_ENTRIES entries on a line 16 m away (nobody's nearest), so
+    that the codebook has an ordinary size and only the MESH is tiny."""
+    far = np.tile(np.eye(4, dtype=np.float32), (PE_FAR_ENTRIES, 1, 1))
+    far[:, 0, 3] = 16.0 + np.arange(PE_FAR_ENTRIES, dtype=np.float32) * 2.0 ** -10
+    far[:, 1, 3] = far[:, 2, 3] = 16.0
+    assert np.abs(poses[:, :3, 3]).max() < 1.0
+    return np.concatenate([poses, far])
+
+
+PE_FACE_MS = (163, 164, 180)       # 2.4872 mm: "outside the grown grid = pruned" is armed (FIELD_EXPAND = 2.5 mm); 2.5024 mm and 2.7466 mm: it is not
+PE_FACE_OUT = (170, 180, 181, 400)  # units outward that lie beyond the grown grid: FIELD_EXPAND 1.01 = 165.5 units plus a cell
+
+
+def pe_face_world(m):
+    """Mesh faces and the field's reach: a mesh of 15 vertices whose extreme vertex on each axis stands alone at +-100 units; a
+    particle straight outward from it at m and m + 1 units (on the sphere, one unit beyond) and at PE_FACE_OUT units, beyond the
+    grown grid.  Straight outward the extreme vertex is the nearest, so d is the offset itself (asserted): with m = 180 the particle
+    at 170 and 180 units is outside the grid AND within thr - kept; with m = 163 every particle outside the grid is pruned."""
+    R = 100
+    verts = [(0, 0, 0)] + [tuple(R * np.array(a)) for a in PE_AXES] + [(sx * 40, sy * 40, sz * 40) for sx in (1, -1) for sy in (1, -1) for sz in (1, -1)]
+    outs = sorted({m, m + 1} | set(PE_FACE_OUT))
+    parts = [tuple((R + o) * np.array(a)) for a in PE_AXES for o in outs]
+    w = _pe_brute_world(f"face-{m}", m, verts, parts)
+    assert np.array_equal(w.d2, np.array([o * o for _ in PE_AXES for o in outs]))
+    assert FIELD_EXPAND_UNITS * 1.01 + 4 < min(PE_FACE_OUT) and (m != 180 or w.keep.reshape(6, -1)[:, :2].all())
+    w.outside = np.array([o in PE_FACE_OUT for _ in PE_AXES for o in outs])
+    return w
+
+
+FIELD_EXPAND_UNITS = 0.0025 / PE_U   # csrc/tree.hip FIELD_EXPAND in lattice units: 163.84
+PE_TINY_SIZES = (1, 2, 16, 17, 256, 257)
+
+
+def pe_tiny_world(nv, m=PE_M):
+    """Tiny meshes: nv vertices in all on a line, 3 units apart (lists padded with rho = inf records, a header rho = inf up to 256
+    vertices, a tree of one leaf); particles around the first and the last vertex at m, m + 1 straight outward, on a direction
+    class of the sphere, one at 0 and one far off."""
+    verts = [(3 * i, 0, 0) for i in range(nv)]
+    end = 3 * (nv - 1)
+    a, b, c = pe_classes(m)[1]
+    parts = [(-m, 0, 0), (-m - 1, 0, 0), (end + m, 0, 0), (end + m + 1, 0, 0), (-c, a, b), (-c, a, b + 1), (end + c, -b, a), (end + c, -b - 1, a),
+             (0, 0, 0), (end, m, 0), (end, 0, -m - 1), (end + 20 * m, 7, 0)]
+    w = _pe_brute_world(f"tiny-{nv}", m, verts, parts)
+    assert w.keep.tolist() == [True, False, True, False, True, False, True, False, True, True, False, False], (nv, w.keep.tolist())
+    return w
+
+
+# the ulp family, off the lattice: float64 vertices and float32 particles whose spec distance d2 = fma(dz, dz, fma(dy, dy, dx dx))
+# (csrc/tree_search.hpp dist2, oracle mo_nn3) is exactly t2 = squared_threshold(thr) - kept, and above fl(thr thr) for these
+# thresholds - or the next double above t2 - pruned.
+PE_ULP_THRS = (0.002, 1e-4, 0.004)
+PE_ULP_PER_SIDE = 12
+
+
+def _fma1(a, b, c):
+    from fractions import Fraction
+    return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+
+
+def pe_ulp_d2(p, v, variant="spec"):
+    """The squared distance of the float32 particle p (as float64) from the float64 vertex v as the spec adds it up, or as a mutant
+    does: "reversed" (the chain from dz), "uncontracted" ((dx dx + dy dy) + dz dz with every product rounded)."""
+    dx, dy, dz = (float(p[i]) - float(v[i]) for i in range(3))
+    if variant == "spec":
+        return _fma1(dz, dz, _fma1(dy, dy, dx * dx))
+    if variant == "reversed":
+        return _fma1(dx, dx, _fma1(dy, dy, dz * dz))
+    if variant == "uncontracted":
+        return (dx * dx + dy * dy) + dz * dz
+    raise ValueError(variant)
+
+
+_PE_ULP = {}
+
+
+def pe_ulp_world(thr, per_side=PE_ULP_PER_SIDE, max_trials=4000):
+    """Per side ("on": d2 == t2, kept; "above": d2 == the next double, pruned) `per_side` cases found by search: the particle a
+    float32 point of a 2^-5 m grid in the plane z = 0 (its own entry), the vertex v = p - d with d drawn inside the sphere and dz
+    stepped by ulps until the chain lands on the target exactly.  The cases of each side are chosen so that, where the search finds
+    them, some separate the mutants: a reversed chain or an uncontracted sum puts them on the other side of t2 (`flips`, counted per
+    variant; for all three thresholds of PE_ULP_THRS the search finds both within its first few hundred trials).  Asserts t2 !=
+    thr thr, and that sqrt(d2) > thr agrees with d2 > t2 on every point."""
+    import types
+    if thr in _PE_ULP:
+        return _PE_ULP[thr]
+    t2 = pe_squared_threshold(thr)
+    assert t2 != thr * thr and t2 == np.nextafter(thr * thr, np.inf), "a threshold whose t2 is thr thr: the family needs another"
+    rng = np.random.default_rng(int(thr * 1e7) + 18)
+    P, V, keep, flips = [], [], [], {"reversed": 0, "uncontracted": 0}
+    for side, target in (("on", t2), ("above", float(np.nextafter(t2, np.inf)))):
+        found, want_flip = [], {"reversed": 2, "uncontracted": 2}
+        for trial in range(max_trials):
+            if len(found) >= per_side:
+                break
+            i = len(P) + len(found)
+            p = np.array([(i % 8 - 4) * 2.0 ** -5, (i // 8 - 3) * 2.0 ** -5, 0.0])
+            ab = rng.uniform(-0.65, 0.65, 2) * thr
+            v = np.array([p[0] - ab[0], p[1] - ab[1], 0.0])
+            dx, dy = p[0] - v[0], p[1] - v[1]
+            s = _fma1(dy, dy, dx * dx)
+            z = float(np.sqrt(target - s)) * (1 if trial % 2 else -1)
+            for k in range(-6, 7):
+                zk = z
+                for _ in range(abs(k)):
+                    zk = float(np.nextafter(zk, np.inf if k > 0 else -np.inf))
+                v[2] = -zk
+                if pe_ulp_d2(p, v) == target:
+                    fl = {var: (pe_ulp_d2(p, v, var) > t2) != (target > t2) for var in flips}
+                    need = [var for var in fl if fl[var] and want_flip[var] > 0]
+                    if need or len(found) < per_side - sum(want_flip.values()):
+                        for var in need:
+                            want_flip[var] -= 1
+                        found.append((p.copy(), v.copy(), fl))
+                    break
+        assert len(found) == per_side, (thr, side, len(found))
+        for p, v, fl in found:
+            d2 = pe_ulp_d2(p, v)
+            assert (np.sqrt(d2) > thr) == (d2 > t2) == (side == "above")
+            P.append(p)
+            V.append(v)
+            keep.append(side == "on")
+            for var in flips:
+                flips[var] += fl[var]
+    P, V = np.array(P), np.array(V)
+    n = len(P)
+    assert np.array_equal(P.astype(np.float32).astype(np.float64), P) and len({tuple(p) for p in P}) == n
+    ident = np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+    ident[:, :3, 3] = P.astype(np.float32)
+    w = types.SimpleNamespace(name=f"ulp-{thr}", thr=thr, t2=t2, n=n, keep=np.array(keep), cb_poses=_pe_with_far_entries(ident), poses=ident.copy(), verts64=V,
+                              flips=flips, emb=rng.standard_normal((n + PE_FAR_ENTRIES, PE_D)).astype(np.float32), code=rng.standard_normal(PE_D))
+    _PE_ULP[thr] = w
+    return w
+
+
+def pe_tiled(w, n):
+    """The particles of a small world repeated up to n (several particles on one pose are ordinary): -> (poses, the case of each)."""
+    idx = np.arange(n) % w.n
+    return w.poses[idx], idx

@@ -40,7 +40,7 @@ def test_sure_hits_and_misses_are_exact(thr, scale):
     d2f = _d2f(tq, vf)
     d = tq.astype(np.float64) - v
     exact_hit = np.sqrt((d * d).sum(1)) <= thr                      # the oracle's predicate (nn3_dist > pen_max is a miss)
-    sure_hit, sure_miss = d2f <= t2lo, d2f >= t2hi
+    sure_hit, sure_miss = d2f <= t2lo, d2f > t2hi                   # (the miss is strict: see test_zero_threshold_at_the_origin)
     assert not (sure_hit & sure_miss).any()
     assert exact_hit[sure_hit].all(), "a sure hit that is not a hit"
     assert (~exact_hit[sure_miss]).all(), "a sure miss that is a hit"
@@ -57,5 +57,18 @@ def test_nan_and_infinite_are_never_sure():
     t2lo, t2hi = _thresholds(tq, 2e-3)
     with np.errstate(invalid="ignore"):
         d2f = _d2f(tq, vf)
-        assert not (d2f[0] <= t2lo[0]) and not (d2f[0] >= t2hi[0])  # NaN: ambiguous -> the float64 path decides
-        assert d2f[1] >= t2hi[1]                                     # padding: a sure miss
+        assert not (d2f[0] <= t2lo[0]) and not (d2f[0] > t2hi[0])   # NaN: ambiguous -> the float64 path decides
+        assert d2f[1] > t2hi[1]                                      # padding: a sure miss
+
+
+def test_zero_threshold_at_the_origin():
+    """thr = 0 and a translation of exactly (0, 0, 0): E = 0, so t2hi = 0.  A vertex ON the particle (d2f = 0) is kept by the rule
+    (0 > 0 is false) and must not be a sure miss - with `>=` it was; strictly, it is ambiguous and the float64 records decide.  A
+    vertex a lattice unit away has d2f > 0 and is a sure miss; one so close that its square underflows is ambiguous too."""
+    tq = np.zeros((3, 3), dtype=f32)
+    vf = np.array([[0, 0, 0], [2.0 ** -16, 0, 0], [0, -1e-30, 0]], dtype=f32)
+    t2lo, t2hi = _thresholds(tq, 0.0)
+    d2f = _d2f(tq, vf)
+    assert t2hi[0] == 0.0 and (t2lo == -1.0).all()
+    assert not (d2f[0] <= t2lo[0]) and not (d2f[0] > t2hi[0]) and d2f[0] >= t2hi[0]
+    assert d2f[1] > t2hi[1] and d2f[2] == 0.0 and not (d2f[2] > t2hi[2])

@@ -29,6 +29,11 @@ as-is produce the outputs stored here:
       counts exactly at min_samples, single-pair bridges and on-eps border links
       (modules/particle_filter.py:208-217) - written by tools/gen_dbscan_edges.py from the
       recipes in tests/_recipes.py, with this file's import_reference and new_pf.
+  G18 particle_filter.remove_invalid_particles on the lattice world of the prune's edges: a
+      vertex exactly on the threshold sphere and one unit either side, the list-depth, tie and
+      tree families, thresholds 131 u, 0, +inf, -1e-3 and NaN (modules/particle_filter.py:379-403) -
+      written by tools/gen_prune_edges.py from the recipes in tests/_recipes.py, with this
+      file's import_reference and new_pf.
 
 A fixture is data only: inputs + the reference's outputs (+ the RNG draws it consumed).
 Usage:  python tools/gen_goldens.py            (rewrites tests/golden/*.npz)
