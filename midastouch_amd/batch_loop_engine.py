@@ -5,7 +5,9 @@ BatchFilterEngine / PipelinedBatchFilterEngine batch the fixed-N part of the fra
 onto them never clusters or anneals.  Here every trajectory is a LoopEngine's particle set - its own live count in its own control
 block, its own labels, cluster rows and log ring - and the kernels of the small-set frame run with the trajectory as grid.y.
 Trajectory b draws from the Philox streams keyed (seed + b, frame): frame for frame it holds the bits of a LoopEngine built with
-seed + b and stepped with row b of the operands.
+seed + b and stepped with row b of the operands.  The host side is LoopEngine's too: `loop_engine._LoopBase` with the lead (B,) -
+its state table, control-block writers, phase mask, seeded frame and frame completion; what stands here is the batch's own (the
+regimes, the scratch, the three entry points, list inputs and per-trajectory results).
 
 The regime is the small set: at most 16 384 particles per trajectory (`_lib.LOOP_BATCH_MAX_CAP`; `wide=True`, below: 131 072), a
 float32 codebook scored sparsely.  Sharding stays with the sharded engine.  A DBSCAN frame clusters all B trajectories in ONE pass
@@ -35,12 +37,12 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
-from ._lib import LoopArgs, MidasError, _ptr
-from .engine import RESAMPLE_MODES, advance_epoch, codebook_index, frame_operands, sparse_scoring
-from .loop_engine import ALL_PHASES, log_records
+from ._lib import MidasError, _ptr
+from .engine import frame_operands, sparse_scoring
+from .loop_engine import ALL_PHASES, TOPK_TIES, _LoopBase, log_records
 
 
-class BatchLoopEngine:
+class BatchLoopEngine(_LoopBase):
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, batch: int, num_particles: int, *, sig_t=2e-4, sig_r=0.5,
                  pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2,
                  cluster: bool = True, cluster_every: int = 50, log_frames: int = 4096, device=None, wide: bool = False,
@@ -61,51 +63,13 @@ class BatchLoopEngine:
                 raise MidasError(f"a wide BatchLoopEngine holds at most 2^24 particles in all, not {B} x {cap}")
         elif cap < 1 or cap > _lib.LOOP_BATCH_MAX_CAP:
             raise MidasError(f"BatchLoopEngine holds 1 .. {_lib.LOOP_BATCH_MAX_CAP} particles per trajectory (larger sets: LoopEngine)")
-        self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3 = codebook_index(
-            cb_poses, cb_embeddings, mesh_vertices, device)
-        self.device = d = self.ctx.device
-        self.K, self.D = self.codebook.K, self.codebook.D
+        self._setup(cb_poses, cb_embeddings, mesh_vertices, device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps,
+                    cluster, cluster_every, log_frames)
         if not sparse_scoring(self.codebook, switch=False):
             raise MidasError("BatchLoopEngine scores sparsely: a float32 codebook with D in {128, 256, 512, 1024}")
-        self.sig_t, self.sig_r, self.pen_max = float(sig_t), float(sig_r), float(pen_max)
-        self.seed, self.softmax, self.floor, self.eps = int(seed), bool(softmax), int(floor), float(eps)
-        self.cluster, self.cluster_every = bool(cluster), max(int(cluster_every), 1)
-        self.mode = RESAMPLE_MODES[resample]
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=d)  # noqa: E731
-        self.ctl_i, self.ctl_d = z((B, 32), torch.int32), z((B, 16), torch.float64)
-        self._poses, self.poses_prop = z((B, cap, 4, 4), torch.float32), z((B, cap, 4, 4), torch.float32)
-        self._hint = torch.full((B, cap), -1, dtype=torch.int32, device=d)
-        self._nn_idx, self._valid = z((B, cap), torch.int32), z((B, cap), torch.uint8)
-        self._x, self._e, self._w, self._w_res = (z((B, cap), torch.float64) for _ in range(4))
-        self._labels, self._labels_next = z((B, cap), torch.int32), z((B, cap), torch.int32)
-        self._labels_prev = self._labels
-        self._src, self._ridx = z((B, cap), torch.int32), z((B, cap), torch.int32)
-        self._scores = z((B, self.K), torch.float64)
-        self._part_rmse = z((B, 2 * ((cap + 63) // 64)), torch.float64)
-        self._cl_poses = z((B, _lib.LOOP_MAX_CLUSTERS, 4, 4), torch.float32)
-        self._cl_stds = z((B, _lib.LOOP_MAX_CLUSTERS, 3), torch.float32)
-        self.log_frames = int(log_frames)
-        self._log = z((B, self.log_frames, _lib.LOOP_LOG_DOUBLES), torch.float64)
-        self.telemetry = z(16, torch.int64)  # (cumulative over the batch)
-        self._stamps, self._epoch = z((B, self.K), torch.int32), 0  # sparse scoring per trajectory (include/midas_hip.h score_stamps_dev)
-        self.step_count = 0   # frames enqueued (Philox counter, log row)
-        self._n_host = None   # the B live counts as last read (None: ask the device)
-        # what never changes between frames
-        a = self._args = LoopArgs()
-        a.cap = cap
-        a.ctl_i, a.ctl_d = _ptr(self.ctl_i), _ptr(self.ctl_d)
-        a.poses, a.poses_prop = _ptr(self._poses), _ptr(self.poses_prop)
-        a.hint, a.nn_idx, a.valid = _ptr(self._hint), _ptr(self._nn_idx), _ptr(self._valid)
-        a.x, a.e, a.weights, a.weights_out = _ptr(self._x), _ptr(self._e), _ptr(self._w), _ptr(self._w_res)
-        a.src, a.ridx, a.scores = _ptr(self._src), _ptr(self._ridx), _ptr(self._scores)
-        a.cb_poses = _ptr(self.cb_poses)
-        a.cluster_poses, a.cluster_stds = _ptr(self._cl_poses), _ptr(self._cl_stds)
-        a.seed, a.prune_thr, a.softmax, a.resample_mode = self.seed, self.pen_max, int(self.softmax), self.mode
-        a.floor, a.eps = self.floor, self.eps
-        a.telemetry, a.score_stamps = _ptr(self.telemetry), _ptr(self._stamps)
-        a.topk_ties = _lib.TOPK_TIES_INDEX
-        a.dbscan_batched = int(self.batched_dbscan)
         self._topk_ties = "index"
+        self._alloc_state((B,), self._topk_ties)
+        self._args.dbscan_batched = int(self.batched_dbscan)
         self.torch_streams = None  # seed_torch_streams
         # The scratch every phase combination of a batch frame asks for, reserved now so that no frame allocates: per trajectory the
         # hand-over records of the front (32 B a particle), the block results, the cluster-moment partials (64 x 36 doubles per 256
@@ -126,7 +90,7 @@ class BatchLoopEngine:
     def topk_ties(self, rule):
         if rule == "aten_cpu" and self.wide:
             raise MidasError("a wide BatchLoopEngine breaks ties by index: the ATen tie rule beyond 16 384 particles stays with LoopEngine")
-        self._args.topk_ties = {"index": _lib.TOPK_TIES_INDEX, "aten_cpu": _lib.TOPK_TIES_ATEN_CPU}[rule]
+        self._args.topk_ties = TOPK_TIES[rule]
         if rule == "aten_cpu":  # the walk's queue, stopper lists, marks and block counts per trajectory, beside the frame's own
             cap = self.cap
             self._scratch = max(self._scratch, (128 << 20) + 256 * cap + self.B * (self._per_traj() + 25 * cap + 4 * ((cap + 4095) // 4096)) + 80 * 256)
@@ -172,41 +136,24 @@ class BatchLoopEngine:
             for b, (lb, n) in enumerate(zip(labels, ns)):
                 if lb.numel() != n:
                     raise MidasError(f"trajectory {b}: {lb.numel()} labels for {n} particles")
-        ci = torch.zeros((self.B, 32), dtype=torch.int32)
-        if not reset_annealing:
-            old = self.ctl_i.cpu()
-            for k in (_lib.LOOP_I_INIT, _lib.LOOP_I_VARSET, _lib.LOOP_I_FRAME):
-                ci[:, k] = old[:, k]
         self._hint.fill_(-1)
         self._labels.zero_()
+        ncl = [1] * self.B  # label 0 everywhere
         for b, (p, n) in enumerate(zip(poses, ns)):
             self._poses[b, :n].copy_(p)
-            ncl = 1  # label 0 everywhere
             if labels is not None:
                 self._labels[b, :n].copy_(labels[b])
-                ncl = int(labels[b].max().item()) + 1
-            ci[b, _lib.LOOP_I_N] = n
-            ci[b, _lib.LOOP_I_NSET] = n
-            ci[b, _lib.LOOP_I_NCL] = ncl
-        if reset_annealing:
-            self.ctl_d.zero_()
-        self.ctl_i.copy_(ci)
+                ncl[b] = int(labels[b].max().item()) + 1
+        self._write_particles_block(ns, ncl, reset_annealing)
         self._n_host = ns
 
     def set_annealing_state(self, particle_vars, init_particles):
         """particle_filter.particle_var / init_particles (particle_filter.py:413-417) of every trajectory, B of each - for restarts
         and replays, as LoopEngine.set_annealing_state per row."""
-        import numpy as np
         pv, ip = [float(v) for v in particle_vars], [int(v) for v in init_particles]
         if len(pv) != self.B or len(ip) != self.B:
             raise MidasError(f"{len(pv)} variances and {len(ip)} counts for a batch of {self.B} trajectories")
-        ci, cd = self.ctl_i.cpu(), self.ctl_d.cpu()
-        for b in range(self.B):
-            ci[b, _lib.LOOP_I_VARSET] = 0 if np.isinf(pv[b]) else 1
-            ci[b, _lib.LOOP_I_INIT] = ip[b]
-            cd[b, _lib.LOOP_D_VARPREV] = float(np.float32(pv[b])) if not np.isinf(pv[b]) else 0.0
-        self.ctl_i.copy_(ci)
-        self.ctl_d.copy_(cd)
+        self._write_annealing_state(pv, ip)
 
     # ---- seeded runs ----------------------------------------------------------------------------------------------
     def seed_torch_streams(self, seeds):
@@ -229,19 +176,10 @@ class BatchLoopEngine:
         seeds = list(seeds)
         if len(seeds) != self.B:
             raise MidasError(f"{len(seeds)} seeds for a batch of {self.B} trajectories")
-        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
-            raise MidasError("a seeded torch stream reproduces torch.multinomial's draws: resample='weighted_random' only")
         from .torch_rng import TorchCpuStreams
-        st = TorchCpuStreams(seeds, self.device, overlap=False, pieces=0)
-        st._normal_tables()  # (uploaded now, not by the first frame)
-        B, cap, d = self.B, self.cap, self.device
-        self._tn, self._rot = (torch.zeros((B, cap, 3), dtype=torch.float32, device=d) for _ in range(2))
-        self._u = torch.zeros((B, cap), dtype=torch.float64, device=d)
-        self._mt_status = torch.zeros((B, self.log_frames), dtype=torch.int32, device=d)  # the counted calls' status, a word per log row
+        st, need = self._seed_streams(TorchCpuStreams, seeds)
         self.topk_ties = "aten_cpu"
-        ci = (self.ctl_i, _lib.LOOP_I_N)
-        self._scratch = max(self._scratch, st.counted_scratch_bytes([("normal", 0.0, 1.0, *ci, 3, cap)] * 2),
-                            st.counted_scratch_bytes([("rand64", *ci, cap)]))
+        self._scratch = max(self._scratch, need)
         self.ctx.call("midas_scratch_reserve", self._scratch)  # (the generator shares the engine's context)
         self.torch_streams = st
         return st
@@ -267,35 +205,17 @@ class BatchLoopEngine:
             raise MidasError("frame_view needs a completed frame")
         if not 0 <= b < self.B:
             raise MidasError(f"trajectory {b} of a batch of {self.B}")
-        rec = self.read_log(self.step_count - 1, self.step_count, rows=(b,))[0][0]
-        nb, ns = rec["n"], rec["n_after"]
-        rec.update(poses_prop=self.poses_prop[b, :nb], nn_idx=self._nn_idx[b, :nb], valid=self._valid[b, :nb], weights=self._w[b, :nb],
-                   labels_frame=self._labels_prev[b, :nb], src=self._src[b, :ns], ridx=self._ridx[b, :ns], poses=self._poses[b, :ns],
-                   weights_res=self._w_res[b, :ns], labels=self._labels[b, :ns], hint=self._hint[b, :ns],
-                   ctl_i=self.ctl_i[b].cpu().numpy(), ctl_d=self.ctl_d[b].cpu().numpy())
-        return rec
+        return self._frame_view(self.read_log(self.step_count - 1, self.step_count, rows=(b,))[0][0], b)
 
     # ---- one batch frame ------------------------------------------------------------------------------------------
     def step(self, odoms, codes, gts=None, u32=-1.0, multiplier: float = 1.0, dbscan=None, unit_weights: bool = False):
         """Enqueues one frame of every trajectory and reads nothing back: odoms (B,4,4), codes (B,D), gts (B,4,4) or None.
         dbscan: None = on every `cluster_every`-th frame (filter.py:182), True / False to force - for all trajectories alike."""
-        phases = ALL_PHASES
-        if not self.cluster:
-            phases &= ~(_lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL)
-        elif dbscan is False or (dbscan is None and self.step_count % self.cluster_every != 0):
-            phases &= ~_lib.LOOP_DBSCAN
+        phases = self._phase_mask(ALL_PHASES, dbscan)
         odoms, codes, gts = frame_operands(self.device, (self.B,), self.D, odoms, codes, gts)
-        a = self._args
-        a.labels, a.labels_out = _ptr(self._labels), _ptr(self._labels_next)
-        a.log = C.c_void_p(self._log.data_ptr() + (self.step_count % self.log_frames) * _lib.LOOP_LOG_DOUBLES * 8)
+        a = self._frame_scalars(u32, multiplier, unit_weights)
         a.odom16, a.code, a.gt16 = _ptr(odoms), _ptr(codes), _ptr(gts)
         a.part_rmse = _ptr(self._part_rmse) if gts is not None else None
-        a.u32 = float(u32)
-        mul = max(float(multiplier), 1.0)
-        a.std_t, a.std_r = mul * self.sig_t, mul * self.sig_r
-        a.step = self.step_count
-        a.unit_weights = int(bool(unit_weights))
-        a.score_epoch = advance_epoch(self)
         self._keep = (odoms, codes, gts)  # keep operands alive until the stream has consumed them
         st, log_stride = self.torch_streams, self.log_frames * _lib.LOOP_LOG_DOUBLES
 
@@ -304,22 +224,14 @@ class BatchLoopEngine:
             self.ctx.check(entry(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(ph), self.B, log_stride))
 
         if st is not None:
-            # the stream's draws: the motion noise sized by every row's live count, the frame up to annealing, the uniforms sized by
-            # every row's annealed count, the resample - four enqueues, the counts never leave the device
-            slot = self.step_count % self.log_frames
-            if slot == 0:
-                self._mt_status.zero_()  # (the ring starts over, as the log's rows do)
-            status = (self._mt_status, slot, self.log_frames)
-            st.draws_counted_async([("normal", 0.0, a.std_t, self.ctl_i, _lib.LOOP_I_N, 3, self.cap),
-                                    ("normal", 0.0, a.std_r, self.ctl_i, _lib.LOOP_I_N, 3, self.cap)], outs=[self._tn, self._rot], status=status)
+            # the stream's draws, every row's sized by ITS live and annealed counts: a row whose weights are all zero or hold a NaN
+            # draws no uniforms on this frame - its stream stays where it is, the other rows' move on
             a.tn, a.rot, a.u = _ptr(self._tn), _ptr(self._rot), _ptr(self._u)
             a.stream_draws = 1
             try:
-                call(self.ctx.lib.midas_loop_step_batch_draws, phases & ~_lib.LOOP_RESAMPLE)
-                # every row's NDRAW, not NSET: a row whose weights are all zero or hold a NaN draws nothing on this frame, as the
-                # reference's resampler (particle_filter.py:237-241) - its stream stays where it is, the other rows' move on
-                st.draws_counted_async([("rand64", self.ctl_i, _lib.LOOP_I_NDRAW, self.cap)], outs=[self._u], status=status)
-                call(self.ctx.lib.midas_loop_step_batch_draws, _lib.LOOP_RESAMPLE)
+                self._seeded_frame(st, (a.std_t, a.std_r), self.cap, self.cap,
+                                   lambda: call(self.ctx.lib.midas_loop_step_batch_draws, phases & ~_lib.LOOP_RESAMPLE),
+                                   lambda: call(self.ctx.lib.midas_loop_step_batch_draws, _lib.LOOP_RESAMPLE), status=(self.log_frames,))
             finally:
                 a.tn = a.rot = a.u = None
                 a.stream_draws = 0
@@ -329,18 +241,14 @@ class BatchLoopEngine:
             call(self.ctx.lib.midas_loop_step_batch_wide, phases)
         else:
             call(self.ctx.lib.midas_loop_step_batch, phases)
-        self._labels_prev = self._labels
-        self._labels, self._labels_next = self._labels_next, self._labels
-        self.step_count += 1
-        self._n_host = None
+        self._frame_done()
 
     # ---- results --------------------------------------------------------------------------------------------------
     def read_log(self, first: int = 0, last: int = None, strict: bool = True, rows=None):
         """Per trajectory, LoopEngine.read_log's records of frames [first, last) - a list of B lists, one read-back - with its
         handling of the frames' condition bits, a seeded stream's short or out-of-range draw included (reported for the trajectory
         it happened to).  rows: only these trajectories (a list in their order)."""
-        last = self.step_count if last is None else min(last, self.step_count)
-        first = max(first, last - self.log_frames)
+        first, last = self._log_window(first, last)
         which = range(self.B) if rows is None else rows
         log = (self._log if rows is None else self._log[list(rows)]).cpu().numpy()
         mt = None

@@ -12,7 +12,8 @@ Two random-draw modes:
   * device mode  - the kernels draw from the Philox spec streams keyed by (seed, step).
 
 The frame setup every engine form shares (single, batch, loop, shard: midastouch_amd/loop_engine.py, dist.py) lives here too:
-`codebook_index`, `RESAMPLE_MODES`, `sparse_scoring`, `advance_epoch` and the operand checks.
+`codebook_index`, `RESAMPLE_MODES`, `sparse_scoring`, `advance_epoch` and the operand checks.  The fixed-N engines share `_Engine`
+below; the two loop engines share `loop_engine._LoopBase` (state table, cached `LoopArgs`, control-block writers, seeded frame).
 """
 from __future__ import annotations
 

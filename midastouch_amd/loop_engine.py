@@ -17,12 +17,17 @@ particles on one codebook entry share a weight) annealing's `torch.topk` keeps w
 and the device then walks that kernel's algorithm (topk_aten.hip) instead of its own radix select (ties by index).
 `seed_torch_stream(seed)` takes those same draws from torch's CPU stream on the device, sized by the counts in the control
 block: the replay without the read-backs and without splitting the frame by hand.
+
+BatchLoopEngine (batch_loop_engine.py) is this engine for B trajectories; what the two share - the set-up, the state table and
+the constant part of `LoopArgs` made from it, the phase mask, the control-block writers, `frame_view`, the seeded streams' set-up
+and frame, the frame's scalars and its completion - is `_LoopBase`, by a lead shape: () here, (B,) there.
 """
 from __future__ import annotations
 
 import ctypes as C
-
 import os
+import time
+import warnings
 
 import numpy as np
 import torch
@@ -32,52 +37,201 @@ from ._lib import LoopArgs, MidasError, _ptr
 from .engine import RESAMPLE_MODES, advance_epoch, check_motion_draws, codebook_index, frame_operands, operand, sparse_scoring
 
 ALL_PHASES = _lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL | _lib.LOOP_RESAMPLE
+TOPK_TIES = {"index": _lib.TOPK_TIES_INDEX, "aten_cpu": _lib.TOPK_TIES_ATEN_CPU}
 
 
-class LoopEngine:
-    def __init__(self, cb_poses, cb_embeddings, mesh_vertices, num_particles: int, *, sig_t=2e-4, sig_r=0.5, pen_max=0.002,
-                 seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2, cluster: bool = True,
-                 cluster_every: int = 50, log_frames: int = 4096, device=None,
-                 topk_ties: str = "index"):
+def state_table(cap: int, K: int, log_frames: int, ctl_d: int = 16):
+    """The state of one trajectory: (attribute, LoopArgs field or None, shape behind the lead, dtype, fill).  A field named here
+    never changes between frames (`labels` / `labels_out` swap when a frame completes; LoopEngine hands `score_stamps` over only
+    on the calls that score sparsely)."""
+    f32, f64, i32, n, ncl = torch.float32, torch.float64, torch.int32, (cap,), _lib.LOOP_MAX_CLUSTERS
+    return (("ctl_i", "ctl_i", (32,), i32, 0), ("ctl_d", "ctl_d", (ctl_d,), f64, 0),
+            ("_poses", "poses", (cap, 4, 4), f32, 0), ("poses_prop", "poses_prop", (cap, 4, 4), f32, 0),
+            ("_hint", "hint", n, i32, -1), ("_nn_idx", "nn_idx", n, i32, 0), ("_valid", "valid", n, torch.uint8, 0),
+            ("_x", "x", n, f64, 0), ("_e", "e", n, f64, 0), ("_w", "weights", n, f64, 0), ("_w_res", "weights_out", n, f64, 0),
+            ("_labels", "labels", n, i32, 0), ("_labels_next", "labels_out", n, i32, 0), ("_src", "src", n, i32, 0), ("_ridx", "ridx", n, i32, 0),
+            ("_scores", "scores", (K,), f64, 0), ("_part_rmse", None, (2 * ((cap + 63) // 64),), f64, 0),  # (handed over with a ground truth)
+            ("_cl_poses", "cluster_poses", (ncl, 4, 4), f32, 0), ("_cl_stds", "cluster_stds", (ncl, 3), f32, 0),
+            ("_log", None, (log_frames, _lib.LOOP_LOG_DOUBLES), f64, 0),  # (a frame gets its row)
+            ("telemetry", "telemetry", (16,), torch.int64, 0),  # (no lead: cumulative over a batch)
+            ("_stamps", "score_stamps", (K,), i32, 0))  # sparse scoring (include/midas_hip.h score_stamps_dev)
+
+
+def particles_block(n, ncl, old, reset_annealing: bool):
+    """The control block(s) `set_particles` writes, on the host: n, ncl = live count and cluster count (label maximum + 1) of one
+    trajectory or of B -> (32,) or (B, 32) int32 with N = NSET = n, NCL = ncl and, unless annealing starts over, INIT, VARSET and
+    FRAME of `old` (the block as it stands, on the host); every other word 0."""
+    n = torch.as_tensor(n, dtype=torch.int32)
+    ci = torch.zeros(n.shape + (32,), dtype=torch.int32)
+    if not reset_annealing:
+        for k in (_lib.LOOP_I_INIT, _lib.LOOP_I_VARSET, _lib.LOOP_I_FRAME):
+            ci[..., k] = old[..., k]
+    ci[..., _lib.LOOP_I_N] = ci[..., _lib.LOOP_I_NSET] = n
+    ci[..., _lib.LOOP_I_NCL] = torch.as_tensor(ncl, dtype=torch.int32)
+    return ci
+
+
+def annealing_block(ci, cd, particle_var, init_particles):
+    """`set_annealing_state` on the host copies of ctl_i / ctl_d (one row or B, changed in place and returned):
+    particle_filter.particle_var as annealing keeps it - float32, "unset" while infinite - and init_particles."""
+    pv = np.asarray(particle_var, dtype=np.float64)
+    unset = np.isinf(pv)
+    ci[..., _lib.LOOP_I_VARSET] = torch.as_tensor(np.where(unset, 0, 1), dtype=torch.int32)
+    ci[..., _lib.LOOP_I_INIT] = torch.as_tensor(init_particles, dtype=torch.int32)
+    cd[..., _lib.LOOP_D_VARPREV] = torch.as_tensor(np.where(unset, 0.0, pv.astype(np.float32)), dtype=torch.float64)
+    return ci, cd
+
+
+class _LoopBase:
+    """What LoopEngine and BatchLoopEngine share: the codebook index, the filter's parameters, the state of one trajectory or of B
+    (`_lead` = () or (B,)) with the `LoopArgs` that point at it, and the host's part of a frame."""
+
+    def _setup(self, cb_poses, cb_embeddings, mesh_vertices, device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps,
+               cluster, cluster_every, log_frames):
         self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3 = codebook_index(
             cb_poses, cb_embeddings, mesh_vertices, device)
-        self.device = d = self.ctx.device
+        self.device = self.ctx.device
         self.K, self.D = self.codebook.K, self.codebook.D
         self.sig_t, self.sig_r, self.pen_max = float(sig_t), float(sig_r), float(pen_max)
         self.seed, self.softmax, self.floor, self.eps = int(seed), bool(softmax), int(floor), float(eps)
         self.cluster, self.cluster_every = bool(cluster), max(int(cluster_every), 1)
-        # whom annealing's torch.topk takes inside a tie: "index" (torch's CUDA rule, the radix select) or "aten_cpu" (the
-        # reference as it runs on the CPU - the rule of a seeded replay; topk_aten.hip)
-        self.topk_ties = {"index": _lib.TOPK_TIES_INDEX, "aten_cpu": _lib.TOPK_TIES_ATEN_CPU}[topk_ties]
         self.mode = RESAMPLE_MODES[resample]
+        self.log_frames = int(log_frames)
+        self.step_count = 0   # frames enqueued (Philox counter, log row)
+        self._n_host = None   # live count(s) as last known by the host (None: ask the device)
+        self._epoch = 0
+
+    def _alloc_state(self, lead, topk_ties: str, ctl_d: int = 16):
+        """The state table's tensors behind `lead`, and `_args`: what never changes between frames."""
+        self._lead, self._state = lead, state_table(self.cap, self.K, self.log_frames, ctl_d)
+        a = self._args = LoopArgs()
+        for attr, field, shape, dt, fill in self._state:
+            t = torch.full((() if attr == "telemetry" else lead) + shape, fill, dtype=dt, device=self.device)
+            setattr(self, attr, t)
+            if field is not None:
+                setattr(a, field, _ptr(t))
+        self._labels_prev = self._labels
+        a.cap, a.cb_poses, a.topk_ties = self.cap, _ptr(self.cb_poses), TOPK_TIES[topk_ties]
+        self._write_params()
+
+    def _write_params(self):
+        a = self._args
+        a.seed, a.prune_thr, a.softmax, a.resample_mode = self.seed, self.pen_max, int(self.softmax), self.mode
+        a.floor, a.eps = self.floor, self.eps
+
+    # ---- state ----------------------------------------------------------------------------------------------------
+    def _write_particles_block(self, n, ncl, reset_annealing: bool):
+        """set_particles' control block(s) to the device; returned as written."""
+        ci = particles_block(n, ncl, None if reset_annealing else self.ctl_i.cpu(), reset_annealing)
+        if reset_annealing:
+            self.ctl_d.zero_()
+        self.ctl_i.copy_(ci)
+        return ci
+
+    def _write_annealing_state(self, particle_var, init_particles):
+        ci, cd = annealing_block(self.ctl_i.cpu(), self.ctl_d.cpu(), particle_var, init_particles)
+        self.ctl_i.copy_(ci)
+        self.ctl_d.copy_(cd)
+
+    def _frame_view(self, rec, b):
+        """rec: the log record of the latest completed frame of trajectory b (() for the only one) -> with the views of its arrays."""
+        nb, ns = rec["n"], rec["n_after"]
+        rec.update(poses_prop=self.poses_prop[b][:nb], nn_idx=self._nn_idx[b][:nb], valid=self._valid[b][:nb], weights=self._w[b][:nb],
+                   labels_frame=self._labels_prev[b][:nb], src=self._src[b][:ns], ridx=self._ridx[b][:ns], poses=self._poses[b][:ns],
+                   weights_res=self._w_res[b][:ns], labels=self._labels[b][:ns], hint=self._hint[b][:ns],
+                   ctl_i=self.ctl_i[b].cpu().numpy(), ctl_d=self.ctl_d[b].cpu().numpy())
+        return rec
+
+    def _log_window(self, first: int, last):
+        """[first, last) clamped to the frames enqueued and to what the log ring still holds."""
+        last = self.step_count if last is None else min(last, self.step_count)
+        return max(first, last - self.log_frames), last
+
+    # ---- seeded runs ----------------------------------------------------------------------------------------------
+    def _seed_streams(self, cls, seeds):
+        """The device replica(s) of torch's CPU generator (torch_rng `cls`) with their tables uploaded now, not by the first frame,
+        and the buffers a seeded frame draws into -> (streams, scratch bytes of the generator's two counted calls at capacity)."""
+        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
+            raise MidasError("a seeded torch stream reproduces torch.multinomial's draws: resample='weighted_random' only")
+        st = cls(seeds, self.device, overlap=False, pieces=0)
+        st._normal_tables()
+        lead, cap, d = self._lead, self.cap, self.device
+        self._tn, self._rot = (torch.zeros(lead + (cap, 3), dtype=torch.float32, device=d) for _ in range(2))
+        self._u = torch.zeros(lead + (cap,), dtype=torch.float64, device=d)
+        self._mt_status = torch.zeros(lead + (self.log_frames,), dtype=torch.int32, device=d)  # the counted calls' status, a word per log row
+        ci = (self.ctl_i, _lib.LOOP_I_N)
+        return st, max(st.counted_scratch_bytes([("normal", 0.0, 1.0, *ci, 3, cap)] * 2), st.counted_scratch_bytes([("rand64", *ci, cap)]))
+
+    def _seeded_frame(self, st, stds, bound: int, u_bound: int, front, resample, status=()):
+        """One frame with the stream's draws: the motion noise sized by the live count (stds = None: none), the frame up to
+        annealing (`front()`), the uniforms sized by the annealed count, the resample (`resample()`) - four enqueues, the counts
+        never leave the device."""
+        slot, ci = self.step_count % self.log_frames, self.ctl_i
+        if slot == 0:
+            self._mt_status.zero_()  # (the ring starts over, as the log's rows do)
+        status = (self._mt_status, slot) + status
+        if stds is not None:
+            st.draws_counted_async([("normal", 0.0, stds[0], ci, _lib.LOOP_I_N, 3, bound), ("normal", 0.0, stds[1], ci, _lib.LOOP_I_N, 3, bound)],
+                                   outs=[self._tn, self._rot], status=status)
+        front()
+        # NDRAW, not NSET: the resampler returns its input before it draws when the weights are all zero or hold a NaN
+        # (particle_filter.py:237-241) - the stream must not move on such a frame (a zero count consumes nothing)
+        st.draws_counted_async([("rand64", ci, _lib.LOOP_I_NDRAW, u_bound)], outs=[self._u], status=status)
+        resample()
+
+    # ---- one frame ------------------------------------------------------------------------------------------------
+    def _phase_mask(self, phases: int, dbscan) -> int:
+        """`phases` without what this frame does not run: no clustering at all, or DBSCAN on every `cluster_every`-th frame only."""
+        if not self.cluster:
+            return phases & ~(_lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL)
+        if dbscan is False or (dbscan is None and self.step_count % self.cluster_every != 0):
+            return phases & ~_lib.LOOP_DBSCAN
+        return phases
+
+    def _frame_scalars(self, u32, multiplier, unit_weights, std_override=None, score: bool = True):
+        """What every call of a frame is told: its log row, the scalars, and - when it scores sparsely - its epoch."""
+        a = self._args
+        a.log = C.c_void_p(self._log.data_ptr() + (self.step_count % self.log_frames) * _lib.LOOP_LOG_DOUBLES * 8)
+        a.u32 = float(u32)
+        mul = max(float(multiplier), 1.0)
+        a.std_t, a.std_r = (mul * self.sig_t, mul * self.sig_r) if std_override is None else std_override
+        a.step = self.step_count
+        a.unit_weights = int(bool(unit_weights))
+        a.score_stamps, a.score_epoch = (_ptr(self._stamps), advance_epoch(self)) if score else (None, 0)
+        return a
+
+    def _frame_done(self, n_host=None):
+        self._labels_prev = self._labels
+        self._labels, self._labels_next = self._labels_next, self._labels
+        a = self._args
+        a.labels, a.labels_out = a.labels_out, a.labels
+        self.step_count += 1
+        self._n_host = n_host
+
+
+class LoopEngine(_LoopBase):
+    def __init__(self, cb_poses, cb_embeddings, mesh_vertices, num_particles: int, *, sig_t=2e-4, sig_r=0.5, pen_max=0.002,
+                 seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2, cluster: bool = True,
+                 cluster_every: int = 50, log_frames: int = 4096, device=None,
+                 topk_ties: str = "index"):
+        self._setup(cb_poses, cb_embeddings, mesh_vertices, device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps,
+                    cluster, cluster_every, log_frames)
         self.cap = cap = int(num_particles)
         if cap < 1 or cap > (1 << 20):
             raise MidasError("LoopEngine holds 1 .. 2^20 particles")
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=d)  # noqa: E731
-        self.ctl_i, self.ctl_d = z(32, torch.int32), z(104 if os.environ.get("MIDAS_ANNEAL_CLOCKS") else 16, torch.float64)  # (104: profiling builds)
-        self._poses, self.poses_prop = z((cap, 4, 4), torch.float32), z((cap, 4, 4), torch.float32)
-        self._hint = torch.full((cap,), -1, dtype=torch.int32, device=d)
-        self._nn_idx, self._valid = z(cap, torch.int32), z(cap, torch.uint8)
-        self._x, self._e, self._w, self._w_res = (z(cap, torch.float64) for _ in range(4))
-        self._labels, self._labels_next = z(cap, torch.int32), z(cap, torch.int32)
-        self._src, self._ridx = z(cap, torch.int32), z(cap, torch.int32)
-        self._scores = z(self.K, torch.float64)
-        self._part_rmse = z(2 * ((cap + 63) // 64), torch.float64)
-        self._cl_poses, self._cl_stds = z((_lib.LOOP_MAX_CLUSTERS, 4, 4), torch.float32), z((_lib.LOOP_MAX_CLUSTERS, 3), torch.float32)
-        self.log_frames = int(log_frames)
-        self._log = z((self.log_frames, _lib.LOOP_LOG_DOUBLES), torch.float64)
-        self.telemetry = z(16, torch.int64)
+        # whom annealing's torch.topk takes inside a tie: "index" (torch's CUDA rule, the radix select) or "aten_cpu" (the
+        # reference as it runs on the CPU - the rule of a seeded replay; topk_aten.hip)
+        self.topk_ties = TOPK_TIES[topk_ties]
+        self._alloc_state((), topk_ties, ctl_d=104 if os.environ.get("MIDAS_ANNEAL_CLOCKS") else 16)  # (104: profiling builds)
         self.sparse_scores = sparse_scoring(self.codebook)
-        self._stamps, self._epoch = z(self.K, torch.int32), 0  # sparse scoring (include/midas_hip.h score_stamps_dev)
         # {frames completed, live count} as the device last reported them, in pinned host memory: lets step() size its launches
         # to the live set without waiting for anything (an upper bound is all it needs, see _count_bound)
         self._mirror = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self._args.host_mirror = C.c_void_p(self._mirror.data_ptr())
         self._frames_at_reset, self._n_at_reset, self._steps_at_reset, self._grid_n = 0, cap, 0, cap
         self.max_ahead = 1         # frames the host may enqueue ahead of the device's last report (None: no limit)
         self.allow_frozen = True   # see _frozen()
         self._init_known = None    # init_particles as the host knows it (None: annealing's first call will take the live count)
-        self.step_count = 0        # frames enqueued (Philox counter, log row)
-        self._n_host = None        # particle count as last known by the host (None: ask the device)
         self._pending_phases = 0
         self.use_hint = True
         self.torch_stream = None   # seed_torch_stream
@@ -102,19 +256,8 @@ class LoopEngine:
             labels = torch.as_tensor(labels).to(self.device).to(torch.int32)
             self._labels[:n].copy_(labels)
             ncl = int(labels.max().item()) + 1
-        ci = torch.zeros(32, dtype=torch.int32)
-        if not reset_annealing:
-            old = self.ctl_i.cpu()
-            for k in (_lib.LOOP_I_INIT, _lib.LOOP_I_VARSET, _lib.LOOP_I_FRAME):
-                ci[k] = old[k]
-            self._init_known = int(old[_lib.LOOP_I_INIT]) if int(old[_lib.LOOP_I_VARSET]) else None
-        else:
-            self.ctl_d.zero_()
-            self._init_known = None
-        ci[_lib.LOOP_I_N] = n
-        ci[_lib.LOOP_I_NSET] = n
-        ci[_lib.LOOP_I_NCL] = ncl
-        self.ctl_i.copy_(ci)
+        ci = self._write_particles_block(n, ncl, reset_annealing)
+        self._init_known = int(ci[_lib.LOOP_I_INIT]) if int(ci[_lib.LOOP_I_VARSET]) else None  # (both 0 once annealing starts over)
         self._n_host = n
         self._pending_phases = 0
         torch.cuda.current_stream(self.device).synchronize()  # the control block is in place, nothing older is in flight
@@ -132,7 +275,6 @@ class LoopEngine:
         # next is being enqueued keeps the device busy (enqueueing a frame takes less than running it); the wait is a look
         # at pinned memory.
         if self.max_ahead is not None and enq - (int(self._mirror[0]) - self._frames_at_reset) > self.max_ahead:
-            import time
             t0 = time.perf_counter()
             while enq - (int(self._mirror[0]) - self._frames_at_reset) > self.max_ahead and time.perf_counter() - t0 < 0.05:
                 pass
@@ -158,13 +300,7 @@ class LoopEngine:
     def set_annealing_state(self, particle_var: float, init_particles: int):
         """particle_filter.particle_var / init_particles (particle_filter.py:413-417) - for restarts and tests."""
         self._init_known = int(init_particles)
-        ci = self.ctl_i.cpu()
-        ci[_lib.LOOP_I_VARSET] = 0 if np.isinf(particle_var) else 1
-        ci[_lib.LOOP_I_INIT] = int(init_particles)
-        self.ctl_i.copy_(ci)
-        cd = self.ctl_d.cpu()
-        cd[_lib.LOOP_D_VARPREV] = float(np.float32(particle_var)) if not np.isinf(particle_var) else 0.0
-        self.ctl_d.copy_(cd)
+        self._write_annealing_state(float(particle_var), int(init_particles))
 
     def project_to_codebook(self):
         """poses := codebook pose nearest to each particle (filter/filter.py:159-160)."""
@@ -194,13 +330,8 @@ class LoopEngine:
         (n_after entries: src, ridx) and the resampled particle set (n_after entries: poses, weights_res, labels, hint)."""
         if self.step_count == 0 or self._pending_phases:
             raise MidasError("frame_view needs a completed frame")
-        rec = self.read_log(self.step_count - 1, self.step_count)[0]
-        nb, ns = rec["n"], rec["n_after"]
-        rec.update(poses_prop=self.poses_prop[:nb], nn_idx=self._nn_idx[:nb], valid=self._valid[:nb], weights=self._w[:nb],
-                   labels_frame=self._labels_prev[:nb], src=self._src[:ns], ridx=self._ridx[:ns], poses=self._poses[:ns],
-                   weights_res=self._w_res[:ns], labels=self._labels[:ns], hint=self._hint[:ns],
-                   ctl_i=self.ctl_i.cpu().numpy(), ctl_d=self.ctl_d.cpu().numpy())
-        self._n_host = ns
+        rec = self._frame_view(self.read_log(self.step_count - 1, self.step_count)[0], ())
+        self._n_host = rec["n_after"]
         return rec
 
     # ---- seeded runs ----------------------------------------------------------------------------------------------
@@ -218,47 +349,29 @@ class LoopEngine:
         if seed is None:
             self.torch_stream = None
             return None
-        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
-            raise MidasError("a seeded torch stream reproduces torch.multinomial's draws: resample='weighted_random' only")
         from .torch_rng import TorchCpuStream
-        st = TorchCpuStream(seed, self.device, overlap=False, pieces=0)
-        st._normal_tables()  # (uploaded now, not by the first frame)
-        cap, d = self.cap, self.device
-        self._tn, self._rot, self._no_noise = (torch.zeros((cap, 3), dtype=torch.float32, device=d) for _ in range(3))
-        self._u = torch.zeros(cap, dtype=torch.float64, device=d)
-        self._mt_status = torch.zeros(self.log_frames, dtype=torch.int32, device=d)  # the counted calls' status, a word per log row
-        ci = (self.ctl_i, _lib.LOOP_I_N)
-        need = max(st.counted_scratch_bytes([("normal", 0.0, 1.0, *ci, 3, cap)] * 2), st.counted_scratch_bytes([("rand64", *ci, cap)]))
-        self.ctx.call("midas_scratch_reserve", max((128 << 20) + 256 * cap, need))  # (the generator shares the engine's context)
+        st, need = self._seed_streams(TorchCpuStream, seed)
+        self._no_noise = torch.zeros_like(self._tn)
+        self.ctx.call("midas_scratch_reserve", max((128 << 20) + 256 * self.cap, need))  # (the generator shares the engine's context)
         self.torch_stream = st
         return st
 
     def _seeded_step(self, odom, code, gt, u32, multiplier, dbscan, std_override, unit_weights, motion_draws):
-        """One frame with the stream's draws: the motion noise sized by the live count, the frame up to annealing, the uniforms sized
-        by the annealed count (or none: NDRAW), the resample - four enqueues, the counts never leave the device."""
-        st, ci = self.torch_stream, self.ctl_i
+        """_seeded_frame with draws bounded by _count_bound(), and by what annealing can make of it; motion_draws=False draws no
+        motion noise."""
         if self._pending_phases:
             raise MidasError("a seeded frame is enqueued whole: finish the frame in progress first")
         b = self._count_bound()
-        slot = self.step_count % self.log_frames
-        if slot == 0:
-            self._mt_status.zero_()  # (the ring starts over, as the log's rows do)
-        status = (self._mt_status, slot)
+        tn, rot, stds = self._no_noise, self._no_noise, None
         if motion_draws:
             mul = max(float(multiplier), 1.0)
-            std_t, std_r = (mul * self.sig_t, mul * self.sig_r) if std_override is None else std_override
-            st.draws_counted_async([("normal", 0.0, std_t, ci, _lib.LOOP_I_N, 3, b), ("normal", 0.0, std_r, ci, _lib.LOOP_I_N, 3, b)],
-                                   outs=[self._tn, self._rot], status=status)
-            tn, rot = self._tn, self._rot
-        else:
-            tn = rot = self._no_noise
-        self._enqueue(odom, code, gt, tn, rot, None, u32, multiplier, dbscan, _lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL,
-                      std_override, unit_weights, bound=b, stream_draws=True)
-        # NDRAW, not NSET: the resampler returns its input before it draws when the weights are all zero or hold a NaN
-        # (particle_filter.py:237-241) - the stream must not move on such a frame (a zero count consumes nothing)
-        st.draws_counted_async([("rand64", ci, _lib.LOOP_I_NDRAW, min(self.cap, b + b // 3))], outs=[self._u], status=status)
-        self._enqueue(None, None, None, None, None, self._u, u32, multiplier, dbscan, _lib.LOOP_RESAMPLE, std_override, unit_weights,
-                      stream_draws=True)
+            tn, rot, stds = self._tn, self._rot, (mul * self.sig_t, mul * self.sig_r) if std_override is None else std_override
+        self._seeded_frame(
+            self.torch_stream, stds, b, min(self.cap, b + b // 3),
+            lambda: self._enqueue(odom, code, gt, tn, rot, None, u32, multiplier, dbscan, _lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL,
+                                  std_override, unit_weights, bound=b, stream_draws=True),
+            lambda: self._enqueue(None, None, None, None, None, self._u, u32, multiplier, dbscan, _lib.LOOP_RESAMPLE, std_override,
+                                  unit_weights, stream_draws=True))
 
     # ---- one frame ------------------------------------------------------------------------------------------------
     def step(self, odom, code, gt=None, tn=None, rot=None, u=None, u32=-1.0, multiplier: float = 1.0, dbscan=None,
@@ -287,63 +400,34 @@ class LoopEngine:
         frame_start = self._pending_phases == 0
         if phases is None:
             phases = ALL_PHASES & ~self._pending_phases if not frame_start else ALL_PHASES
-        if not self.cluster:
-            phases &= ~(_lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL)
-        elif dbscan is False or (dbscan is None and self.step_count % self.cluster_every != 0):
-            phases &= ~_lib.LOOP_DBSCAN
-        a = LoopArgs()
-        a.cap = self.cap
-        a.ctl_i, a.ctl_d = _ptr(self.ctl_i), _ptr(self.ctl_d)
-        a.poses, a.poses_prop = _ptr(self._poses), _ptr(self.poses_prop)
-        a.hint, a.nn_idx, a.valid = _ptr(self._hint), _ptr(self._nn_idx), _ptr(self._valid)
-        a.x, a.e, a.weights, a.weights_out = _ptr(self._x), _ptr(self._e), _ptr(self._w), _ptr(self._w_res)
-        a.labels, a.labels_out = _ptr(self._labels), _ptr(self._labels_next)
-        a.src, a.ridx, a.scores = _ptr(self._src), _ptr(self._ridx), _ptr(self._scores)
-        a.cb_poses = _ptr(self.cb_poses)
-        a.cluster_poses, a.cluster_stds = _ptr(self._cl_poses), _ptr(self._cl_stds)
-        a.log = C.c_void_p(self._log.data_ptr() + (self.step_count % self.log_frames) * _lib.LOOP_LOG_DOUBLES * 8)
-        keep = []
-        if phases & _lib.LOOP_FRONT:
+        phases = self._phase_mask(phases, dbscan)
+        # the cached struct: a call reads NULL / 0 in an operand or switch as "not given", so every field that is not the state
+        # table's is written on every call - what this call does not hand over as None or 0, never left from the call before
+        front = bool(phases & _lib.LOOP_FRONT)
+        if front:
             check_motion_draws(tn, rot)
             odom, code, gt = frame_operands(d, (), self.D, odom, code, gt)
             if tn is not None and bound is None:
                 n = self.n
                 tn, rot = operand(tn, "tn", torch.float32, (n, 3), d), operand(rot, "rot", torch.float32, (n, 3), d)
-            a.odom16, a.code, a.gt16, a.tn, a.rot = _ptr(odom), _ptr(code), _ptr(gt), _ptr(tn), _ptr(rot)
-            a.part_rmse = _ptr(self._part_rmse) if gt is not None else None
-            keep += [odom, code, gt, tn, rot]
-        if phases & _lib.LOOP_RESAMPLE and u is not None:
-            u = torch.as_tensor(u).to(d, torch.float64).contiguous().reshape(-1)
-            a.u = _ptr(u)
-            keep.append(u)
-        a.u32 = float(u32)
-        mul = max(float(multiplier), 1.0)
-        a.std_t, a.std_r = (mul * self.sig_t, mul * self.sig_r) if std_override is None else std_override
-        a.seed, a.step = self.seed, self.step_count
-        a.prune_thr, a.softmax, a.resample_mode = self.pen_max, int(self.softmax), self.mode
-        a.floor, a.eps = self.floor, self.eps
-        a.unit_weights = int(bool(unit_weights))
+        else:
+            odom = code = gt = tn = rot = None
+        u = torch.as_tensor(u).to(d, torch.float64).contiguous().reshape(-1) if phases & _lib.LOOP_RESAMPLE and u is not None else None
+        a = self._frame_scalars(u32, multiplier, unit_weights, std_override, score=self.sparse_scores and front)
+        a.odom16, a.code, a.gt16, a.tn, a.rot, a.u = _ptr(odom), _ptr(code), _ptr(gt), _ptr(tn), _ptr(rot), _ptr(u)
+        a.part_rmse = _ptr(self._part_rmse) if gt is not None else None
+        self._write_params()  # (floor, eps ... stay settable between frames)
         if frame_start:
             self._grid_n = self._count_bound() if bound is None else bound
-        a.host_mirror = C.c_void_p(self._mirror.data_ptr())
-        a.grid_n = self._grid_n
-        a.anneal_small = int(self._grid_n <= 16384)
-        a.anneal_frozen = int(self._frozen())
-        a.topk_ties = self.topk_ties
-        a.stream_draws = int(bool(stream_draws))
-        a.telemetry = _ptr(self.telemetry)
-        if self.sparse_scores and phases & _lib.LOOP_FRONT:
-            a.score_stamps, a.score_epoch = _ptr(self._stamps), advance_epoch(self)
-        self._keep = keep
+        a.grid_n, a.anneal_small, a.anneal_frozen = self._grid_n, int(self._grid_n <= 16384), int(self._frozen())
+        a.topk_ties, a.stream_draws = self.topk_ties, int(bool(stream_draws))
+        self._keep = [odom, code, gt, tn, rot, u]  # the operands of the call in flight
         self.ctx.bind_current_stream()
         self.ctx.check(self.ctx.lib.midas_loop_step(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(phases)))
         self._pending_phases |= phases
         if phases & _lib.LOOP_RESAMPLE:  # frame complete
-            self._labels_prev = self._labels
-            self._labels, self._labels_next = self._labels_next, self._labels
             self._pending_phases = 0
-            self.step_count += 1
-            self._n_host = None if self.cluster else self._n_host
+            self._frame_done(n_host=None if self.cluster else self._n_host)
 
     # ---- results --------------------------------------------------------------------------------------------------
     def read_log(self, first: int = 0, last: int = None, strict: bool = True):
@@ -353,8 +437,7 @@ class LoopEngine:
         were sized for; bits 5 / 6: DBSCAN's cell structure did not apply; a seeded stream's counted draw that set its status)
         raise MidasError once every row is parsed (the records are attached to the exception as `.records`); strict=False reports
         them as warnings like the benign ones (cluster limits)."""
-        last = self.step_count if last is None else min(last, self.step_count)
-        first = max(first, last - self.log_frames)
+        first, last = self._log_window(first, last)
         rows = self._log.cpu().numpy()
         mt = self._mt_status.cpu().numpy() if self.torch_stream is not None else None  # (seed_torch_stream: the counted draws' status)
         return log_records(rows, first, last, mt=mt, strict=strict)
@@ -364,7 +447,6 @@ def log_records(rows, first: int, last: int, mt=None, strict: bool = True, who: 
     """Frames [first, last) of a log ring `rows` (log_frames x LOOP_LOG_DOUBLES, on the host) as LoopEngine.read_log's records,
     with its handling of the frames' condition bits; mt: the counted draws' status words of a seeded stream, a word per row;
     who: what the messages call the ring's owner (a batch's "trajectory b, ")."""
-    import warnings
     log_frames = rows.shape[0]
     out, fatal = [], []
     for f in range(first, last):

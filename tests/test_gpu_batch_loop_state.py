@@ -1,5 +1,5 @@
-"""BatchLoopEngine's state handling: the scratch reserved at construction holds every frame (no frame allocates), and a
-`set_particles` call that is refused leaves the engine as it was."""
+"""BatchLoopEngine's state handling: the scratch reserved at construction holds every frame (no frame allocates), its state
+and cached LoopArgs are LoopEngine's behind a lead of B, and a `set_particles` call that is refused leaves the engine as it was."""
 import os
 import subprocess
 import sys
@@ -49,6 +49,57 @@ def test_batch_loop_no_frame_allocates(dev):
     assert "DONE" in r.stdout
     before, after = r.stderr.split("MARK")
     assert "reserved one chunk" in before and "[midas] scratch" not in after, r.stderr
+
+
+def test_loop_engines_share_one_state_table(dev):
+    """LoopEngine and BatchLoopEngine are made from one state table: a batch tensor is the single one behind a lead of B (the
+    telemetry words have none), same dtype and fill, and the cached LoopArgs of both point at the table's tensors.  A frame swaps
+    the label buffers in the struct and leaves no draws behind; the second call of a split LoopEngine frame carries nothing of the
+    first's operands."""
+    from midastouch_amd import BatchLoopEngine, _lib
+    from midastouch_amd.loop_engine import LoopEngine
+    from midastouch_amd.synthetic import make_codebook, make_trajectory
+    cb = make_codebook(K=3000, D=256, seed=1013, mesh_points=20000)
+    tr = make_trajectory(cb, T=3, seed=2001)
+    rng = np.random.default_rng(2)
+    B, cap = 3, 64
+    single = LoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, cap, seed=4100, floor=16, device=dev)
+    batch = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, cap, seed=4100, floor=16, device=dev)
+    assert single._state == batch._state and len(single._state) == 22
+    for attr, field, shape, dt, fill in single._state:
+        s, b = getattr(single, attr), getattr(batch, attr)
+        assert tuple(b.shape) == (() if attr == "telemetry" else (B,)) + tuple(s.shape) and tuple(s.shape)[-len(shape):] == shape, attr
+        assert s.dtype == b.dtype == dt and bool((s == fill).all()) and bool((b == fill).all()), attr
+        if field is not None:
+            assert getattr(single._args, field) == s.data_ptr() and getattr(batch._args, field) == b.data_ptr(), (attr, field)
+    assert int(single._hint[0]) == -1 and tuple(batch._scores.shape) == (B, 3000) and tuple(single._stamps.shape) == (3000,)
+
+    def null(a, *fields):
+        return all(not getattr(a, f) for f in fields)
+
+    poses = torch.as_tensor(cb.poses[rng.integers(0, 3000, cap)])
+    odom, code, gt = (torch.as_tensor(x[1]).to(dev) for x in (tr.odoms, tr.codes, tr.gt_poses))
+    single.set_particles(poses)
+    batch.set_particles(poses[None].repeat(B, 1, 1, 1))
+    rep = lambda t: t[None].repeat(B, *([1] * t.dim())).contiguous()  # noqa: E731
+    for eng, operands in ((single, (odom, code)), (batch, (rep(odom), rep(code)))):
+        a, before = eng._args, (eng._args.labels, eng._args.labels_out)
+        assert before == (eng._labels.data_ptr(), eng._labels_next.data_ptr())
+        eng.step(*operands)
+        assert (a.labels, a.labels_out) == (before[1], before[0]) == (eng._labels.data_ptr(), eng._labels_next.data_ptr())
+        assert null(a, "tn", "rot", "u", "stream_draws")
+    # a split frame: the front with every operand it can take, then the rest of the frame
+    a = single._args
+    z = torch.zeros((single.n, 3), dtype=torch.float32, device=dev)
+    single.step(odom, code, gt=gt, tn=z, rot=z, phases=_lib.LOOP_FRONT)
+    assert not null(a, "odom16") and not null(a, "code") and not null(a, "gt16") and not null(a, "tn") and not null(a, "rot")
+    assert a.part_rmse == single._part_rmse.data_ptr() and single.sparse_scores
+    assert a.score_stamps == single._stamps.data_ptr() and a.score_epoch > 0
+    single.step(None, None)
+    assert null(a, "odom16", "code", "gt16", "tn", "rot", "u", "part_rmse", "score_stamps", "score_epoch", "stream_draws")
+    torch.cuda.synchronize()
+    assert single.step_count == 2 and all(r["err"] == 0 for r in single.read_log(strict=False))
+    assert all(r[0]["err"] == 0 for r in batch.read_log(strict=False))
 
 
 def test_batch_loop_refused_set_particles_changes_nothing(dev):
