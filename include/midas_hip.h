@@ -1037,6 +1037,33 @@ int midas_loop_step_batch_draws(midas_ctx* ctx, const midas_codebook* cb, const 
 #define MIDAS_LOOP_BATCH_WIDE_MAX_CAP 131072
 int midas_loop_step_batch_wide(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                                const midas_loop_args* args, int32_t phases, int32_t B, int64_t log_stride);
+/* The object axis of the reference's sweep (bash/run_filter.sh: ten objects x five logs, one process each; every process builds
+ * its own tactile_tree and mesh, filter/filter.py:82,89-93): the objects the rows of one batch frame localise on.  n_obj objects,
+ * object i = {cbs[i], tree6s[i] (with tree3s[i]'s vertex lists attached, midas_tree_attach_mesh), tree3s[i], cb_poses_devs[i]
+ * (K_i x 16 float32, 16-byte aligned)}; row b of the batch stands on object row_object[b] (host array of B indices in any order;
+ * rows of one object need not be adjacent).  The set keeps, in device memory, one record per object with what the front of a frame
+ * reads from the handles - both trees, the vertex lists with their screening copy, the mesh's distance field, the embeddings with
+ * their norms and K_i, the poses - the row map, and a table of every row's poses; K_max = max K_i.  The handles and the poses stay
+ * the caller's and must outlive the set.  MIDAS_ERR_INVALID (reason through midas_last_error), nothing allocated: n_obj < 1, a row
+ * index outside [0, n_obj), a codebook that is not float32, a D outside {128, 256, 512, 1024} or differing between objects, a
+ * tree6 whose K differs from its codebook's, a tree of the wrong dimension, misaligned rows or poses. */
+typedef struct midas_object_set midas_object_set;
+int midas_object_set_create(midas_ctx* ctx, int32_t n_obj, const midas_codebook* const* cbs, const midas_tree* const* tree6s,
+                            const midas_tree* const* tree3s, const float* const* cb_poses_devs, int32_t B, const int32_t* row_object,
+                            midas_object_set** out);
+/* The end of a sweep (bash/run_filter.sh; the objects of filter/filter.py:82,89-93 go with their processes): waits for the context's
+ * stream and frees the set's device memory; the objects' handles are not touched. */
+int midas_object_set_destroy(midas_object_set* set);
+/* midas_loop_step_batch with every row on its own object - B processes of bash/run_filter.sh over objects x logs x trials in one
+ * launch set: filter/filter.py:150-190 per row, against the codebook, trees and mesh that row's process would have built
+ * (filter/filter.py:82,89-93).  Arguments and layout are midas_loop_step_batch's with K_max as the extent of scores and score_stamps
+ * ((B, K_max); row b touches its first K_b slots) and B == the set's; args->cb_poses_dev is not read: a row whose particles were all
+ * pruned goes back onto its own object's poses (filter.py:176-179).  Filter parameters stay shared by the rows.  wide = 0: the regime
+ * of midas_loop_step_batch_draws (Philox or the caller's draws, either tie rule, any subset of phases); wide = 1: that of
+ * midas_loop_step_batch_wide.  One launch of the front for all rows (every workgroup reads its row's record), every other launch
+ * as in midas_loop_step_batch: row b holds, frame for frame, the bits of midas_loop_step on object row_object[b] with seed + b. */
+int midas_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args* args, int32_t phases, int32_t B,
+                                  int64_t log_stride, int32_t wide);
 /* cluster_particles(method="euclidean") alone (particle_filter.py:208-217): labels_dev[i] = DBSCAN label of pose i's
  * translation, eps as given, min_samples < 0 -> N / 5.  Exact float64 predicate |dx|^2 <= eps^2, clusters numbered by their
  * first core point, border points to the smallest adjacent cluster - what sklearn's DBSCAN returns.  Any extent (dense cell grid

@@ -29,17 +29,29 @@ per-trajectory state reserved at construction.  Row b holds the bits of a LoopEn
 wide engine runs the launches of a plain one.  Open follow-up: `seed_torch_streams` and `topk_ties = "aten_cpu"` raise on a wide
 engine - the one-wave walk of ATen's top-k takes 1.4 - 11 ms at 100 000 particles per trajectory, which a batch frame cannot carry;
 seeded replays at these sizes stay with LoopEngine.
+
+Rows on different objects: `BatchLoopEngine.for_objects(objects, row_object, num_particles, ...)` - the object axis of the reference's
+sweep (`bash/run_filter.sh`: objects x logs x trials) in ONE batch.  Every object gets its own codebook index on the one context, an
+object set (`midas_object_set_create`) tells the front which record a row's workgroups read, and a frame goes through
+`midas_loop_step_batch_objects`: one launch set for all rows, whatever they stand on.  Row b holds the bits of a LoopEngine built on
+object row_object[b] with seed + b.  Scores and stamps are (B, K_max); the filter's parameters stay shared by the rows.
 """
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 
 import torch
 
 from . import _lib, ops
 from ._lib import MidasError, _ptr
-from .engine import frame_operands, sparse_scoring
+from .engine import codebook_index, frame_operands, sparse_scoring
 from .loop_engine import ALL_PHASES, TOPK_TIES, _LoopBase, log_records
+
+
+# the constructor's keywords and their defaults: what `for_objects` takes as **kw (tests hold __init__'s signature to this table)
+DEFAULTS = dict(sig_t=2e-4, sig_r=0.5, pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor=1000, eps=1e-2,
+                cluster=True, cluster_every=50, log_frames=4096, device=None, wide=False, batched_dbscan=None)
 
 
 class BatchLoopEngine(_LoopBase):
@@ -47,6 +59,39 @@ class BatchLoopEngine(_LoopBase):
                  pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2,
                  cluster: bool = True, cluster_every: int = 50, log_frames: int = 4096, device=None, wide: bool = False,
                  batched_dbscan=None):
+        self._init([(cb_poses, cb_embeddings, mesh_vertices)], None, batch, num_particles, sig_t=sig_t, sig_r=sig_r, pen_max=pen_max,
+                   seed=seed, softmax=softmax, resample=resample, floor=floor, eps=eps, cluster=cluster, cluster_every=cluster_every,
+                   log_frames=log_frames, device=device, wide=wide, batched_dbscan=batched_dbscan)
+
+    def _init(self, objects, row_object, batch, num_particles, *, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps, cluster,
+              cluster_every, log_frames, device, wide, batched_dbscan):
+        """The one initialiser behind the constructor (one object, row_object None) and `for_objects`: the bounds, the set-up on the
+        first row's object, for an object batch every object's index and the object set, then the state and the scratch."""
+        self._check_regime(batch, num_particles, wide, batched_dbscan)
+        first = 0 if row_object is None else row_object[0]  # the handles `_LoopBase` names (ctx, cb_poses, tree6, codebook, tree3): row 0's object
+        self._setup(*objects[first], device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps, cluster, cluster_every, log_frames)
+        if not sparse_scoring(self.codebook, switch=False):
+            raise MidasError("BatchLoopEngine scores sparsely: a float32 codebook with D in {128, 256, 512, 1024}")
+        self.objects = self.row_object = self.Ks = self._set = None  # (for_objects)
+        if row_object is not None:
+            self.objects = []
+            for i, o in enumerate(objects):
+                if i == first:
+                    ix = (self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3)
+                else:
+                    ix = codebook_index(*o, self.device)
+                if ix[0] is not self.ctx:
+                    raise MidasError("for_objects: every object's index lives on the engine's context")
+                if not sparse_scoring(ix[4], switch=False):
+                    raise MidasError(f"object {i}: BatchLoopEngine scores sparsely: a float32 codebook with D in {{128, 256, 512, 1024}}")
+                self.objects.append(SimpleNamespace(cb_poses=ix[1], cb_feat=ix[2], tree6=ix[3], codebook=ix[4], tree3=ix[5]))
+            self.row_object, self.Ks = list(row_object), [int(o.codebook.K) for o in self.objects]
+            self._set = ops.ObjectSet(self.ctx, self.objects, row_object)
+            self.K = max(self.Ks)  # scores and stamps are (B, K_max): row b touches the first Ks[row_object[b]] slots of its rows
+        self._alloc_batch()
+
+    def _check_regime(self, batch, num_particles, wide, batched_dbscan):
+        """The constructor's bounds, checked before a context is asked for."""
         self.B, self.cap = B, cap = int(batch), int(num_particles)
         self.wide = bool(wide)
         if B < 1 or B > 65535:
@@ -63,10 +108,10 @@ class BatchLoopEngine(_LoopBase):
                 raise MidasError(f"a wide BatchLoopEngine holds at most 2^24 particles in all, not {B} x {cap}")
         elif cap < 1 or cap > _lib.LOOP_BATCH_MAX_CAP:
             raise MidasError(f"BatchLoopEngine holds 1 .. {_lib.LOOP_BATCH_MAX_CAP} particles per trajectory (larger sets: LoopEngine)")
-        self._setup(cb_poses, cb_embeddings, mesh_vertices, device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps,
-                    cluster, cluster_every, log_frames)
-        if not sparse_scoring(self.codebook, switch=False):
-            raise MidasError("BatchLoopEngine scores sparsely: a float32 codebook with D in {128, 256, 512, 1024}")
+
+    def _alloc_batch(self):
+        """The state of B trajectories behind the set-up (self.K scores and stamps a row) and the frames' scratch."""
+        B, cap = self.B, self.cap
         self._topk_ties = "index"
         self._alloc_state((B,), self._topk_ties)
         self._args.dbscan_batched = int(self.batched_dbscan)
@@ -79,6 +124,35 @@ class BatchLoopEngine(_LoopBase):
         per_traj = self._per_traj()
         self._scratch = (128 << 20) + 256 * cap + B * per_traj + (64 + 32 * self.batched_dbscan) * 256
         self.ctx.call("midas_scratch_reserve", self._scratch)
+
+    @classmethod
+    def for_objects(cls, objects, row_object, num_particles: int, **kw):
+        """A batch whose rows stand on different objects - the reference's sweep over objects, logs and trials (bash/run_filter.sh) as
+        one engine.  objects: a list of (cb_poses, cb_embeddings, mesh_vertices) triples, or of (tactile_tree, None, ops.Tree) as the
+        constructor takes them; row_object: for each of the B rows the index of its object, in any order; **kw: the constructor's
+        keywords (wide, batched_dbscan, seed, floor, ...), shared by all rows.  Every object's codebook index is built on one context;
+        all codebooks are float32 with one D.  New attributes: `objects` (per object: cb_poses, cb_feat, tree6, codebook, tree3),
+        `row_object` and `Ks` (the objects' codebook sizes; `K` is the largest, the extent of a row's scores)."""
+        objects, row_object = list(objects), [int(i) for i in row_object]
+        if not objects:
+            raise MidasError("for_objects needs at least one object")
+        if not row_object:
+            raise MidasError("for_objects needs at least one row")
+        for b, i in enumerate(row_object):
+            if not 0 <= i < len(objects):
+                raise MidasError(f"row {b}: object index {i} outside the {len(objects)} objects")
+
+        def dim(o):  # D of an object's codebook as given, without touching a device
+            return int(o[0].codebook.D) if o[1] is None else int(torch.as_tensor(o[1]).shape[-1])
+        Ds = [dim(o) for o in objects]
+        if len(set(Ds)) > 1:
+            raise MidasError(f"for_objects needs codebooks of one D, got {Ds}")
+        unknown = sorted(set(kw) - set(DEFAULTS))
+        if unknown:
+            raise MidasError(f"for_objects: unknown keyword(s) {unknown}; the constructor's are {sorted(DEFAULTS)}")
+        self = cls.__new__(cls)
+        self._init(objects, row_object, len(row_object), num_particles, **{**DEFAULTS, **kw})
+        return self
 
     # whom annealing's torch.topk takes inside a tie: "index" (torch's CUDA rule, the radix select: midas_loop_step_batch as ever) or
     # "aten_cpu" (the reference as it runs on the CPU, topk_aten.hip: midas_loop_step_batch_draws); settable between frames
@@ -185,10 +259,12 @@ class BatchLoopEngine(_LoopBase):
         return st
 
     def project_to_codebook(self):
-        """poses := codebook pose nearest to each particle (filter/filter.py:159-160), every trajectory's live set."""
+        """poses := codebook pose nearest to each particle (filter/filter.py:159-160), every trajectory's live set - on the codebook
+        of its own object."""
         for b, n in enumerate(self.n):
-            idx = ops.nn6(self.tree6, ops.se3_feature(self._poses[b, :n]))
-            self._poses[b, :n].copy_(ops.gather_rows(self.cb_poses, idx))
+            o = self if self.objects is None else self.objects[self.row_object[b]]
+            idx = ops.nn6(o.tree6, ops.se3_feature(self._poses[b, :n]))
+            self._poses[b, :n].copy_(ops.gather_rows(o.cb_poses, idx))
             self._hint[b, :n].copy_(idx)
 
     @property
@@ -221,6 +297,10 @@ class BatchLoopEngine(_LoopBase):
 
         def call(entry, ph):
             self.ctx.bind_current_stream()
+            if self._set is not None:  # rows on different objects: one entry, the regime of `entry` by its `wide` flag
+                self.ctx.check(self.ctx.lib.midas_loop_step_batch_objects(self.ctx.h, self._set.h, C.byref(a), int(ph), self.B, log_stride,
+                                                                          int(self.wide)))
+                return
             self.ctx.check(entry(self.ctx.h, self.codebook.h, self.tree6.h, self.tree3.h, C.byref(a), int(ph), self.B, log_stride))
 
         if st is not None:

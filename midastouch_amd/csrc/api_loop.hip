@@ -1,7 +1,11 @@
 // api_loop.hip - the loop engine's entry points: the whole loop body on a variable-size particle set, for one trajectory
-// (midas_loop_step) and for B per launch (midas_loop_step_batch, midas_loop_step_batch_draws, midas_loop_step_batch_wide).  One
-// argument check for the four.
+// (midas_loop_step) and for B per launch (midas_loop_step_batch, midas_loop_step_batch_draws, midas_loop_step_batch_wide; with every row on an
+// object of its own: midas_object_set_create / _destroy and midas_loop_step_batch_objects).  One argument check for the five.
+#include <new>
+#include <vector>
+
 #include "api_entry.hpp"
+#include "tree_search.hpp"  // view_of: the trees as an object record holds them
 
 using namespace midas;
 
@@ -12,7 +16,8 @@ using namespace midas;
 enum class LoopRegime { single, batch, batch_draws, batch_wide };
 
 static int loop_args_check(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
-                           const midas_loop_args* args, int32_t phases, LoopRegime regime, int32_t B = 1, int64_t log_stride = 0) {
+                           const midas_loop_args* args, int32_t phases, LoopRegime regime, int32_t B = 1, int64_t log_stride = 0,
+                           const midas_object_set* objects = nullptr) {  // objects: in place of cb, the trees and args->cb_poses_dev
     MIDAS_REQUIRE(ctx, args != nullptr && phases != 0 && (phases & ~15) == 0);
     const midas_loop_args& s = *args;
     const bool batch = regime != LoopRegime::single;
@@ -40,11 +45,16 @@ static int loop_args_check(midas_ctx* ctx, const midas_codebook* cb, const midas
         MIDAS_REQUIRE(ctx, s.grid_n == 0 && s.anneal_frozen == 0);
         MIDAS_REQUIRE(ctx, s.log_dev == nullptr || log_stride >= MIDAS_LOOP_LOG_DOUBLES || B == 1);
     }
+    if (objects) MIDAS_REQUIRE(ctx, batch && objects->ctx == ctx && objects->B == B);
     if (phases & MIDAS_LOOP_FRONT) {
-        MIDAS_REQUIRE(ctx, cb && tree6 && tree3 && tree6->dim == 6 && tree3->dim == 3 && tree6->K == cb->K);
-        MIDAS_REQUIRE(ctx, s.odom16_dev && s.code_dev && s.cb_poses_dev && (uintptr_t)s.cb_poses_dev % 16 == 0);
+        if (!objects) {
+            MIDAS_REQUIRE(ctx, cb && tree6 && tree3 && tree6->dim == 6 && tree3->dim == 3 && tree6->K == cb->K);
+            MIDAS_REQUIRE(ctx, s.odom16_dev && s.code_dev && s.cb_poses_dev && (uintptr_t)s.cb_poses_dev % 16 == 0);
+        } else {  // (the set's creation checked every object's codebook, trees and poses; args->cb_poses_dev is not read)
+            MIDAS_REQUIRE(ctx, s.odom16_dev && s.code_dev);
+        }
         if (batch) {  // every trajectory's particle waves score the rows they need from its own code
-            MIDAS_REQUIRE(ctx, sparse_score_ok(cb, s.code_dev));
+            MIDAS_REQUIRE(ctx, objects ? (uintptr_t)s.code_dev % 16 == 0 : sparse_score_ok(cb, s.code_dev));
             MIDAS_REQUIRE(ctx, s.score_stamps_dev != nullptr && s.score_epoch != 0);
         } else {
             MIDAS_REQUIRE(ctx, (s.tn_dev == nullptr) == (s.rot_dev == nullptr));
@@ -87,6 +97,83 @@ MIDAS_EXPORT int midas_loop_step_batch_wide(midas_ctx* ctx, const midas_codebook
     MIDAS_ENTER(ctx);
     if (int rc = loop_args_check(ctx, cb, tree6, tree3, args, phases, LoopRegime::batch_wide, B, log_stride)) return rc;
     return launch_loop_step_batch(ctx, cb, tree6, tree3, *args, phases, B, log_stride, true);
+}
+
+// ---- rows on different objects ------------------------------------------------------------------------------------------------
+MIDAS_EXPORT int midas_object_set_create(midas_ctx* ctx, int32_t n_obj, const midas_codebook* const* cbs, const midas_tree* const* tree6s,
+                                         const midas_tree* const* tree3s, const float* const* cb_poses_devs, int32_t B,
+                                         const int32_t* row_object, midas_object_set** out) {
+    MIDAS_ENTER(ctx);
+    const auto refuse = [&](const char* why) { return midas_set_error(ctx, MIDAS_ERR_INVALID, "midas_object_set_create", why); };
+    if (!out) return refuse("no place for the handle");
+    if (n_obj < 1 || !cbs || !tree6s || !tree3s || !cb_poses_devs) return refuse("an empty object set");
+    if (B < 1 || B > 65535 || !row_object) return refuse("1 .. 65535 rows, each with its object");
+    for (int32_t b = 0; b < B; ++b)
+        if (row_object[b] < 0 || row_object[b] >= n_obj) return refuse("a row's object index outside [0, n_obj)");
+    std::vector<ObjectRecord> recs((size_t)n_obj);
+    int64_t K_max = 0;
+    for (int32_t i = 0; i < n_obj; ++i) {
+        const midas_codebook* cb = cbs[i];
+        const midas_tree *t6 = tree6s[i], *t3 = tree3s[i];
+        if (!cb || !t6 || !t3 || !cb_poses_devs[i]) return refuse("an object without codebook, trees or poses");
+        if (cb->dtype != MIDAS_F32) return refuse("a codebook that is not float32");
+        if (!(cb->D == 128 || cb->D == 256 || cb->D == 512 || cb->D == 1024)) return refuse("a codebook whose D is not 128, 256, 512 or 1024");
+        if (cb->D != cbs[0]->D) return refuse("codebooks of different D");
+        if ((uintptr_t)cb->emb % 16 != 0) return refuse("misaligned codebook rows");
+        if (t6->dim != 6 || t3->dim != 3) return refuse("a tree of the wrong dimension");
+        if (t6->K != cb->K) return refuse("a 6-d index whose K differs from its codebook's");
+        if ((uintptr_t)cb_poses_devs[i] % 16 != 0) return refuse("misaligned codebook poses");
+        ObjectRecord& r = recs[(size_t)i];
+        r.t6 = view_of<Kd6>(t6);
+        r.t3 = view_of<Kd3>(t3);
+        r.vlist = (t6->vlist && t6->vlist_mesh == t3) ? (const MeshRec*)t6->vlist : nullptr;  // as fill_particle_update
+        r.vscr = r.vlist ? (const MeshScr*)t6->vscr : nullptr;
+        r.field = t3->field;
+        r.emb = (const float*)cb->emb; r.norms = cb->norms; r.K = cb->K; r.cb_poses = cb_poses_devs[i];
+        K_max = cb->K > K_max ? cb->K : K_max;
+    }
+    std::vector<const float*> rows((size_t)B);
+    for (int32_t b = 0; b < B; ++b) rows[(size_t)b] = cb_poses_devs[row_object[b]];
+    const size_t rec_bytes = recs.size() * sizeof(ObjectRecord), row_bytes = rows.size() * sizeof(const float*);
+    midas_object_set* set = new (std::nothrow) midas_object_set();
+    if (!set) return midas_set_error(ctx, MIDAS_ERR_NOMEM, "new midas_object_set", "");
+    if (hipMalloc(&set->dev, rec_bytes + row_bytes + (size_t)B * sizeof(int32_t)) != hipSuccess) {
+        delete set;
+        return midas_set_error(ctx, MIDAS_ERR_NOMEM, "hipMalloc(object set)", "");
+    }
+    char* d = (char*)set->dev;
+    hipError_t e = hipMemcpy(d, recs.data(), rec_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + rec_bytes, rows.data(), row_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + rec_bytes + row_bytes, row_object, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(set->dev);
+        delete set;
+        return midas_set_error(ctx, MIDAS_ERR_HIP, "hipMemcpy(object set)", hipGetErrorString(e));
+    }
+    set->ctx = ctx; set->n_obj = n_obj; set->B = B; set->D = cbs[0]->D; set->K_max = K_max;
+    set->recs = (const ObjectRecord*)d;
+    set->cb_poses_rows = (const float* const*)(d + rec_bytes);
+    set->row_object = (const int32_t*)(d + rec_bytes + row_bytes);
+    set->cb_poses_row0 = rows[0];
+    *out = set;
+    return MIDAS_OK;
+}
+
+MIDAS_EXPORT int midas_object_set_destroy(midas_object_set* set) {
+    if (!set) return MIDAS_OK;
+    (void)hipStreamSynchronize(set->ctx->stream);
+    (void)hipFree(set->dev);
+    delete set;
+    return MIDAS_OK;
+}
+
+MIDAS_EXPORT int midas_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args* args, int32_t phases,
+                                               int32_t B, int64_t log_stride, int32_t wide) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, set != nullptr && (wide == 0 || wide == 1));
+    const LoopRegime regime = wide ? LoopRegime::batch_wide : LoopRegime::batch_draws;
+    if (int rc = loop_args_check(ctx, nullptr, nullptr, nullptr, args, phases, regime, B, log_stride, set)) return rc;
+    return launch_loop_step_batch_objects(ctx, set, *args, phases, log_stride, wide != 0);
 }
 
 }  // extern "C"

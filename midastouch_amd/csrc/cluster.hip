@@ -223,7 +223,8 @@ __global__ __launch_bounds__(256) void k_loop_cluster_moments(const int32_t* __r
 #else
 #define WCK(i) do { } while (0)
 #endif
-__global__ __launch_bounds__(256) void k_loop_weights_moments(LoopWeightsArgs a, const int32_t* __restrict__ labels,
+template <class Args>  // LoopWeightsArgs, or LoopWeightsRowsArgs - rows on different objects (loop_weights.hpp)
+__global__ __launch_bounds__(256) void k_loop_weights_moments(Args a, const int32_t* __restrict__ labels,
                                                               double* __restrict__ part, bool skip) {
 #ifdef MIDAS_ANNEAL_CLOCKS
     const long long wck0 = wall_clock64();
@@ -630,11 +631,14 @@ static bool moments_skip() {  // MIDAS_MOMENTS_SKIP=0: every cluster summed by e
 // (the decision only needs the translation spreads: the eigenvector runs beside the selection)
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsArgs* weights, int32_t B) {
+                        const LoopWeightsRowsArgs* weights, int32_t B) {
     const unsigned by = (unsigned)(B > 1 ? B : 1);
-    if (weights)
-        hipLaunchKernelGGL(k_loop_weights_moments, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream, *weights, labels, part,
-                           moments_skip());
+    if (weights && weights->cb_poses_rows)  // rows on different objects (midas_loop_step_batch_objects)
+        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsRowsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
+                           *weights, labels, part, moments_skip());
+    else if (weights)
+        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
+                           static_cast<const LoopWeightsArgs&>(*weights), labels, part, moments_skip());
     else
         hipLaunchKernelGGL(k_loop_cluster_moments, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream, ctl_i, poses, w64,
                            labels, part, moments_skip(), (int32_t)cap);

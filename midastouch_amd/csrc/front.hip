@@ -1,6 +1,6 @@
 // front.hip - the fused front of the step: launch_frame_front (which form of the front a frame takes), the forms of
 // k_frame_front without folded resample (the folded ones: front_folded.hip, front_batch.hip), the forms for small particle sets
-// (k_frame_front_a + k_particle_nn_prune, k_front_small), and the unfused particle update (k_particle_update) with the reduction
+// (k_frame_front_a + k_particle_nn_prune, k_front_small, k_front_small_objects), and the unfused particle update (k_particle_update) with the reduction
 // of its per-wave partials.
 // (The small-set kernels share this unit with the plain forms on purpose: in a unit of their own every caller of
 // score_claimed_rows_nj passes dense = false, the compiler folds that into the callee before inlining it, and
@@ -297,6 +297,34 @@ __global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small(TreeView<Kd6
     particle_nn_prune_wg<4>(t6, t3, a, feat);
 }
 
+// k_front_small for a batch whose rows stand on different objects (midas_loop_step_batch_objects): the workgroup takes its row's
+// object from the set's row map and that object's record - trees, vertex lists, distance field, embeddings - from the set's
+// table.  Both addresses depend on blockIdx.y alone, so the record arrives by scalar loads and stays in SGPRs, where k_front_small
+// holds the same values as kernel arguments; nothing is stored before they are read.  Every row takes its offsets, row 0 included
+// (its offsets are zero); score and stamp rows are a.score_stride = K_max apart and row b touches the first K_b slots of its own.
+__global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small_objects(const ObjectRecord* __restrict__ recs,
+                                                                            const int32_t* __restrict__ row_object, ParticleUpdateArgs a,
+                                                                            int nwaves, PuFeat* __restrict__ feat) {
+    const int64_t b = blockIdx.y, o = b * a.N;
+    const ObjectRecord& r = recs[row_object[b]];
+    const TreeView<Kd6> t6 = r.t6;
+    const TreeView<Kd3> t3 = r.t3;
+    a.vlist = r.vlist; a.vscr = r.vscr; a.field = r.field;
+    a.sp.emb = r.emb; a.sp.norms = r.norms; a.sp.K = r.K;
+    a.n_live += b * LOOP_CTL_I;
+    a.poses_in += o * 16; a.poses_prop += o * 16; a.odom16 += b * 16;
+    if (a.hint_in) a.hint_in += o;
+    a.nn_idx += o; a.valid += o;
+    if (a.gt16) { a.gt16 += b * 16; a.part_rmse += 2 * b * nwaves; }
+    a.sp.stamps += b * a.score_stride; a.sp.scores += b * a.score_stride; a.sp.code += b * (int64_t)(a.sp.nj * 64);
+    a.seed += (uint64_t)b;  // (the row, not its object: the draws of a single engine built with seed + row)
+    if (a.tn) { a.tn += o * 3; a.rot += o * 3; }
+    feat += o;
+    if (threadIdx.x < 64 && (int)blockIdx.x < nwaves) particle_front_wave(a, (int64_t)blockIdx.x, nullptr, feat);
+    __syncthreads();  // (as in k_front_small)
+    particle_nn_prune_wg<4>(t6, t3, a, feat);
+}
+
 template <int NJ, bool LAZY>
 static void launch_front_a(const FrontLaunch& L, PuFeat* feat) {
     hipLaunchKernelGGL((k_frame_front_a<float, NJ, LAZY>), L.grid, dim3(256), 0, L.ctx->stream, L.a, L.n_pu, L.nwaves, feat,
@@ -447,6 +475,28 @@ int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_t
     if (rc) return rc;
     hipLaunchKernelGGL(k_front_small, dim3((unsigned)ceil_div(a.N, 64), (unsigned)B), dim3(256), 0, ctx->stream, view_of<Kd6>(t6),
                        view_of<Kd3>(t3), a, nwaves, (PuFeat*)feat);
+    MIDAS_HIP_CHECK(ctx, hipGetLastError());
+    return MIDAS_OK;
+}
+
+int launch_front_small_objects(midas_ctx* ctx, const midas_object_set* set, const ParticleUpdateArgs& a_in, const double* code,
+                               double* scores, bool wide) {
+    ParticleUpdateArgs a = a_in;
+    // (the set's creation checked every codebook: float32, one D of the sparse scoring's, aligned rows)
+    if (!(a.n_live && a.N > 0 && (a.N <= 16384 || (wide && a.N <= MIDAS_LOOP_BATCH_WIDE_MAX_CAP)) && a.sp.stamps && !a.rs.enabled &&
+          (uintptr_t)code % 16 == 0))
+        return midas_set_error(ctx, MIDAS_ERR_INVALID, "launch_front_small_objects", "no small-set front for these arguments");
+    a.scores = nullptr;  // deferred: k_loop_xe gathers the scores
+    a.sp.code = code; a.sp.scores = scores; a.sp.nj = set->D / 64;
+    a.sp.pred_tag = 0; a.sp.list = nullptr;
+    a.score_stride = set->K_max;
+    a.batch = set->B;
+    const int nwaves = particle_update_blocks(a.N);
+    void* feat;
+    const int rc = midas_scratch(ctx, (size_t)set->B * a.N * sizeof(PuFeat), &feat);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_front_small_objects, dim3((unsigned)ceil_div(a.N, 64), (unsigned)set->B), dim3(256), 0, ctx->stream, set->recs,
+                       set->row_object, a, nwaves, (PuFeat*)feat);
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
 }

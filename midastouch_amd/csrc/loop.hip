@@ -29,13 +29,13 @@
 #include <cstdlib>
 
 #include "midas_internal.hpp"
-#include "loop_weights.hpp"   // LoopWeightsArgs: the merged weights travel from the front to the cluster-moment launch
+#include "loop_weights.hpp"   // LoopWeightsRowsArgs: the merged weights travel from the front to the cluster-moment launch
 #include "anneal_decide.hpp"  // LOOP_SMALL_MAX
 
 namespace midas {
 
 // ANNEAL, first half: the clusters' moments (with the merged weights at their head) into scratch the selection reads
-static int loop_cluster_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopWeightsArgs* merged, LoopMoments& m) {
+static int loop_cluster_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopWeightsRowsArgs* merged, LoopMoments& m) {
     const size_t Bz = (size_t)g.B;
     void *part, *cen, *sd, *cnt, *rot;
     int rc;
@@ -59,7 +59,7 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
     g.clocks = s.ctl_d_dev;
 #endif
     int rc;
-    LoopWeightsArgs wa{};
+    LoopWeightsRowsArgs wa{};
     bool weights_merged = false;
     if (phases & MIDAS_LOOP_FRONT) {
         ParticleUpdateArgs pa;
@@ -111,24 +111,31 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 // wide (midas_loop_step_batch_wide, cap <= MIDAS_LOOP_BATCH_WIDE_MAX_CAP, device draws and ties by index): a capacity beyond
 // LOOP_SMALL_MAX takes k_front_small over as many waves as it has, and - one trajectory's keys no longer fit one workgroup - the
 // single call's decision and radix selection with the trajectory as grid.y (launch_select).  Up to LOOP_SMALL_MAX the launches above.
-int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
-                           const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride, bool wide) {
+// objects (midas_loop_step_batch_objects): every row on the object the set names for it - the front takes trees, lists, field and
+// codebook from the set's records (k_front_small_objects; cb, t6 and t3 are null) and the weights re-project a drifted row onto its
+// own object's poses; the score rows are K_max apart.  Every other phase works on the (B, ...) arrays and never sees a codebook.
+static int loop_step_batch_frame(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
+                                 const midas_object_set* objects, const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride,
+                                 bool wide) {
     const int64_t cap = s.cap;
     const bool large = wide && cap > LOOP_SMALL_MAX;
     LoopGrid g;
     g.cap = cap; g.B = B; g.slice = (int32_t)cap; g.log_stride = log_stride;
     g.lp_stride = (int32_t)(cap + SCAN_CHUNK);  // (the resample reads whole chunks)
     int rc;
-    LoopWeightsArgs wa{};
+    LoopWeightsRowsArgs wa{};
     bool weights_merged = false;
     if (phases & MIDAS_LOOP_FRONT) {
+        static const midas_tree no_tree{};  // (objects: the kernel takes the lists and the field from the row's record)
         ParticleUpdateArgs pa;
-        fill_particle_update(pa, s, t6, t3, cap, s.poses_dev, s.hint_dev, s.valid_dev, s.score_stamps_dev,
-                             (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
+        fill_particle_update(pa, s, objects ? &no_tree : t6, objects ? &no_tree : t3, cap, s.poses_dev, s.hint_dev, s.valid_dev,
+                             s.score_stamps_dev, (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
         pa.n_live = s.ctl_i_dev + LOOP_I_N;
-        if ((rc = launch_front_small_batch(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, B, large))) return rc;
+        if (objects) rc = launch_front_small_objects(ctx, objects, pa, s.code_dev, s.scores_dev, large);
+        else rc = launch_front_small_batch(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, B, large);
+        if (rc) return rc;
         weights_merged = loop_weights_mergeable(phases);
-        if ((rc = loop_weights_phase(ctx, s, g, cb->K, pa.gt16 != nullptr, weights_merged, wa))) return rc;
+        if ((rc = loop_weights_phase(ctx, s, g, objects ? objects->K_max : cb->K, pa.gt16 != nullptr, weights_merged, wa, objects))) return rc;
     }
     if ((phases & MIDAS_LOOP_DBSCAN) && s.dbscan_batched) {
         // all trajectories in one set of launches, each in its own region of the cell tables (dbscan.hip): the labels of the passes below
@@ -159,6 +166,16 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
         if ((rc = loop_ndraw_phase(ctx, s, g, cap))) return rc;
     }
     return MIDAS_OK;
+}
+
+int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
+                           const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride, bool wide) {
+    return loop_step_batch_frame(ctx, cb, t6, t3, nullptr, s, phases, B, log_stride, wide);
+}
+
+int launch_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args& s, int32_t phases,
+                                   int64_t log_stride, bool wide) {
+    return loop_step_batch_frame(ctx, nullptr, nullptr, nullptr, set, s, phases, set->B, log_stride, wide);
 }
 
 // (the units cut out of this one are loaded with it: midas_ctx_create warms "loop")

@@ -117,7 +117,9 @@ __global__ __launch_bounds__(256) void k_loop_xe(const int32_t* __restrict__ ctl
 // S = blocks summed in order; guard; w = (e or x) / S * valid; every particle back onto its codebook pose when all of them
 // were pruned (filter.py:176-179); block 0 finalises the control block and the rmse.  (The arithmetic lives in loop_weights.hpp:
 // frames whose cluster moments follow in the same call have it at the head of that launch instead, cluster.hip.)
-__global__ __launch_bounds__(256) void k_loop_weights(LoopWeightsArgs a) {
+// (Args: LoopWeightsArgs, or LoopWeightsRowsArgs - rows on different objects, loop_weights.hpp)
+template <class Args>
+__global__ __launch_bounds__(256) void k_loop_weights(Args a) {
     __shared__ double s_sum[LAZY_MAX_BLOCKS];
     __shared__ double s_red[8], s_ab[8];
     __shared__ int s_ired[8];
@@ -164,7 +166,7 @@ static int carve_block_results(midas_ctx* ctx, size_t count, LoopBlockResults& b
     br.bnan = br.bkept + count;
     return MIDAS_OK;
 }
-static void fill_loop_weights(LoopWeightsArgs& wa, const midas_loop_args& s, const LoopBlockResults& br, int32_t grid_n, unsigned nbcap,
+static void fill_loop_weights(LoopWeightsRowsArgs& wa, const midas_loop_args& s, const LoopBlockResults& br, int32_t grid_n, unsigned nbcap,
                               bool rmse) {
     wa.ctl_i = s.ctl_i_dev; wa.ctl_d = s.ctl_d_dev; wa.grid_n = grid_n; wa.nbl = (int32_t)nbcap;
     wa.bsum = br.bsum; wa.bmax = br.bmax; wa.bmin = br.bmin; wa.bkept = br.bkept; wa.bnan = br.bnan;
@@ -180,7 +182,7 @@ bool loop_weights_mergeable(int32_t phases) { return (phases & MIDAS_LOOP_ANNEAL
 
 // behind the front: k_loop_xe, then the weights - launched here, or (merged) left in `wa` for the cluster-moment launch
 int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t K, bool rmse, bool merged,
-                       LoopWeightsArgs& wa) {
+                       LoopWeightsRowsArgs& wa, const midas_object_set* objects) {
     const unsigned nbcap = g.nbcap();
     LoopBlockResults br;
     if (int rc = carve_block_results(ctx, (size_t)g.B * nbcap, br)) return rc;
@@ -188,7 +190,13 @@ int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid&
                        (const int32_t*)s.nn_idx_dev, (const uint8_t*)s.valid_dev, s.softmax, s.unit_weights, s.x_dev, s.e_dev, br.bsum, br.bmax,
                        br.bmin, br.bkept, br.bnan, loop_bound(g.cap), K, g.clocks);
     fill_loop_weights(wa, s, br, loop_bound(g.cap), nbcap, rmse);
-    if (!merged) hipLaunchKernelGGL(k_loop_weights, dim3(nbcap, g.by()), dim3(256), 0, ctx->stream, wa);
+    wa.cb_poses_rows = nullptr;
+    if (objects) {  // (row 0 takes `cb_poses` as it stands: the kernels look at the table for blockIdx.y != 0 only)
+        wa.cb_poses = objects->cb_poses_row0;
+        wa.cb_poses_rows = objects->cb_poses_rows;
+    }
+    if (!merged && objects) hipLaunchKernelGGL(k_loop_weights<LoopWeightsRowsArgs>, dim3(nbcap, g.by()), dim3(256), 0, ctx->stream, wa);
+    else if (!merged) hipLaunchKernelGGL(k_loop_weights<LoopWeightsArgs>, dim3(nbcap, g.by()), dim3(256), 0, ctx->stream, static_cast<const LoopWeightsArgs&>(wa));
     LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }

@@ -30,6 +30,12 @@ struct LoopWeightsArgs {
     const double* part_rmse;  // nullable
     int32_t softmax;
 };
+// The record as the host carries it through a frame: cb_poses_rows is null, or (B) row b's codebook poses - rows on different objects
+// (midas_loop_step_batch_objects; cb_poses is then row 0's).  The kernels are templates over the record they take: a frame without
+// the table launches the LoopWeightsArgs instantiation - the field and its branch are not in that kernel.
+struct LoopWeightsRowsArgs : LoopWeightsArgs {
+    const float* const* cb_poses_rows = nullptr;
+};
 
 // trajectory b of a batch (midas_loop_step_batch; blockIdx.y): every array is (B, ...) contiguous - grid_n particles (the capacity),
 // nbl block results, ceil(grid_n / 64) pairs of rmse partials and one control block per trajectory; the codebook poses are shared
@@ -39,6 +45,11 @@ MD void loop_weights_batch(LoopWeightsArgs& a, int64_t b) {
     a.bsum += ob; a.bmax += ob; a.bmin += ob; a.bkept += ob; a.bnan += ob;
     a.x += o; a.e += o; a.valid += o; a.nn_idx += o; a.poses_prop += o * 16; a.w_out += o; a.src += o;
     if (a.part_rmse) a.part_rmse += 2 * b * (((int64_t)a.grid_n + 63) / 64);
+}
+// ... with the row's own codebook poses
+MD void loop_weights_batch(LoopWeightsRowsArgs& a, int64_t b) {
+    loop_weights_batch(static_cast<LoopWeightsArgs&>(a), b);
+    if (a.cb_poses_rows) a.cb_poses = a.cb_poses_rows[b];
 }
 
 // what a thread requests before the live count is looked at (the control block is another launch's output: these travel with it)

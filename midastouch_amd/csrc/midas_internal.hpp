@@ -141,6 +141,34 @@ struct midas_tree {
     midas::MeshField field;  // dim 3: distance field of the vertices (d == nullptr: none); library-owned
 };
 
+// One object of a midas_object_set as the front of a batch frame reads it (k_front_small_objects): everything
+// launch_front_small_batch and fill_particle_update take from the codebook and the two tree handles, and the poses the drift
+// re-projection gathers from.  Lives in device memory; a workgroup reads its row's record through a uniform address.
+namespace midas {
+struct ObjectRecord {
+    TreeView<Kd6> t6;
+    TreeView<Kd3> t3;
+    const MeshRec* vlist;   // nullable, as ParticleUpdateArgs::vlist
+    const MeshScr* vscr;
+    MeshField field;
+    const float* emb;
+    const double* norms;
+    int64_t K;
+    const float* cb_poses;  // [K x 16]
+};
+}  // namespace midas
+
+struct midas_object_set {
+    midas_ctx* ctx;
+    int32_t n_obj, B, D;
+    int64_t K_max;
+    void* dev;                           // one allocation: the records, the poses table, the row map
+    const midas::ObjectRecord* recs;     // [n_obj]
+    const float* const* cb_poses_rows;   // [B] row b's codebook poses
+    const int32_t* row_object;           // [B]
+    const float* cb_poses_row0;          // (host copy of cb_poses_rows[0])
+};
+
 // ---- error helpers ----------------------------------------------------------------------------
 int midas_set_error(midas_ctx* ctx, int code, const char* what, const char* detail);
 
@@ -388,6 +416,10 @@ int launch_particle_update(midas_ctx* ctx, const midas_tree* t6, const midas_tre
 // LOOP_CTL_I entries apart
 int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t3, const ParticleUpdateArgs& a,
                              const midas_codebook* cb, const double* code, double* scores, int32_t B, bool wide = false);
+// the same for rows on different objects (midas_loop_step_batch_objects, k_front_small_objects): `a` without the trees, the vertex
+// lists, the field and the codebook - every workgroup takes those from its row's record of the set; scores and stamps (B, K_max)
+int launch_front_small_objects(midas_ctx* ctx, const midas_object_set* set, const ParticleUpdateArgs& a, const double* code,
+                               double* scores, bool wide);
 // One launch of a front as launch_frame_front hands it to the units that hold the kernels, and the form of k_frame_front it asks
 // for (the template's LAZY, FW, SCR, PREF, STATS: front_wave.hpp).  A family's launcher launches the form if it is one of its own
 // and says whether it was.
@@ -596,10 +628,10 @@ constexpr int ESTIMATE_PART_DOUBLES = 36;  // doubles of one 256-particle block'
 int launch_shard_estimate_moments(midas_ctx* ctx, int64_t N, const float* poses, const double* w64, double* part);
 int launch_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* part_all, float* center, float* stds);
 
-struct LoopWeightsArgs;  // loop_weights.hpp
+struct LoopWeightsRowsArgs;  // loop_weights.hpp
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop_weights.hip)
+                        const LoopWeightsRowsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop_weights.hip)
                         int32_t B = 1);  // trajectories (grid.y): every array (B, ...) contiguous, the scratch ones included
 
 // loop.hip / dbscan.hip - the reference's whole loop body on a variable-size particle set (midas_loop_step)
@@ -608,6 +640,9 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                            const midas_loop_args& a, int32_t phases, int32_t B, int64_t log_stride,
                            bool wide = false);  // midas_loop_step_batch_wide: capacities beyond the small-set regime
+// the same frame with every row on the object the set names for it (midas_loop_step_batch_objects): set->B rows
+int launch_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args& a, int32_t phases,
+                                   int64_t log_stride, bool wide);
 
 // The phases of a loop frame, what launch_loop_step and launch_loop_step_batch launch alike: each is the host launcher of the unit
 // that holds its kernels.  What they are launched over - the single call: one trajectory, the slice strides 0 (the kernels' defaults).
@@ -625,7 +660,10 @@ struct LoopGrid {
 inline int32_t loop_bound(int64_t n) { return (int32_t)(n < (1 << 30) ? n : (1 << 30)); }  // a particle bound as the kernels take it
 // loop_weights.hip - FRONT, second half: k_loop_xe, then the weights - launched, or (merged) left in `wa` for the cluster-moment launch
 bool loop_weights_mergeable(int32_t phases);
-int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t K, bool rmse, bool merged, LoopWeightsArgs& wa);
+// (objects: rows on different objects - K is then the set's K_max, the stride of the score rows and k_loop_xe's clamp, and the drift
+// re-projection gathers row b's poses from the set's table)
+int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t K, bool rmse, bool merged, LoopWeightsRowsArgs& wa,
+                       const midas_object_set* objects = nullptr);
 // anneal.hip - ANNEAL behind the clusters' moments (loop_cluster_phase, loop.hip): the decision and the annealed set as an index list
 struct LoopMoments { float *cen, *sd; int64_t* cnt; double* rot; };
 enum class LoopAnneal {

@@ -150,6 +150,32 @@ class Tree:
             pass
 
 
+class ObjectSet:
+    """midas_object_set handle: the objects the rows of one batch frame stand on (BatchLoopEngine.for_objects).  objects: per object
+    its `codebook`, `tree6` (with `tree3`'s vertex lists attached), `tree3` and float32 `cb_poses` on the device; row_object: the
+    object of every row.  The handles are kept alive with the set."""
+
+    def __init__(self, ctx, objects, row_object):
+        self.ctx, self.objects, n, B = ctx, list(objects), len(objects), len(row_object)
+        arr = lambda hs: (C.c_void_p * n)(*[h.value if isinstance(h, C.c_void_p) else h for h in hs])  # noqa: E731
+        cbs, t6s, t3s = (arr([getattr(o, k).h for o in self.objects]) for k in ("codebook", "tree6", "tree3"))
+        poses = arr([o.cb_poses.data_ptr() for o in self.objects])
+        rows = (C.c_int32 * B)(*[int(i) for i in row_object])
+        h = C.c_void_p()
+        ctx.call("midas_object_set_create", n, cbs, t6s, t3s, poses, B, rows, C.byref(h))
+        self.h = h
+
+    def __del__(self, _finalizing=sys.is_finalizing):  # pragma: no cover  # (bound at import: module globals are gone by then)
+        if _finalizing():
+            return
+        try:
+            if self.h:
+                self.ctx.lib.midas_object_set_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
 def se3_feature(poses: torch.Tensor, w: float = 0.01) -> torch.Tensor:
     """R3_SE3 (tactile_tree/tactile_tree.py:73-77)."""
     poses = _poses(poses)

@@ -16,7 +16,16 @@ One JSON line per engine form with each figure's median over the repeats and [mi
   LoopEngine frames; --floor=N: annealing's floor (default 1000).  The fixed-N form is left out.
 --dbscan serial|batched: the batch engine's DBSCAN frame as B passes one after the other (batched_dbscan=False) or as the one batched pass
   (batched_dbscan=True; B x N0 <= 2^20); default: the engine's own choice (batched whenever it fits).
---profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch), no timing."""
+--objects G: the rows stand on G synthetic objects (K, D as above; row b on object b G // B, an object's rows side by side) - BatchLoopEngine.for_objects, one launch set
+  for the mixed batch (midas_loop_step_batch_objects).  Forms, each selectable alone with --form=NAME (a process per form, to alternate):
+  objects_mixed   the for_objects engine, B rows over the G objects per frame
+  objects_split   how a sweep over objects ran before: G plain BatchLoopEngines of the rows of one object each (B / G), stepped one
+                  after the other - a frame is all G steps; engine i is seeded with its first row's key, so every row replays its row of
+                  the mixed batch (compare n_final_min / n_final_max).  It uses the plain constructor only: to take the figure on an
+                  earlier commit, copy this file into that checkout's tools/ and run it there with --form=objects_split
+  single_object   one plain BatchLoopEngine of the same B with every row on object 0 (what G codebooks cost beside one)
+--profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch, with --objects the mixed
+  batch, with --form=NAME that form), no timing."""
 import json
 import os
 import statistics
@@ -36,7 +45,15 @@ args = sys.argv[1:]
 if "--dbscan" in args:  # `--dbscan VALUE`: taken out with its value, so that the value is no positional argument
     i = args.index("--dbscan")
     args[i:i + 2] = ["--dbscan=" + (args[i + 1] if i + 1 < len(args) else "")]
+G, FORM = 0, None
+if "--objects" in args:  # `--objects G`, as --dbscan
+    i = args.index("--objects")
+    args[i:i + 2] = ["--objects=" + (args[i + 1] if i + 1 < len(args) else "")]
 for a in args:
+    if a.startswith("--objects="):
+        G = int(a.split("=", 1)[1])
+    if a.startswith("--form="):
+        FORM = a.split("=", 1)[1]
     if a.startswith("--dbscan="):
         if a.split("=", 1)[1] not in ("serial", "batched"):
             sys.exit("bench_batch_loop.py: --dbscan serial|batched")
@@ -50,13 +67,17 @@ if wide and seeded:
 for a in sys.argv[1:]:
     if a.startswith("--floor="):
         FLOOR = int(a.split("=", 1)[1])
+if G and (seeded or G < 1 or G > B):
+    sys.exit("bench_batch_loop.py: --objects G with 1 <= G <= B, Philox draws")
 dev = torch.device("cuda", 0)
-cb = make_codebook(K=K, D=D, seed=1000)
-trajs = [make_trajectory(cb, T=T + 1, seed=2000 + b) for b in range(B)]
+NAMES = ("004_sugar_box", "035_power_drill", "025_mug", "cotter-pin")
+cbs = [make_codebook(NAMES[i % len(NAMES)], K=K, D=D, seed=1000 + i) for i in range(max(G, 1))]
+cb, ROW_OBJ = cbs[0], [b * max(G, 1) // B for b in range(B)]  # (an object's rows side by side: a plain engine seeded with the first replays them)
+trajs = [make_trajectory(cbs[ROW_OBJ[b]], T=T + 1, seed=2000 + b) for b in range(B)]
 odoms = torch.as_tensor(np.stack([tr.odoms for tr in trajs], axis=1)).to(dev)            # (T + 1, B, 4, 4)
 codes = torch.as_tensor(np.stack([tr.codes for tr in trajs], axis=1)).to(dev)            # (T + 1, B, D)
 gts = torch.as_tensor(np.stack([tr.gt_poses for tr in trajs], axis=1)).to(dev, torch.float32)
-starts = torch.as_tensor(np.stack([wide_start(cb.extents, trajs[b].gt_poses[0], N0, 3000 + b) for b in range(B)])).to(dev, torch.float32)
+starts = torch.as_tensor(np.stack([wide_start(cbs[ROW_OBJ[b]].extents, trajs[b].gt_poses[0], N0, 3000 + b) for b in range(B)])).to(dev, torch.float32)
 kw = dict(floor=FLOOR, cluster_every=EVERY, device=dev)
 
 
@@ -114,6 +135,49 @@ def run_fixed():
     return ms, {}
 
 
+def triple(c):
+    return (c.poses, c.embeddings, c.mesh_vertices)
+
+
+def run_objects_mixed():
+    eng = BatchLoopEngine.for_objects([triple(c) for c in cbs], ROW_OBJ, N0, seed=SEED, batched_dbscan=DBSCAN, **kw, **({"wide": True} if wide else {}))
+    eng.set_particles(starts)
+    eng.project_to_codebook()
+    ms = timed(lambda t: eng.step(odoms[t + 1], codes[t + 1], gts=gts[t + 1]), T)
+    n = eng.n
+    return ms, {"n_final_min": min(n), "n_final_max": max(n)}
+
+
+def run_objects_split():
+    rows = [torch.as_tensor([b for b in range(B) if ROW_OBJ[b] == i], device=dev) for i in range(G)]
+    # (engine i's row j is row rows[i][0] + j of the mixed batch: the same Philox key, the same trajectory, the same live counts)
+    engs = [BatchLoopEngine(*triple(cbs[i]), len(rows[i]), N0, seed=SEED + int(rows[i][0]), batched_dbscan=DBSCAN, **kw, **({"wide": True} if wide else {}))
+            for i in range(G)]
+    ops = [(odoms[:, r].contiguous(), codes[:, r].contiguous(), gts[:, r].contiguous()) for r in rows]
+    for e, r in zip(engs, rows):
+        e.set_particles(starts[r])
+        e.project_to_codebook()
+
+    def step(t):
+        for e, (o, c, g) in zip(engs, ops):
+            e.step(o[t + 1], c[t + 1], gts=g[t + 1])
+    ms = timed(step, T)
+    n = [v for e in engs for v in e.n]
+    return ms, {"n_final_min": min(n), "n_final_max": max(n), "engines": G}
+
+
+def run_single_object():
+    tr = [make_trajectory(cb, T=T + 1, seed=2000 + b) for b in range(B)]
+    o, c, g = (torch.as_tensor(np.stack([getattr(x, k) for x in tr], axis=1)).to(dev) for k in ("odoms", "codes", "gt_poses"))
+    st = torch.as_tensor(np.stack([wide_start(cb.extents, tr[b].gt_poses[0], N0, 3000 + b) for b in range(B)])).to(dev, torch.float32)
+    eng = BatchLoopEngine(*triple(cb), B, N0, seed=SEED, batched_dbscan=DBSCAN, **kw, **({"wide": True} if wide else {}))
+    eng.set_particles(st)
+    eng.project_to_codebook()
+    ms = timed(lambda t: eng.step(o[t + 1], c[t + 1], gts=g[t + 1].float()), T)
+    n = eng.n
+    return ms, {"n_final_min": min(n), "n_final_max": max(n)}
+
+
 def run_batch_seeded():
     return run_batch([SEED + b for b in range(B)])
 
@@ -122,19 +186,24 @@ def run_single_seeded():
     return run_single(SEED)
 
 
-if profile:
-    (run_batch_seeded if seeded else run_batch)()
-    torch.cuda.synchronize()
-    sys.exit(0)
-
 head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R, **({"wide": True} if wide else {}),
-        **({} if DBSCAN is None else {"dbscan": "batched" if DBSCAN else "serial"})}
+        **({} if DBSCAN is None else {"dbscan": "batched" if DBSCAN else "serial"}), **({"objects": G} if G else {})}
 out = {}
 forms = (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed))
 if wide:
     forms = forms[:2]
 if seeded:
     forms = (("batch_loop_seeded", run_batch_seeded), ("single_loop_seeded", run_single_seeded), ("batch_loop", run_batch))
+if G:
+    forms = (("objects_mixed", run_objects_mixed), ("objects_split", run_objects_split), ("single_object", run_single_object))
+if FORM is not None:
+    forms = tuple(f for f in forms if f[0] == FORM)
+    if not forms:
+        sys.exit(f"bench_batch_loop.py: no form {FORM!r} in this mode")
+if profile:  # (the first form: the batch engine of the mode, or the one --form names)
+    forms[0][1]()
+    torch.cuda.synchronize()
+    sys.exit(0)
 for name, run in forms:
     run()  # warm-up: code objects, scratch, allocator
     rows, extra = [], {}
@@ -143,6 +212,12 @@ for name, run in forms:
         rows.append(summary(ms))
     out[name] = over_repeats(rows)
     print(json.dumps({"form": name, **head, **out[name], **extra, "per_repeat": rows}), flush=True)
+if G and FORM is None:
+    mixed, split, one_obj = (out[k]["frame_median_us"]["median"] for k in ("objects_mixed", "objects_split", "single_object"))
+    print(json.dumps({"form": "comparison_objects", **head, "mixed_frame_us": mixed, "split_frame_us": split, "single_object_frame_us": one_obj,
+                      "split_over_mixed": round(split / mixed, 3), "mixed_over_single_object": round(mixed / one_obj, 3)}), flush=True)
+if G or FORM is not None:
+    sys.exit(0)
 one, batch = (out["single_loop_seeded"], out["batch_loop_seeded"]) if seeded else (out["single_loop"], out["batch_loop"])
 print(json.dumps({"form": "comparison_seeded" if seeded else "comparison", **head,
                   "B_single_frames_us": round(B * one["frame_median_us"]["median"], 1),
