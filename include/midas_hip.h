@@ -1064,6 +1064,27 @@ int midas_object_set_destroy(midas_object_set* set);
  * as in midas_loop_step_batch: row b holds, frame for frame, the bits of midas_loop_step on object row_object[b] with seed + b. */
 int midas_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args* args, int32_t phases, int32_t B,
                                   int64_t log_stride, int32_t wide);
+/* particle_filter.init_filter (modules/particle_filter.py:129-145, called from filter/filter.py:156-158 on every frame seen while
+ * prev_idx == 0) for B rows in one launch: slots [0, n_host[b]) of poses_dev[b] (B x cap x 16 float32, 16-byte aligned) :=
+ * gt16_dev[b] @ [R | t], the slots behind are left alone.  R is scipy's extrinsic from_euler("zyx", rot, degrees=True) - the float32
+ * degrees widened to float64, R = Rx(rot[2]) Ry(rot[1]) Rz(rot[0]) in float64, rounded to float32 as the reference's float32 Tn
+ * stores it - and the product is float32.  sig_dev (B x 2 float32): row b's init_noise, {translation sigma in metres, rotation sigma
+ * in degrees} (particle_filter.py:124-127: the first depends on the row's mesh).  n_host: host array of B counts, 1 <= n_b <= cap.
+ * tn_dev / rot_dev (both or neither; B x cap x 3 float32, already scaled): the caller's draws; NULL: Philox normals keyed seed + b,
+ * slot keys from 0, scaled as midas_propagate scales its noise, at the step word 0xFFFFFFFF - draw - frames count their step words
+ * up from 0, so `draw` (the caller's count of starts so far) never meets one, and a second start draws fresh numbers as the
+ * reference's second init_filter does.  Reads nothing back; MIDAS_ERR_INVALID enqueues nothing. */
+int midas_init_particles_batch(midas_ctx* ctx, int32_t B, int64_t cap, const int32_t* n_host, const float* gt16_dev,
+                               const float* sig_dev, uint64_t seed, uint32_t draw, const float* tn_dev, const float* rot_dev,
+                               float* poses_dev);
+/* particles.poses, _, _ = codebook.SE3_NN(particles.poses) behind init_filter (filter/filter.py:159-160) for B rows in one launch:
+ * slots [0, n_host[b]) of poses_dev[b] (in place) := the codebook pose nearest to each, hint_out_dev[b] (B x cap int32) := its
+ * index - bit for bit midas_gather_rows(cb_poses, midas_nn6(tree6, midas_se3_feature(poses, 0.01))) on the row's slice.  set: every
+ * row on its own object (cb, tree6 and cb_poses_dev are then not read; B == the set's); NULL: every row on cb / tree6 /
+ * cb_poses_dev (K x 16 float32, 16-byte aligned).  Reads nothing back; MIDAS_ERR_INVALID enqueues nothing. */
+int midas_project_batch(midas_ctx* ctx, const midas_object_set* set, const midas_codebook* cb, const midas_tree* tree6,
+                        const float* cb_poses_dev, int32_t B, int64_t cap, const int32_t* n_host, float* poses_dev,
+                        int32_t* hint_out_dev);
 /* cluster_particles(method="euclidean") alone (particle_filter.py:208-217): labels_dev[i] = DBSCAN label of pose i's
  * translation, eps as given, min_samples < 0 -> N / 5.  Exact float64 predicate |dx|^2 <= eps^2, clusters numbered by their
  * first core point, border points to the smallest adjacent cluster - what sklearn's DBSCAN returns.  Any extent (dense cell grid

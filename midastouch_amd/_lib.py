@@ -293,6 +293,8 @@ SIGNATURES = {
     "midas_object_set_create": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, C.POINTER(_P)]),
     "midas_object_set_destroy": (C.c_int, [_P]),
     "midas_loop_step_batch_objects": (C.c_int, [_P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64, _I32]),
+    "midas_init_particles_batch": (C.c_int, [_P, _I32, _I64, _P, _P, _P, _U64, C.c_uint32, _P, _P, _P]),
+    "midas_project_batch": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _P, _P, _P]),
     "midas_dbscan": (C.c_int, [_P, _I64, _P, _D, _I64, _P, _P]),
     "midas_dbscan_batch": (C.c_int, [_P, _I32, _I64, _P, _I64, _P, _D, _I64, _P, _P, _I32]),
     "midas_dbscan_points": (C.c_int, [_P, _I64, C.c_int32, _P, _D, _I64, _P, _P]),

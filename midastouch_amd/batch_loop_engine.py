@@ -116,6 +116,7 @@ class BatchLoopEngine(_LoopBase):
         self._alloc_state((B,), self._topk_ties)
         self._args.dbscan_batched = int(self.batched_dbscan)
         self.torch_streams = None  # seed_torch_streams
+        self._std_override = None  # set for the length of one step_still() only
         # The scratch every phase combination of a batch frame asks for, reserved now so that no frame allocates: per trajectory the
         # hand-over records of the front (32 B a particle), the block results, the cluster-moment partials (64 x 36 doubles per 256
         # particles) and cluster rows, the resample's prefix values, a wide engine's select state; once, DBSCAN's cell tables (84 MB +
@@ -286,10 +287,11 @@ class BatchLoopEngine(_LoopBase):
     # ---- one batch frame ------------------------------------------------------------------------------------------
     def step(self, odoms, codes, gts=None, u32=-1.0, multiplier: float = 1.0, dbscan=None, unit_weights: bool = False):
         """Enqueues one frame of every trajectory and reads nothing back: odoms (B,4,4), codes (B,D), gts (B,4,4) or None.
-        dbscan: None = on every `cluster_every`-th frame (filter.py:182), True / False to force - for all trajectories alike."""
+        dbscan: None = on every `cluster_every`-th frame (filter.py:182), True / False to force - for all trajectories alike.
+        A frame with another motion noise than multiplier x (sig_t, sig_r) - LoopEngine.step's `std_override` - is `step_still`."""
         phases = self._phase_mask(ALL_PHASES, dbscan)
         odoms, codes, gts = frame_operands(self.device, (self.B,), self.D, odoms, codes, gts)
-        a = self._frame_scalars(u32, multiplier, unit_weights)
+        a = self._frame_scalars(u32, multiplier, unit_weights, self._std_override)
         a.odom16, a.code, a.gt16 = _ptr(odoms), _ptr(codes), _ptr(gts)
         a.part_rmse = _ptr(self._part_rmse) if gts is not None else None
         self._keep = (odoms, codes, gts)  # keep operands alive until the stream has consumed them
@@ -322,6 +324,16 @@ class BatchLoopEngine(_LoopBase):
         else:
             call(self.ctx.lib.midas_loop_step_batch, phases)
         self._frame_done()
+
+    def step_still(self, odoms, codes, gts=None, std_override=(0.0, 0.0), **kw):
+        """`step()` with this one frame's motion noise (std_t, std_r) in place of multiplier x (sig_t, sig_r), shared by the rows, as
+        LoopEngine.step(std_override=...) - by default (0.0, 0.0): the frames the reference starts from, where it does not call
+        motionModel (filter/filter.py:152-160).  The override holds for this call alone, also when the call raises."""
+        self._std_override = (float(std_override[0]), float(std_override[1]))
+        try:
+            self.step(odoms, codes, gts, **kw)
+        finally:
+            self._std_override = None
 
     # ---- results --------------------------------------------------------------------------------------------------
     def read_log(self, first: int = 0, last: int = None, strict: bool = True, rows=None):

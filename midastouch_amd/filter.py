@@ -39,6 +39,7 @@ class Sequence:
     mesh_vertices: np.ndarray
     obj_model: str
     mesh_tree: Optional[object] = None  # an ops.Tree over mesh_vertices already on the device (shared with other engines)
+    log_id: Optional[object] = None     # the log's number in `filter_stats` (None: cfg.expt.log_id)
 
 
 def synthetic_sequence(cfg, device, T: int = 100, D: Optional[int] = None, seed: int = 0) -> Sequence:
@@ -91,9 +92,16 @@ def step(engine: FilterEngine, odom: torch.Tensor, tactile_code: torch.Tensor, g
 
 
 # ---- the reference loop -----------------------------------------------------------------------------
+def _log_id(seq, expt_cfg) -> str:
+    """`filter_stats["log_id"]` (filter.py:114): the sequence's own number when it carries one, the config's otherwise."""
+    own = getattr(seq, "log_id", None)
+    return str(expt_cfg.log_id if own is None else own).zfill(2)
+
+
 def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str = "fixed", max_frames: int = None,
            cluster: bool = True, progress: bool = False, softmax: bool = True, update_freq: int = 1, floor: int = 1000,
-           results_path: Optional[str] = None, draws: str = "device", seed: int = 4000) -> dict:
+           results_path: Optional[str] = None, draws: str = "device", seed: int = 4000, start: str = "host",
+           cluster_every: int = 50) -> dict:
     """Run the filter over a sequence; returns the reference's `filter_stats` dict (filter.py:99-116).
 
     The loop body (filter.py:150-190: motionModel -> particle_rmse -> SE3_NN + get_similarity -> remove_invalid_particles
@@ -118,6 +126,10 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
     The defaults are `filter/filter.py`'s; `filter_real(...)` presets the real-data script's variations
     (`filter/filter_real.py`: raw scores :208-210, measurement update every `update_freq`-th frame with unit weights in
     between :205-212, annealing floor 10000 :228).  results_path: directory `filter_stats.npy` is written to (:252).
+    start="host" (default): the frames seen while prev_idx == 0 start as the reference does - `init_filter` on the host (torch.normal,
+    scipy's Euler conversion), an upload and the projection.  start="device": `LoopEngine.start` - the same arithmetic in two
+    launches, the draws from Philox (draws="device" only); what `filter_sweep` does for every row, so the single-run yardstick of a
+    sweep.  cluster_every: DBSCAN on every cluster_every-th frame (50: filter.py:182).
     """
     from . import _lib
     from .loop_engine import LoopEngine
@@ -125,6 +137,11 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if draws not in ("device", "host", "seeded"):
         raise ValueError("draws must be 'device', 'host' or 'seeded'")
+    if start not in ("host", "device"):
+        raise ValueError("start must be 'host' or 'device'")
+    if start == "device" and draws != "device":
+        raise ValueError("start='device' draws the initial particles from Philox: draws='device' only")
+    cluster_every = max(int(cluster_every), 1)
     expt_cfg = cfg.expt
     init_particles = int(expt_cfg.params.num_particles)
     noise_ratio = expt_cfg.params.noise_ratio
@@ -164,7 +181,7 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
         "rmse_t": [], "rmse_r": [], "time": [], "traj_size": traj_size, "avg_time": None, "total_time": 0,
         "cluster_poses": [], "cluster_stds": [], "obj_name": seq.obj_model, "tree_size": len(codebook),
         "noise_ratio": noise_ratio, "init_noise": pf.init_noise, "init_particles": init_particles,
-        "num_particles": [], "log_id": str(expt_cfg.log_id).zfill(2), "trial_id": 0,
+        "num_particles": [], "log_id": _log_id(seq, expt_cfg), "trial_id": 0,
     }
     motion_time = []
     events = [torch.cuda.Event(enable_timing=True)]
@@ -187,18 +204,21 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
             if count and count % eng.log_frames == 0:
                 # wall-clock pace on a fast host repeats frames: more iterations than the engine's frame log (a ring) holds
                 records.extend(eng.read_log(count - eng.log_frames, count))
-            start = time.time()
+            t_start = time.time()  # (the reference's `start`; here that name is the parameter)
             moving = prev_idx > 0
             if not moving:  # (filter.py:152,156-160) - like the reference, frames seen while prev_idx == 0 re-initialise
-                stream_to(False)  # init_filter draws on the host generator
-                particles = pf.init_filter(gt_p[idx, :], init_particles)
-                eng.set_particles(particles.poses, reset_annealing=count == 0)
-                eng.project_to_codebook()
+                if start == "device":
+                    eng.start(gt_p[idx, :], pf.init_noise, n=init_particles, reset_annealing=count == 0)
+                else:
+                    stream_to(False)  # init_filter draws on the host generator
+                    particles = pf.init_filter(gt_p[idx, :], init_particles)
+                    eng.set_particles(particles.poses, reset_annealing=count == 0)
+                    eng.project_to_codebook()
                 odom = eye
             else:
                 odom = step_odoms[prev_idx] if idx == prev_idx + 1 else inv_meas[prev_idx] @ meas_p[idx, :]
             unit = count % max(int(update_freq), 1) != 0  # filter_real.py:205-212: no measurement update on this frame
-            kw = dict(gt=gt_p[idx, :], dbscan=cluster and count % 50 == 0, unit_weights=unit, std_override=None if moving else (0.0, 0.0))
+            kw = dict(gt=gt_p[idx, :], dbscan=cluster and count % cluster_every == 0, unit_weights=unit, std_override=None if moving else (0.0, 0.0))
             if draws == "host":
                 n = eng.n
                 if moving:  # add_noise_to_odom's draws, its order (:326-335); the initial frames draw inside init_filter
@@ -224,7 +244,7 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
             events.append(ev)
             if every_frame:
                 ev.synchronize()
-                total_time += events[-2].elapsed_time(ev) * 1e-3 if pace != "wallclock" else time.time() - start
+                total_time += events[-2].elapsed_time(ev) * 1e-3 if pace != "wallclock" else time.time() - t_start
             if viz is not None:
                 heatmap_weights = pf.get_similarity(seq.codes[idx][None], heatmap_embeddings, softmax=False)
                 rec = eng.frame_view()
@@ -236,7 +256,7 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
                 rec = eng.read_log(count, count + 1)[0]
                 print(f"[{idx}] RMSE {1000 * rec['rmse_t']:.1f} mm {rec['rmse_r']:.0f} deg P {rec['n_after']} "
                       f"rate {1.0 / max(events[-2].elapsed_time(ev) * 1e-3, 1e-9):.1f} Hz")
-            motion_time.append(time.time() - start)
+            motion_time.append(time.time() - t_start)
             frame_idx.append(idx)
             prev_idx = idx
             count += 1
@@ -283,6 +303,160 @@ def filter_real(cfg, seq: Optional[Sequence] = None, **kw) -> dict:
     kw.setdefault("softmax", False)
     kw.setdefault("floor", 10000)
     return filter(cfg, seq, **kw)
+
+
+# ---- the reference's experiment: objects x logs x trials (bash/run_filter.sh) as one batch -----------------------------------------
+def sweep_plan(runs, trials: int = 1, max_length=None, max_frames=None) -> dict:
+    """Rows of a sweep, on the host: runs that share one `codebook` object are one object of the batch (in order of first
+    appearance), row r * trials + k is run r, trial k.  -> objects (for each object the index of its first run), run_object,
+    row_object, row_run, row_trial, run_lengths and lengths (frames of every run and of every row: the log's, cut by max_length -
+    cfg.expt.max_length - and max_frames) and T_max."""
+    runs = list(runs)
+    if not runs:
+        raise ValueError("filter_sweep needs at least one run")
+    if int(trials) < 1:
+        raise ValueError(f"filter_sweep needs trials >= 1, got {trials}")
+    trials = int(trials)
+    seen, objects, run_object = {}, [], []
+    for r, seq in enumerate(runs):
+        key = id(seq.codebook)
+        if key not in seen:
+            seen[key] = len(objects)
+            objects.append(r)
+        run_object.append(seen[key])
+    run_len = []
+    for seq in runs:
+        T = int(seq.gt_p.shape[0])
+        if max_length not in (None, "None"):
+            T = min(T, int(max_length))
+        if max_frames is not None:
+            T = min(T, int(max_frames))
+        run_len.append(T)
+    row_run = [r for r in range(len(runs)) for _ in range(trials)]
+    row_trial = [k for _ in range(len(runs)) for k in range(trials)]
+    lengths = [run_len[r] for r in row_run]
+    return dict(objects=objects, run_object=run_object, row_object=[run_object[r] for r in row_run], row_run=row_run,
+                row_trial=row_trial, run_lengths=run_len, lengths=lengths, T_max=max(lengths))
+
+
+def sweep_stats(records, times, host_times, **fixed) -> dict:
+    """One row's `filter_stats` (filter.py:99-116, the keys `filter` returns) from its frame-log records and the batch frames'
+    periods - both cut to the row's own frames by the caller; fixed: the entries that do not depend on the frames."""
+    n = len(records)
+    times, host_times = [float(t) for t in times[:n]], [float(t) for t in host_times[:n]]
+    stats = dict(fixed)
+    stats.update(rmse_t=[rec["rmse_t"] for rec in records], rmse_r=[rec["rmse_r"] for rec in records], time=times,
+                 cluster_poses=[torch.as_tensor(rec["cluster_poses"]) for rec in records],
+                 cluster_stds=[torch.as_tensor(rec["cluster_stds"]) for rec in records],
+                 num_particles=[rec["n_after"] for rec in records], traj_size=n)
+    stats["total_time"] = sum(times)
+    stats["avg_time"] = stats["total_time"] / max(n, 1)
+    stats["avg_timer"] = {"tactile": 0.0, "motion": 0.0, "meas": stats["avg_time"],
+                          "host_enqueue": float(np.average(host_times)) if host_times else 0.0}
+    stats["frames"], stats["frame_idx"], stats["host_time"] = records, list(range(n)), host_times
+    return stats
+
+
+def sweep_inputs(runs, plan, device):
+    """The frames of every row, time-major and built once - (T_max, B, 4, 4) odometry, (T_max, B, D) tactile codes, (T_max, B, 4, 4)
+    ground truth - so that a frame's operands are slices.  Odometry is `filter`'s: identity on the frames the filter starts from,
+    inv(meas[t-1]) @ meas[t] behind them.  A row whose log has ended goes on with identity odometry, its last code and its last gt."""
+    T_max, per_run = plan["T_max"], []
+    for seq, T in zip(runs, plan["run_lengths"]):
+        meas_p = seq.meas_p.to(device)
+        odom = torch.eye(4, device=device).repeat(T_max, 1, 1)
+        if T > 2:  # (exactly filter()'s products: the whole log's, then cut)
+            odom[2:T] = torch.matmul(torch.linalg.inv(meas_p)[:-1], meas_p[1:])[1:T - 1]
+        last = torch.full((T_max - T,), T - 1, dtype=torch.long, device=device)
+        pick = torch.cat([torch.arange(T, device=device), last])
+        per_run.append((odom, seq.codes.to(device, torch.float64)[pick], seq.gt_p.to(device, torch.float32)[pick]))
+    rows = plan["row_run"]
+    return tuple(torch.stack([per_run[r][i] for r in rows], dim=1).contiguous() for i in range(3))
+
+
+def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, max_frames: int = None, cluster: bool = True,
+                 cluster_every: int = 50, softmax: bool = True, update_freq: int = 1, floor: int = 1000,
+                 results_root: Optional[str] = None, draws: str = "device") -> list:
+    """The reference's experiment - `bash/run_filter.sh`: objects x logs x trials, one `filter/filter.py` process each - as ONE batch
+    on the device: every (run, trial) is a row of a `BatchLoopEngine.for_objects`, a frame of all rows is one `step()`.
+
+    runs: a list of `Sequence`; runs that share one `codebook` object stand on one object of the batch.  Row r * trials + k is run r,
+    trial k, on the Philox streams of seed + row: it holds, frame for frame, what `filter(cfg, runs[r], seed=seed + row,
+    start="device", ...)` computes.  Pace is fixed: frame t of every row is frame t of its log.  Rows start on the device on the frames
+    seen while prev_idx == 0 (frames 0 and 1, filter.py:152-160; `BatchLoopEngine.start`); DBSCAN runs on every cluster_every-th
+    frame, the measurement update on every update_freq-th (unit weights in between, filter_real.py:205-212).  Logs of different
+    lengths: a row whose log has ended is stepped on (identity odometry, its last code and gt) and its surplus frames are never read
+    - not their results, not their condition bits; a condition inside a row's own frames raises as in `filter`.
+    -> one `filter_stats` dict per row (`filter`'s keys; `time` is the batch frame's period on the device's clock) with
+    `batch_rows`, `trial_id` = k and `log_id` = the run's `Sequence.log_id` (None: cfg.expt.log_id); with results_root each is saved to
+    `<results_root>/<obj>/<log>/trial_<kk>/filter_stats.npy` (filter.py:252).
+    draws: "device" only - a seeded sweep would need one host generator per row through `init_filter`."""
+    import gc
+    import os
+
+    from . import _lib
+    from .batch_loop_engine import BatchLoopEngine
+    from .loop_engine import log_records
+
+    if draws != "device":
+        raise ValueError(f"filter_sweep draws on the device (draws='device'), not {draws!r}: a seeded sweep needs a host generator "
+                         "per row through init_filter, which is out of its scope - run filter(draws='seeded') per row")
+    expt_cfg = cfg.expt
+    runs = list(runs)
+    plan = sweep_plan(runs, trials, expt_cfg.max_length, max_frames)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    init_particles = int(expt_cfg.params.num_particles)
+    noise_ratio = expt_cfg.params.noise_ratio
+    cluster_every, update_freq = max(int(cluster_every), 1), max(int(update_freq), 1)
+    B, T_max = len(plan["row_run"]), plan["T_max"]
+
+    pfs = []
+    for r in plan["objects"]:  # one particle_filter per object: init_noise (the mesh's diagonal), pen_max, the mesh tree
+        pf = particle_filter(cfg, runs[r].mesh_vertices, noise_ratio, downsample=1, device=device)
+        if runs[r].mesh_tree is not None:
+            pf._mesh_tree = runs[r].mesh_tree
+        pfs.append(pf)
+    eng = BatchLoopEngine.for_objects([(runs[r].codebook, None, pf.mesh_kdtree) for r, pf in zip(plan["objects"], pfs)],
+                                      plan["row_object"], init_particles, sig_t=pfs[0].motion_noise["sig_t"],
+                                      sig_r=pfs[0].motion_noise["sig_r"], pen_max=pfs[0].pen_max, seed=seed, softmax=softmax, floor=floor,
+                                      cluster=cluster, cluster_every=cluster_every, log_frames=max(T_max + 8, 64), device=device,
+                                      wide=init_particles > _lib.LOOP_BATCH_MAX_CAP)
+    odoms, codes, gts = sweep_inputs(runs, plan, device)
+    init_noise = torch.tensor([pfs[i].init_noise for i in plan["row_object"]], dtype=torch.float32, device=device)
+
+    events = [torch.cuda.Event(enable_timing=True)]
+    host_times = []
+    gc.collect()
+    gc.freeze()  # (as in filter)
+    try:
+        events[0].record()
+        for t in range(T_max):
+            t0 = time.time()
+            starting = t < 2  # prev_idx == 0 (filter.py:152): frames 0 and 1 re-initialise
+            if starting:
+                eng.start(gts[t], init_noise, n=init_particles, reset_annealing=t == 0)
+            # (the reference does not call motionModel on the starting frames: no motion noise there)
+            (eng.step_still if starting else eng.step)(odoms[t], codes[t], gts=gts[t], dbscan=cluster and t % cluster_every == 0,
+                                                       unit_weights=t % update_freq != 0)
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            events.append(ev)
+            host_times.append(time.time() - t0)
+        torch.cuda.synchronize(device)
+    finally:
+        gc.unfreeze()
+    times = [e0.elapsed_time(e1) * 1e-3 for e0, e1 in zip(events, events[1:])]
+    log = eng._log.cpu().numpy()  # one read-back; every row is parsed up to its own last frame only
+    out = []
+    for row, (r, k, T) in enumerate(zip(plan["row_run"], plan["row_trial"], plan["lengths"])):
+        seq, pf = runs[r], pfs[plan["row_object"][row]]
+        stats = sweep_stats(log_records(log[row], 0, T, who=f"row {row}, "), times[:T], host_times[:T], obj_name=seq.obj_model,
+                            tree_size=len(seq.codebook), noise_ratio=noise_ratio, init_noise=pf.init_noise,
+                            init_particles=init_particles, log_id=_log_id(seq, expt_cfg), trial_id=k, batch_rows=B)
+        if results_root is not None:
+            save_filter_stats(stats, os.path.join(results_root, str(seq.obj_model), stats["log_id"], f"trial_{k:02d}"))
+        out.append(stats)
+    return out
 
 
 def main(argv=None):

@@ -25,6 +25,7 @@ and frame, the frame's scalars and its completion - is `_LoopBase`, by a lead sh
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 import time
 import warnings
@@ -98,6 +99,7 @@ class _LoopBase:
         self.mode = RESAMPLE_MODES[resample]
         self.log_frames = int(log_frames)
         self.step_count = 0   # frames enqueued (Philox counter, log row)
+        self.starts = 0       # start() calls so far (the step word of a start's draws: 0xFFFFFFFF - starts)
         self._n_host = None   # live count(s) as last known by the host (None: ask the device)
         self._epoch = 0
 
@@ -132,6 +134,59 @@ class _LoopBase:
         ci, cd = annealing_block(self.ctl_i.cpu(), self.ctl_d.cpu(), particle_var, init_particles)
         self.ctl_i.copy_(ci)
         self.ctl_d.copy_(cd)
+
+    def start(self, gts, init_noise, n=None, project: bool = True, tn=None, rot=None, reset_annealing=None):
+        """Start (or restart) every trajectory on the device - `init_filter` and the projection onto the codebook that the reference
+        runs on each frame seen while prev_idx == 0 (filter/filter.py:156-160; particle_filter.py:129-145) - without a host draw, an
+        upload of poses or a read-back: two launches for all rows (`midas_init_particles_batch`, `midas_project_batch`).
+        gts: (4,4), or (B,4,4) for a batch; init_noise: `particle_filter.init_noise` - (sigma_t in metres, sigma_r in degrees), or B
+        such pairs, a row's sigma_t being its object's; n: the live count(s) to start with (None: the capacity).  tn / rot: the
+        caller's draws, lead + (cap, 3) float32 already scaled (both or neither); None: Philox normals keyed (seed + b, 0xFFFFFFFF -
+        starts) - `starts` counts the calls, so a second start draws fresh numbers as the reference's second init_filter does, on a
+        step word no frame uses.  project=False leaves the particles off the codebook (hints -1).
+        Poses, hints, labels 0 and the control blocks come out as `set_particles(poses, reset_annealing=...)` leaves them;
+        reset_annealing None: the engine's first start resets annealing, later ones keep particle_var, init_particles and the frame
+        count (filter/filter.py re-initialises without touching them)."""
+        B = self._lead[0] if self._lead else 1
+        cap, d = self.cap, self.device
+        reset = self.starts == 0 if reset_annealing is None else bool(reset_annealing)
+        ns = [cap] * B if n is None else ([int(n)] * B if isinstance(n, numbers.Integral) else [int(v) for v in n])
+        if len(ns) != B or min(ns) < 1 or max(ns) > cap:
+            raise MidasError(f"start: {B} live counts within 1 .. {cap} expected, got {ns if len(ns) <= 8 else len(ns)}")
+        gts = operand(gts, "gt poses", torch.float32, (B, 4, 4), d)
+        sig = torch.as_tensor(init_noise, dtype=torch.float32).reshape(-1, 2)
+        sig = operand(sig.expand(B, 2) if sig.shape[0] == 1 else sig, "init_noise", torch.float32, (B, 2), d)
+        check_motion_draws(tn, rot)
+        if tn is not None:
+            tn, rot = operand(tn, "tn", torch.float32, (B, cap, 3), d), operand(rot, "rot", torch.float32, (B, cap, 3), d)
+        poses, hint = self._poses.view(B, cap, 4, 4), self._hint.view(B, cap)
+        hint.fill_(-1)
+        self._labels.zero_()
+        ops.init_particles_batch(poses, gts, sig, ns, seed=self.seed, draw=self.starts, tn=tn, rot=rot)
+        if project:
+            if getattr(self, "_set", None) is not None:
+                ops.project_batch(poses, hint, ns, object_set=self._set)
+            else:
+                ops.project_batch(poses, hint, ns, tree6=self.tree6, codebook=self.codebook, cb_poses=self.cb_poses)
+        # particles_block on the device: N = NSET = n, NCL = 1 (label 0 everywhere) and, unless annealing starts over, the INIT,
+        # VARSET and FRAME that stand there; every other word 0
+        ci = torch.zeros_like(self.ctl_i)
+        if reset:
+            self.ctl_d.zero_()
+        else:
+            keep = [_lib.LOOP_I_INIT, _lib.LOOP_I_VARSET, _lib.LOOP_I_FRAME]
+            ci[..., keep] = self.ctl_i[..., keep]
+        n_dev = torch.tensor(ns, dtype=torch.int32).to(d).reshape(self._lead)
+        ci[..., _lib.LOOP_I_N] = n_dev
+        ci[..., _lib.LOOP_I_NSET] = n_dev
+        ci[..., _lib.LOOP_I_NCL] = 1
+        self.ctl_i.copy_(ci)
+        self.starts += 1
+        self._started(ns, reset)
+
+    def _started(self, ns, reset: bool):
+        """The host's bookkeeping behind start()."""
+        self._n_host = ns
 
     def _frame_view(self, rec, b):
         """rec: the log record of the latest completed frame of trajectory b (() for the only one) -> with the views of its arrays."""
@@ -263,6 +318,26 @@ class LoopEngine(_LoopBase):
         torch.cuda.current_stream(self.device).synchronize()  # the control block is in place, nothing older is in flight
         self._mirror[0], self._mirror[1] = int(ci[_lib.LOOP_I_FRAME]), n
         self._frames_at_reset, self._n_at_reset, self._steps_at_reset = int(ci[_lib.LOOP_I_FRAME]), n, self.step_count
+
+    def _started(self, ns, reset: bool):
+        """set_particles' bookkeeping without its read of the control block: annealing's init_particles, once a frame has taken it,
+        is the count that frame started from (annealing's first call takes the live count, particle_filter.py:413-417), and the frame
+        count is what the device last reported - all of it, once the stream has drained.
+        Assumption behind `_init_known`: since the last reset either no frame ran, or whole frames with the ANNEAL phase did (what
+        filter() and filter_sweep enqueue).  A caller that stepped partial phase masks without ANNEAL, or wrote
+        set_annealing_state() (which sets `_init_known` itself), is not second-guessed here; `_init_known` only feeds `_frozen()`,
+        whose claim the device checks (log row err bit 7), so a wrong guess is reported, never silent."""
+        n = ns[0]
+        if reset:
+            self._init_known = None
+        elif self._init_known is None and self.cluster and self.step_count > self._steps_at_reset:
+            self._init_known = self._n_at_reset
+        self._n_host = n
+        self._pending_phases = 0
+        torch.cuda.current_stream(self.device).synchronize()  # the control block is in place, nothing older is in flight
+        frame = 0 if reset else int(self._mirror[0])
+        self._mirror[0], self._mirror[1] = frame, n
+        self._frames_at_reset, self._n_at_reset, self._steps_at_reset = frame, n, self.step_count
 
     def _count_bound(self) -> int:
         """An upper bound of the live count at the start of the frame about to be enqueued, from what the device reported

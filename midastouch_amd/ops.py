@@ -176,6 +176,67 @@ class ObjectSet:
             pass
 
 
+def _counts(ns, B: int):
+    """B host counts as the C ABI reads them."""
+    ns = [int(v) for v in ns]
+    if len(ns) != B:
+        raise MidasError(f"{len(ns)} particle counts for {B} rows")
+    return (C.c_int32 * B)(*ns)
+
+
+def init_particles_batch(poses: torch.Tensor, gts: torch.Tensor, sigmas: torch.Tensor, ns, seed: int = 0, draw: int = 0,
+                         tn: torch.Tensor | None = None, rot: torch.Tensor | None = None) -> torch.Tensor:
+    """init_filter (modules/particle_filter.py:129-145) for B rows in one launch, in place: poses (B, cap, 4, 4) float32, slots
+    [0, ns[b]) of row b := gts[b] @ T(from_euler('zyx', rot, degrees), tn); the slots behind stay.  gts (B, 4, 4); sigmas (B, 2): row
+    b's init_noise (metres, degrees).  tn / rot (B, cap, 3) float32, already scaled: the caller's draws; None: Philox normals keyed
+    (seed + b, 0xFFFFFFFF - draw) (`midas_init_particles_batch`)."""
+    if poses.dim() != 4 or poses.dtype != torch.float32 or not poses.is_contiguous():
+        raise MidasError("init_particles_batch writes in place: contiguous float32 poses (B, cap, 4, 4)")
+    if (tn is None) != (rot is None):
+        raise MidasError("tn and rot (the start's draws) come together or not at all")
+    if not 0 <= int(draw) <= 0xFFFFFFFF:
+        raise MidasError("draw counts the starts so far: 0 .. 2^32 - 1")
+    B, cap, d = poses.shape[0], poses.shape[1], poses.device
+    n_host = _counts(ns, B)
+    gts = gts.to(d, torch.float32).contiguous()
+    sigmas = sigmas.to(d, torch.float32).contiguous()
+    if tuple(gts.shape) != (B, 4, 4) or tuple(sigmas.shape) != (B, 2):
+        raise MidasError(f"expected gts ({B},4,4) and sigmas ({B},2), got {tuple(gts.shape)} and {tuple(sigmas.shape)}")
+    if tn is not None:
+        tn, rot = (t.to(d, torch.float32).contiguous() for t in (tn, rot))
+        if tuple(tn.shape) != (B, cap, 3) or tuple(rot.shape) != (B, cap, 3):
+            raise MidasError(f"expected tn and rot ({B},{cap},3), got {tuple(tn.shape)} and {tuple(rot.shape)}")
+    _ctx(poses).call("midas_init_particles_batch", B, cap, n_host, _ptr(gts), _ptr(sigmas), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw),
+                     _ptr(tn), _ptr(rot), _ptr(poses))
+    return poses
+
+
+def project_batch(poses: torch.Tensor, hint: torch.Tensor, ns, tree6: "Tree" = None, codebook: "Codebook" = None,
+                  cb_poses: torch.Tensor | None = None, object_set: "ObjectSet" = None) -> torch.Tensor:
+    """particles.poses, _, _ = codebook.SE3_NN(particles.poses) (filter/filter.py:159-160) for B rows in one launch, in place: slots
+    [0, ns[b]) of poses (B, cap, 4, 4) := the nearest codebook pose, of hint (B, cap) int32 := its index - on object_set's object of
+    the row, or on (tree6, codebook, cb_poses) for every row.  Row b holds the bits of gather_rows(cb_poses, nn6(tree6,
+    se3_feature(poses[b, :ns[b]]))) (`midas_project_batch`)."""
+    if poses.dim() != 4 or poses.dtype != torch.float32 or not poses.is_contiguous():
+        raise MidasError("project_batch writes in place: contiguous float32 poses (B, cap, 4, 4)")
+    B, cap = poses.shape[0], poses.shape[1]
+    if hint.dtype != torch.int32 or not hint.is_contiguous() or tuple(hint.shape) != (B, cap) or hint.device != poses.device:
+        raise MidasError(f"project_batch writes in place: contiguous int32 hints ({B}, {cap}) beside the poses")
+    n_host = _counts(ns, B)
+    if object_set is None:
+        if tree6 is None or codebook is None or cb_poses is None:
+            raise MidasError("project_batch needs an object set, or a tree, its codebook and the codebook's poses")
+        if cb_poses.dtype != torch.float32 or not cb_poses.is_contiguous() or cb_poses.device != poses.device:
+            raise MidasError("project_batch reads contiguous float32 codebook poses on the particles' device")
+        if cb_poses.numel() != 16 * tree6.K:
+            raise MidasError(f"{cb_poses.shape[0]} codebook poses for a tree over {tree6.K} entries")
+        args = (None, codebook.h, tree6.h, _ptr(cb_poses))
+    else:
+        args = (object_set.h, None, None, None)
+    _ctx(poses).call("midas_project_batch", *args, B, cap, n_host, _ptr(poses), _ptr(hint))
+    return hint
+
+
 def se3_feature(poses: torch.Tensor, w: float = 0.01) -> torch.Tensor:
     """R3_SE3 (tactile_tree/tactile_tree.py:73-77)."""
     poses = _poses(poses)

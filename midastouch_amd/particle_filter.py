@@ -87,6 +87,24 @@ def _cfg_get(node, *path):
     return node
 
 
+def start_transforms(tn, rot_deg) -> np.ndarray:
+    """Host statement of the device start's formula - nothing at run time calls it; it is the spec csrc/start.hip is read against
+    and what tests/test_filter_sweep_plan.py holds to scipy, the oracle and fixture G8.  The float32 Tn = [R | t] of `init_filter`
+    (:129-145) as the device start evaluates it:
+    scipy's extrinsic from_euler("zyx", rot, degrees=True) written out - the float32 degrees widened to float64,
+    R = Rx(rot[2]) Ry(rot[1]) Rz(rot[0]) in float64, rounded to float32.  -> (N, 4, 4) float32."""
+    tn, rot = np.asarray(tn, dtype=np.float32).reshape(-1, 3), np.asarray(rot_deg, dtype=np.float32).reshape(-1, 3)
+    ang = rot.astype(np.float64) * (np.pi / 180.0)
+    (sa, sb, sc), (ca, cb, cc) = np.sin(ang).T, np.cos(ang).T
+    R = np.empty((tn.shape[0], 3, 3), dtype=np.float64)
+    R[:, 0, 0], R[:, 0, 1], R[:, 0, 2] = cb * ca, -(cb * sa), sb
+    R[:, 1, 0], R[:, 1, 1], R[:, 1, 2] = cc * sa + sc * sb * ca, cc * ca - sc * sb * sa, -(sc * cb)
+    R[:, 2, 0], R[:, 2, 1], R[:, 2, 2] = sc * sa - cc * sb * ca, sc * ca + cc * sb * sa, cc * cb
+    Tn = np.zeros((tn.shape[0], 4, 4), dtype=np.float32)
+    Tn[:, :3, :3], Tn[:, :3, 3], Tn[:, 3, 3] = R.astype(np.float32), tn, 1.0
+    return Tn
+
+
 class particle_filter:
     """Update and propagation of SE(3) particles on a mesh (:93-469)."""
 
