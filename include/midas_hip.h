@@ -1064,6 +1064,40 @@ int midas_object_set_destroy(midas_object_set* set);
  * as in midas_loop_step_batch: row b holds, frame for frame, the bits of midas_loop_step on object row_object[b] with seed + b. */
 int midas_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args* args, int32_t phases, int32_t B,
                                   int64_t log_stride, int32_t wide);
+/* The filter's own parameters of ONE row of a batch (midas_loop_step_batch_rows): B of these records, contiguous in device memory,
+ * row b's at index b.  A record stands for what one process of the reference's sweep takes from its config and its runner:
+ *   std_t, std_r   the motion noise of this frame (modules/particle_filter.py:326-335, add_noise_to_odom: torch.normal's std for
+ *                  the translation in metres and the rotation in degrees) - float32, already multiplied as midas_loop_args.std_t / std_r are;
+ *   prune_thr      remove_invalid_particles' penetration threshold (:379-403), and
+ *   prune_t2       its square as the kernels compare it: the largest float64 t2 with sqrt(t2) <= prune_thr (-1 for a negative or NaN
+ *                  threshold, +inf for +inf), formed by the caller on the host - a kernel takes no root and no square of it;
+ *   floor          annealing's smallest particle count (:405-447; filter/filter.py 1000, filter/filter_real.py 10 000);
+ *   softmax        get_similarity's softmax over the scores (:449-469), 0: the raw scores are the weights (filter/filter_real.py:208-210);
+ *   unit_weights   1: no measurement update on this frame - every particle scores 1 (filter/filter_real.py:205-212, `update_freq`:
+ *                  rows with different cadences differ here from frame to frame).
+ * 40 bytes, no pointers; a workgroup reads its row's record through an address that depends on blockIdx.y alone. */
+typedef struct midas_loop_row_params {
+    float std_t, std_r;
+    double prune_thr;
+    double prune_t2;
+    int32_t floor;
+    int32_t softmax;
+    int32_t unit_weights;
+    int32_t pad_;                  /* 0 */
+} midas_loop_row_params;
+/* midas_loop_step_batch_objects' frame with the filter's parameters per row - objects x logs x trials of bash/run_filter.sh where the
+ * rows also differ in config (config/expt/ycb.yaml: noise_t 2e-4; config/expt/mcmaster.yaml: 1e-4) or runner (filter/filter.py /
+ * filter/filter_real.py), or a grid of parameters over the same logs: rows_dev[b] replaces args->std_t, std_r, prune_thr, floor,
+ * softmax and unit_weights for row b; those fields of `args` are not read by a kernel and only have to pass the argument check.
+ * Everything else - set, args, layout, B == the set's, K_max - is midas_loop_step_batch_objects'; eps, the DBSCAN phase, the resample
+ * mode and the seed stay shared.  The regime: device draws (tn_dev, rot_dev, u_dev NULL) and topk_ties == MIDAS_TOPK_TIES_INDEX, with
+ * wide = 0 cap <= MIDAS_LOOP_BATCH_MAX_CAP, with wide = 1 midas_loop_step_batch_wide's bounds; rows_dev non-NULL and 8-byte aligned;
+ * anything else is MIDAS_ERR_INVALID with nothing enqueued.  The records' values are the caller's to check (a kernel reads them as
+ * they stand).  The same number of launches as midas_loop_step_batch_objects, by kernels that read the row's record where their
+ * twins read a kernel argument: row b holds, frame for frame, the bits of midas_loop_step on object row_object[b] with seed + b and
+ * row b's parameters. */
+int midas_loop_step_batch_rows(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args* args,
+                               const midas_loop_row_params* rows_dev, int32_t phases, int32_t B, int64_t log_stride, int32_t wide);
 /* particle_filter.init_filter (modules/particle_filter.py:129-145, called from filter/filter.py:156-158 on every frame seen while
  * prev_idx == 0) for B rows in one launch: slots [0, n_host[b]) of poses_dev[b] (B x cap x 16 float32, 16-byte aligned) :=
  * gt16_dev[b] @ [R | t], the slots behind are left alone.  R is scipy's extrinsic from_euler("zyx", rot, degrees=True) - the float32

@@ -206,6 +206,18 @@ class LoopArgs(C.Structure):
     ]
 
 
+class LoopRowParams(C.Structure):
+    """midas_loop_row_params (include/midas_hip.h): the filter's parameters of one row of midas_loop_step_batch_rows."""
+
+    _fields_ = [("std_t", C.c_float), ("std_r", C.c_float), ("prune_thr", C.c_double), ("prune_t2", C.c_double),
+                ("floor", C.c_int32), ("softmax", C.c_int32), ("unit_weights", C.c_int32), ("pad_", C.c_int32)]
+
+
+# the same record as a numpy dtype: a table of B rows is one array, uploaded as bytes
+LOOP_ROW_PARAMS_DTYPE = [("std_t", "<f4"), ("std_r", "<f4"), ("prune_thr", "<f8"), ("prune_t2", "<f8"), ("floor", "<i4"),
+                         ("softmax", "<i4"), ("unit_weights", "<i4"), ("pad_", "<i4")]
+
+
 # phases of midas_loop_step and the control-block indices (include/midas_hip.h MIDAS_LOOP_*)
 LOOP_FRONT, LOOP_DBSCAN, LOOP_ANNEAL, LOOP_RESAMPLE = 1, 2, 4, 8
 MT19937_HIST_WORDS = 20560  # MIDAS_MT19937_HIST_WORDS
@@ -293,6 +305,7 @@ SIGNATURES = {
     "midas_object_set_create": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, C.POINTER(_P)]),
     "midas_object_set_destroy": (C.c_int, [_P]),
     "midas_loop_step_batch_objects": (C.c_int, [_P, _P, C.POINTER(LoopArgs), _I32, _I32, _I64, _I32]),
+    "midas_loop_step_batch_rows": (C.c_int, [_P, _P, C.POINTER(LoopArgs), _P, _I32, _I32, _I64, _I32]),
     "midas_init_particles_batch": (C.c_int, [_P, _I32, _I64, _P, _P, _P, _U64, C.c_uint32, _P, _P, _P]),
     "midas_project_batch": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _P, _P, _P]),
     "midas_dbscan": (C.c_int, [_P, _I64, _P, _D, _I64, _P, _P]),

@@ -34,13 +34,24 @@ Rows on different objects: `BatchLoopEngine.for_objects(objects, row_object, num
 sweep (`bash/run_filter.sh`: objects x logs x trials) in ONE batch.  Every object gets its own codebook index on the one context, an
 object set (`midas_object_set_create`) tells the front which record a row's workgroups read, and a frame goes through
 `midas_loop_step_batch_objects`: one launch set for all rows, whatever they stand on.  Row b holds the bits of a LoopEngine built on
-object row_object[b] with seed + b.  Scores and stamps are (B, K_max); the filter's parameters stay shared by the rows.
+object row_object[b] with seed + b.  Scores and stamps are (B, K_max).
+
+The filter's parameters per row: `sig_t`, `sig_r`, `pen_max`, `floor` and `softmax` are each one value for the batch or B values,
+`step(unit_weights=)` a bool or B bools, `set_row_params(**kw)` changes them between frames - two datasets' configs
+(config/expt/ycb.yaml, mcmaster.yaml), the two runners' presets (filter/filter.py, filter_real.py) or a parameter grid as rows of ONE
+batch.  A frame with any per-row value goes through `midas_loop_step_batch_rows` with a table of B `midas_loop_row_params` on the
+device (built on the host when a frame's inputs are not among the last ROW_TABLES_KEPT, sent without a stall after the first, kept resident) - the same number of launches, nothing read back;
+row b then holds the bits of a LoopEngine built with row b's parameters and seed + b.  With scalars only the engine takes the entries
+above, unchanged.  Shared by all rows still: `eps`, the DBSCAN flag and cadence, the resample mode, `multiplier` and `step_still`'s
+`std_override`; seeded streams and the ATen tie rule refuse per-row values (their counted draws carry one std per segment).
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -52,6 +63,61 @@ from .loop_engine import ALL_PHASES, TOPK_TIES, _LoopBase, log_records
 # the constructor's keywords and their defaults: what `for_objects` takes as **kw (tests hold __init__'s signature to this table)
 DEFAULTS = dict(sig_t=2e-4, sig_r=0.5, pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor=1000, eps=1e-2,
                 cluster=True, cluster_every=50, log_frames=4096, device=None, wide=False, batched_dbscan=None)
+
+
+ROW_PARAMS = ("sig_t", "sig_r", "pen_max", "floor", "softmax")  # what a row may hold for itself (set_row_params' keywords)
+ROW_TABLES_KEPT = 16  # resident parameter tables (40 B a row each): a sweep alternates between two (still / moving frames), rows with
+#                        different update cadences cycle through lcm(frequencies) unit-weight patterns (BatchLoopEngine._row_table)
+
+
+def squared_threshold(thr: float) -> float:
+    """csrc/midas_internal.hpp squared_threshold on the host: the largest float64 t2 with sqrt(t2) <= thr, so that sqrt(d2) > thr <=>
+    d2 > t2 exactly; -1 for a negative or NaN threshold, +inf for +inf.  (IEEE square roots on both sides: the same double.)"""
+    thr = float(thr)
+    if not thr >= 0.0:
+        return -1.0
+    if math.isinf(thr):
+        return math.inf
+    t = thr * thr
+    while math.sqrt(t) > thr:
+        t = math.nextafter(t, 0.0)
+    while math.sqrt(math.nextafter(t, math.inf)) <= thr:
+        t = math.nextafter(t, math.inf)
+    return t
+
+
+def row_values(name: str, value, B: int):
+    """One of ROW_PARAMS (or `unit_weights`) as given -> (scalar, None) or (None, list of B), checked: a sequence of another length,
+    a negative or NaN sigma, a floor below 1.  Nothing else is looked at (a threshold may be NaN or infinite, as a scalar may)."""
+    if isinstance(value, (torch.Tensor, np.ndarray)):
+        value = value.tolist()
+    seq = isinstance(value, (list, tuple))
+    vals = list(value) if seq else [value]
+    if seq and len(vals) != B:
+        raise MidasError(f"{name}: {len(vals)} values for a batch of {B} rows (one value, or one per row)")
+    conv = {"sig_t": float, "sig_r": float, "pen_max": float, "floor": int, "softmax": bool, "unit_weights": bool}[name]
+    try:
+        vals = [conv(v) for v in vals]
+    except (TypeError, ValueError) as e:
+        raise MidasError(f"{name}: {e}") from e
+    for b, v in enumerate(vals):
+        where = f"row {b}: " if seq else ""
+        if name in ("sig_t", "sig_r") and not v >= 0.0:
+            raise MidasError(f"{where}{name} = {v}: a motion noise is a standard deviation, >= 0")
+        if name == "floor" and v < 1:
+            raise MidasError(f"{where}floor = {v}: annealing's floor is at least 1 particle")
+    return (None, vals) if seq else (vals[0], None)
+
+
+def row_params_table(B: int, std_t, std_r, pen_max, floor, softmax, unit_weights) -> np.ndarray:
+    """B `midas_loop_row_params` on the host from six columns, each a scalar or B values; std_t / std_r as float32 already."""
+    tab = np.zeros(B, dtype=_lib.LOOP_ROW_PARAMS_DTYPE)
+    tab["std_t"], tab["std_r"] = std_t, std_r
+    tab["prune_thr"] = pen_max
+    t2 = {}
+    tab["prune_t2"] = [t2.setdefault(float(v).hex(), squared_threshold(v)) for v in tab["prune_thr"]]  # (one search per distinct threshold)
+    tab["floor"], tab["softmax"], tab["unit_weights"] = floor, np.asarray(softmax, dtype=bool), np.asarray(unit_weights, dtype=bool)
+    return tab
 
 
 class BatchLoopEngine(_LoopBase):
@@ -68,6 +134,11 @@ class BatchLoopEngine(_LoopBase):
         """The one initialiser behind the constructor (one object, row_object None) and `for_objects`: the bounds, the set-up on the
         first row's object, for an object batch every object's index and the object set, then the state and the scratch."""
         self._check_regime(batch, num_particles, wide, batched_dbscan)
+        # each of ROW_PARAMS: one value for the batch, or B - the set-up then gets row 0's as the shared value (midas_loop_args'
+        # field only has to pass the argument check) and the rows' own go into the parameter table of every frame
+        given = {k: row_values(k, v, self.B) for k, v in dict(sig_t=sig_t, sig_r=sig_r, pen_max=pen_max, floor=floor, softmax=softmax).items()}
+        rows = {k: v[1] for k, v in given.items()}
+        sig_t, sig_r, pen_max, floor, softmax = (given[k][0] if rows[k] is None else rows[k][0] for k in ROW_PARAMS)
         first = 0 if row_object is None else row_object[0]  # the handles `_LoopBase` names (ctx, cb_poses, tree6, codebook, tree3): row 0's object
         self._setup(*objects[first], device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps, cluster, cluster_every, log_frames)
         if not sparse_scoring(self.codebook, switch=False):
@@ -88,6 +159,8 @@ class BatchLoopEngine(_LoopBase):
             self.row_object, self.Ks = list(row_object), [int(o.codebook.K) for o in self.objects]
             self._set = ops.ObjectSet(self.ctx, self.objects, row_object)
             self.K = max(self.Ks)  # scores and stamps are (B, K_max): row b touches the first Ks[row_object[b]] slots of its rows
+        self._rows, self._rows_version, self._row_set, self._row_tables = rows, 0, self._set, {}
+        self.row_table_uploads = 0  # parameter tables sent to the device so far (a sweep: two)
         self._alloc_batch()
 
     def _check_regime(self, batch, num_particles, wide, batched_dbscan):
@@ -155,6 +228,81 @@ class BatchLoopEngine(_LoopBase):
         self._init(objects, row_object, len(row_object), num_particles, **{**DEFAULTS, **kw})
         return self
 
+    # ---- the filter's parameters per row ---------------------------------------------------------------------------------
+    @property
+    def per_row(self):
+        """The ROW_PARAMS that hold a value per row at the moment (a tuple of names; empty: every parameter is shared)."""
+        return tuple(k for k in ROW_PARAMS if self._rows[k] is not None)
+
+    def row_params(self):
+        """ROW_PARAMS as the rows hold them now: name -> list of B values."""
+        return {k: list(self._rows[k]) if self._rows[k] is not None else [getattr(self, k)] * self.B for k in ROW_PARAMS}
+
+    def set_row_params(self, **kw):
+        """Changes `sig_t`, `sig_r`, `pen_max`, `floor` and / or `softmax` between frames: each one value for the batch or B values
+        (a scalar makes the parameter shared again).  Every value is checked before any is taken: a refused call - another length than
+        B, a negative or NaN sigma, a floor below 1, per-row values on an engine with seeded streams or the ATen tie rule - leaves the
+        engine as it was.  Nothing is enqueued; the next frame's table carries the new values."""
+        unknown = sorted(set(kw) - set(ROW_PARAMS))
+        if unknown:
+            raise MidasError(f"set_row_params: unknown keyword(s) {unknown}; a row's parameters are {list(ROW_PARAMS)}")
+        new = {k: row_values(k, v, self.B) for k, v in kw.items()}
+        rows = dict(self._rows, **{k: v[1] for k, v in new.items()})
+        if any(v is not None for v in rows.values()):
+            self._check_rows_regime()
+        for k, (scalar, _) in new.items():
+            if scalar is not None:
+                setattr(self, k, scalar)
+        self._rows = rows
+        self._rows_version += 1  # (the resident tables are keyed by it: none of them is this setting's)
+        self._write_params()
+
+    def _check_rows_regime(self):
+        if self.torch_streams is not None or self._topk_ties == "aten_cpu":
+            raise MidasError("per-row filter parameters need device draws and ties by index: a seeded frame's counted draw carries one std "
+                             "per segment, and the ATen tie rule stays shared-parameter (seed_torch_streams(None) / topk_ties = 'index' first)")
+
+    def _row_plan(self, multiplier, unit_weights, std_override):
+        """What a frame's parameter table is made from, checked - nothing is built, uploaded or changed here: -> (key, shared
+        unit_weights).  key is None when every parameter and `unit_weights` are shared (the frame takes the entries it always took);
+        else (version of the rows' parameters, the five shared attributes as they stand, multiplier, std_override, unit_weights as a
+        bool or a tuple of B) - the table is a
+        function of the key, so a steady frame looks its table up without building anything."""
+        unit = row_values("unit_weights", unit_weights, self.B)
+        if unit[1] is None and not self.per_row:
+            return None, unit[0]
+        self._check_rows_regime()
+        override = None if std_override is None else (float(std_override[0]), float(std_override[1]))
+        shared = tuple(getattr(self, k) for k in ROW_PARAMS)  # (a shared parameter may be set as an attribute, as on the shared frame)
+        return (self._rows_version, shared, max(float(multiplier), 1.0), override, unit[0] if unit[1] is None else tuple(unit[1])), False
+
+    def _row_table(self, key):
+        """The table of `_row_plan`'s key on the device.  The last ROW_TABLES_KEPT keys' tables stay resident; a key that is not among
+        them builds its table on the host - a row's std is float32(max(multiplier, 1) * sig_b), the product formed in float64 as
+        LoopEngine forms it - and sends it from pinned memory without waiting for the copy (40 B a row; the engine's first miss allocates the page-locked
+        buffer, which may synchronise - later misses take it from torch's host cache; the stream orders the copy in
+        front of the frame, and a replaced table's memory behind the frames that read it).  A sweep builds two (still and moving
+        frames); rows with different `update_freq` cycle through lcm(frequencies) unit-weight patterns - beyond ROW_TABLES_KEPT of
+        them every frame that misses builds and sends its table again (O(B) host work, no stall)."""
+        dev = self._row_tables.pop(key, None)
+        if dev is None:
+            _, _, mul, override, unit = key
+            col = self.row_params()
+            if override is None:
+                std_t, std_r = ((mul * np.asarray(col[k], dtype=np.float64)).astype(np.float32) for k in ("sig_t", "sig_r"))
+            else:
+                std_t, std_r = np.float32(override[0]), np.float32(override[1])
+            tab = row_params_table(self.B, std_t, std_r, col["pen_max"], col["floor"], col["softmax"], unit)
+            dev = torch.from_numpy(tab.view(np.uint8)).pin_memory().to(self.device, non_blocking=True)
+            while len(self._row_tables) >= ROW_TABLES_KEPT:
+                self._row_tables.pop(next(iter(self._row_tables)))  # (the least recently used)
+            self.row_table_uploads += 1
+        self._row_tables[key] = dev  # (most recently used last)
+        if self._row_set is None:  # one codebook: the rows entry reads objects from a set - one object, every row on it
+            me = SimpleNamespace(cb_poses=self.cb_poses, cb_feat=self.cb_feat, tree6=self.tree6, codebook=self.codebook, tree3=self.tree3)
+            self._row_set = ops.ObjectSet(self.ctx, [me], [0] * self.B)
+        return dev
+
     # whom annealing's torch.topk takes inside a tie: "index" (torch's CUDA rule, the radix select: midas_loop_step_batch as ever) or
     # "aten_cpu" (the reference as it runs on the CPU, topk_aten.hip: midas_loop_step_batch_draws); settable between frames
     @property
@@ -165,6 +313,8 @@ class BatchLoopEngine(_LoopBase):
     def topk_ties(self, rule):
         if rule == "aten_cpu" and self.wide:
             raise MidasError("a wide BatchLoopEngine breaks ties by index: the ATen tie rule beyond 16 384 particles stays with LoopEngine")
+        if rule == "aten_cpu" and self.per_row:
+            raise MidasError(f"the ATen tie rule stays shared-parameter: {list(self.per_row)} hold a value per row (set_row_params with scalars first)")
         self._args.topk_ties = TOPK_TIES[rule]
         if rule == "aten_cpu":  # the walk's queue, stopper lists, marks and block counts per trajectory, beside the frame's own
             cap = self.cap
@@ -248,6 +398,9 @@ class BatchLoopEngine(_LoopBase):
             return None
         if self.wide:
             raise MidasError("a wide BatchLoopEngine draws from Philox: seeded torch streams beyond 16 384 particles stay with LoopEngine")
+        if self.per_row:
+            raise MidasError(f"seeded torch streams stay shared-parameter (one std per counted draw): {list(self.per_row)} hold a value per "
+                             "row (set_row_params with scalars first)")
         seeds = list(seeds)
         if len(seeds) != self.B:
             raise MidasError(f"{len(seeds)} seeds for a batch of {self.B} trajectories")
@@ -285,12 +438,15 @@ class BatchLoopEngine(_LoopBase):
         return self._frame_view(self.read_log(self.step_count - 1, self.step_count, rows=(b,))[0][0], b)
 
     # ---- one batch frame ------------------------------------------------------------------------------------------
-    def step(self, odoms, codes, gts=None, u32=-1.0, multiplier: float = 1.0, dbscan=None, unit_weights: bool = False):
+    def step(self, odoms, codes, gts=None, u32=-1.0, multiplier: float = 1.0, dbscan=None, unit_weights=False):
         """Enqueues one frame of every trajectory and reads nothing back: odoms (B,4,4), codes (B,D), gts (B,4,4) or None.
         dbscan: None = on every `cluster_every`-th frame (filter.py:182), True / False to force - for all trajectories alike.
+        unit_weights: a frame without measurement update (filter_real.py:205-212) - a bool, or B bools: the rows' own cadences.
         A frame with another motion noise than multiplier x (sig_t, sig_r) - LoopEngine.step's `std_override` - is `step_still`."""
+        row_key, unit_weights = self._row_plan(multiplier, unit_weights, self._std_override)  # (checks only)
         phases = self._phase_mask(ALL_PHASES, dbscan)
         odoms, codes, gts = frame_operands(self.device, (self.B,), self.D, odoms, codes, gts)
+        rows = None if row_key is None else self._row_table(row_key)  # (behind every refusal: a refused frame has changed nothing)
         a = self._frame_scalars(u32, multiplier, unit_weights, self._std_override)
         a.odom16, a.code, a.gt16 = _ptr(odoms), _ptr(codes), _ptr(gts)
         a.part_rmse = _ptr(self._part_rmse) if gts is not None else None
@@ -299,6 +455,10 @@ class BatchLoopEngine(_LoopBase):
 
         def call(entry, ph):
             self.ctx.bind_current_stream()
+            if rows is not None:  # the filter's parameters per row: the objects frame by the kernels that read the table
+                self.ctx.check(self.ctx.lib.midas_loop_step_batch_rows(self.ctx.h, self._row_set.h, C.byref(a), _ptr(rows), int(ph), self.B,
+                                                                       log_stride, int(self.wide)))
+                return
             if self._set is not None:  # rows on different objects: one entry, the regime of `entry` by its `wide` flag
                 self.ctx.check(self.ctx.lib.midas_loop_step_batch_objects(self.ctx.h, self._set.h, C.byref(a), int(ph), self.B, log_stride,
                                                                           int(self.wide)))

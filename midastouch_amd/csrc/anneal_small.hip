@@ -16,47 +16,40 @@ namespace midas {
 // and k_loop_anneal_small<true> comes out with other instructions (one compare inverted) than beside this caller's run-time value.
 // Workgroup 0: the select state cleared (hist null: the decision alone - the batch's ATen walk, no radix select follows), the decision
 // by thread 0; workgroup 1: the centres' rotations.
+// (the body is a file of its own, included here and in the twin that takes floor_n from the rows' parameter table: the twin then
+// shares every statement, and this kernel's token stream - so its code, instruction for instruction - is what it was)
 __global__ __launch_bounds__(256) void k_loop_decide(int32_t* __restrict__ ctl_i, double* __restrict__ ctl_d,
                                                      const float* __restrict__ centers_all, const float* __restrict__ stds_all,
                                                      const int64_t* __restrict__ counts_all, float* __restrict__ centers_out,
                                                      float* __restrict__ stds_out, uint32_t* __restrict__ hist,
                                                      int32_t* __restrict__ sel_state, int32_t floor_n, const double* __restrict__ rot,
                                                      int32_t frozen = 0, int32_t aten_order = 0) {
-    if (blockIdx.y) {  // a batch of trajectories: LOOP_MAX_CLUSTERS cluster rows each; no select state (midas_loop_step_batch_draws'
-        const int64_t b = blockIdx.y;  // ATen walk), or every trajectory's own histograms and state (midas_loop_step_batch_wide)
-        ctl_i += b * LOOP_CTL_I; ctl_d += b * LOOP_CTL_D;
-        centers_all += b * LOOP_MAX_CLUSTERS * 16; stds_all += b * LOOP_MAX_CLUSTERS * 3; counts_all += b * LOOP_MAX_CLUSTERS;
-        centers_out += b * LOOP_MAX_CLUSTERS * 16; stds_out += b * LOOP_MAX_CLUSTERS * 3; rot += b * LOOP_MAX_CLUSTERS * 10;
-        if (hist) { hist += b * SEL_HIST_WORDS; sel_state += b * SEL_STATE_WORDS; }
-    }
-    if (blockIdx.x == 1) { loop_rotations(ctl_i, counts_all, rot, centers_out); return; }
-    const int t = threadIdx.x;
-    if (!hist) {  // the decision alone (the batch's ATen walk: no radix select follows)
-        if (t != 0) return;
-        int mode, k;
-        loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k, aten_order != 0);
-        return;
-    }
-    for (int i = t; i < SEL_HIST_WORDS; i += 256) hist[i] = 0u;
-    for (int i = t; i < SEL_STATE_WORDS; i += 256) sel_state[i] = 0;
-    __syncthreads();
-    if (t != 0) return;
-    int mode, k;
-    loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k, aten_order != 0);
-    if (frozen && mode) {  // the caller said annealing cannot act and no selection was launched: the set stays, the frame says so
-        ctl_i[LOOP_I_ERR] |= 128;
-        ctl_i[LOOP_I_MODE] = 0; ctl_i[LOOP_I_K] = 0; ctl_i[LOOP_I_NSET] = ctl_i[LOOP_I_N];
-        k = 0;
-    }
-    sel_state[0] = 0; sel_state[1] = 0; sel_state[2] = k;  // pass 0: empty prefix, rank k
+#include "loop_decide_body.hpp"
 }
 
+// k_loop_decide with annealing's floor of row blockIdx.y's record (midas_loop_step_batch_rows, the wide regime's decision in front of
+// the radix select): one scalar load through a uniform address in place of a kernel argument.  The regime has no frozen frames and
+// breaks ties by index; the two switches stay run-time values, as in the twin (see the note on loop_decide above).
+__global__ __launch_bounds__(256) void k_loop_decide_rows(int32_t* __restrict__ ctl_i, double* __restrict__ ctl_d,
+                                                          const float* __restrict__ centers_all, const float* __restrict__ stds_all,
+                                                          const int64_t* __restrict__ counts_all, float* __restrict__ centers_out,
+                                                          float* __restrict__ stds_out, uint32_t* __restrict__ hist,
+                                                          int32_t* __restrict__ sel_state, const midas_loop_row_params* __restrict__ rows,
+                                                          const double* __restrict__ rot, int32_t frozen, int32_t aten_order) {
+    const int32_t floor_n = rows[blockIdx.y].floor;
+#include "loop_decide_body.hpp"
+}
 
 int launch_loop_decide(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopMoments& m, uint32_t* hist,
                        int32_t* sel_state, int32_t frozen, int32_t aten_order) {
-    hipLaunchKernelGGL(k_loop_decide, dim3(2, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
-                       (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, hist, sel_state, s.floor,
-                       (const double*)m.rot, frozen, aten_order);
+    if (g.rows)
+        hipLaunchKernelGGL(k_loop_decide_rows, dim3(2, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
+                           (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, hist, sel_state, g.rows,
+                           (const double*)m.rot, frozen, aten_order);
+    else
+        hipLaunchKernelGGL(k_loop_decide, dim3(2, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
+                           (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, hist, sel_state, s.floor,
+                           (const double*)m.rot, frozen, aten_order);
     return MIDAS_OK;
 }
 
@@ -346,6 +339,8 @@ MD void anneal_small_select(int* s_w, const uint64_t* wkey, int32_t* __restrict_
 }
 
 // DECIDE: the frame's decision by thread 0 and, second workgroup, the centres' rotations; else a plan the host left in ctl_i
+// (the body is a file of its own, included here and in the twin that takes floor_n from the rows' parameter table: the twin then
+// shares every statement, and this kernel's token stream - so its code, instruction for instruction - is what it was)
 template <bool DECIDE>
 __global__ __launch_bounds__(1024) void k_loop_anneal_small(int32_t* __restrict__ ctl_i, double* __restrict__ ctl_d,
                                                             const float* __restrict__ centers_all, const float* __restrict__ stds_all,
@@ -353,43 +348,31 @@ __global__ __launch_bounds__(1024) void k_loop_anneal_small(int32_t* __restrict_
                                                             float* __restrict__ stds_out, int32_t floor_n,
                                                             const double* __restrict__ w, int32_t* __restrict__ src,
                                                             const double* __restrict__ rot, int32_t cap = 0) {
-#ifdef MIDAS_ANNEAL_CLOCKS
-    const long long ck0 = wall_clock64();
-#else
-    const long long ck0 = 0;
-#endif
-    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): `cap` particles and LOOP_MAX_CLUSTERS cluster rows per trajectory
-        const int64_t b = blockIdx.y;
-        ctl_i += b * LOOP_CTL_I; ctl_d += b * LOOP_CTL_D;
-        centers_all += b * LOOP_MAX_CLUSTERS * 16; stds_all += b * LOOP_MAX_CLUSTERS * 3; counts_all += b * LOOP_MAX_CLUSTERS;
-        centers_out += b * LOOP_MAX_CLUSTERS * 16; stds_out += b * LOOP_MAX_CLUSTERS * 3; rot += b * LOOP_MAX_CLUSTERS * 10;
-        w += b * cap; src += b * cap;
-    }
-    if (DECIDE && blockIdx.x == 1) { loop_rotations(ctl_i, counts_all, rot, centers_out); ACK(7); return; }
-    __shared__ int s_w[40];
-    const int t = threadIdx.x;
-    if (t == 0) {
-        int mode = ctl_i[LOOP_I_MODE], k = ctl_i[LOOP_I_K];  // !DECIDE: a plan made by the host (midas_anneal_select)
-        if (DECIDE) loop_decide(ctl_i, ctl_d, centers_all, stds_all, counts_all, centers_out, stds_out, floor_n, mode, k);
-        const int n0 = ctl_i[LOOP_I_N];
-        if (n0 > LOOP_SMALL_MAX) { ctl_i[LOOP_I_ERR] |= 4; mode = 0; }  // the caller's bound was wrong: no annealing, flagged
-        s_w[36] = mode; s_w[37] = k; s_w[38] = n0; s_w[39] = 0;
-    }
-    __syncthreads();
-    ACK(0);
-    __shared__ uint64_t s_key[LOOP_SMALL_PAIRS];
-    __shared__ int32_t s_idx[LOOP_SMALL_PAIRS];
-    uint64_t wkey[16];
-    small_keys(w, s_w[38], wkey);
-    anneal_small_select(s_w, wkey, src, ctl_i, ctl_d, ck0, s_key, s_idx);
-    if (threadIdx.x == 0) ctl_d_count(ctl_d, 35);  // launches that got here
+#include "loop_anneal_small_body.hpp"
+}
+
+// k_loop_anneal_small<true> with annealing's floor of row blockIdx.y's record (midas_loop_step_batch_rows): one scalar load through a
+// uniform address in place of a kernel argument; only the deciding thread uses the value.
+__global__ __launch_bounds__(1024) void k_loop_anneal_small_rows(int32_t* __restrict__ ctl_i, double* __restrict__ ctl_d,
+                                                                 const float* __restrict__ centers_all, const float* __restrict__ stds_all,
+                                                                 const int64_t* __restrict__ counts_all, float* __restrict__ centers_out,
+                                                                 float* __restrict__ stds_out,
+                                                                 const midas_loop_row_params* __restrict__ rows,
+                                                                 const double* __restrict__ w, int32_t* __restrict__ src,
+                                                                 const double* __restrict__ rot, int32_t cap) {
+    constexpr bool DECIDE = true;
+    const int32_t floor_n = rows[blockIdx.y].floor;
+#include "loop_anneal_small_body.hpp"
 }
 
 // B trajectories (grid.y; slices g.slice particles apart): a frame's annealing from the moments m, or - m null - the selection alone on
 // a plan the host left in ctl_i (launch_anneal_select: one workgroup, no cluster arrays)
 int launch_anneal_small(midas_ctx* ctx, const LoopGrid& g, int32_t* ctl_i, double* ctl_d, const LoopMoments* m, float* centers_out,
                         float* stds_out, int32_t floor_n, const double* w, int32_t* src) {
-    if (m)
+    if (m && g.rows)
+        hipLaunchKernelGGL(k_loop_anneal_small_rows, dim3(2, g.by()), dim3(1024), 0, ctx->stream, ctl_i, ctl_d, (const float*)m->cen,
+                           (const float*)m->sd, (const int64_t*)m->cnt, centers_out, stds_out, g.rows, w, src, (const double*)m->rot, g.slice);
+    else if (m)
         hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, g.by()), dim3(1024), 0, ctx->stream, ctl_i, ctl_d, (const float*)m->cen,
                            (const float*)m->sd, (const int64_t*)m->cnt, centers_out, stds_out, floor_n, w, src, (const double*)m->rot, g.slice);
     else

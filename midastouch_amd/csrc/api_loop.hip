@@ -1,6 +1,7 @@
 // api_loop.hip - the loop engine's entry points: the whole loop body on a variable-size particle set, for one trajectory
 // (midas_loop_step) and for B per launch (midas_loop_step_batch, midas_loop_step_batch_draws, midas_loop_step_batch_wide; with every row on an
-// object of its own: midas_object_set_create / _destroy and midas_loop_step_batch_objects).  One argument check for the five.
+// object of its own: midas_object_set_create / _destroy and midas_loop_step_batch_objects; with the filter's parameters per row as
+// well: midas_loop_step_batch_rows).  One argument check for the six.
 #include <new>
 #include <vector>
 
@@ -174,6 +175,20 @@ MIDAS_EXPORT int midas_loop_step_batch_objects(midas_ctx* ctx, const midas_objec
     const LoopRegime regime = wide ? LoopRegime::batch_wide : LoopRegime::batch_draws;
     if (int rc = loop_args_check(ctx, nullptr, nullptr, nullptr, args, phases, regime, B, log_stride, set)) return rc;
     return launch_loop_step_batch_objects(ctx, set, *args, phases, log_stride, wide != 0);
+}
+
+// ---- ... and the filter's parameters per row -------------------------------------------------------------------------------------
+MIDAS_EXPORT int midas_loop_step_batch_rows(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args* args,
+                                            const midas_loop_row_params* rows_dev, int32_t phases, int32_t B, int64_t log_stride,
+                                            int32_t wide) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, set != nullptr && (wide == 0 || wide == 1));
+    MIDAS_REQUIRE(ctx, rows_dev != nullptr && (uintptr_t)rows_dev % 8 == 0);
+    // device draws and ties by index: the counted draw of a seeded frame carries one std per segment, the ATen walk stays shared-parameter
+    const LoopRegime regime = wide ? LoopRegime::batch_wide : LoopRegime::batch;
+    if (int rc = loop_args_check(ctx, nullptr, nullptr, nullptr, args, phases, regime, B, log_stride, set)) return rc;
+    MIDAS_REQUIRE(ctx, args->stream_draws == 0);
+    return launch_loop_step_batch_objects(ctx, set, *args, phases, log_stride, wide != 0, rows_dev);
 }
 
 }  // extern "C"

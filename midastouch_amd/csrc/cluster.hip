@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void k_loop_cluster_moments(const int32_t* __r
 #else
 #define WCK(i) do { } while (0)
 #endif
-template <class Args>  // LoopWeightsArgs, or LoopWeightsRowsArgs - rows on different objects (loop_weights.hpp)
+template <class Args>  // LoopWeightsArgs, LoopWeightsRowsArgs - rows on different objects - or LoopWeightsParamRowsArgs (loop_weights.hpp)
 __global__ __launch_bounds__(256) void k_loop_weights_moments(Args a, const int32_t* __restrict__ labels,
                                                               double* __restrict__ part, bool skip) {
 #ifdef MIDAS_ANNEAL_CLOCKS
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void k_loop_weights_moments(Args a, const int3
     __shared__ double s_sum[LAZY_MAX_BLOCKS];
     __shared__ double s_red[8], s_ab[8];
     __shared__ int s_ired[8];
-    if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch)
+    if (blockIdx.y || loop_weights_every_row(a)) {  // a batch of trajectories (midas_loop_step_batch)
         labels += (int64_t)blockIdx.y * a.grid_n;
         part += (size_t)blockIdx.y * gridDim.x * LOOP_MAX_CLUSTERS * CL_MOM;
         loop_weights_batch(a, blockIdx.y);
@@ -631,11 +631,14 @@ static bool moments_skip() {  // MIDAS_MOMENTS_SKIP=0: every cluster summed by e
 // (the decision only needs the translation spreads: the eigenvector runs beside the selection)
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsRowsArgs* weights, int32_t B) {
+                        const LoopWeightsParamRowsArgs* weights, int32_t B) {
     const unsigned by = (unsigned)(B > 1 ? B : 1);
-    if (weights && weights->cb_poses_rows)  // rows on different objects (midas_loop_step_batch_objects)
-        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsRowsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
+    if (weights && weights->rows)  // ... with their own filter parameters (midas_loop_step_batch_rows)
+        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsParamRowsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
                            *weights, labels, part, moments_skip());
+    else if (weights && weights->cb_poses_rows)  // rows on different objects (midas_loop_step_batch_objects)
+        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsRowsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
+                           static_cast<const LoopWeightsRowsArgs&>(*weights), labels, part, moments_skip());
     else if (weights)
         hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
                            static_cast<const LoopWeightsArgs&>(*weights), labels, part, moments_skip());

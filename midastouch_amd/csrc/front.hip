@@ -302,27 +302,25 @@ __global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small(TreeView<Kd6
 // table.  Both addresses depend on blockIdx.y alone, so the record arrives by scalar loads and stays in SGPRs, where k_front_small
 // holds the same values as kernel arguments; nothing is stored before they are read.  Every row takes its offsets, row 0 included
 // (its offsets are zero); score and stamp rows are a.score_stride = K_max apart and row b touches the first K_b slots of its own.
+// (the body is a file of its own, included here and in the twin that takes std_t, std_r, thr and t2 from the rows' parameter table: the twin then
+// shares every statement, and this kernel's token stream - so its code, instruction for instruction - is what it was)
 __global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small_objects(const ObjectRecord* __restrict__ recs,
                                                                             const int32_t* __restrict__ row_object, ParticleUpdateArgs a,
                                                                             int nwaves, PuFeat* __restrict__ feat) {
-    const int64_t b = blockIdx.y, o = b * a.N;
-    const ObjectRecord& r = recs[row_object[b]];
-    const TreeView<Kd6> t6 = r.t6;
-    const TreeView<Kd3> t3 = r.t3;
-    a.vlist = r.vlist; a.vscr = r.vscr; a.field = r.field;
-    a.sp.emb = r.emb; a.sp.norms = r.norms; a.sp.K = r.K;
-    a.n_live += b * LOOP_CTL_I;
-    a.poses_in += o * 16; a.poses_prop += o * 16; a.odom16 += b * 16;
-    if (a.hint_in) a.hint_in += o;
-    a.nn_idx += o; a.valid += o;
-    if (a.gt16) { a.gt16 += b * 16; a.part_rmse += 2 * b * nwaves; }
-    a.sp.stamps += b * a.score_stride; a.sp.scores += b * a.score_stride; a.sp.code += b * (int64_t)(a.sp.nj * 64);
-    a.seed += (uint64_t)b;  // (the row, not its object: the draws of a single engine built with seed + row)
-    if (a.tn) { a.tn += o * 3; a.rot += o * 3; }
-    feat += o;
-    if (threadIdx.x < 64 && (int)blockIdx.x < nwaves) particle_front_wave(a, (int64_t)blockIdx.x, nullptr, feat);
-    __syncthreads();  // (as in k_front_small)
-    particle_nn_prune_wg<4>(t6, t3, a, feat);
+#include "front_objects_body.hpp"
+}
+
+// k_front_small_objects with the motion noise and the prune threshold per row (midas_loop_step_batch_rows): std_t, std_r, thr and t2
+// come from row blockIdx.y's record of the parameter table instead of the argument record - four more values by scalar loads through a
+// uniform address, in SGPRs where the twin holds kernel arguments (the squared threshold is the host's: no root, no square here);
+// no lane loads anything it did not load there.  Behind that head the twin's body.
+__global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small_rows(const ObjectRecord* __restrict__ recs,
+                                                                         const int32_t* __restrict__ row_object,
+                                                                         const midas_loop_row_params* __restrict__ rows,
+                                                                         ParticleUpdateArgs a, int nwaves, PuFeat* __restrict__ feat) {
+    const midas_loop_row_params& rp = rows[blockIdx.y];
+    a.std_t = rp.std_t; a.std_r = rp.std_r; a.thr = rp.prune_thr; a.t2 = rp.prune_t2;
+#include "front_objects_body.hpp"
 }
 
 template <int NJ, bool LAZY>
@@ -480,7 +478,7 @@ int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_t
 }
 
 int launch_front_small_objects(midas_ctx* ctx, const midas_object_set* set, const ParticleUpdateArgs& a_in, const double* code,
-                               double* scores, bool wide) {
+                               double* scores, bool wide, const midas_loop_row_params* rows) {
     ParticleUpdateArgs a = a_in;
     // (the set's creation checked every codebook: float32, one D of the sparse scoring's, aligned rows)
     if (!(a.n_live && a.N > 0 && (a.N <= 16384 || (wide && a.N <= MIDAS_LOOP_BATCH_WIDE_MAX_CAP)) && a.sp.stamps && !a.rs.enabled &&
@@ -495,8 +493,9 @@ int launch_front_small_objects(midas_ctx* ctx, const midas_object_set* set, cons
     void* feat;
     const int rc = midas_scratch(ctx, (size_t)set->B * a.N * sizeof(PuFeat), &feat);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_front_small_objects, dim3((unsigned)ceil_div(a.N, 64), (unsigned)set->B), dim3(256), 0, ctx->stream, set->recs,
-                       set->row_object, a, nwaves, (PuFeat*)feat);
+    const dim3 grid((unsigned)ceil_div(a.N, 64), (unsigned)set->B);
+    if (rows) hipLaunchKernelGGL(k_front_small_rows, grid, dim3(256), 0, ctx->stream, set->recs, set->row_object, rows, a, nwaves, (PuFeat*)feat);
+    else hipLaunchKernelGGL(k_front_small_objects, grid, dim3(256), 0, ctx->stream, set->recs, set->row_object, a, nwaves, (PuFeat*)feat);
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
 }

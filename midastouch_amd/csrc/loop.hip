@@ -35,7 +35,7 @@
 namespace midas {
 
 // ANNEAL, first half: the clusters' moments (with the merged weights at their head) into scratch the selection reads
-static int loop_cluster_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopWeightsRowsArgs* merged, LoopMoments& m) {
+static int loop_cluster_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopWeightsParamRowsArgs* merged, LoopMoments& m) {
     const size_t Bz = (size_t)g.B;
     void *part, *cen, *sd, *cnt, *rot;
     int rc;
@@ -59,7 +59,7 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
     g.clocks = s.ctl_d_dev;
 #endif
     int rc;
-    LoopWeightsRowsArgs wa{};
+    LoopWeightsParamRowsArgs wa{};
     bool weights_merged = false;
     if (phases & MIDAS_LOOP_FRONT) {
         ParticleUpdateArgs pa;
@@ -114,16 +114,20 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 // objects (midas_loop_step_batch_objects): every row on the object the set names for it - the front takes trees, lists, field and
 // codebook from the set's records (k_front_small_objects; cb, t6 and t3 are null) and the weights re-project a drifted row onto its
 // own object's poses; the score rows are K_max apart.  Every other phase works on the (B, ...) arrays and never sees a codebook.
+// rows (midas_loop_step_batch_rows; objects only, device draws, ties by index): B records of the filter's parameters - the front, the
+// weights and the annealing decision are launched as the instantiations that take std, threshold, softmax, unit_weights and floor
+// from row blockIdx.y's record (g.rows) where their twins take them from `s`; launch for launch the frame above.
 static int loop_step_batch_frame(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                                  const midas_object_set* objects, const midas_loop_args& s, int32_t phases, int32_t B, int64_t log_stride,
-                                 bool wide) {
+                                 bool wide, const midas_loop_row_params* rows = nullptr) {
     const int64_t cap = s.cap;
     const bool large = wide && cap > LOOP_SMALL_MAX;
     LoopGrid g;
     g.cap = cap; g.B = B; g.slice = (int32_t)cap; g.log_stride = log_stride;
     g.lp_stride = (int32_t)(cap + SCAN_CHUNK);  // (the resample reads whole chunks)
+    g.rows = rows;
     int rc;
-    LoopWeightsRowsArgs wa{};
+    LoopWeightsParamRowsArgs wa{};
     bool weights_merged = false;
     if (phases & MIDAS_LOOP_FRONT) {
         static const midas_tree no_tree{};  // (objects: the kernel takes the lists and the field from the row's record)
@@ -131,7 +135,7 @@ static int loop_step_batch_frame(midas_ctx* ctx, const midas_codebook* cb, const
         fill_particle_update(pa, s, objects ? &no_tree : t6, objects ? &no_tree : t3, cap, s.poses_dev, s.hint_dev, s.valid_dev,
                              s.score_stamps_dev, (s.gt16_dev && s.part_rmse_dev) ? s.gt16_dev : nullptr, s.part_rmse_dev);
         pa.n_live = s.ctl_i_dev + LOOP_I_N;
-        if (objects) rc = launch_front_small_objects(ctx, objects, pa, s.code_dev, s.scores_dev, large);
+        if (objects) rc = launch_front_small_objects(ctx, objects, pa, s.code_dev, s.scores_dev, large, rows);
         else rc = launch_front_small_batch(ctx, t6, t3, pa, cb, s.code_dev, s.scores_dev, B, large);
         if (rc) return rc;
         weights_merged = loop_weights_mergeable(phases);
@@ -174,8 +178,8 @@ int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas
 }
 
 int launch_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args& s, int32_t phases,
-                                   int64_t log_stride, bool wide) {
-    return loop_step_batch_frame(ctx, nullptr, nullptr, nullptr, set, s, phases, set->B, log_stride, wide);
+                                   int64_t log_stride, bool wide, const midas_loop_row_params* rows) {
+    return loop_step_batch_frame(ctx, nullptr, nullptr, nullptr, set, s, phases, set->B, log_stride, wide, rows);
 }
 
 // (the units cut out of this one are loaded with it: midas_ctx_create warms "loop")

@@ -36,6 +36,14 @@ struct LoopWeightsArgs {
 struct LoopWeightsRowsArgs : LoopWeightsArgs {
     const float* const* cb_poses_rows = nullptr;
 };
+// ... and rows is null, or (B) the rows' own filter parameters (midas_loop_step_batch_rows): `softmax` is then row b's, for EVERY
+// row - row 0's too, which the other two records leave as the host wrote it.  The third instantiation of the two weight kernels.
+struct LoopWeightsParamRowsArgs : LoopWeightsRowsArgs {
+    const midas_loop_row_params* rows = nullptr;
+};
+// does row 0 take something from a table as well?  (a constant of the record's type: the branch it guards is not in the other kernels)
+constexpr bool loop_weights_every_row(const LoopWeightsArgs&) { return false; }
+constexpr bool loop_weights_every_row(const LoopWeightsParamRowsArgs&) { return true; }
 
 // trajectory b of a batch (midas_loop_step_batch; blockIdx.y): every array is (B, ...) contiguous - grid_n particles (the capacity),
 // nbl block results, ceil(grid_n / 64) pairs of rmse partials and one control block per trajectory; the codebook poses are shared
@@ -50,6 +58,11 @@ MD void loop_weights_batch(LoopWeightsArgs& a, int64_t b) {
 MD void loop_weights_batch(LoopWeightsRowsArgs& a, int64_t b) {
     loop_weights_batch(static_cast<LoopWeightsArgs&>(a), b);
     if (a.cb_poses_rows) a.cb_poses = a.cb_poses_rows[b];
+}
+// ... and the row's own softmax switch (b = 0 included: its offsets are zero); the record's address depends on b = blockIdx.y alone
+MD void loop_weights_batch(LoopWeightsParamRowsArgs& a, int64_t b) {
+    loop_weights_batch(static_cast<LoopWeightsRowsArgs&>(a), b);
+    a.softmax = a.rows[b].softmax;
 }
 
 // what a thread requests before the live count is looked at (the control block is another launch's output: these travel with it)

@@ -418,8 +418,9 @@ int launch_front_small_batch(midas_ctx* ctx, const midas_tree* t6, const midas_t
                              const midas_codebook* cb, const double* code, double* scores, int32_t B, bool wide = false);
 // the same for rows on different objects (midas_loop_step_batch_objects, k_front_small_objects): `a` without the trees, the vertex
 // lists, the field and the codebook - every workgroup takes those from its row's record of the set; scores and stamps (B, K_max)
+// rows (midas_loop_step_batch_rows): std_t, std_r, thr and t2 of `a` are then not read - k_front_small_rows takes row b's
 int launch_front_small_objects(midas_ctx* ctx, const midas_object_set* set, const ParticleUpdateArgs& a, const double* code,
-                               double* scores, bool wide);
+                               double* scores, bool wide, const midas_loop_row_params* rows = nullptr);
 // One launch of a front as launch_frame_front hands it to the units that hold the kernels, and the form of k_frame_front it asks
 // for (the template's LAZY, FW, SCR, PREF, STATS: front_wave.hpp).  A family's launcher launches the form if it is one of its own
 // and says whether it was.
@@ -628,10 +629,10 @@ constexpr int ESTIMATE_PART_DOUBLES = 36;  // doubles of one 256-particle block'
 int launch_shard_estimate_moments(midas_ctx* ctx, int64_t N, const float* poses, const double* w64, double* part);
 int launch_shard_estimate_finish(midas_ctx* ctx, int64_t nblocks, const double* part_all, float* center, float* stds);
 
-struct LoopWeightsRowsArgs;  // loop_weights.hpp
+struct LoopWeightsParamRowsArgs;  // loop_weights.hpp
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsRowsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop_weights.hip)
+                        const LoopWeightsParamRowsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop_weights.hip)
                         int32_t B = 1);  // trajectories (grid.y): every array (B, ...) contiguous, the scratch ones included
 
 // loop.hip / dbscan.hip - the reference's whole loop body on a variable-size particle set (midas_loop_step)
@@ -640,9 +641,10 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
 int launch_loop_step_batch(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
                            const midas_loop_args& a, int32_t phases, int32_t B, int64_t log_stride,
                            bool wide = false);  // midas_loop_step_batch_wide: capacities beyond the small-set regime
-// the same frame with every row on the object the set names for it (midas_loop_step_batch_objects): set->B rows
+// the same frame with every row on the object the set names for it (midas_loop_step_batch_objects): set->B rows; rows
+// (midas_loop_step_batch_rows): the filter's parameters per row, set->B records in device memory
 int launch_loop_step_batch_objects(midas_ctx* ctx, const midas_object_set* set, const midas_loop_args& a, int32_t phases,
-                                   int64_t log_stride, bool wide);
+                                   int64_t log_stride, bool wide, const midas_loop_row_params* rows = nullptr);
 
 // The phases of a loop frame, what launch_loop_step and launch_loop_step_batch launch alike: each is the host launcher of the unit
 // that holds its kernels.  What they are launched over - the single call: one trajectory, the slice strides 0 (the kernels' defaults).
@@ -653,6 +655,7 @@ struct LoopGrid {
     int32_t lp_stride = 0;     //          prefix values between their tables,
     int64_t log_stride = 0;    //          doubles between their log rows
     double* clocks = nullptr;  // MIDAS_ANNEAL_CLOCKS (the single call): k_loop_xe's phase clocks
+    const midas_loop_row_params* rows = nullptr;  // midas_loop_step_batch_rows: B records, the phases launch the kernels that read them
     unsigned nbcap() const { return (unsigned)ceil_div(cap, SCAN_BLOCK); }
     unsigned by() const { return (unsigned)B; }
     bool batch() const { return slice != 0; }
@@ -662,8 +665,8 @@ inline int32_t loop_bound(int64_t n) { return (int32_t)(n < (1 << 30) ? n : (1 <
 bool loop_weights_mergeable(int32_t phases);
 // (objects: rows on different objects - K is then the set's K_max, the stride of the score rows and k_loop_xe's clamp, and the drift
 // re-projection gathers row b's poses from the set's table)
-int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t K, bool rmse, bool merged, LoopWeightsRowsArgs& wa,
-                       const midas_object_set* objects = nullptr);
+int loop_weights_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, int64_t K, bool rmse, bool merged,
+                       LoopWeightsParamRowsArgs& wa, const midas_object_set* objects = nullptr);
 // anneal.hip - ANNEAL behind the clusters' moments (loop_cluster_phase, loop.hip): the decision and the annealed set as an index list
 struct LoopMoments { float *cen, *sd; int64_t* cnt; double* rot; };
 enum class LoopAnneal {
@@ -677,10 +680,12 @@ inline LoopAnneal loop_anneal_regime(bool frozen, bool aten, bool small) {
 }
 int loop_anneal_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopMoments& m, LoopAnneal regime);
 // anneal_small.hip - the decision alone, for the regimes of anneal.hip (hist / sel_state: the select state it clears, or null)
+// (g.rows: every row's floor from its record - k_loop_decide_rows; frozen and aten_order are then 0)
 int launch_loop_decide(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopMoments& m, uint32_t* hist,
                        int32_t* sel_state, int32_t frozen, int32_t aten_order);
 // the single-workgroup annealing of B trajectories: with the decision from the moments m (a second workgroup
-// writes the centres' rotations), or - m null - on a plan the host left in ctl_i (launch_anneal_select)
+// writes the centres' rotations), or - m null - on a plan the host left in ctl_i (launch_anneal_select); g.rows (with m): floor_n is
+// not read, row b's floor comes from its record (k_loop_anneal_small_rows)
 int launch_anneal_small(midas_ctx* ctx, const LoopGrid& g, int32_t* ctl_i, double* ctl_d, const LoopMoments* m, float* centers_out,
                         float* stds_out, int32_t floor_n, const double* w, int32_t* src);
 // loop_resample.hip - RESAMPLE over the cap2 slots a trajectory the annealed set may take; stream_draws, a call that ends in front of

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .engine import FilterEngine
-from .particle_filter import Particles, particle_filter, particle_rmse
+from .particle_filter import Particles, cfg_motion_noise, particle_filter, particle_rmse
 from .synthetic import make_codebook, make_trajectory
 from .tactile_tree import tactile_tree
 
@@ -40,6 +40,8 @@ class Sequence:
     obj_model: str
     mesh_tree: Optional[object] = None  # an ops.Tree over mesh_vertices already on the device (shared with other engines)
     log_id: Optional[object] = None     # the log's number in `filter_stats` (None: cfg.expt.log_id)
+    cfg: Optional[object] = None        # the run's own config in a `filter_sweep` (None: the sweep's) - its dataset's noise_t, noise_r,
+                                        # num_particles and noise_ratio (config/expt/ycb.yaml, mcmaster.yaml) and pen.max
 
 
 def synthetic_sequence(cfg, device, T: int = 100, D: Optional[int] = None, seed: int = 0) -> Sequence:
@@ -339,6 +341,41 @@ def sweep_plan(runs, trials: int = 1, max_length=None, max_frames=None) -> dict:
                 row_trial=row_trial, run_lengths=run_len, lengths=lengths, T_max=max(lengths))
 
 
+def sweep_row_params(cfg, runs, plan, softmax=True, floor=1000, update_freq=1) -> dict:
+    """What the rows of a sweep take for themselves, on the host: run r's config is `runs[r].cfg` (None: the sweep's `cfg`) - its
+    num_particles, noise_ratio, motion noise (noise_t, noise_r) and prune threshold (tdn.render.pen.max) - and its runner's preset is
+    softmax / floor / update_freq, each one value for the sweep or one per run (filter/filter.py: softmax, floor 1000;
+    filter/filter_real.py: raw scores, floor 10 000, update_freq).  Row r * trials + k takes run r's.
+    -> run_cfgs; per row: num_particles, noise_ratio, sig_t, sig_r, pen_max, softmax, floor, update_freq; capacity (the largest
+    count), wide (beyond 16 384) and engine: the keywords `BatchLoopEngine.for_objects` gets - a scalar where all rows agree (with
+    scalars only the batch runs the shared-parameter frame), a list of B values otherwise."""
+    from . import _lib
+    from .particle_filter import _cfg_get
+
+    R = len(runs)
+
+    def per_run(name, v, conv):
+        if isinstance(v, (list, tuple)):
+            if len(v) != R:
+                raise ValueError(f"filter_sweep: {len(v)} values of {name} for {R} runs (one value, or one per run)")
+            return [conv(x) for x in v]
+        return [conv(v)] * R
+    presets = dict(softmax=per_run("softmax", softmax, bool), floor=per_run("floor", floor, int),
+                   update_freq=[max(u, 1) for u in per_run("update_freq", update_freq, int)])
+    run_cfgs = [cfg if getattr(seq, "cfg", None) is None else seq.cfg for seq in runs]
+    noise = [cfg_motion_noise(c) for c in run_cfgs]
+    of_run = dict(num_particles=[int(c.expt.params.num_particles) for c in run_cfgs],
+                  noise_ratio=[c.expt.params.noise_ratio for c in run_cfgs],
+                  sig_t=[m["sig_t"] for m in noise], sig_r=[m["sig_r"] for m in noise],
+                  pen_max=[float(_cfg_get(c, "tdn", "render", "pen", "max")) for c in run_cfgs], **presets)
+    out = {k: [v[r] for r in plan["row_run"]] for k, v in of_run.items()}
+    out["run_cfgs"] = run_cfgs
+    out["capacity"] = max(out["num_particles"])
+    out["wide"] = out["capacity"] > _lib.LOOP_BATCH_MAX_CAP
+    out["engine"] = {k: (out[k][0] if all(v == out[k][0] for v in out[k]) else list(out[k])) for k in ("sig_t", "sig_r", "pen_max", "floor", "softmax")}
+    return out
+
+
 def sweep_stats(records, times, host_times, **fixed) -> dict:
     """One row's `filter_stats` (filter.py:99-116, the keys `filter` returns) from its frame-log records and the batch frames'
     periods - both cut to the row's own frames by the caller; fixed: the entries that do not depend on the frames."""
@@ -375,14 +412,19 @@ def sweep_inputs(runs, plan, device):
 
 
 def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, max_frames: int = None, cluster: bool = True,
-                 cluster_every: int = 50, softmax: bool = True, update_freq: int = 1, floor: int = 1000,
+                 cluster_every: int = 50, softmax=True, update_freq=1, floor=1000,
                  results_root: Optional[str] = None, draws: str = "device") -> list:
     """The reference's experiment - `bash/run_filter.sh`: objects x logs x trials, one `filter/filter.py` process each - as ONE batch
     on the device: every (run, trial) is a row of a `BatchLoopEngine.for_objects`, a frame of all rows is one `step()`.
 
     runs: a list of `Sequence`; runs that share one `codebook` object stand on one object of the batch.  Row r * trials + k is run r,
-    trial k, on the Philox streams of seed + row: it holds, frame for frame, what `filter(cfg, runs[r], seed=seed + row,
-    start="device", ...)` computes.  Pace is fixed: frame t of every row is frame t of its log.  Rows start on the device on the frames
+    trial k, on the Philox streams of seed + row: it holds, frame for frame, what `filter(run_cfg, runs[r], seed=seed + row,
+    start="device", softmax=..., floor=..., update_freq=..., cluster_every=...)` computes.  run_cfg is the run's own `Sequence.cfg`
+    (None: `cfg`): a run takes its dataset's noise_t, noise_r, num_particles, noise_ratio and pen.max from it - config/expt/ycb.yaml
+    and mcmaster.yaml in one sweep; the batch's capacity is the largest count, wide beyond 16 384.  softmax, floor and update_freq are
+    each one value or one per run - `filter` and `filter_real`'s presets as rows of one batch.  Rows that differ in any of these go
+    through the engine's per-row parameter table (two uploads a sweep: the still and the moving frames); eps, the DBSCAN cadence and
+    the resample mode stay the sweep's.  Pace is fixed: frame t of every row is frame t of its log.  Rows start on the device on the frames
     seen while prev_idx == 0 (frames 0 and 1, filter.py:152-160; `BatchLoopEngine.start`); DBSCAN runs on every cluster_every-th
     frame, the measurement update on every update_freq-th (unit weights in between, filter_real.py:205-212).  Logs of different
     lengths: a row whose log has ended is stepped on (identity odometry, its last code and gt) and its surplus frames are never read
@@ -394,7 +436,6 @@ def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, m
     import gc
     import os
 
-    from . import _lib
     from .batch_loop_engine import BatchLoopEngine
     from .loop_engine import log_records
 
@@ -405,24 +446,25 @@ def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, m
     runs = list(runs)
     plan = sweep_plan(runs, trials, expt_cfg.max_length, max_frames)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    init_particles = int(expt_cfg.params.num_particles)
-    noise_ratio = expt_cfg.params.noise_ratio
-    cluster_every, update_freq = max(int(cluster_every), 1), max(int(update_freq), 1)
+    rp = sweep_row_params(cfg, runs, plan, softmax, floor, update_freq)
+    cluster_every = max(int(cluster_every), 1)
     B, T_max = len(plan["row_run"]), plan["T_max"]
 
     pfs = []
-    for r in plan["objects"]:  # one particle_filter per object: init_noise (the mesh's diagonal), pen_max, the mesh tree
-        pf = particle_filter(cfg, runs[r].mesh_vertices, noise_ratio, downsample=1, device=device)
-        if runs[r].mesh_tree is not None:
-            pf._mesh_tree = runs[r].mesh_tree
+    for r, seq in enumerate(runs):  # one particle_filter per RUN, deliberately, where one per object did before: init_noise (the mesh's
+        # diagonal x the run's noise_ratio), pen_max and log_id follow the run's own cfg.  Runs of one object repeat the mesh's host-side
+        # set-up (vertices, diagonal: no device work); the mesh tree is asked of an object's first run only.  Same results.
+        pf = particle_filter(rp["run_cfgs"][r], seq.mesh_vertices, rp["run_cfgs"][r].expt.params.noise_ratio, downsample=1, device=device)
+        if seq.mesh_tree is not None:
+            pf._mesh_tree = seq.mesh_tree
         pfs.append(pf)
-    eng = BatchLoopEngine.for_objects([(runs[r].codebook, None, pf.mesh_kdtree) for r, pf in zip(plan["objects"], pfs)],
-                                      plan["row_object"], init_particles, sig_t=pfs[0].motion_noise["sig_t"],
-                                      sig_r=pfs[0].motion_noise["sig_r"], pen_max=pfs[0].pen_max, seed=seed, softmax=softmax, floor=floor,
-                                      cluster=cluster, cluster_every=cluster_every, log_frames=max(T_max + 8, 64), device=device,
-                                      wide=init_particles > _lib.LOOP_BATCH_MAX_CAP)
+    eng = BatchLoopEngine.for_objects([(runs[r].codebook, None, pfs[r].mesh_kdtree) for r in plan["objects"]],
+                                      plan["row_object"], rp["capacity"], seed=seed, cluster=cluster, cluster_every=cluster_every,
+                                      log_frames=max(T_max + 8, 64), device=device, wide=rp["wide"], **rp["engine"])
     odoms, codes, gts = sweep_inputs(runs, plan, device)
-    init_noise = torch.tensor([pfs[i].init_noise for i in plan["row_object"]], dtype=torch.float32, device=device)
+    init_noise = torch.tensor([pfs[r].init_noise for r in plan["row_run"]], dtype=torch.float32, device=device)
+    counts = rp["num_particles"]
+    shared_freq = rp["update_freq"][0] if len(set(rp["update_freq"])) == 1 else None
 
     events = [torch.cuda.Event(enable_timing=True)]
     host_times = []
@@ -434,10 +476,11 @@ def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, m
             t0 = time.time()
             starting = t < 2  # prev_idx == 0 (filter.py:152): frames 0 and 1 re-initialise
             if starting:
-                eng.start(gts[t], init_noise, n=init_particles, reset_annealing=t == 0)
+                eng.start(gts[t], init_noise, n=counts, reset_annealing=t == 0)
             # (the reference does not call motionModel on the starting frames: no motion noise there)
+            unit = t % shared_freq != 0 if shared_freq is not None else [t % f != 0 for f in rp["update_freq"]]
             (eng.step_still if starting else eng.step)(odoms[t], codes[t], gts=gts[t], dbscan=cluster and t % cluster_every == 0,
-                                                       unit_weights=t % update_freq != 0)
+                                                       unit_weights=unit)
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
             events.append(ev)
@@ -449,10 +492,10 @@ def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, m
     log = eng._log.cpu().numpy()  # one read-back; every row is parsed up to its own last frame only
     out = []
     for row, (r, k, T) in enumerate(zip(plan["row_run"], plan["row_trial"], plan["lengths"])):
-        seq, pf = runs[r], pfs[plan["row_object"][row]]
+        seq, pf = runs[r], pfs[r]
         stats = sweep_stats(log_records(log[row], 0, T, who=f"row {row}, "), times[:T], host_times[:T], obj_name=seq.obj_model,
-                            tree_size=len(seq.codebook), noise_ratio=noise_ratio, init_noise=pf.init_noise,
-                            init_particles=init_particles, log_id=_log_id(seq, expt_cfg), trial_id=k, batch_rows=B)
+                            tree_size=len(seq.codebook), noise_ratio=rp["noise_ratio"][row], init_noise=pf.init_noise,
+                            init_particles=counts[row], log_id=_log_id(seq, rp["run_cfgs"][r].expt), trial_id=k, batch_rows=B)
         if results_root is not None:
             save_filter_stats(stats, os.path.join(results_root, str(seq.obj_model), stats["log_id"], f"trial_{k:02d}"))
         out.append(stats)

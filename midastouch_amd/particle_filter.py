@@ -105,6 +105,21 @@ def start_transforms(tn, rot_deg) -> np.ndarray:
     return Tn
 
 
+def cfg_motion_noise(cfg, real: bool = False) -> dict:
+    """`particle_filter.motion_noise` of a config, without a mesh: {"mu": 0, "sig_r", "sig_t"} from cfg.expt.params.noise_r / noise_t -
+    the {sim, real} form of expt/ycb.yaml or the scalar form of expt/mcmaster.yaml:19-20."""
+    which = "real" if real else "sim"
+
+    def _noise(key):
+        v = _cfg_get(cfg, "expt", "params", key)
+        try:
+            return float(_cfg_get(v, which))
+        except (TypeError, KeyError, AttributeError):
+            return float(v)
+
+    return {"mu": 0, "sig_r": _noise("noise_r"), "sig_t": _noise("noise_t")}
+
+
 class particle_filter:
     """Update and propagation of SE(3) particles on a mesh (:93-469)."""
 
@@ -115,16 +130,7 @@ class particle_filter:
         self.mesh_scale = float(np.linalg.norm(verts.max(axis=0) - verts.min(axis=0)))  # trimesh mesh.scale
         self.mesh_vertices = verts[::downsample, :]
         self._mesh_tree = None  # built on first use (needs the GPU)
-        which = "real" if real else "sim"
-
-        def _noise(key):  # accepts {sim, real} (expt/ycb.yaml) and the scalar form of expt/mcmaster.yaml:19-20
-            v = _cfg_get(cfg, "expt", "params", key)
-            try:
-                return float(_cfg_get(v, which))
-            except (TypeError, KeyError, AttributeError):
-                return float(v)
-
-        self.motion_noise = {"mu": 0, "sig_r": _noise("noise_r"), "sig_t": _noise("noise_t")}
+        self.motion_noise = cfg_motion_noise(cfg, real)
         self.particle_var = torch.tensor([float("inf")])
         self.topk_ties = "index"  # annealing(): whom torch.topk takes inside a tie ("aten_cpu": as the reference on the CPU)
         self.init_noise = [self.mesh_diagonal() / 3.0 * noise, 180.0 / 3.0 * noise]  # (:124-127)

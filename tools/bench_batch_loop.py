@@ -24,12 +24,15 @@ One JSON line per engine form with each figure's median over the repeats and [mi
                   the mixed batch (compare n_final_min / n_final_max).  It uses the plain constructor only: to take the figure on an
                   earlier commit, copy this file into that checkout's tools/ and run it there with --form=objects_split
   single_object   one plain BatchLoopEngine of the same B with every row on object 0 (what G codebooks cost beside one)
+  objects_rows    objects_mixed with the filter's parameters per row (midas_loop_step_batch_rows), the SAME values in every row: the same
+                  work, so the difference to objects_mixed is the cost of the parameter table (--form=objects_rows only)
 --profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch, with --objects the mixed
   batch, with --form=NAME that form), no timing."""
 import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -79,16 +82,20 @@ codes = torch.as_tensor(np.stack([tr.codes for tr in trajs], axis=1)).to(dev)   
 gts = torch.as_tensor(np.stack([tr.gt_poses for tr in trajs], axis=1)).to(dev, torch.float32)
 starts = torch.as_tensor(np.stack([wide_start(cbs[ROW_OBJ[b]].extents, trajs[b].gt_poses[0], N0, 3000 + b) for b in range(B)])).to(dev, torch.float32)
 kw = dict(floor=FLOOR, cluster_every=EVERY, device=dev)
+HOST_US = None  # of the latest timed() run
 
 
 def timed(step, frames):
     """ms of every frame by events around its enqueue (the stream is idle at the start, the frames queue behind each other)."""
+    global HOST_US
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(frames + 1)]
     torch.cuda.synchronize()
     ev[0].record()
+    t0 = time.perf_counter()
     for t in range(frames):
         step(t)
         ev[t + 1].record()
+    HOST_US = round(1e6 * (time.perf_counter() - t0) / frames, 2)  # the host's time to enqueue a frame (and record its event)
     torch.cuda.synchronize()
     return [ev[t].elapsed_time(ev[t + 1]) for t in range(frames)]
 
@@ -139,13 +146,19 @@ def triple(c):
     return (c.poses, c.embeddings, c.mesh_vertices)
 
 
-def run_objects_mixed():
-    eng = BatchLoopEngine.for_objects([triple(c) for c in cbs], ROW_OBJ, N0, seed=SEED, batched_dbscan=DBSCAN, **kw, **({"wide": True} if wide else {}))
+def run_objects_mixed(per_row=False):
+    rows_kw = dict(floor=[FLOOR] * B, sig_t=[2e-4] * B, sig_r=[0.5] * B, pen_max=[0.002] * B, softmax=[True] * B) if per_row else {}
+    eng = BatchLoopEngine.for_objects([triple(c) for c in cbs], ROW_OBJ, N0, seed=SEED, batched_dbscan=DBSCAN, **{**kw, **rows_kw},
+                                      **({"wide": True} if wide else {}))
     eng.set_particles(starts)
     eng.project_to_codebook()
     ms = timed(lambda t: eng.step(odoms[t + 1], codes[t + 1], gts=gts[t + 1]), T)
     n = eng.n
-    return ms, {"n_final_min": min(n), "n_final_max": max(n)}
+    return ms, {"n_final_min": min(n), "n_final_max": max(n), "host_enqueue_us": HOST_US, **({"row_table_uploads": eng.row_table_uploads} if per_row else {})}
+
+
+def run_objects_rows():
+    return run_objects_mixed(per_row=True)
 
 
 def run_objects_split():
@@ -197,7 +210,7 @@ if seeded:
 if G:
     forms = (("objects_mixed", run_objects_mixed), ("objects_split", run_objects_split), ("single_object", run_single_object))
 if FORM is not None:
-    forms = tuple(f for f in forms if f[0] == FORM)
+    forms = tuple(f for f in forms + ((("objects_rows", run_objects_rows),) if G else ()) if f[0] == FORM)
     if not forms:
         sys.exit(f"bench_batch_loop.py: no form {FORM!r} in this mode")
 if profile:  # (the first form: the batch engine of the mode, or the one --form names)

@@ -10,6 +10,11 @@ and commits can be alternated; one JSON line with each figure's median over the 
   filter_runs   filter() on each of the B runs in turn (seed + row): wall seconds of all B calls, median frame.  --start=device: with
                 filter(start="device").  It uses nothing newer than filter() itself: to take the figure on an earlier commit, copy this
                 file into that checkout's tools/ and run it there
+  sweep_mixed   two datasets in ONE sweep: the first G / 2 objects' runs under a ycb-like config (N0 particles, noise_t 2e-4), the others'
+                under a mcmaster-like one (N0 / 2 particles, or --nb=N of them; noise_t 1e-4) through `Sequence.cfg` - the rows take their parameters from
+                the engine's per-row table
+  sweep_split   the same runs as two sweeps in turn, one per config - what the two datasets cost before (works on an earlier commit, as
+                filter_runs does): wall seconds of both calls, the moving-frame median of each
   start_device  BatchLoopEngine.start() of the B rows: wall milliseconds of the call with the device drained behind it
   start_host    the host route for the same rows: init_filter per row, set_particles, project_to_codebook (works on an earlier commit, as
                 filter_runs does)"""
@@ -30,8 +35,10 @@ from midastouch_amd.particle_filter import particle_filter
 from midastouch_amd.synthetic import make_codebook, make_trajectory
 from midastouch_amd.tactile_tree import tactile_tree
 
-FORM, START = None, "host"
+FORM, START, NB = None, "host", None
 for a in sys.argv[1:]:
+    if a.startswith("--nb="):
+        NB = int(a.split("=", 1)[1])
     if a.startswith("--form="):
         FORM = a.split("=", 1)[1]
     if a.startswith("--start="):
@@ -39,8 +46,8 @@ for a in sys.argv[1:]:
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 G, B, N0, K, T, R = (int(argv[i]) if len(argv) > i else d for i, d in enumerate((10, 50, 10000, 50000, 300, 3)))
 D, FLOOR, SEED = 512, 1000, 4000
-if FORM not in ("sweep", "filter_runs", "start_device", "start_host") or B % G:
-    sys.exit("bench_filter_sweep.py --form=sweep|filter_runs|start_device|start_host [G B N0 K T repeats], G dividing B")
+if FORM not in ("sweep", "filter_runs", "sweep_mixed", "sweep_split", "start_device", "start_host") or B % G:
+    sys.exit("bench_filter_sweep.py --form=sweep|filter_runs|sweep_mixed|sweep_split|start_device|start_host [G B N0 K T repeats], G dividing B")
 dev = torch.device("cuda", 0)
 NAMES = ("004_sugar_box", "035_power_drill", "025_mug", "cotter-pin")
 cfg = load_config([f"expt.params.num_particles={N0}"])
@@ -90,6 +97,26 @@ def form_filter_runs():
     return {"wall_s": round(w, 4), "frame_median_us": med, "start_frame_mean_us": first}
 
 
+# the two datasets of sweep_mixed / sweep_split: the runs of the first G / 2 objects and of the others
+HALF = (G // 2) * (B // G)
+CFG_B = load_config(["expt=mcmaster", f"expt.params.num_particles={N0 // 2 if NB is None else NB}"])
+
+
+def form_sweep_mixed():
+    for row, seq in enumerate(runs):
+        seq.cfg = cfg if row < HALF else CFG_B
+    w, stats = wall(lambda: runner.filter_sweep(cfg, runs, seed=SEED, device=dev, floor=FLOOR))
+    med, first = frames_us(stats[:1])
+    return {"wall_s": round(w, 4), "frame_median_us": med, "start_frame_mean_us": first}
+
+
+def form_sweep_split():
+    w, (a, b) = wall(lambda: (runner.filter_sweep(cfg, runs[:HALF], seed=SEED, device=dev, floor=FLOOR),
+                              runner.filter_sweep(CFG_B, runs[HALF:], seed=SEED + HALF, device=dev, floor=FLOOR)))
+    (med_a, _), (med_b, _) = frames_us(a[:1]), frames_us(b[:1])
+    return {"wall_s": round(w, 4), "frame_median_us": round(med_a + med_b, 2), "frame_median_a_us": med_a, "frame_median_b_us": med_b}
+
+
 def start_engine():
     objs, pfs = [], []
     for i in range(G):
@@ -123,8 +150,9 @@ def form_start_host():
     return {"wall_ms": round(1e3 * w, 3)}
 
 
-run = {"sweep": form_sweep, "filter_runs": form_filter_runs, "start_device": form_start_device, "start_host": form_start_host}[FORM]
-if FORM == "sweep":
+run = {"sweep": form_sweep, "filter_runs": form_filter_runs, "sweep_mixed": form_sweep_mixed, "sweep_split": form_sweep_split,
+       "start_device": form_start_device, "start_host": form_start_host}[FORM]
+if FORM.startswith("sweep"):
     run()  # warm-up: code objects, scratch, allocator
 if FORM == "filter_runs":
     runner.filter(cfg, runs[0], device=dev, seed=SEED, floor=FLOOR, **({"start": START} if START != "host" else {}))  # (the same)
