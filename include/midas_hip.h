@@ -211,8 +211,15 @@ int midas_mt19937_rand64_chunked(midas_ctx* ctx, uint32_t* state_dev, int64_t sk
  * pieces as midas_mt19937_rand64_chunked, J_c counting the words of ALL segments (2 per float64, count (+ 16 when count is not a
  * multiple of 16) per normal draw); in pieces the sum must be >= MIDAS_MT19937_HIST_WORDS.  NULL / 0: the sequential walk, which
  * leaves the history (when hist_dev is given and the sum is long enough) for a following call in pieces. */
+/* MIDAS_MT_SEGMENT_RAND32: torch.rand(1) of a float32 value - the offset of the reference's systematic resampler (low_var,
+ * modules/particle_filter.py:291): ONE 32-bit output, its low 24 bits times 2^-24.  count must be 1; out_dev takes the value as
+ * the float64 that holds it exactly (one double a stream), where the resample kernels read it (u32 == MIDAS_U32_FROM_U).  In the
+ * counted calls the segment's count is a CONTROL WORD: one value when it is not zero, none (and no word consumed) when it is
+ * zero - ctl_i[MIDAS_LOOP_I_NDRAW] of a loop frame, since the reference's resampler returns before it draws when the weights are
+ * all zero or hold a NaN (:237-241); per must be 1, the word must lie in [0, bound], and stream b's value lands at out_dev + b bound. */
 #define MIDAS_MT_SEGMENT_RAND64 0
 #define MIDAS_MT_SEGMENT_NORMAL32 1
+#define MIDAS_MT_SEGMENT_RAND32 2
 typedef struct midas_mt_segment {
     int32_t kind;
     int32_t pad_;
@@ -243,7 +250,8 @@ int midas_mt19937_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* states_dev, i
  *   count_dev  one device integer, read when the kernels run; the segment draws numel = per x count values (per = 3 for an (n, 3)
  *              normal, 1 for n uniforms);
  *   bound      host-known upper bound of the count: sizes the scratch and the grids, nothing else (out_dev holds per x bound values);
- *   mean / std / out_dev as midas_mt_segment; kind MIDAS_MT_SEGMENT_RAND64 or MIDAS_MT_SEGMENT_NORMAL32.
+ *   mean / std / out_dev as midas_mt_segment; kind MIDAS_MT_SEGMENT_RAND64, MIDAS_MT_SEGMENT_NORMAL32 or MIDAS_MT_SEGMENT_RAND32
+ *              (see there: the count is then a control word, 0 or 1 values).
  * For the counts found there the call is midas_mt19937_draws with those counts, number for number: the outputs, the state afterwards
  * and the words consumed (skip_words, then 2 per float64, numel (+ 16 when numel is not a multiple of 16) per normal draw).  A segment
  * whose count is 0 consumes and writes nothing; output elements at or beyond numel are not written.
@@ -288,7 +296,14 @@ int midas_mt19937_draws_counted_batch(midas_ctx* ctx, int32_t B, uint32_t* state
 int midas_cdf(midas_ctx* ctx, int64_t N, const double* w_dev, double* cdf_dev, int32_t* status_dev);
 /* idx[i] for M output slots. MULTINOMIAL: first j with cdf[j] >= u[i]; u_dev = M float64 uniforms
  * (NULL -> Philox spec stream (seed, step)).  SYSTEMATIC: first j with cdf[j] > fmod(i/M + u32/M, 1);
- * u32 < 0 -> Philox.  Replaces torch.multinomial / the low_var loop (particle_filter.py:245,295-303). */
+ * u32 < 0 -> Philox.  Replaces torch.multinomial / the low_var loop (particle_filter.py:245,295-303).
+ * The systematic offset has a third source, here and in every argument record that carries `u32` beside a pointer to the
+ * uniforms (midas_loop_args, the step and tail records; not the sharded routes): u32 == MIDAS_U32_FROM_U takes it from DEVICE
+ * memory - the first double of the trajectory's row of uniforms (u_dev[0] here and for a single trajectory, u_dev[b x row] for
+ * trajectory b of a batch, the row being what the multinomial mode's uniforms take: N, or the capacity of a loop engine), a float64
+ * that holds a float32 value exactly (MIDAS_MT_SEGMENT_RAND32 writes it).  u_dev must then be given.  Every other u32 means what
+ * it meant: >= 0 the offset itself, any other negative value Philox. */
+#define MIDAS_U32_FROM_U (-2.0f)
 int midas_resample_search(midas_ctx* ctx, int64_t N, const double* cdf_dev, int64_t M, int32_t mode,
                           const double* u_dev, float u32, uint64_t seed, uint64_t step,
                           int32_t* idx_dev);

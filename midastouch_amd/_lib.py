@@ -172,7 +172,8 @@ class MtSegment(C.Structure):
                 ("out_dev", C.c_void_p)]
 
 
-MT_SEGMENT_RAND64, MT_SEGMENT_NORMAL32 = 0, 1
+MT_SEGMENT_RAND64, MT_SEGMENT_NORMAL32, MT_SEGMENT_RAND32 = 0, 1, 2
+U32_FROM_U = -2.0  # MIDAS_U32_FROM_U: the systematic offset stands in device memory, the first double of the trajectory's row of `u`
 
 
 class MtCountedSegment(C.Structure):

@@ -49,6 +49,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 from types import SimpleNamespace
 
 import numpy as np
@@ -381,11 +382,23 @@ class BatchLoopEngine(_LoopBase):
         self._write_annealing_state(pv, ip)
 
     # ---- seeded runs ----------------------------------------------------------------------------------------------
+    def seed_torch_streams_low_var(self, seeds):
+        """seed_torch_streams for an engine built with resample="low_var" / "low_var_batch": behind annealing row b draws the one
+        float32 `torch.rand(1)` of the systematic resampler (particle_filter.py:291) - none on a frame where the resampler returns
+        before it draws (NDRAW = 0: the row's stream stands still) - and the resample reads row b's offset from device memory
+        (MIDAS_U32_FROM_U).  Row b is bit for bit a LoopEngine with seed_torch_stream_low_var(seeds[b]).  A method of its own:
+        seed_torch_streams on a systematic engine refuses, as it always did."""
+        return self._seed_torch_streams(seeds, True)
+
     def seed_torch_streams(self, seeds):
+        return self._seed_torch_streams(seeds, False)
+
+    def _seed_torch_streams(self, seeds, systematic: bool):
         """Trajectory b draws as a process of the reference under torch.manual_seed(seeds[b]) (or continues the torch.Generator
         seeds[b]): `torch.normal(0, mul * sig_t, (n_b, 3))`, `torch.normal(0, mul * sig_r, (n_b, 3))` with n_b ITS live count
         (add_noise_to_odom, particle_filter.py:326-335) and, behind annealing, n_set_b float64 uniforms (the resampler's
-        torch.multinomial, :245) - none for a row whose weights are all zero or hold a NaN on that frame, where the resampler returns
+        torch.multinomial, :245) or - seed_torch_streams_low_var on an engine built with resample="low_var" -
+        its one float32 offset (torch.rand(1), :291) - none for a row whose weights are all zero or hold a NaN on that frame, where the resampler returns
         before it draws (:237-241; ctl_i[b][LOOP_I_NDRAW]) - all counts read on the device (midas_mt19937_draws_counted_batch); ties of annealing's top-k follow
         ATen's CPU kernel (`topk_ties` becomes "aten_cpu").  Returns the TorchCpuStreams (manual_seed / from_host / to_host per
         row).  seeds=None: back to Philox draws and ties by index.
@@ -405,7 +418,7 @@ class BatchLoopEngine(_LoopBase):
         if len(seeds) != self.B:
             raise MidasError(f"{len(seeds)} seeds for a batch of {self.B} trajectories")
         from .torch_rng import TorchCpuStreams
-        st, need = self._seed_streams(TorchCpuStreams, seeds)
+        st, need = self._seed_streams(TorchCpuStreams, seeds, systematic)
         self.topk_ties = "aten_cpu"
         self._scratch = max(self._scratch, need)
         self.ctx.call("midas_scratch_reserve", self._scratch)  # (the generator shares the engine's context)
@@ -442,8 +455,15 @@ class BatchLoopEngine(_LoopBase):
         """Enqueues one frame of every trajectory and reads nothing back: odoms (B,4,4), codes (B,D), gts (B,4,4) or None.
         dbscan: None = on every `cluster_every`-th frame (filter.py:182), True / False to force - for all trajectories alike.
         unit_weights: a frame without measurement update (filter_real.py:205-212) - a bool, or B bools: the rows' own cadences.
+        u32: the systematic resampler's offset (resample="low_var") - a number for every row (< 0: Philox, keyed by seed + row), or B
+        values (a host or device tensor, a list): row b resamples with its own, as a LoopEngine stepped with u32 = values[b] does.
+        The B values go to device memory (MIDAS_U32_FROM_U) through the entry that takes draws: not for a wide engine or per-row
+        parameters, and not on a seeded frame, where the streams draw the offsets.
         A frame with another motion noise than multiplier x (sig_t, sig_r) - LoopEngine.step's `std_override` - is `step_still`."""
         row_key, unit_weights = self._row_plan(multiplier, unit_weights, self._std_override)  # (checks only)
+        u32_rows = None if isinstance(u32, numbers.Real) else self._u32_rows(u32, row_key)  # (checks, then a (B,) column write)
+        u32 = _lib.U32_FROM_U if u32_rows is not None else u32
+        u32_seeded = self._seeded_u32(u32) if self.torch_streams is not None else None  # (a check as well)
         phases = self._phase_mask(ALL_PHASES, dbscan)
         odoms, codes, gts = frame_operands(self.device, (self.B,), self.D, odoms, codes, gts)
         rows = None if row_key is None else self._row_table(row_key)  # (behind every refusal: a refused frame has changed nothing)
@@ -470,6 +490,7 @@ class BatchLoopEngine(_LoopBase):
             # draws no uniforms on this frame - its stream stays where it is, the other rows' move on
             a.tn, a.rot, a.u = _ptr(self._tn), _ptr(self._rot), _ptr(self._u)
             a.stream_draws = 1
+            a.u32 = u32_seeded
             try:
                 self._seeded_frame(st, (a.std_t, a.std_r), self.cap, self.cap,
                                    lambda: call(self.ctx.lib.midas_loop_step_batch_draws, phases & ~_lib.LOOP_RESAMPLE),
@@ -477,6 +498,12 @@ class BatchLoopEngine(_LoopBase):
             finally:
                 a.tn = a.rot = a.u = None
                 a.stream_draws = 0
+        elif u32_rows is not None:  # the rows' own offsets, read from the first slot of each row of uniforms
+            a.u = _ptr(u32_rows)
+            try:
+                call(self.ctx.lib.midas_loop_step_batch_draws, phases)
+            finally:
+                a.u = None
         elif self._topk_ties == "aten_cpu":
             call(self.ctx.lib.midas_loop_step_batch_draws, phases)  # (Philox draws, the ATen tie rule)
         elif self.wide:
@@ -484,6 +511,25 @@ class BatchLoopEngine(_LoopBase):
         else:
             call(self.ctx.lib.midas_loop_step_batch, phases)
         self._frame_done()
+
+    def _u32_rows(self, u32, row_key):
+        """B systematic offsets as a frame reads them from device memory: the first double of every row of a (B, cap) buffer of the
+        engine's, rewritten per frame on the stream (the float32 values, exactly)."""
+        if self.mode != _lib.RESAMPLE_SYSTEMATIC:
+            raise MidasError("u32 per row is the systematic resampler's offset: resample='low_var' / 'low_var_batch' only")
+        if self.torch_streams is not None:
+            raise MidasError("seed_torch_streams: the streams draw the systematic offsets - passing u32 would desynchronise them from the "
+                             "reference's")
+        if self.wide or row_key is not None:
+            raise MidasError("u32 per row goes through the entry that takes draws: not on a wide engine, not with per-row parameters "
+                             "or unit_weights")
+        v = torch.as_tensor(u32)
+        if v.numel() != self.B:
+            raise MidasError(f"u32: expected one offset or {self.B} (one per row), got {v.numel()}")
+        if getattr(self, "_u32_buf", None) is None:
+            self._u32_buf = torch.zeros((self.B, self.cap), dtype=torch.float64, device=self.device)
+        self._u32_buf[:, 0] = v.to(self.device).to(torch.float32).to(torch.float64).reshape(self.B)
+        return self._u32_buf
 
     def step_still(self, odoms, codes, gts=None, std_override=(0.0, 0.0), **kw):
         """`step()` with this one frame's motion noise (std_t, std_r) in place of multiplier x (sig_t, sig_r), shared by the rows, as

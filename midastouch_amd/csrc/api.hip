@@ -450,8 +450,9 @@ MIDAS_EXPORT int midas_mt19937_draws(midas_ctx* ctx, uint32_t* state_dev, int64_
     for (int i = 0; i < nseg; ++i) {
         const midas_mt_segment& g = segs[i];
         MIDAS_REQUIRE(ctx, (g.kind == MIDAS_MT_SEGMENT_RAND64 && g.count >= 0 && (g.count == 0 || g.out_dev)) ||
+                               (g.kind == MIDAS_MT_SEGMENT_RAND32 && g.count == 1 && g.out_dev) ||
                                (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && g.count >= 16 && g.out_dev && radius_dev && cos_dev && sin_dev));
-        total += g.kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * g.count : g.count + ((g.count & 15) ? 16 : 0);
+        total += g.kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * g.count : g.kind == MIDAS_MT_SEGMENT_RAND32 ? g.count : g.count + ((g.count & 15) ? 16 : 0);
     }
     const bool chunked = polys_dev && pieces > 0;
     MIDAS_REQUIRE(ctx, !chunked || (hist_dev != nullptr && pieces <= 1024 && total >= MIDAS_MT19937_HIST_WORDS));
@@ -468,8 +469,9 @@ MIDAS_EXPORT int midas_mt19937_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* 
     for (int i = 0; i < nseg; ++i) {
         const midas_mt_segment& g = segs[i];
         MIDAS_REQUIRE(ctx, (g.kind == MIDAS_MT_SEGMENT_RAND64 && g.count >= 0 && (g.count == 0 || g.out_dev)) ||
+                               (g.kind == MIDAS_MT_SEGMENT_RAND32 && g.count == 1 && g.out_dev) ||
                                (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && g.count >= 16 && g.out_dev && radius_dev && cos_dev && sin_dev));
-        total += g.kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * g.count : g.count + ((g.count & 15) ? 16 : 0);
+        total += g.kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * g.count : g.kind == MIDAS_MT_SEGMENT_RAND32 ? g.count : g.count + ((g.count & 15) ? 16 : 0);
     }
     const bool chunked = polys_dev && pieces > 0;
     MIDAS_REQUIRE(ctx, !chunked || (hist_dev != nullptr && pieces <= 1024 && total >= MIDAS_MT19937_HIST_WORDS));
@@ -484,7 +486,8 @@ MIDAS_EXPORT int midas_mt19937_draws_counted(midas_ctx* ctx, uint32_t* state_dev
     MIDAS_REQUIRE(ctx, state_dev != nullptr && skip_words >= 0 && nseg >= 1 && nseg <= 8 && segs != nullptr && status_dev != nullptr);
     for (int i = 0; i < nseg; ++i) {
         const midas_mt_counted_segment& g = segs[i];
-        MIDAS_REQUIRE(ctx, g.kind == MIDAS_MT_SEGMENT_RAND64 || (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && radius_dev && cos_dev && sin_dev));
+        MIDAS_REQUIRE(ctx, g.kind == MIDAS_MT_SEGMENT_RAND64 || (g.kind == MIDAS_MT_SEGMENT_RAND32 && g.per == 1) ||
+                               (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && radius_dev && cos_dev && sin_dev));
         // (the grids and the scratch are sized by per x bound: up to 2^31 - 1 values a segment)
         MIDAS_REQUIRE(ctx, g.count_dev != nullptr && g.per >= 1 && g.bound >= 0 && g.bound <= 0x7fffffff / g.per && (g.bound == 0 || g.out_dev));
     }
@@ -500,7 +503,8 @@ MIDAS_EXPORT int midas_mt19937_draws_counted_batch(midas_ctx* ctx, int32_t B, ui
     MIDAS_REQUIRE(ctx, B == 1 || (count_stride > 0 && status_stride > 0));  // (every stream its own counts and status word)
     for (int i = 0; i < nseg; ++i) {
         const midas_mt_counted_segment& g = segs[i];
-        MIDAS_REQUIRE(ctx, g.kind == MIDAS_MT_SEGMENT_RAND64 || (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && radius_dev && cos_dev && sin_dev));
+        MIDAS_REQUIRE(ctx, g.kind == MIDAS_MT_SEGMENT_RAND64 || (g.kind == MIDAS_MT_SEGMENT_RAND32 && g.per == 1) ||
+                               (g.kind == MIDAS_MT_SEGMENT_NORMAL32 && radius_dev && cos_dev && sin_dev));
         MIDAS_REQUIRE(ctx, g.count_dev != nullptr && g.per >= 1 && g.bound >= 0 && g.bound <= 0x7fffffff / g.per && (g.bound == 0 || g.out_dev));
     }
     return launch_mt_draws_counted_batch(ctx, B, states_dev, skip_words, nseg, segs, count_stride, radius_dev, cos_dev, sin_dev, status_dev,

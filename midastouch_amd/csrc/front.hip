@@ -41,6 +41,7 @@ int launch_particle_update(midas_ctx* ctx, const midas_tree* t6, const midas_tre
 // tie rule, the same "first event in record order" of the prune list).
 
 // part A of a particle wave: what particle_update_wave does before the nearest-neighbour search, plus its rmse epilogue
+template <bool FU = false>
 MD void particle_front_wave(ParticleUpdateArgs a, int64_t wave, const double* rs_lds, PuFeat* __restrict__ feat) {
     const int lane = threadIdx.x & 63;
     if (a.n_live) {
@@ -58,7 +59,7 @@ MD void particle_front_wave(ParticleUpdateArgs a, int64_t wave, const double* rs
     double et2 = 0.0, ang2 = 0.0;
     int64_t src = n;
     if (rs_lds && live) {
-        src = lazy_source(a.rs, rs_lds, n, a.N);
+        src = lazy_source<const double*, const double*, NoMid, FU>(a.rs, rs_lds, n, a.N);
         if (a.rs.ridx_out) a.rs.ridx_out[n] = (int32_t)src;
     }
     const float* pose_src = rs_lds ? a.rs.poses_prev : a.poses_in;
@@ -88,7 +89,7 @@ MD void particle_front_wave(ParticleUpdateArgs a, int64_t wave, const double* rs
     }
 }
 
-template <typename T, int NJ, bool LAZY>
+template <typename T, int NJ, bool LAZY, bool FU = false>
 __global__ __launch_bounds__(256) void k_frame_front_a(ParticleUpdateArgs a, int n_pu, int nwaves, PuFeat* __restrict__ feat,
                                                        const T* __restrict__ emb, const double* __restrict__ norms,
                                                        const double* __restrict__ code, double* __restrict__ scores, int64_t K) {
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void k_frame_front_a(ParticleUpdateArgs a, int
     if ((int)blockIdx.x < n_pu) {
         if (LAZY) lazy_tables(a.rs, s_rs);
         const int64_t wave = (int64_t)blockIdx.x * 4 + w;
-        if (wave < nwaves) particle_front_wave(a, wave, LAZY ? s_rs : nullptr, feat);
+        if (wave < nwaves) particle_front_wave<FU>(a, wave, LAZY ? s_rs : nullptr, feat);
     } else {
         score_wave<T, NJ, 0>(emb, norms, code, scores, K, (int64_t)(blockIdx.x - n_pu) * 4 + w);
     }
@@ -323,9 +324,9 @@ __global__ __launch_bounds__(256, MIDAS_NNP_OCC) void k_front_small_rows(const O
 #include "front_objects_body.hpp"
 }
 
-template <int NJ, bool LAZY>
+template <int NJ, bool LAZY, bool FU = false>
 static void launch_front_a(const FrontLaunch& L, PuFeat* feat) {
-    hipLaunchKernelGGL((k_frame_front_a<float, NJ, LAZY>), L.grid, dim3(256), 0, L.ctx->stream, L.a, L.n_pu, L.nwaves, feat,
+    hipLaunchKernelGGL((k_frame_front_a<float, NJ, LAZY, FU>), L.grid, dim3(256), 0, L.ctx->stream, L.a, L.n_pu, L.nwaves, feat,
                        (const float*)L.cb->emb, L.cb->norms, L.code, L.scores, L.cb->K);
 }
 
@@ -344,6 +345,8 @@ int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t
     if (a_in.batch > 1 && !(a_in.rs.enabled && a_in.rs.nb <= LAZY_WAVE_LD && a_in.sp.stamps)) return MIDAS_OK;
     if ((uintptr_t)cb->emb % 16 != 0 || (uintptr_t)code % 16 != 0) return MIDAS_OK;
     if (cb->D != 512 && cb->D != 256 && cb->D != 128 && cb->D != 1024) return MIDAS_OK;
+    if (front_from_u(a_in) && !a_in.rs.u)
+        return midas_set_error(ctx, MIDAS_ERR_INVALID, "u32_prev", "MIDAS_U32_FROM_U without the uniforms' pointer");
     ParticleUpdateArgs a = a_in;
     static const int ablate = getenv("MIDAS_ABLATE") ? atoi(getenv("MIDAS_ABLATE")) : 0;
     a.ablate = ablate;
@@ -392,7 +395,8 @@ int launch_frame_front(midas_ctx* ctx, const midas_tree* t6, const midas_tree* t
         } else {
             const FrontLaunch L{ctx, t6, t3, a, cb, code, scores, dim3(grid), n_pu, nwaves};
             with_nj(cb->D, [&](auto nj) {
-                if (a.rs.enabled) launch_front_a<decltype(nj)::value, true>(L, (PuFeat*)feat);
+                if (front_from_u(a)) launch_front_a<decltype(nj)::value, true, true>(L, (PuFeat*)feat);
+                else if (a.rs.enabled) launch_front_a<decltype(nj)::value, true>(L, (PuFeat*)feat);
                 else launch_front_a<decltype(nj)::value, false>(L, (PuFeat*)feat);
             });
             if (lpp == 4)

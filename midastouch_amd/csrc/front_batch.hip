@@ -35,6 +35,7 @@ MD void presort_offset_traj(ParticleUpdateArgs& a, int traj) {
 // every wave builds the block tables for itself (lazy_tables_wave), then the four copy the trajectory's chunk-end table (the
 // softmax or the raw variant, as the guard decided) into LDS - N = 10 000: 5 KB - and a lane finds its chunk there; the scattered
 // fetches of a search drop from 25 sixteen-byte pieces to 9 (this kernel is bound by the vector cache's look-up rate: 35 -> 15 us).
+template <bool FU>
 __global__ __launch_bounds__(256) void k_presort_search(ParticleUpdateArgs a, int32_t* __restrict__ src_out, int32_t* __restrict__ hint_out) {
     __shared__ alignas(16) double s_rs[4][LAZY_WAVE_LDS];
     __shared__ double s_gend[PS_GEND_MAX];
@@ -52,8 +53,8 @@ __global__ __launch_bounds__(256) void k_presort_search(ParticleUpdateArgs a, in
     }
     const int64_t n = (int64_t)blockIdx.x * 256 + t;
     if (n >= a.N) return;
-    const int64_t src = staged ? lazy_source<lds_cdp>(a.rs, s_rs[w], n, a.N, LAZY_WAVE_LD, (lds_cdp)s_gend)
-                               : lazy_source(a.rs, s_rs[w], n, a.N, LAZY_WAVE_LD);
+    const int64_t src = staged ? lazy_source<lds_cdp, const double*, NoMid, FU>(a.rs, s_rs[w], n, a.N, LAZY_WAVE_LD, (lds_cdp)s_gend)
+                               : lazy_source<const double*, const double*, NoMid, FU>(a.rs, s_rs[w], n, a.N, LAZY_WAVE_LD);
     if (a.rs.ridx_out) a.rs.ridx_out[n] = (int32_t)src;
     src_out[o + n] = (int32_t)src;
     hint_out[o + n] = a.rs.nn_prev[src];
@@ -146,6 +147,7 @@ struct PresortLds {  // dynamic LDS of k_presort_fused
     int w[PS_THREADS / 64];
     int fail;
 };
+template <bool FU>
 __global__ __launch_bounds__(PS_THREADS) void k_presort_fused(ParticleUpdateArgs a, int32_t* __restrict__ order, int32_t* __restrict__ srcr, int deal, int chunk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ps_raw[];
     PresortLds& L = *reinterpret_cast<PresortLds*>(ps_raw);
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(PS_THREADS) void k_presort_fused(ParticleUpdateArgs
         const int64_t n = base + (int64_t)j * PS_THREADS + t;
         sv[j] = 0; hv[j] = -1;
         if (n < end) {
-            const int64_t src = lazy_source<lds_cdp, lds_cdp>(a.rs, L.rs[wv], n, N, LAZY_WAVE_LD, (lds_cdp)L.gend, (lds_cdp)L.lp);
+            const int64_t src = lazy_source<lds_cdp, lds_cdp, NoMid, FU>(a.rs, L.rs[wv], n, N, LAZY_WAVE_LD, (lds_cdp)L.gend, (lds_cdp)L.lp);
             if (a.rs.ridx_out) a.rs.ridx_out[n] = (int32_t)src;
             sv[j] = (int)src;
             hv[j] = a.rs.nn_prev[src];
@@ -251,7 +253,8 @@ int launch_presort(midas_ctx* ctx, ParticleUpdateArgs& a) {
         static int ncu_dev[MAXDEV] = {};
         const int di = ctx->device >= 0 && ctx->device < MAXDEV ? ctx->device : 0;
         if (!attr_set[di] || ctx->device != di) {
-            MIDAS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_presort_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PresortLds)));
+            MIDAS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_presort_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PresortLds)));
+            MIDAS_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_presort_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PresortLds)));
             attr_set[di] = true;
         }
         // One workgroup per CU is all the kernel's LDS allows, and a workgroup's life is a chain of round trips whatever its share: as many
@@ -268,12 +271,18 @@ int launch_presort(midas_ctx* ctx, ParticleUpdateArgs& a) {
         int64_t chunk = ceil_div(ceil_div(a.N, nch), 64) * 64;
         if (chunk < 1024) chunk = 1024;  // (a chunk groups its own slots only: small ones share few list records)
         if (chunk_env >= 64 && chunk_env <= PS_CHUNK && chunk_env % 64 == 0) chunk = chunk_env;
-        hipLaunchKernelGGL(k_presort_fused, dim3((unsigned)ceil_div(a.N, chunk), (unsigned)a.batch), dim3(PS_THREADS), sizeof(PresortLds), ctx->stream,
-                           a, (int32_t*)p_order, (int32_t*)p_srcr, run, (int)chunk);
+        const dim3 grid((unsigned)ceil_div(a.N, chunk), (unsigned)a.batch);
+        if (front_from_u(a))
+            hipLaunchKernelGGL(k_presort_fused<true>, grid, dim3(PS_THREADS), sizeof(PresortLds), ctx->stream, a, (int32_t*)p_order, (int32_t*)p_srcr, run, (int)chunk);
+        else
+            hipLaunchKernelGGL(k_presort_fused<false>, grid, dim3(PS_THREADS), sizeof(PresortLds), ctx->stream, a, (int32_t*)p_order, (int32_t*)p_srcr, run, (int)chunk);
     } else {
         if ((rc = midas_scratch(ctx, bytes, &p_src))) return rc;  // (the two-kernel form hands sources and hints over through memory)
         if ((rc = midas_scratch(ctx, bytes, &p_hint))) return rc;
-        hipLaunchKernelGGL(k_presort_search, dim3((unsigned)ceil_div(a.N, 256), (unsigned)a.batch), dim3(256), 0, ctx->stream, a, (int32_t*)p_src, (int32_t*)p_hint);
+        if (front_from_u(a))
+            hipLaunchKernelGGL(k_presort_search<true>, dim3((unsigned)ceil_div(a.N, 256), (unsigned)a.batch), dim3(256), 0, ctx->stream, a, (int32_t*)p_src, (int32_t*)p_hint);
+        else
+            hipLaunchKernelGGL(k_presort_search<false>, dim3((unsigned)ceil_div(a.N, 256), (unsigned)a.batch), dim3(256), 0, ctx->stream, a, (int32_t*)p_src, (int32_t*)p_hint);
         hipLaunchKernelGGL(k_presort_group, dim3((unsigned)ceil_div(a.N, PS_CHUNK), (unsigned)a.batch), dim3(PS_THREADS), 0, ctx->stream, a.N,
                            (const int32_t*)p_src, (const int32_t*)p_hint, (int32_t*)p_order, (int32_t*)p_srcr, run);
     }
@@ -296,6 +305,6 @@ bool launch_front_batch(const FrontLaunch& L, const FrontForm& f) {
                            (const double*)L.a.pre_rmse_terms, L.a.part_rmse);
     return true;
 }
-MIDAS_WARM_TU(front_batch, k_presort_search)
+MIDAS_WARM_TU(front_batch, k_presort_search<false>)
 
 }  // namespace midas

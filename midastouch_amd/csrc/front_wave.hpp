@@ -136,7 +136,10 @@ MD void lazy_tables_wave(const LazyResample& rs, const LazyRecords& r, double* r
 // gend_lds / lp_lds (both or gend_lds alone): the caller's LDS copies of the chunk-end / per-slot tables
 // mid: arithmetic of the caller's that does not depend on the search, run once while the guide entries travel (NoMid: none; a lane
 // that leaves the search before that point has not run it - the caller looks at its own flag)
-template <typename GT = const double*, typename LT = const double*, typename MID = NoMid>
+// FU: the twin of a systematic frame with u32 == MIDAS_U32_FROM_U - the trajectory's offset is the first double of its row of `u`
+// (midas_math.hpp systematic_draw; front_from_u below picks the twin at the launch).  Every other frame runs FU = false: the code it
+// always ran.
+template <typename GT = const double*, typename LT = const double*, typename MID = NoMid, bool FU = false>
 MD int64_t lazy_source(const LazyResample& rs, const double* rs_lds, int64_t n, int64_t N, int ld = 256, GT gend_lds = nullptr,
                        LT lp_lds = nullptr, MID mid = MID()) {
     const double* s_bp = rs_lds;
@@ -153,7 +156,7 @@ MD int64_t lazy_source(const LazyResample& rs, const double* rs_lds, int64_t n, 
         tq = rs.u ? rs.u[n] : philox_uniform53((uint64_t)(n + rs.key_base), rs.seed, rs.step);
         upper = false;
     } else {
-        const float r = rs.u32 >= 0.0f ? rs.u32 : philox_uniform24(rs.seed + (uint64_t)rs.traj, rs.step);
+        const float r = systematic_draw<FU>(rs.u32, rs.u, rs.seed + (uint64_t)rs.traj, rs.step);
         const float off = r / (float)N;
         tq = (double)n / (double)N + (double)off;
         tq = tq >= 1.0 ? tq - 1.0 : tq;
@@ -191,7 +194,7 @@ MD int64_t lazy_source(const LazyResample& rs, const double* rs_lds, int64_t n, 
 // PRES: the presorted form (pre_order / pre_src, batch kernels only) is compiled in; elsewhere the arguments are ignored
 // NANPART: the per-wave extrema of x carry a NaN score on (k_particle_update alone: the one kernel whose partials a guard reads -
 // the eager step's legacy tail, k_tail_a; every other form of the tail gathers the scores itself)
-template <bool WT = false, bool SCREEN = false, bool PREF = false, bool STATS = false, bool PRES = false, bool NANPART = false>
+template <bool WT = false, bool SCREEN = false, bool PREF = false, bool STATS = false, bool PRES = false, bool NANPART = false, bool FU = false>
 MD void particle_update_wave(const TreeView<Kd6>& t6, const TreeView<Kd3>& t3, ParticleUpdateArgs a, int64_t wave,
                              int nwaves, int traj, double* s_cd, double* rs_lds = nullptr) {
     const int lane = threadIdx.x & 63;
@@ -279,7 +282,8 @@ MD void particle_update_wave(const TreeView<Kd6>& t6, const TreeView<Kd3>& t3, P
         MIDAS_PTICK(0);  // records there, tables built (draws done under their trip)
         auto mid = [&]() { noise_apply(O, tnv, rotv, NO); no_done = true; };
         if (rs_lds && live && !presorted && !(ablate & 8)) {
-            src = lazy_source(a.rs, rs_lds, n, a.N, LAZY_WAVE_LD, (const double*)nullptr, (const double*)nullptr, mid);
+            src = lazy_source<const double*, const double*, decltype(mid), FU>(a.rs, rs_lds, n, a.N, LAZY_WAVE_LD, (const double*)nullptr,
+                                                                               (const double*)nullptr, mid);
             if (a.rs.ridx_out) a.rs.ridx_out[n] = (int32_t)src;
         }
         if (live && !no_done) mid();
@@ -290,7 +294,7 @@ MD void particle_update_wave(const TreeView<Kd6>& t6, const TreeView<Kd3>& t3, P
             src = src_pre;  // (ridx_out was written by the presort)
         } else if (!WT) {
             // ablate 8 (profiling): no search, own slot
-            src = (ablate & 8) ? n : lazy_source(a.rs, rs_lds, n, a.N, 256);
+            src = (ablate & 8) ? n : lazy_source<const double*, const double*, NoMid, FU>(a.rs, rs_lds, n, a.N, 256);
             if (a.rs.ridx_out) a.rs.ridx_out[n] = (int32_t)src;
         }
     }
@@ -498,7 +502,7 @@ __device__ long long g_ff_clk[16384];  // per frame parity and workgroup: start,
 #define FF_T0 do { } while (0)
 #define FF_END do { } while (0)
 #endif
-template <typename T, int NJ, int LAZY, int FW, bool SCR = true, bool PREF = false, bool STATS = false>
+template <typename T, int NJ, int LAZY, int FW, bool SCR = true, bool PREF = false, bool STATS = false, bool FU = false>
 __global__ __launch_bounds__(64 * FW, (!SCR && FW == 1) ? MIDAS_BATCH_OCC : (FW == 4 && LAZY == 1) ? MIDAS_FRONT4_OCC : MIDAS_FRONT_OCC) void k_frame_front(TreeView<Kd6> t6, TreeView<Kd3> t3, ParticleUpdateArgs a,
                                                          int n_pu, int nwaves, const T* __restrict__ emb,
                                                          const double* __restrict__ norms, const double* __restrict__ code,
@@ -518,8 +522,8 @@ __global__ __launch_bounds__(64 * FW, (!SCR && FW == 1) ? MIDAS_BATCH_OCC : (FW 
             // one-wave workgroups = the small-set regime (see launch_frame_front): screened scans
             constexpr bool SCREEN = FW == 1 && MIDAS_SCREEN && SCR;
             const int traj = (int)by;
-            if (LAZY == 2) particle_update_wave<true, SCREEN, PREF, STATS, !SCR && !STATS>(t6, t3, a, wave, nwaves, traj, s_cd[w], s_rs + w * LAZY_WAVE_LDS);
-            else particle_update_wave<false, SCREEN, PREF, STATS>(t6, t3, a, wave, nwaves, traj, s_cd[w], LAZY ? s_rs : nullptr);
+            if (LAZY == 2) particle_update_wave<true, SCREEN, PREF, STATS, !SCR && !STATS, false, FU>(t6, t3, a, wave, nwaves, traj, s_cd[w], s_rs + w * LAZY_WAVE_LDS);
+            else particle_update_wave<false, SCREEN, PREF, STATS, false, false, FU>(t6, t3, a, wave, nwaves, traj, s_cd[w], LAZY ? s_rs : nullptr);
         }
     } else if (a.sp.list) {  // prediction list: the rows the previous frame used, four per wave-instruction
         if ((int)bx == n_pu && threadIdx.x == 0 && a.telemetry) {  // rows scored off the list (cumulative, for the bench's byte count)
@@ -553,9 +557,13 @@ void with_nj(int32_t D, F&& f) {
         default: f(std::integral_constant<int, 16>()); break;
     }
 }
-template <int NJ, int LAZY, int FW, bool SCR, bool PREF, bool STATS>
+// the folded resample's systematic offset stands in device memory (MIDAS_U32_FROM_U): the FU twins of the folded forms
+inline bool front_from_u(const ParticleUpdateArgs& a) {
+    return a.rs.enabled && a.rs.mode == MIDAS_RESAMPLE_SYSTEMATIC && a.rs.u32 == MIDAS_U32_FROM_U;
+}
+template <int NJ, int LAZY, int FW, bool SCR, bool PREF, bool STATS, bool FU = false>
 void launch_front_kernel(const FrontLaunch& L) {
-    hipLaunchKernelGGL((k_frame_front<float, NJ, LAZY, FW, SCR, PREF, STATS>), L.grid, dim3(64 * FW), 0, L.ctx->stream, view_of<Kd6>(L.t6),
+    hipLaunchKernelGGL((k_frame_front<float, NJ, LAZY, FW, SCR, PREF, STATS, FU>), L.grid, dim3(64 * FW), 0, L.ctx->stream, view_of<Kd6>(L.t6),
                        view_of<Kd3>(L.t3), L.a, L.n_pu, L.nwaves, (const float*)L.cb->emb, L.cb->norms, L.code, L.scores, L.cb->K);
 }
 // launches form f if it is <LAZY, FW, SCR, PREF, STATS> (a unit's launcher lists its forms with this, each once); the profiling
@@ -563,8 +571,20 @@ void launch_front_kernel(const FrontLaunch& L) {
 template <int LAZY, int FW, bool SCR, bool PREF, bool STATS = false>
 bool launch_if_form(const FrontLaunch& L, const FrontForm& f) {
     if (f.lazy != LAZY || f.fw != FW || f.scr != SCR || f.pref != PREF || f.stats != STATS) return false;
-    if constexpr (STATS) launch_front_kernel<8, LAZY, FW, SCR, PREF, true>(L);
-    else with_nj(L.cb->D, [&](auto nj) { launch_front_kernel<decltype(nj)::value, LAZY, FW, SCR, PREF, false>(L); });
+    if constexpr (STATS) {
+        if (front_from_u(L.a)) return false;  // (the profiling forms have no FU twin)
+        launch_front_kernel<8, LAZY, FW, SCR, PREF, true>(L);
+    } else {
+        with_nj(L.cb->D, [&](auto nj) {
+            if constexpr (LAZY != 0) {
+                if (front_from_u(L.a)) {
+                    launch_front_kernel<decltype(nj)::value, LAZY, FW, SCR, PREF, false, true>(L);
+                    return;
+                }
+            }
+            launch_front_kernel<decltype(nj)::value, LAZY, FW, SCR, PREF, false>(L);
+        });
+    }
     return true;
 }
 

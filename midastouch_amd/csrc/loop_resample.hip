@@ -137,6 +137,9 @@ struct LoopResampleArgs {
 // n_set draws over cdf_i = (BP_b + lp_i) / total (last slot 1): lower bound (multinomial) / upper bound (systematic) by
 // bisection on the exact values; the drawn particle's rows are fetched through src.  All-zero or NaN weights: the annealed
 // set goes on unresampled (particle_filter.py:240-241).
+// FROM_U: the twin a systematic frame with u32 == MIDAS_U32_FROM_U launches - its offset is the first double of the trajectory's row of
+// `u` (midas_math.hpp systematic_draw); every other frame launches the kernel it always did.
+template <bool FROM_U>
 __global__ __launch_bounds__(256) void k_loop_resample(LoopResampleArgs a) {
 #ifdef MIDAS_ANNEAL_CLOCKS  // phase clocks of workgroup 0, thread 0 (anneal_clocks.hpp: RCK)
     const long long ck0 = wall_clock64();
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(256) void k_loop_resample(LoopResampleArgs a) {
             if (!upper) {
                 uq = a.u ? a.u[i] : philox_uniform53((uint64_t)i, a.seed, a.step);
             } else {
-                const float r = a.u32 >= 0.0f ? a.u32 : philox_uniform24(a.seed, a.step);
+                const float r = systematic_draw<FROM_U>(a.u32, a.u, a.seed, a.step);
                 const float off = r / (float)n2;
                 uq = (double)i / (double)n2 + (double)off;
                 uq = uq >= 1.0 ? uq - 1.0 : uq;
@@ -343,7 +346,12 @@ int loop_resample_phase(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid
     fill_loop_resample(r, s, sc.lp, sc.bt, sc.bn);  // (a batch's u_dev: NULL, or (B, cap) through midas_loop_step_batch_draws)
     r.cap2 = loop_bound(cap2); r.cap = g.slice; r.lp_stride = g.lp_stride; r.log_stride = g.log_stride;
     r.check_ndraw = s.stream_draws;
-    hipLaunchKernelGGL(k_loop_resample, dim3((unsigned)ceil_div(cap2, 256), g.by()), dim3(256), 0, ctx->stream, r);
+    const bool from_u = r.mode == MIDAS_RESAMPLE_SYSTEMATIC && r.u32 == MIDAS_U32_FROM_U;
+    if (from_u && !r.u) return midas_set_error(ctx, MIDAS_ERR_INVALID, "u32", "MIDAS_U32_FROM_U without u_dev");
+    if (from_u)
+        hipLaunchKernelGGL(k_loop_resample<true>, dim3((unsigned)ceil_div(cap2, 256), g.by()), dim3(256), 0, ctx->stream, r);
+    else
+        hipLaunchKernelGGL(k_loop_resample<false>, dim3((unsigned)ceil_div(cap2, 256), g.by()), dim3(256), 0, ctx->stream, r);
     LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }

@@ -180,6 +180,15 @@ MD float philox_uniform24(uint64_t seed, uint64_t step) {
     return (float)(w.x >> 8) * 5.9604644775390625e-8f;
 }
 
+// The systematic resampler's offset draw r (particle_filter.py:291, torch.rand(1)): the caller's u32 when it is >= 0, else Philox's -
+// or, in the FROM_U twin of a kernel and under u32 == MIDAS_U32_FROM_U, the float32 value the first double of the trajectory's row of
+// uniforms holds (a seeded stream's draw, or per-row offsets of a batch).  FROM_U = false is the expression the kernels always had.
+template <bool FROM_U>
+MD float systematic_draw(float u32, const double* __restrict__ u_row, uint64_t seed, uint64_t step) {
+    if (FROM_U && u32 == -2.0f) return (float)u_row[0];
+    return u32 >= 0.0f ? u32 : philox_uniform24(seed, step);
+}
+
 // ---- small matrices (row-major), k-ordered fma chains -----------------------------------------
 MD void mat3_mul(const float* A, const float* B, float* C) {
 #pragma unroll

@@ -416,6 +416,23 @@ int launch_mt_normal32(midas_ctx* ctx, uint32_t* state, int64_t skip_words, int6
     return MIDAS_OK;
 }
 
+// torch.rand(1) (float32, CPU generator): ONE 32-bit output, its low 24 bits times 2^-24 (at::uniform_real_distribution<float>) - the
+// offset of the reference's systematic resampler (modules/particle_filter.py:291).  Stored as the float64 that holds the float32
+// value exactly: the resample kernels take it from the first slot of a trajectory's row of uniforms (midas_internal.hpp
+// systematic_offset).
+__device__ __forceinline__ double mt_u24(uint32_t w) { return (double)((float)(mt_temper(w) & MT_U24) * 5.9604644775390625e-08f); }
+// words a segment of n values takes of the stream
+__host__ __device__ __forceinline__ long long mt_segment_words(int kind, long long n) {
+    return kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * n : kind == MIDAS_MT_SEGMENT_RAND32 ? n : n + ((n & 15) ? 16 : 0);
+}
+// grid.x = stream b (one value a stream: a thread each)
+__global__ __launch_bounds__(64) void k_mt_rand32(const uint32_t* __restrict__ raw, const int32_t* __restrict__ meta, int B, double* __restrict__ out,
+                                                 long long off, long long raw_stride) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    out[b] = mt_u24(raw[(size_t)b * raw_stride + (meta ? meta[b] : 0) + off]);
+}
+
 // ---- several draws of one frame from ONE walk of the generator -----------------------------------------------------------------
 // A seeded frame of the reference takes torch.normal (N, 3) twice and torch.rand N float64 (particle_filter.py:326-335, :245): as
 // three calls that is three jumps, three walks, three launches' worth of Python.  Here the segments' words are generated together
@@ -435,7 +452,7 @@ int launch_mt_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t sk
                           const float* R, const float* C, const float* S, uint32_t* hist, const uint32_t* polys, int32_t G) {
     int64_t total = 0;
     for (int i = 0; i < nseg; ++i)
-        total += segs[i].kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * segs[i].count : segs[i].count + ((segs[i].count & 15) ? 16 : 0);
+        total += mt_segment_words(segs[i].kind, segs[i].count);
     uint32_t* raw;
     int32_t* meta;
     int64_t stride;
@@ -449,6 +466,10 @@ int launch_mt_draws_batch(midas_ctx* ctx, int32_t B, uint32_t* state, int64_t sk
                 hipLaunchKernelGGL(k_mt_emit, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
                                    (const int32_t*)meta, (long long)n, (double*)segs[i].out_dev, (uint32_t*)nullptr, (long long)off, (long long)stride);
             off += 2 * n;
+        } else if (segs[i].kind == MIDAS_MT_SEGMENT_RAND32) {  // (n == 1: the entry point's check)
+            hipLaunchKernelGGL(k_mt_rand32, dim3((unsigned)ceil_div((int64_t)B, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)raw,
+                               (const int32_t*)meta, (int)B, (double*)segs[i].out_dev, (long long)off, (long long)stride);
+            off += n;
         } else {
             const int64_t nw = n + ((n & 15) ? 16 : 0);
             hipLaunchKernelGGL(k_mt_normal, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
@@ -506,7 +527,8 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_counted(uint32_t* __restrict_
         if (i < a.nseg) {
             const long long cnt = a.count[i][b * count_stride];
             if (cnt < 0 || cnt > a.bound[i]) bad |= MIDAS_MT_STATUS_COUNT_RANGE;
-            numel[i] = cnt * a.per[i];
+            // RAND32: the count is a control word - one value when it is not zero (the resampler draws its offset, or returns first)
+            numel[i] = a.kind[i] == MIDAS_MT_SEGMENT_RAND32 ? (cnt != 0 ? 1 : 0) : cnt * a.per[i];
             if (a.kind[i] == MIDAS_MT_SEGMENT_NORMAL32 && numel[i] > 0 && numel[i] < 16) bad |= MIDAS_MT_STATUS_NORMAL_SHORT;
         }
     }
@@ -521,7 +543,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_mt_counted(uint32_t* __restrict_
             meta[1 + 2 * i] = n;
             meta[2 + 2 * i] = total;
         }
-        total += a.kind[i] == MIDAS_MT_SEGMENT_RAND64 ? 2 * n : n + ((n & 15) ? 16 : 0);
+        total += mt_segment_words(a.kind[i], n);
     }
     if (bad) return;  // (uniform)
     mt_walk(state, skip, total, raw, nullptr);
@@ -551,11 +573,21 @@ __global__ __launch_bounds__(256) void k_mt_normal_counted(const uint32_t* __res
     out[i] = mt_normal_value(raw + meta[0] + meta[2 + 2 * seg], numel, i, R, C, S, mean, std);
 }
 
+// grid.x = stream b: the row's one value, when its control word asked for it
+__global__ __launch_bounds__(64) void k_mt_rand32_counted(const uint32_t* __restrict__ raw, const long long* __restrict__ meta, int seg, int B,
+                                                         double* __restrict__ out, long long raw_stride, long long out_stride) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    meta += (size_t)b * MT_COUNTED_META;
+    if (meta[1 + 2 * seg] < 1) return;
+    out[(size_t)b * out_stride] = mt_u24(raw[(size_t)b * raw_stride + meta[0] + meta[2 + 2 * seg]]);
+}
+
 static int64_t mt_counted_raw_words(int32_t nseg, const midas_mt_counted_segment* segs) {
     int64_t words = 3 * MT_N;  // as mt_words: the rest of the block the words start in and of the one they end in
     for (int i = 0; i < nseg; ++i) {
         const int64_t n = segs[i].per * segs[i].bound;
-        words += segs[i].kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * n : n + 16;
+        words += segs[i].kind == MIDAS_MT_SEGMENT_RAND64 ? 2 * n : segs[i].kind == MIDAS_MT_SEGMENT_RAND32 ? 1 : n + 16;
     }
     return words;
 }
@@ -588,6 +620,9 @@ int launch_mt_draws_counted_batch(midas_ctx* ctx, int32_t B, uint32_t* state, in
         if (segs[i].kind == MIDAS_MT_SEGMENT_RAND64)
             hipLaunchKernelGGL(k_mt_emit_counted, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
                                (const long long*)meta, i, (double*)segs[i].out_dev, (long long)raw_stride, (long long)n);
+        else if (segs[i].kind == MIDAS_MT_SEGMENT_RAND32)
+            hipLaunchKernelGGL(k_mt_rand32_counted, dim3((unsigned)ceil_div((int64_t)B, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)raw,
+                               (const long long*)meta, i, (int)B, (double*)segs[i].out_dev, (long long)raw_stride, (long long)n);
         else
             hipLaunchKernelGGL(k_mt_normal_counted, dim3((unsigned)ceil_div(n, 256), (unsigned)B), dim3(256), 0, ctx->stream, (const uint32_t*)raw,
                                (const long long*)meta, i, R, C, S, segs[i].mean, segs[i].std, (float*)segs[i].out_dev, (long long)raw_stride,

@@ -271,30 +271,37 @@ MD int32_t search_upper(const double* __restrict__ cdf, int64_t N, double u) {
     return (int32_t)(lo < N ? lo : N - 1);
 }
 
+static_assert(MIDAS_U32_FROM_U == -2.0f, "midas_math.hpp systematic_draw");
+template <bool FROM_U = false>
 MD int32_t resample_slot(const double* __restrict__ cdf, int64_t N, int64_t M, int64_t i, int32_t mode,
                          const double* __restrict__ u, float u32, uint64_t seed, uint64_t step) {
     if (mode == MIDAS_RESAMPLE_MULTINOMIAL) {
         const double ui = u ? u[i] : philox_uniform53((uint64_t)i, seed, step);
         return search_lower(cdf, N, ui);
     }
-    const float r = u32 >= 0.0f ? u32 : philox_uniform24(seed, step);
+    const float r = systematic_draw<FROM_U>(u32, u, seed, step);
     const float off = r / (float)M;
     double loc = (double)i / (double)M + (double)off;
     loc = loc >= 1.0 ? loc - 1.0 : loc;  // fmod(loc, 1) for loc in [0, 2)
     return search_upper(cdf, N, loc);
 }
 
+template <bool FROM_U>
 __global__ __launch_bounds__(256) void k_search(int64_t N, const double* __restrict__ cdf, int64_t M, int32_t mode,
                                                 const double* __restrict__ u, float u32, uint64_t seed, uint64_t step,
                                                 int32_t* __restrict__ idx) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < M) idx[i] = resample_slot(cdf, N, M, i, mode, u, u32, seed, step);
+    if (i < M) idx[i] = resample_slot<FROM_U>(cdf, N, M, i, mode, u, u32, seed, step);
 }
 int launch_search(midas_ctx* ctx, int64_t N, const double* cdf, int64_t M, int32_t mode, const double* u, float u32,
                   uint64_t seed, uint64_t step, int32_t* idx) {
     if (M == 0) return MIDAS_OK;
-    hipLaunchKernelGGL(k_search, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, N, cdf, M, mode, u, u32,
-                       seed, step, idx);
+    const bool from_u = mode == MIDAS_RESAMPLE_SYSTEMATIC && u32 == MIDAS_U32_FROM_U;
+    if (from_u && !u) return midas_set_error(ctx, MIDAS_ERR_INVALID, "u32", "MIDAS_U32_FROM_U without u_dev");
+    if (from_u)
+        hipLaunchKernelGGL(k_search<true>, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, N, cdf, M, mode, u, u32, seed, step, idx);
+    else
+        hipLaunchKernelGGL(k_search<false>, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, ctx->stream, N, cdf, M, mode, u, u32, seed, step, idx);
     LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }

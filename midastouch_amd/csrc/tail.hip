@@ -461,6 +461,9 @@ struct TailBArgs {
     int64_t slot_base;     // Philox key offset of slot 0 (b * N for trajectory b of a batch)
 };
 
+// FROM_U (k_tail_b, k_tail_b2): the twin a systematic frame with u32 == MIDAS_U32_FROM_U launches - trajectory b's offset is the first
+// double of its row of `u` (midas_math.hpp systematic_draw); every other frame launches the kernel it always did.
+template <bool FROM_U>
 __global__ __launch_bounds__(256) void k_tail_b(TailBArgs a) {
     __shared__ double s_bp[TB_MAX_BLOCKS];
     __shared__ double s_end[TB_MAX_BLOCKS];
@@ -514,7 +517,7 @@ __global__ __launch_bounds__(256) void k_tail_b(TailBArgs a) {
                 t = a.u ? a.u[i] : philox_uniform53((uint64_t)(a.slot_base + i), a.seed, a.step);
                 upper = false;
             } else {
-                const float r = a.u32 >= 0.0f ? a.u32 : philox_uniform24(a.seed + (uint64_t)blockIdx.y, a.step);
+                const float r = systematic_draw<FROM_U>(a.u32, a.u, a.seed + (uint64_t)blockIdx.y, a.step);
                 const float off = r / (float)N;
                 t = (double)i / (double)N + (double)off;
                 t = t >= 1.0 ? t - 1.0 : t;
@@ -615,6 +618,7 @@ struct TailB2Args {
     int64_t tstride;  // > 0: batch with one table block per trajectory (pipelined batch), 0: array-major batch tables
 };
 
+template <bool FROM_U>
 __global__ __launch_bounds__(256) void k_tail_b2(TailB2Args a) {
     // dynamic LDS sized to this launch (nt + 3 nb doubles) so that small N keeps several workgroups per CU
     extern __shared__ double s_dyn[];
@@ -674,7 +678,7 @@ __global__ __launch_bounds__(256) void k_tail_b2(TailB2Args a) {
     }
     double e_i = a.e[ic];
     const bool ok_i = a.valid[ic] != 0;
-    const double u_i = a.u ? a.u[ic] : 0.0;
+    const double u_i = (!FROM_U && a.u) ? a.u[ic] : 0.0;  // (FROM_U: a systematic frame, `u` holds the row's offset only)
     TB2_CLK(1)
     // ---- guard: global extrema of x from TA2's per-block ones (NaN propagates)
     double mx = -INFINITY, mn = INFINITY;
@@ -751,7 +755,7 @@ __global__ __launch_bounds__(256) void k_tail_b2(TailB2Args a) {
                 tq = a.u ? u_i : philox_uniform53((uint64_t)(slot_base + i), a.seed, a.step);
                 upper = false;
             } else {
-                const float r = a.u32 >= 0.0f ? a.u32 : philox_uniform24(a.seed + (uint64_t)blockIdx.y, a.step);
+                const float r = systematic_draw<FROM_U>(a.u32, a.u, a.seed + (uint64_t)blockIdx.y, a.step);
                 const float off = r / (float)N;
                 tq = (double)i / (double)N + (double)off;
                 tq = tq >= 1.0 ? tq - 1.0 : tq;
@@ -852,6 +856,7 @@ __global__ __launch_bounds__(256) void k_tail_b2(TailB2Args a) {
         frame_rmse(a.part_rmse, a.nrm, N, s_rm, a.rmse_out, false, false);
     }
 }
+static bool tail_offset_from_u(const StepTailArgs& a) { return a.mode == MIDAS_RESAMPLE_SYSTEMATIC && a.u32 == MIDAS_U32_FROM_U; }
 int launch_tail_b2(midas_ctx* ctx, const StepTailArgs& a, const TailTables& tb) {
     const int nb = (int)ceil_div(a.N, SCAN_BLOCK), ng = (int)ceil_div(a.N, SCAN_CHUNK);
     if (nb > TB_MAX_BLOCKS) return midas_set_error(ctx, MIDAS_ERR_INVALID, "N", "more than 4 M particles per GPU: shard them");
@@ -871,8 +876,10 @@ int launch_tail_b2(midas_ctx* ctx, const StepTailArgs& a, const TailTables& tb) 
     b.poses_out = a.poses_out; b.weights_out = a.weights_out; b.nn_idx = a.nn_idx; b.hint_out = a.hint_out;
     b.part_rmse = a.part_rmse; b.nrm = a.part_rmse ? particle_update_blocks(a.N) : 0; b.rmse_out = a.rmse_out;
     b.tstride = a.tstride;
-    hipLaunchKernelGGL(k_tail_b2, dim3((unsigned)ceil_div(a.N, 256), (unsigned)(a.batch > 1 ? a.batch : 1)), dim3(256),
-                       (size_t)(nt + 3 * nb) * sizeof(double), ctx->stream, b);
+    const dim3 grid((unsigned)ceil_div(a.N, 256), (unsigned)(a.batch > 1 ? a.batch : 1));
+    const size_t lds = (size_t)(nt + 3 * nb) * sizeof(double);
+    if (tail_offset_from_u(a)) hipLaunchKernelGGL(k_tail_b2<true>, grid, dim3(256), lds, ctx->stream, b);
+    else hipLaunchKernelGGL(k_tail_b2<false>, grid, dim3(256), lds, ctx->stream, b);
     LAUNCH_CHECK(ctx);
     return MIDAS_OK;
 }
@@ -880,6 +887,7 @@ int launch_tail_b2(midas_ctx* ctx, const StepTailArgs& a, const TailTables& tb) 
 int launch_step_tail(midas_ctx* ctx, const StepTailArgs& a, int prof_slot_base) {
     const int nb = (int)ceil_div(a.N, SCAN_BLOCK);
     if (nb > TB_MAX_BLOCKS) return midas_set_error(ctx, MIDAS_ERR_INVALID, "N", "more than 4 M particles per GPU: shard them");
+    if (tail_offset_from_u(a) && !a.u) return midas_set_error(ctx, MIDAS_ERR_INVALID, "u32", "MIDAS_U32_FROM_U without the uniforms' pointer");
     void* sc;
     const int B = a.batch > 1 ? a.batch : 1;
     int rc = midas_scratch(ctx, (size_t)B * nb * 2 * sizeof(double) + (size_t)B * sizeof(int32_t) + 64, &sc);
@@ -915,7 +923,8 @@ int launch_step_tail(midas_ctx* ctx, const StepTailArgs& a, int prof_slot_base) 
     b.weights_out = a.weights_out; b.nn_idx = a.nn_idx; b.hint_out = a.hint_out;
     b.part_rmse = a.part_rmse; b.nrm = a.part_rmse ? particle_update_blocks(a.N) : 0; b.rmse_out = a.rmse_out;
     b.slot_base = 0;
-    hipLaunchKernelGGL(k_tail_b, dim3((unsigned)ceil_div(a.N, 256), (unsigned)B), dim3(256), 0, ctx->stream, b);
+    if (tail_offset_from_u(a)) hipLaunchKernelGGL(k_tail_b<true>, dim3((unsigned)ceil_div(a.N, 256), (unsigned)B), dim3(256), 0, ctx->stream, b);
+    else hipLaunchKernelGGL(k_tail_b<false>, dim3((unsigned)ceil_div(a.N, 256), (unsigned)B), dim3(256), 0, ctx->stream, b);
     LAUNCH_CHECK(ctx);
     prof_mark(ctx, prof_slot_base + 2);
     return MIDAS_OK;

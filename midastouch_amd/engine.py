@@ -18,8 +18,10 @@ below; the two loop engines share `loop_engine._LoopBase` (state table, cached `
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -220,6 +222,32 @@ class _Engine:
         poses.copy_(ops.gather_rows(self.cb_poses, idx).view_as(poses))
         self.hint.copy_(idx.view_as(self.hint))
         return idx
+
+    # ---- systematic offsets in device memory ------------------------------------------------------
+    def _offset_rows(self, vals):
+        """One systematic offset per trajectory as the kernels read it under u32 = MIDAS_U32_FROM_U: a tensor of `u`'s shape whose
+        first double of every trajectory's row holds the float32 value (the rest is never read).  vals: one value per trajectory,
+        on the host or the device; enqueued on the current stream, nothing read back."""
+        bz = self._lead[:-1]
+        v = torch.as_tensor(vals)
+        n = 1
+        for b in bz:
+            n *= b
+        if v.numel() != n:
+            raise MidasError(f"u32: expected one offset or {n} (one per trajectory), got {v.numel()}")
+        buf = torch.empty(self._lead, dtype=torch.float64, device=self.device)
+        buf[..., 0] = v.to(self.device).to(torch.float32).to(torch.float64).reshape(bz)
+        return buf
+
+    def _u32_rows(self, u, u32):
+        """A frame's `u32` as given -> (u, u32) as the C ABI takes them: a number is the offset of every trajectory (< 0: Philox, keyed
+        by seed + trajectory) - today's meaning; B values (a host or device tensor, a list) are one offset per trajectory, handed
+        over in device memory: row b resamples as if run alone with u32 = values[b]."""
+        if isinstance(u32, numbers.Real) or (isinstance(u32, (torch.Tensor, np.ndarray)) and u32.ndim == 0):
+            return u, float(u32)
+        if self.mode != _lib.RESAMPLE_SYSTEMATIC:
+            raise MidasError("u32 per trajectory is the systematic resampler's offset: resample='low_var' / 'low_var_batch' only")
+        return self._offset_rows(u32), _lib.U32_FROM_U
 
     # ---- one frame ------------------------------------------------------------------------------
     def _operands(self, odom, code, gt, tn, rot, u):
@@ -485,12 +513,13 @@ class PipelinedFilterEngine(_FoldedResample, FilterEngine):
     def seed_torch_stream(self, seed, motion: bool = False):
         """Resample draws from the device replica of torch's CPU generator under torch.manual_seed(seed) (torch_rng.py):
         every step() without explicit `u` then resamples with the uniforms torch.multinomial would consume
-        (modules/particle_filter.py:245).  With host motion noise (tn, rot given) the stream first steps over the words those
+        (modules/particle_filter.py:245) - with resample="low_var" every step() without an explicit `u32 >= 0` takes the systematic
+        resampler's one float32 `torch.rand(1)` (:291) instead, which stays in device memory (MIDAS_U32_FROM_U).  With host motion noise (tn, rot given) the stream first steps over the words those
         two torch.normal calls took, so it stays aligned with a host generator seeded alike.
         motion=True: the motion noise comes from the stream too - `torch.normal(0, sig_t, (N, 3))`, `torch.normal(0, sig_r, (N, 3))`
         in front of the resampler's uniforms, the reference's order (:326-335, :245) - i.e. EVERY draw of a frame is the one a
         seeded run of the reference takes, generated on the device (unit normals a frame ahead, scaled where they are used).
-        The stream draws N uniforms EVERY frame, a frame ahead of the status they are used under: the reference's resampler draws
+        The stream draws its N uniforms (or its one offset) EVERY frame, a frame ahead of the status they are used under: the reference's resampler draws
         none on a frame whose weights are all zero or hold a NaN (:237-241), so behind such a guard frame this stream is no longer
         the reference's (LoopEngine.seed_torch_stream skips the draw there).
         seed=None: back to Philox."""
@@ -503,8 +532,11 @@ class PipelinedFilterEngine(_FoldedResample, FilterEngine):
     def step(self, odom, code, gt=None, tn=None, rot=None, u=None, u32=-1.0, multiplier: float = 1.0):
         stream = getattr(self, "torch_stream", None)
         own_u, u_event = False, None  # own_u: generated here (a buffer nobody else holds): kept for the folded frame without a copy
-        if stream is not None and u is None and self.mode == _lib.RESAMPLE_MULTINOMIAL:
+        systematic = self.mode == _lib.RESAMPLE_SYSTEMATIC
+        if stream is not None and (float(u32) < 0.0 if systematic else u is None):
             stream_motion = False
+            # the resampler's draw of this frame: N float64 uniforms, or the systematic resampler's one float32 offset
+            draw = ("rand32",) if systematic else ("rand64", self.N)
             if tn is not None:
                 stream.skip_normal(3 * self.N).skip_normal(3 * self.N)
             elif getattr(self, "torch_motion", False):
@@ -526,11 +558,17 @@ class PipelinedFilterEngine(_FoldedResample, FilterEngine):
             if stream_motion:
                 # ... together with the next frame's unit normals, which follow them in the stream: one walk of the generator
                 # (midas_mt19937_draws) instead of three
-                (u, a, b), ev = stream.draws_async([("rand64", self.N), ("normal", 0.0, 1.0, (self.N, 3)), ("normal", 0.0, 1.0, (self.N, 3))])
+                (u, a, b), ev = stream.draws_async([draw, ("normal", 0.0, 1.0, (self.N, 3)), ("normal", 0.0, 1.0, (self.N, 3))])
                 u_event = ev
                 self._unit_noise = (a, b, ev)
+            elif systematic:
+                (u,), u_event = stream.draws_async([draw])
             else:
                 u, u_event = stream.rand64_async(self.N)
+            if systematic:  # the offset into the row the kernels read, on this stream behind the draw
+                if u_event is not None:
+                    torch.cuda.current_stream(self.device).wait_event(u_event)
+                u, u32, u_event = self._offset_rows(u), _lib.U32_FROM_U, None
         mul = max(float(multiplier), 1.0)
         self._lazy_frame(odom, code, gt, tn, rot, u, u32, own_u, u_event, mul * self.sig_t, mul * self.sig_r)
 
@@ -631,19 +669,29 @@ class BatchFilterEngine(_Engine):
         self._alloc_state()
         self._alloc_estimate(estimate)
 
-    def seed_torch_streams(self, seeds, motion: bool = False, pieces: int = 0):
+    def seed_torch_streams_low_var(self, seeds, motion: bool = False, pieces: int = 0):
+        """seed_torch_streams for an engine built with resample="low_var" / "low_var_batch": the resampler's draw of trajectory b is
+        stream b's one float32 `torch.rand(1)` a frame, the systematic resampler's offset (particle_filter.py:291), which stays in
+        device memory (MIDAS_U32_FROM_U); `motion`, the word skipping for host tn / rot and the limitation behind guard frames are
+        seed_torch_streams'.  A method of its own: seed_torch_streams on a systematic engine refuses, as it always did."""
+        return self.seed_torch_streams(seeds, motion, pieces, _systematic=True)
+
+    def seed_torch_streams(self, seeds, motion: bool = False, pieces: int = 0, _systematic: bool = False):
         """Trajectory b draws from the device replica of torch's CPU generator under torch.manual_seed(seeds[b]) - B seeded runs of
         the reference, one process each (TorchCpuStreams; PipelinedFilterEngine.seed_torch_stream for one trajectory).  `seeds`: B
         ints, or B torch.Generators continued where they stand (from_host), or None: back to Philox.
         motion=False: every step() without `u` resamples trajectory b with the uniforms torch.multinomial(w_b.double(), N, True)
-        would consume on stream b (modules/particle_filter.py:245); with host tn / rot the streams first step over the words of the
+        would consume on stream b (modules/particle_filter.py:245) - after seed_torch_streams_low_var (an engine built with
+        resample="low_var"; this method refuses such an engine, as it always did) every step() without offsets of the
+        caller's (`u32` >= 0 or B values) with stream b's one float32 `torch.rand(1)`, the systematic resampler's offset (:291), which
+        stays in device memory; with host tn / rot the streams first step over the words of the
         two torch.normal((N, 3)) calls.  motion=True: tn, rot and u all come from the streams in the reference's order
         (torch.normal(0, sig_t, (N, 3)), torch.normal(0, sig_r, (N, 3)), N float64 uniforms: :326-335, :245) - unit normals, scaled
         by sig_t / sig_r where they are used (fl(n x std): ATen's fused multiply-add with mean 0) - and explicit tn / rot / u are an
         error.  One walk of the generators per frame; the context's scratch for it is reserved here.  `pieces` (TorchCpuStreams'):
         0 by default - the jump costs B x pieces x 39 workgroups of 78 KB LDS, and at c5 (B = 64) it takes 0.42 ms where the 64
         sequential walks, side by side, take 37 us (the mt19937 paragraph).
-        The streams draw N uniforms EVERY frame, a frame ahead of the status they are used under: the reference's resampler draws
+        The streams draw their N uniforms (or their one offset) EVERY frame, a frame ahead of the status they are used under: the reference's resampler draws
         none on a frame whose weights are all zero or hold a NaN (:237-241), so behind such a guard frame a row's stream is no longer
         the reference's (BatchLoopEngine.seed_torch_streams skips the draw there, per row).
         After a run, `torch_streams.to_host(b, g)` hands stream b back to a host generator."""
@@ -654,46 +702,66 @@ class BatchFilterEngine(_Engine):
         seeds = list(seeds)
         if len(seeds) != self.B:
             raise MidasError(f"seed_torch_streams: {len(seeds)} seeds for {self.B} trajectories")
-        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
-            raise MidasError("seeded torch streams reproduce torch.multinomial's draws: resample='weighted_random' only")
+        if _systematic != (self.mode == _lib.RESAMPLE_SYSTEMATIC):
+            if _systematic:
+                raise MidasError("seed_torch_streams_low_var is the systematic resampler's: resample='low_var' / 'low_var_batch' only")
+            raise MidasError("seeded torch streams reproduce torch.multinomial's draws: resample='weighted_random' only - the systematic "
+                             "resampler's one float32 torch.rand(1) a frame: seed_torch_streams_low_var")
         from .torch_rng import TorchCpuStreams
         st = TorchCpuStreams(seeds, self.device, pieces=pieces)
         N = self.N
-        frame = [("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3)), ("rand64", N)] if motion else [("rand64", N)]
+        frame = [("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3)), self._resampler_draw()] if motion else [self._resampler_draw()]
         st.reserve(frame)
         self.torch_streams, self.torch_motion = st, bool(motion)
         return st
 
-    def _stream_draws(self, tn, rot, u):
-        """This frame's draws from the seeded streams (seed_torch_streams): (tn, rot, u, event of u or None)."""
+    def _resampler_draw(self):
+        """The resampler's draw of one frame as a TorchCpuStreams item: N float64 uniforms (torch.multinomial, particle_filter.py:245)
+        or the systematic resampler's one float32 offset (torch.rand(1), :291)."""
+        return ("rand64", self.N) if self.mode == _lib.RESAMPLE_MULTINOMIAL else ("rand32",)
+
+    def _resampler_rows(self, u, ev):
+        """What the streams drew for the resampler -> (u, u32, event) as the frame takes them: the uniforms as they are, or the B
+        offsets in the rows the kernels read (MIDAS_U32_FROM_U), written on this stream behind the draw."""
+        if self.mode == _lib.RESAMPLE_MULTINOMIAL:
+            return u, -1.0, ev
+        if ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(ev)
+        return self._offset_rows(u), _lib.U32_FROM_U, None
+
+    def _stream_draws(self, tn, rot, u, u32=-1.0):
+        """This frame's draws from the seeded streams (seed_torch_streams): (tn, rot, u, u32, event of u or None); without streams
+        the caller's, `u32` as _u32_rows makes it."""
         st = getattr(self, "torch_streams", None)
-        if st is None:
-            return tn, rot, u, None
+        systematic = self.mode == _lib.RESAMPLE_SYSTEMATIC
+        own = not (isinstance(u32, numbers.Real) and float(u32) < 0.0) if systematic else u is not None  # the caller's resampler draws
+        if st is None or (own and not self.torch_motion):
+            # (no streams, or the caller's uniforms / offsets: the streams are not used this frame)
+            return (tn, rot) + self._u32_rows(u, u32) + (None,)
         B, N = self.B, self.N
         if self.torch_motion:
-            if tn is not None or rot is not None or u is not None:
-                raise MidasError("seed_torch_streams(motion=True): the streams draw tn, rot and u - passing them would desynchronise "
-                                 "the streams from the reference's")
+            if tn is not None or rot is not None or u is not None or own:
+                raise MidasError("seed_torch_streams(motion=True): the streams draw tn, rot and u (the systematic offset too) - passing "
+                                 "them would desynchronise the streams from the reference's")
             return self._seeded_frame()
-        if u is not None:
-            return tn, rot, u, None  # (the caller's uniforms: the streams are not used this frame)
         if tn is not None:
             st.skip_normal(3 * N).skip_normal(3 * N)
-        (u,), ev = st.draws_async([("rand64", N)])
-        return tn, rot, u, ev
+        (u,), ev = st.draws_async([self._resampler_draw()])
+        return (tn, rot) + self._resampler_rows(u, ev)
 
     def _seeded_frame(self):
         """motion=True: the frame's normals and uniforms by one walk (the eager step reads all three at once)."""
         N = self.N
-        (a, b, u), ev = self.torch_streams.draws_async([("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3)), ("rand64", N)])
+        (a, b, u), ev = self.torch_streams.draws_async([("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3)), self._resampler_draw()])
         if ev is not None:
             torch.cuda.current_stream(self.device).wait_event(ev)
-        return a * self.sig_t, b * self.sig_r, u, None
+        return (a * self.sig_t, b * self.sig_r) + self._resampler_rows(u, None)
 
     def step(self, odoms, codes, gts=None, tn=None, rot=None, u=None, u32=-1.0):
-        """odoms (B,4,4) f32, codes (B,D) f64, gts (B,4,4) f32 or None; optional host draws tn/rot (B,N,3), u (B,N)."""
+        """odoms (B,4,4) f32, codes (B,D) f64, gts (B,4,4) f32 or None; optional host draws tn/rot (B,N,3), u (B,N); u32: the
+        systematic offset of every trajectory (a number; < 0: Philox) or B of them, one per trajectory (_u32_rows)."""
         check_motion_draws(tn, rot)  # (before the streams draw)
-        tn, rot, u, ev = self._stream_draws(tn, rot, u)
+        tn, rot, u, u32, ev = self._stream_draws(tn, rot, u, u32)
         if ev is not None:
             torch.cuda.current_stream(self.device).wait_event(ev)
         self._eager_step(self.ctx.lib.midas_filter_step_batch, odoms, codes, gts, tn, rot, u, u32, self.sig_t, self.sig_r, self.B)
@@ -728,13 +796,13 @@ class PipelinedBatchFilterEngine(_FoldedResample, BatchFilterEngine):
         if ev is not None:
             torch.cuda.current_stream(self.device).wait_event(ev)
         tn, rot = a * self.sig_t, b * self.sig_r
-        (u, a, b), ev = st.draws_async([("rand64", N), ("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3))])
+        (u, a, b), ev = st.draws_async([self._resampler_draw(), ("normal", 0.0, 1.0, (N, 3)), ("normal", 0.0, 1.0, (N, 3))])
         self._unit_noise = (a, b, ev)
-        return tn, rot, u, ev
+        return (tn, rot) + self._resampler_rows(u, ev)
 
     def step(self, odoms, codes, gts=None, tn=None, rot=None, u=None, u32=-1.0):
         check_motion_draws(tn, rot)  # (before the streams draw)
         own_u = u is None
-        tn, rot, u, u_event = self._stream_draws(tn, rot, u)
+        tn, rot, u, u32, u_event = self._stream_draws(tn, rot, u, u32)
         own_u = own_u and u is not None  # generated here (a tensor nobody else holds): kept for the folded resample without a copy
         self._lazy_frame(odoms, codes, gts, tn, rot, u, u32, own_u, u_event, self.sig_t, self.sig_r)

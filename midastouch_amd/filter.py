@@ -103,7 +103,7 @@ def _log_id(seq, expt_cfg) -> str:
 def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str = "fixed", max_frames: int = None,
            cluster: bool = True, progress: bool = False, softmax: bool = True, update_freq: int = 1, floor: int = 1000,
            results_path: Optional[str] = None, draws: str = "device", seed: int = 4000, start: str = "host",
-           cluster_every: int = 50) -> dict:
+           cluster_every: int = 50, resample: str = "weighted_random") -> dict:
     """Run the filter over a sequence; returns the reference's `filter_stats` dict (filter.py:99-116).
 
     The loop body (filter.py:150-190: motionModel -> particle_rmse -> SE3_NN + get_similarity -> remove_invalid_particles
@@ -132,11 +132,19 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
     scipy's Euler conversion), an upload and the projection.  start="device": `LoopEngine.start` - the same arithmetic in two
     launches, the draws from Philox (draws="device" only); what `filter_sweep` does for every row, so the single-run yardstick of a
     sweep.  cluster_every: DBSCAN on every cluster_every-th frame (50: filter.py:182).
+    resample: the mode `pf.resampler(particles, resample=...)` is called with (particle_filter.py:230-261) - "weighted_random"
+    (the reference's call), or "low_var" / "low_var_batch": the systematic resampler, whose one draw a frame is a float32
+    `torch.rand(1)` (:291) - with draws="host" drawn here when the resampler draws at all (NDRAW > 0), with draws="seeded" by the
+    device stream, with draws="device" from Philox.
     """
     from . import _lib
+    from .engine import RESAMPLE_MODES
     from .loop_engine import LoopEngine
 
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if resample not in RESAMPLE_MODES:
+        raise ValueError(f"resample must be one of {sorted(RESAMPLE_MODES)}")
+    systematic = RESAMPLE_MODES[resample] == _lib.RESAMPLE_SYSTEMATIC
     if draws not in ("device", "host", "seeded"):
         raise ValueError("draws must be 'device', 'host' or 'seeded'")
     if start not in ("host", "device"):
@@ -158,10 +166,10 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
     if seq.mesh_tree is not None:
         pf._mesh_tree = seq.mesh_tree
     eng = LoopEngine(codebook, None, pf.mesh_kdtree, init_particles, sig_t=pf.motion_noise["sig_t"], sig_r=pf.motion_noise["sig_r"],
-                     pen_max=pf.pen_max, seed=seed, softmax=softmax, floor=floor, cluster=cluster, log_frames=max(traj_size + 8, 64),
-                     device=device, topk_ties="aten_cpu" if draws in ("host", "seeded") else "index")
+                     pen_max=pf.pen_max, seed=seed, softmax=softmax, resample=resample, floor=floor, cluster=cluster,
+                     log_frames=max(traj_size + 8, 64), device=device, topk_ties="aten_cpu" if draws in ("host", "seeded") else "index")
     # seeded: the engine draws every frame's numbers from torch's stream on the device (LoopEngine.seed_torch_stream)
-    stream = eng.seed_torch_stream(0) if draws == "seeded" else None
+    stream = (eng.seed_torch_stream_low_var if systematic else eng.seed_torch_stream)(0) if draws == "seeded" else None
     on_device = False  # seeded: who holds torch's stream at the moment (False: the host's default generator)
 
     def stream_to(dev_side: bool):
@@ -233,8 +241,11 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
                 # (:237-241): the device says how many uniforms this frame draws (NDRAW: n_set or 0)
                 ci = eng.ctl_i.cpu()
                 n_set, n_draw = int(ci[_lib.LOOP_I_NSET]), int(ci[_lib.LOOP_I_NDRAW])
-                u = torch.rand(n_draw, dtype=torch.float64) if n_draw else torch.zeros(n_set, dtype=torch.float64)  # (unused)
-                eng.step(None, None, u=u, phases=_lib.LOOP_RESAMPLE, stream_draws=True)
+                if systematic:  # low_var's one draw (:291), when the resampler gets as far as drawing
+                    eng.step(None, None, u32=float(torch.rand(1)) if n_draw else -1.0, phases=_lib.LOOP_RESAMPLE, stream_draws=True)
+                else:
+                    u = torch.rand(n_draw, dtype=torch.float64) if n_draw else torch.zeros(n_set, dtype=torch.float64)  # (unused)
+                    eng.step(None, None, u=u, phases=_lib.LOOP_RESAMPLE, stream_draws=True)
             elif draws == "seeded":
                 # the same draws, sized on the device: nothing is read back (frames seen while prev_idx == 0 do not call motionModel)
                 stream_to(True)
@@ -413,18 +424,18 @@ def sweep_inputs(runs, plan, device):
 
 def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, max_frames: int = None, cluster: bool = True,
                  cluster_every: int = 50, softmax=True, update_freq=1, floor=1000,
-                 results_root: Optional[str] = None, draws: str = "device") -> list:
+                 results_root: Optional[str] = None, draws: str = "device", resample: str = "weighted_random") -> list:
     """The reference's experiment - `bash/run_filter.sh`: objects x logs x trials, one `filter/filter.py` process each - as ONE batch
     on the device: every (run, trial) is a row of a `BatchLoopEngine.for_objects`, a frame of all rows is one `step()`.
 
     runs: a list of `Sequence`; runs that share one `codebook` object stand on one object of the batch.  Row r * trials + k is run r,
     trial k, on the Philox streams of seed + row: it holds, frame for frame, what `filter(run_cfg, runs[r], seed=seed + row,
-    start="device", softmax=..., floor=..., update_freq=..., cluster_every=...)` computes.  run_cfg is the run's own `Sequence.cfg`
+    start="device", softmax=..., floor=..., update_freq=..., cluster_every=..., resample=...)` computes.  run_cfg is the run's own `Sequence.cfg`
     (None: `cfg`): a run takes its dataset's noise_t, noise_r, num_particles, noise_ratio and pen.max from it - config/expt/ycb.yaml
     and mcmaster.yaml in one sweep; the batch's capacity is the largest count, wide beyond 16 384.  softmax, floor and update_freq are
     each one value or one per run - `filter` and `filter_real`'s presets as rows of one batch.  Rows that differ in any of these go
     through the engine's per-row parameter table (two uploads a sweep: the still and the moving frames); eps, the DBSCAN cadence and
-    the resample mode stay the sweep's.  Pace is fixed: frame t of every row is frame t of its log.  Rows start on the device on the frames
+    the resample mode (`resample`, as `filter`'s) stay the sweep's.  Pace is fixed: frame t of every row is frame t of its log.  Rows start on the device on the frames
     seen while prev_idx == 0 (frames 0 and 1, filter.py:152-160; `BatchLoopEngine.start`); DBSCAN runs on every cluster_every-th
     frame, the measurement update on every update_freq-th (unit weights in between, filter_real.py:205-212).  Logs of different
     lengths: a row whose log has ended is stepped on (identity odometry, its last code and gt) and its surplus frames are never read
@@ -460,7 +471,7 @@ def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, m
         pfs.append(pf)
     eng = BatchLoopEngine.for_objects([(runs[r].codebook, None, pfs[r].mesh_kdtree) for r in plan["objects"]],
                                       plan["row_object"], rp["capacity"], seed=seed, cluster=cluster, cluster_every=cluster_every,
-                                      log_frames=max(T_max + 8, 64), device=device, wide=rp["wide"], **rp["engine"])
+                                      log_frames=max(T_max + 8, 64), device=device, wide=rp["wide"], resample=resample, **rp["engine"])
     odoms, codes, gts = sweep_inputs(runs, plan, device)
     init_noise = torch.tensor([pfs[r].init_noise for r in plan["row_run"]], dtype=torch.float32, device=device)
     counts = rp["num_particles"]

@@ -203,11 +203,14 @@ class _LoopBase:
         return max(first, last - self.log_frames), last
 
     # ---- seeded runs ----------------------------------------------------------------------------------------------
-    def _seed_streams(self, cls, seeds):
+    def _seed_streams(self, cls, seeds, systematic: bool = False):
         """The device replica(s) of torch's CPU generator (torch_rng `cls`) with their tables uploaded now, not by the first frame,
         and the buffers a seeded frame draws into -> (streams, scratch bytes of the generator's two counted calls at capacity)."""
-        if self.mode != _lib.RESAMPLE_MULTINOMIAL:
-            raise MidasError("a seeded torch stream reproduces torch.multinomial's draws: resample='weighted_random' only")
+        if systematic != (self.mode == _lib.RESAMPLE_SYSTEMATIC):
+            if systematic:
+                raise MidasError("the _low_var seeding is the systematic resampler's: resample='low_var' / 'low_var_batch' only")
+            raise MidasError("a seeded torch stream reproduces torch.multinomial's draws: resample='weighted_random' only - the "
+                             "systematic resampler's one float32 torch.rand(1) a frame: seed_torch_stream_low_var / seed_torch_streams_low_var")
         st = cls(seeds, self.device, overlap=False, pieces=0)
         st._normal_tables()
         lead, cap, d = self._lead, self.cap, self.device
@@ -215,12 +218,14 @@ class _LoopBase:
         self._u = torch.zeros(lead + (cap,), dtype=torch.float64, device=d)
         self._mt_status = torch.zeros(lead + (self.log_frames,), dtype=torch.int32, device=d)  # the counted calls' status, a word per log row
         ci = (self.ctl_i, _lib.LOOP_I_N)
-        return st, max(st.counted_scratch_bytes([("normal", 0.0, 1.0, *ci, 3, cap)] * 2), st.counted_scratch_bytes([("rand64", *ci, cap)]))
+        return st, max(st.counted_scratch_bytes([("normal", 0.0, 1.0, *ci, 3, cap)] * 2), st.counted_scratch_bytes([("rand64", *ci, cap)]),
+                       st.counted_scratch_bytes([("rand32", *ci, cap)]))
 
     def _seeded_frame(self, st, stds, bound: int, u_bound: int, front, resample, status=()):
         """One frame with the stream's draws: the motion noise sized by the live count (stds = None: none), the frame up to
-        annealing (`front()`), the uniforms sized by the annealed count, the resample (`resample()`) - four enqueues, the counts
-        never leave the device."""
+        annealing (`front()`), the resampler's draw - the uniforms sized by the annealed count (torch.multinomial,
+        particle_filter.py:245), or the one float32 offset of the systematic resampler (torch.rand(1), :291), which lands in the first
+        slot of every row of `_u` - and the resample (`resample()`): four enqueues, the counts never leave the device."""
         slot, ci = self.step_count % self.log_frames, self.ctl_i
         if slot == 0:
             self._mt_status.zero_()  # (the ring starts over, as the log's rows do)
@@ -231,7 +236,8 @@ class _LoopBase:
         front()
         # NDRAW, not NSET: the resampler returns its input before it draws when the weights are all zero or hold a NaN
         # (particle_filter.py:237-241) - the stream must not move on such a frame (a zero count consumes nothing)
-        st.draws_counted_async([("rand64", ci, _lib.LOOP_I_NDRAW, u_bound)], outs=[self._u], status=status)
+        kind = "rand64" if self.mode == _lib.RESAMPLE_MULTINOMIAL else "rand32"  # (rand32: NDRAW as a switch, 0 or 1 values)
+        st.draws_counted_async([(kind, ci, _lib.LOOP_I_NDRAW, u_bound)], outs=[self._u], status=status)
         resample()
 
     # ---- one frame ------------------------------------------------------------------------------------------------
@@ -242,6 +248,15 @@ class _LoopBase:
         if dbscan is False or (dbscan is None and self.step_count % self.cluster_every != 0):
             return phases & ~_lib.LOOP_DBSCAN
         return phases
+
+    def _seeded_u32(self, u32) -> float:
+        """The `u32` of a seeded frame: the stream draws the systematic offset, as it draws `u` - a caller's own is refused."""
+        if self.mode != _lib.RESAMPLE_SYSTEMATIC:
+            return float(u32)
+        if float(u32) >= 0.0:
+            raise MidasError("seeded torch stream: the stream draws the systematic offset - passing u32 would desynchronise the stream "
+                             "from the reference's")
+        return _lib.U32_FROM_U
 
     def _frame_scalars(self, u32, multiplier, unit_weights, std_override=None, score: bool = True):
         """What every call of a frame is told: its log row, the scalars, and - when it scores sparsely - its epoch."""
@@ -410,11 +425,20 @@ class LoopEngine(_LoopBase):
         return rec
 
     # ---- seeded runs ----------------------------------------------------------------------------------------------
-    def seed_torch_stream(self, seed):
+    def seed_torch_stream_low_var(self, seed):
+        """seed_torch_stream for an engine built with resample="low_var" / "low_var_batch": the resampler's draw of a frame is then
+        the one float32 `torch.rand(1)` of the systematic resampler (particle_filter.py:291), gated by ctl_i[LOOP_I_NDRAW] like the
+        uniforms, left in device memory and read there by the resample (MIDAS_U32_FROM_U); a caller's `u32 >= 0` on such a frame is
+        refused.  A method of its own: seed_torch_stream on a systematic engine refuses, as it always did."""
+        return self.seed_torch_stream(seed, _systematic=True)
+
+    def seed_torch_stream(self, seed, _systematic: bool = False):
         """Every draw of a frame from the device replica of torch's CPU generator under torch.manual_seed(seed) (torch_rng.py),
         in the reference's order and with the reference's sizes: `torch.normal(0, mul * sig_t, (n, 3))`, `torch.normal(0, mul *
         sig_r, (n, 3))` with n the live count (add_noise_to_odom, particle_filter.py:326-335) and, behind annealing, n_set float64
-        uniforms (the resampler's torch.multinomial, :245) - none on a frame whose weights are all zero or hold a NaN, where the
+        uniforms (the resampler's torch.multinomial, :245) or - seed_torch_stream_low_var on an engine built with
+        resample="low_var" (this method refuses such an engine, as it always did: it means multinomial's draws) - the one
+        float32 `torch.rand(1)` of the systematic resampler (:291) - none on a frame whose weights are all zero or hold a NaN, where the
         resampler returns before it draws (:237-241; ctl_i[LOOP_I_NDRAW]).  The counts are read on the device (midas_mt19937_draws_counted): a
         step() without tn / rot / u enqueues the whole frame and reads nothing back.  A run that also draws on the host (init_filter)
         hands the stream over with the returned TorchCpuStream's from_host() / to_host().  seed=None: back to Philox.
@@ -425,7 +449,7 @@ class LoopEngine(_LoopBase):
             self.torch_stream = None
             return None
         from .torch_rng import TorchCpuStream
-        st, need = self._seed_streams(TorchCpuStream, seed)
+        st, need = self._seed_streams(TorchCpuStream, seed, _systematic)
         self._no_noise = torch.zeros_like(self._tn)
         self.ctx.call("midas_scratch_reserve", max((128 << 20) + 256 * self.cap, need))  # (the generator shares the engine's context)
         self.torch_stream = st
@@ -436,6 +460,7 @@ class LoopEngine(_LoopBase):
         motion noise."""
         if self._pending_phases:
             raise MidasError("a seeded frame is enqueued whole: finish the frame in progress first")
+        u32 = self._seeded_u32(u32)
         b = self._count_bound()
         tn, rot, stds = self._no_noise, self._no_noise, None
         if motion_draws:

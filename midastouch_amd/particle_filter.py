@@ -321,7 +321,8 @@ class particle_filter:
     # ---------------------------------------------------------------------------------------------
     def seed_device_stream(self, seed: int):
         """torch.manual_seed(seed), kept on the device: every draw of the class surface - `init_filter`'s and `motionModel`'s
-        torch.normal calls (:129-130, :326-335), the uniforms `resampler("weighted_random")`'s torch.multinomial would consume (:245) -
+        torch.normal calls (:129-130, :326-335), the uniforms `resampler("weighted_random")`'s torch.multinomial would consume (:245),
+        the float32 `torch.rand(1)` offset of `resampler("low_var")` (:291) -
         then comes from the device replica of torch's CPU generator (midastouch_amd/torch_rng.py, torch_normal.py): the numbers of a
         run of the reference under that seed, bit for bit, nothing generated on the host.  `seed=None` returns to the host generator.  A seeded run replays the reference on the CPU, so `annealing` then
         also takes torch.topk's CPU choice inside a tie (`topk_ties`)."""
@@ -336,7 +337,8 @@ class particle_filter:
         "weighted_random" == torch.multinomial(p, N, replacement=True): a float64 CDF and one binary
         search per draw, the draws being torch.rand(N, dtype=float64) of the CPU generator (the stream
         torch.multinomial itself consumes).  "low_var"/"low_var_batch" == systematic resampling with the
-        single float32 torch.rand(1) offset (the batch variant's int16 counter overflow for N > 32767 and
+        single float32 torch.rand(1) offset - the host generator's, or after seed_device_stream() the device replica's, which the
+        search reads from device memory (the batch variant's int16 counter overflow for N > 32767 and
         its first-element miscount, :271,:279, are not reproduced).
         """
         particles = copy.copy(_particles)
@@ -353,8 +355,15 @@ class particle_filter:
             u = stream.rand64(nSamples) if stream is not None else torch.rand(nSamples, dtype=torch.float64)
             idxs = ops.resample_search(cdf, nSamples, _lib.RESAMPLE_MULTINOMIAL, u=u)
         elif resample in ("low_var", "low_var_batch"):
-            offset = torch.rand(1)
-            idxs = ops.resample_search(cdf, nSamples, _lib.RESAMPLE_SYSTEMATIC, u32=float(offset.item()))
+            stream = getattr(self, "torch_stream", None)
+            if stream is not None:  # seed_device_stream(): the offset stays on the device, read by the search from there (no .item())
+                (offset,), ev = stream.draws_async([("rand32",)])
+                if ev is not None:
+                    torch.cuda.current_stream(cdf.device).wait_event(ev)
+                idxs = ops.resample_search(cdf, nSamples, _lib.RESAMPLE_SYSTEMATIC, u=offset, u32=_lib.U32_FROM_U)
+            else:
+                offset = torch.rand(1)
+                idxs = ops.resample_search(cdf, nSamples, _lib.RESAMPLE_SYSTEMATIC, u32=float(offset.item()))
         else:
             raise ValueError(f"unknown resampling mode {resample!r}")
         self.last_resample_indices = idxs

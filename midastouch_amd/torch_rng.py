@@ -35,6 +35,24 @@ def normal_words(numel: int) -> int:
     return numel + (16 if numel % 16 else 0)
 
 
+def counted_segment_words(kind: int, per: int, bound: int) -> int:
+    """Raw words a counted call's scratch holds for one segment at its bound (csrc/mt19937.hip mt_counted_raw_words)."""
+    if kind == _lib.MT_SEGMENT_RAND64:
+        return 2 * per * bound
+    return 1 if kind == _lib.MT_SEGMENT_RAND32 else per * bound + 16
+
+
+def rand32_words(n: int = 1) -> int:
+    """32-bit generator outputs one CPU torch.rand(n) of float32 values consumes: one per value (its low 24 bits times 2^-24).
+    Only the single draw of the reference's systematic resampler (particle_filter.py:291) is modelled."""
+    if int(n) != 1:
+        raise _lib.MidasError("torch.rand of float32 values is modelled for the single draw torch.rand(1) only")
+    return 1
+
+
+_F64_KINDS = (_lib.MT_SEGMENT_RAND64, _lib.MT_SEGMENT_RAND32)  # (a rand32 value leaves the generator as the float64 that holds it)
+
+
 # ---- torch's host generator state <-> a device state row ----------------------------------------------------------------
 # Layout of the host state (CPUGeneratorImpl's legacy pod, 5056 bytes): uint64 seed | int32 left | int32 seeded | uint64 next |
 # uint64 state[624] | ..; a device row is the 624 words of the current block and the number of them consumed (csrc/mt19937.hip).
@@ -107,6 +125,10 @@ class _GeneratorSide:
     def skip_normal(self, numel: int):
         """Step over what torch.normal(mean, std, size) with `numel` float32 values takes."""
         return self.skip_words(normal_words(numel))
+
+    def skip_rand32(self, n: int = 1):
+        """Step over what torch.rand(1) of a float32 value takes (a systematic resampler's offset drawn on the host)."""
+        return self.skip_words(rand32_words(n))
 
     def _chain_polys(self, words: int, pieces: int | None = None):
         """The jump polynomials of a call of `words` words, or None (no history / too short: the sequential walk)."""
@@ -316,9 +338,10 @@ class TorchCpuStream(_GeneratorSide):
         return z
 
     def draws_async(self, spec):
-        """Several consecutive draws by ONE walk of the generator (midas_mt19937_draws): spec = sequence of ("rand64", N) and
-        ("normal", mean, std, size) in the stream's order - a seeded frame of the reference is normal (N, 3) twice and rand64 N
-        (particle_filter.py:326-335, :245).  Returns ([tensors], event or None): the numbers of the separate calls, fresh tensors,
+        """Several consecutive draws by ONE walk of the generator (midas_mt19937_draws): spec = sequence of ("rand64", N),
+        ("normal", mean, std, size) and ("rand32",) in the stream's order - a seeded frame of the reference is normal (N, 3) twice and
+        rand64 N (particle_filter.py:326-335, :245), or with the systematic resampler one rand32: torch.rand(1), a float32 value that
+        comes back as the one-element float64 tensor holding it exactly, as the resample kernels take it (:291).  Returns ([tensors], event or None): the numbers of the separate calls, fresh tensors,
         enqueued on the generator's stream behind the caller's current stream."""
         import ctypes as C
         outs, segs, words, need_tables = [], [], 0, False
@@ -328,6 +351,11 @@ class TorchCpuStream(_GeneratorSide):
                 out = torch.empty(n, dtype=torch.float64, device=self.device)
                 segs.append((_lib.MT_SEGMENT_RAND64, n, 0.0, 1.0, out))
                 words += 2 * n
+            elif item[0] == "rand32":
+                n = rand32_words(item[1] if len(item) > 1 else 1)
+                out = torch.empty(n, dtype=torch.float64, device=self.device)
+                segs.append((_lib.MT_SEGMENT_RAND32, n, 0.0, 1.0, out))
+                words += n
             elif item[0] == "normal":
                 _, mean, std, size = item
                 shape = tuple(size) if hasattr(size, "__len__") else (int(size),)
@@ -365,6 +393,9 @@ class TorchCpuStream(_GeneratorSide):
             if item[0] == "rand64":
                 _, cnt, idx, bound = item
                 items.append((_lib.MT_SEGMENT_RAND64, 0.0, 1.0, cnt, int(idx), 1, int(bound)))
+            elif item[0] == "rand32":  # (the count is a control word: one value when it is not zero; `bound` is its range and the row of `outs`)
+                _, cnt, idx, bound = item
+                items.append((_lib.MT_SEGMENT_RAND32, 0.0, 1.0, cnt, int(idx), 1, int(bound)))
             elif item[0] == "normal":
                 _, mean, std, cnt, idx, per, bound = item
                 items.append((_lib.MT_SEGMENT_NORMAL32, float(mean), float(std), cnt, int(idx), int(per), int(bound)))
@@ -379,12 +410,14 @@ class TorchCpuStream(_GeneratorSide):
         """Scratch one draws_counted_async(spec) call takes of the generator's context (sized by the bounds)."""
         words = 3 * 624
         for kind, _, _, _, _, per, bound in cls._counted_items(spec):
-            words += 2 * per * bound if kind == _lib.MT_SEGMENT_RAND64 else per * bound + 16
+            words += counted_segment_words(kind, per, bound)
         return (4 * words + 255) // 256 * 256 + 256
 
     def draws_counted_async(self, spec, outs=None, status=None):
         """draws_async for draws whose sizes stand in device memory (midas_mt19937_draws_counted): spec = sequence of
-        ("rand64", count_tensor, index, bound) and ("normal", mean, std, count_tensor, index, per, bound) in the stream's order -
+        ("rand64", count_tensor, index, bound), ("normal", mean, std, count_tensor, index, per, bound) and ("rand32", word_tensor,
+        index, bound) - torch.rand(1) when word_tensor[index] is not zero, nothing when it is zero: the systematic resampler's offset
+        on a frame where the resampler draws (ctl_i[LOOP_I_NDRAW]); the value is written to the first of `bound` float64 - in the stream's order -
         the draw takes per x count_tensor[index] values (rand64: per = 1) as that element stands when the kernels run, `bound` is
         what the host knows it cannot exceed.  The reference's loop, whose particle count annealing changes every frame: normal
         (n, 3) twice, then rand64 n_set (particle_filter.py:326-335, :245), enqueued without reading either count back.
@@ -406,10 +439,10 @@ class TorchCpuStream(_GeneratorSide):
         need_tables = False
         for i, (a, (kind, mean, std, cnt, idx, per, bound)) in enumerate(zip(arr, items)):
             if outs[i] is None:
-                outs[i] = torch.empty(per * bound, dtype=torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32, device=self.device)
+                outs[i] = torch.empty(per * bound, dtype=torch.float64 if kind in _F64_KINDS else torch.float32, device=self.device)
                 if self.side is not None:
                     outs[i].record_stream(self.side)
-            elif (outs[i].dtype != (torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32) or outs[i].numel() < per * bound
+            elif (outs[i].dtype != (torch.float64 if kind in _F64_KINDS else torch.float32) or outs[i].numel() < per * bound
                   or not outs[i].is_contiguous() or outs[i].device != self.device):
                 raise _lib.MidasError(f"draw {i}: `outs` wants a contiguous device tensor of at least {per * bound} values of the draw's type")
             need_tables |= kind == _lib.MT_SEGMENT_NORMAL32
@@ -426,6 +459,14 @@ class TorchCpuStream(_GeneratorSide):
         """The _lib.MT_STATUS_* bits draws_counted_async calls have set in the stream's own status word (one small read-back)."""
         st = getattr(self, "_status", None)
         return 0 if st is None else int(st.item())
+
+    def rand32(self) -> torch.Tensor:
+        """The next torch.rand(1) (float32, one generator output), ordered behind the caller's current stream: a fresh (1,) float32
+        tensor.  No read-back: the value stays on the device."""
+        (u,), ev = self.draws_async([("rand32",)])
+        if ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(ev)
+        return u.to(torch.float32)
 
     def rand64(self, N: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """The next N values of torch.rand(N, dtype=torch.float64) (== the draws of torch.multinomial(w64, N, True)), ordered
@@ -526,6 +567,10 @@ class TorchCpuStreams(_GeneratorSide):
                 n = int(item[1])
                 segs.append((_lib.MT_SEGMENT_RAND64, n, 0.0, 1.0, (n,)))
                 words += 2 * n
+            elif item[0] == "rand32":
+                n = rand32_words(item[1] if len(item) > 1 else 1)
+                segs.append((_lib.MT_SEGMENT_RAND32, n, 0.0, 1.0, (n,)))
+                words += n
             elif item[0] == "normal":
                 _, mean, std, size = item
                 shape = tuple(int(d) for d in size) if hasattr(size, "__len__") else (int(size),)
@@ -548,7 +593,7 @@ class TorchCpuStreams(_GeneratorSide):
         segs, words = self._segments(spec)
         outs, call = [], []
         for kind, count, mean, std, shape in segs:
-            dt = torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32
+            dt = torch.float64 if kind in _F64_KINDS else torch.float32
             out = torch.empty((self.B,) + shape, dtype=dt, device=self.device)
             if self.side is not None:
                 out.record_stream(self.side)
@@ -591,7 +636,7 @@ class TorchCpuStreams(_GeneratorSide):
         """Scratch one draws_counted_async(spec) call takes of the generator's context: B x TorchCpuStream's at the same bounds."""
         words = 3 * 624
         for kind, _, _, _, _, per, bound in self._counted_items(spec):
-            words += 2 * per * bound if kind == _lib.MT_SEGMENT_RAND64 else per * bound + 16
+            words += counted_segment_words(kind, per, bound)
         r = lambda b: (b + 255) // 256 * 256  # noqa: E731  (the allocator's rounding)
         return r(4 * words * self.B) + r(8 * 17 * self.B)
 
@@ -623,7 +668,7 @@ class TorchCpuStreams(_GeneratorSide):
         arr = (_lib.MtCountedSegment * len(items))()
         need_tables = False
         for i, (a, (kind, mean, std, cnt, idx, per, bound)) in enumerate(zip(arr, items)):
-            dt = torch.float64 if kind == _lib.MT_SEGMENT_RAND64 else torch.float32
+            dt = torch.float64 if kind in _F64_KINDS else torch.float32
             if outs[i] is None:
                 outs[i] = torch.empty((self.B, per * bound), dtype=dt, device=self.device)
                 if self.side is not None:

@@ -26,6 +26,8 @@ One JSON line per engine form with each figure's median over the repeats and [mi
   single_object   one plain BatchLoopEngine of the same B with every row on object 0 (what G codebooks cost beside one)
   objects_rows    objects_mixed with the filter's parameters per row (midas_loop_step_batch_rows), the SAME values in every row: the same
                   work, so the difference to objects_mixed is the cost of the parameter table (--form=objects_rows only)
+--resample=MODE: the engines' resample mode (weighted_random by default; low_var: the systematic resampler - with --seeded its one
+  float32 offset per row and frame in place of n_set float64 uniforms).
 --profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch, with --objects the mixed
   batch, with --form=NAME that form), no timing."""
 import json
@@ -82,6 +84,10 @@ codes = torch.as_tensor(np.stack([tr.codes for tr in trajs], axis=1)).to(dev)   
 gts = torch.as_tensor(np.stack([tr.gt_poses for tr in trajs], axis=1)).to(dev, torch.float32)
 starts = torch.as_tensor(np.stack([wide_start(cbs[ROW_OBJ[b]].extents, trajs[b].gt_poses[0], N0, 3000 + b) for b in range(B)])).to(dev, torch.float32)
 kw = dict(floor=FLOOR, cluster_every=EVERY, device=dev)
+for a in sys.argv[1:]:
+    if a.startswith("--resample="):
+        kw["resample"] = a.split("=", 1)[1]
+SYSTEMATIC = kw.get("resample", "weighted_random") != "weighted_random"  # (a seeded systematic engine: seed_torch_stream_low_var)
 HOST_US = None  # of the latest timed() run
 
 
@@ -115,7 +121,7 @@ def over_repeats(rows):
 def run_batch(seeds=None):
     eng = BatchLoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, B, N0, seed=SEED, batched_dbscan=DBSCAN, **kw, **({"wide": True} if wide else {}))
     if seeds is not None:
-        eng.seed_torch_streams(seeds)
+        (eng.seed_torch_streams_low_var if SYSTEMATIC else eng.seed_torch_streams)(seeds)
     eng.set_particles(starts)
     eng.project_to_codebook()
     ms = timed(lambda t: eng.step(odoms[t + 1], codes[t + 1], gts=gts[t + 1]), T)
@@ -126,7 +132,7 @@ def run_batch(seeds=None):
 def run_single(seed=None):
     eng = LoopEngine(cb.poses, cb.embeddings, cb.mesh_vertices, N0, seed=SEED, topk_ties="index" if seed is None else "aten_cpu", **kw)
     if seed is not None:
-        eng.seed_torch_stream(seed)
+        (eng.seed_torch_stream_low_var if SYSTEMATIC else eng.seed_torch_stream)(seed)
     eng.set_particles(starts[0])
     eng.project_to_codebook()
     ms = timed(lambda t: eng.step(odoms[t + 1, 0], codes[t + 1, 0], gt=gts[t + 1, 0]), T)
@@ -200,7 +206,8 @@ def run_single_seeded():
 
 
 head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R, **({"wide": True} if wide else {}),
-        **({} if DBSCAN is None else {"dbscan": "batched" if DBSCAN else "serial"}), **({"objects": G} if G else {})}
+        **({} if DBSCAN is None else {"dbscan": "batched" if DBSCAN else "serial"}), **({"objects": G} if G else {}),
+        **({"resample": kw["resample"]} if "resample" in kw else {})}
 out = {}
 forms = (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed))
 if wide:
