@@ -331,6 +331,18 @@ int midas_rmse(midas_ctx* ctx, int64_t N, const float* poses_dev, const float* g
 int midas_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses_dev, const double* weights64_dev,
                           const float* weights32_dev, const int64_t* labels_dev, int32_t C, const int64_t* label_values_dev,
                           float* centers_dev, float* stds_dev, int64_t* counts_dev);
+/* get_cluster_centers(method="logmap"), the reference signature's default (modules/particle_filter.py:153-206 with
+ * pose.log_map_averaged, modules/pose.py:101-109): midas_cluster_centers' arguments, limits, scratch rule, summation order, float32
+ * weights, flatten rule, NaN rule and empty-label rows; the centre is exp(sum w xi / sum w) of the members' se(3) logarithms
+ * xi = [V^-1 t, omega] (midas_se3_log) - its translation is NOT the weighted mean translation - and the spread is taken around
+ * that centre's float32 translation.  DESIGN.md 2, "The log-map centre's arithmetic". */
+int midas_cluster_centers_logmap(midas_ctx* ctx, int64_t N, const float* poses_dev, const double* weights64_dev,
+                                 const float* weights32_dev, const int64_t* labels_dev, int32_t C, const int64_t* label_values_dev,
+                                 float* centers_dev, float* stds_dev, int64_t* counts_dev);
+/* xi_dev (N x 6 float64) = [u, omega] of the N poses (N x 16 float32, 16-byte aligned): omega the float32 SO(3) logarithm of
+ * midas_se3_feature widened, u = t - a / 2 + c (omega x a) with a = omega x t and
+ * c = theta > 1e-6 ? (1 - (theta / 2) cos(theta / 2) / sin(theta / 2)) / theta^2 : 1 / 12 in float64 (theseus SE3.log_map). */
+int midas_se3_log(midas_ctx* ctx, int64_t N, const float* poses_dev, double* xi_dev);
 
 /* ---- single-touch evaluation: top-n of similarity rows + best pose error (next-3) ------------- */
 /* eval/single_touch_test.py:35-73 top_n_error: for each of the B query rows of scores_dev (B x K float64, row b = the
@@ -887,6 +899,10 @@ int midas_tail_resample(midas_ctx* ctx, const midas_tail_resample_args* args);
 #define MIDAS_LOOP_DBSCAN 2
 #define MIDAS_LOOP_ANNEAL 4
 #define MIDAS_LOOP_RESAMPLE 8
+/* not a phase but the form of ANNEAL's cluster centres: set, they are the log-map centres of midas_cluster_centers_logmap (the
+ * frame's spreads, the annealing decision and the log row's cluster_poses / cluster_stds follow), clear, the quaternion form's.
+ * Allowed only together with MIDAS_LOOP_ANNEAL (MIDAS_ERR_INVALID before any launch otherwise); taken by all six loop entries. */
+#define MIDAS_LOOP_CENTERS_LOGMAP 16
 #define MIDAS_LOOP_MAX_CLUSTERS 64
 /* ctl_i (32 x int32) */
 #define MIDAS_LOOP_I_N 0       /* live particle count (set by the caller before the first frame) */

@@ -221,6 +221,7 @@ LOOP_ROW_PARAMS_DTYPE = [("std_t", "<f4"), ("std_r", "<f4"), ("prune_thr", "<f8"
 
 # phases of midas_loop_step and the control-block indices (include/midas_hip.h MIDAS_LOOP_*)
 LOOP_FRONT, LOOP_DBSCAN, LOOP_ANNEAL, LOOP_RESAMPLE = 1, 2, 4, 8
+LOOP_CENTERS_LOGMAP = 16  # the form of ANNEAL's cluster centres (MIDAS_LOOP_CENTERS_LOGMAP): only together with LOOP_ANNEAL
 MT19937_HIST_WORDS = 20560  # MIDAS_MT19937_HIST_WORDS
 TOPK_TIES_INDEX, TOPK_TIES_ATEN_CPU = 0, 1  # whom annealing's torch.topk takes inside a tie (include/midas_hip.h)
 LOOP_MAX_CLUSTERS, LOOP_LOG_DOUBLES = 64, 168
@@ -287,6 +288,8 @@ SIGNATURES = {
     "midas_tsne_gradient": (C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P]),
     "midas_tsne_optimize": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _I32, _D, _D, _I32, _I32, _I32, _D, _P]),
     "midas_cluster_centers": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "midas_cluster_centers_logmap": (C.c_int, [_P, _I64, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "midas_se3_log": (C.c_int, [_P, _I64, _P, _P]),
     "midas_filter_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(StepArgs)]),
     "midas_filter_step_batch": (C.c_int, [_P, _P, _P, _P, C.POINTER(StepArgs), _I32]),
     "midas_lazy_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(LazyArgs)]),

@@ -63,7 +63,7 @@ from .loop_engine import ALL_PHASES, TOPK_TIES, _LoopBase, log_records
 
 # the constructor's keywords and their defaults: what `for_objects` takes as **kw (tests hold __init__'s signature to this table)
 DEFAULTS = dict(sig_t=2e-4, sig_r=0.5, pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor=1000, eps=1e-2,
-                cluster=True, cluster_every=50, log_frames=4096, device=None, wide=False, batched_dbscan=None)
+                cluster=True, cluster_every=50, log_frames=4096, device=None, wide=False, batched_dbscan=None, centers="quat_avg")
 
 
 ROW_PARAMS = ("sig_t", "sig_r", "pen_max", "floor", "softmax")  # what a row may hold for itself (set_row_params' keywords)
@@ -125,13 +125,13 @@ class BatchLoopEngine(_LoopBase):
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, batch: int, num_particles: int, *, sig_t=2e-4, sig_r=0.5,
                  pen_max=0.002, seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2,
                  cluster: bool = True, cluster_every: int = 50, log_frames: int = 4096, device=None, wide: bool = False,
-                 batched_dbscan=None):
+                 batched_dbscan=None, centers: str = "quat_avg"):
         self._init([(cb_poses, cb_embeddings, mesh_vertices)], None, batch, num_particles, sig_t=sig_t, sig_r=sig_r, pen_max=pen_max,
                    seed=seed, softmax=softmax, resample=resample, floor=floor, eps=eps, cluster=cluster, cluster_every=cluster_every,
-                   log_frames=log_frames, device=device, wide=wide, batched_dbscan=batched_dbscan)
+                   log_frames=log_frames, device=device, wide=wide, batched_dbscan=batched_dbscan, centers=centers)
 
     def _init(self, objects, row_object, batch, num_particles, *, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps, cluster,
-              cluster_every, log_frames, device, wide, batched_dbscan):
+              cluster_every, log_frames, device, wide, batched_dbscan, centers="quat_avg"):
         """The one initialiser behind the constructor (one object, row_object None) and `for_objects`: the bounds, the set-up on the
         first row's object, for an object batch every object's index and the object set, then the state and the scratch."""
         self._check_regime(batch, num_particles, wide, batched_dbscan)
@@ -141,7 +141,8 @@ class BatchLoopEngine(_LoopBase):
         rows = {k: v[1] for k, v in given.items()}
         sig_t, sig_r, pen_max, floor, softmax = (given[k][0] if rows[k] is None else rows[k][0] for k in ROW_PARAMS)
         first = 0 if row_object is None else row_object[0]  # the handles `_LoopBase` names (ctx, cb_poses, tree6, codebook, tree3): row 0's object
-        self._setup(*objects[first], device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps, cluster, cluster_every, log_frames)
+        self._setup(*objects[first], device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps, cluster, cluster_every, log_frames,
+                    centers)
         if not sparse_scoring(self.codebook, switch=False):
             raise MidasError("BatchLoopEngine scores sparsely: a float32 codebook with D in {128, 256, 512, 1024}")
         self.objects = self.row_object = self.Ks = self._set = None  # (for_objects)

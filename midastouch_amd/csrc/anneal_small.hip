@@ -42,12 +42,13 @@ __global__ __launch_bounds__(256) void k_loop_decide_rows(int32_t* __restrict__ 
 
 int launch_loop_decide(midas_ctx* ctx, const midas_loop_args& s, const LoopGrid& g, const LoopMoments& m, uint32_t* hist,
                        int32_t* sel_state, int32_t frozen, int32_t aten_order) {
+    const unsigned wgs = g.logmap ? 1u : 2u;  // (log-map centres are whole when they get here: no workgroup for the rotations)
     if (g.rows)
-        hipLaunchKernelGGL(k_loop_decide_rows, dim3(2, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
+        hipLaunchKernelGGL(k_loop_decide_rows, dim3(wgs, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
                            (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, hist, sel_state, g.rows,
                            (const double*)m.rot, frozen, aten_order);
     else
-        hipLaunchKernelGGL(k_loop_decide, dim3(2, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
+        hipLaunchKernelGGL(k_loop_decide, dim3(wgs, g.by()), dim3(256), 0, ctx->stream, s.ctl_i_dev, s.ctl_d_dev, (const float*)m.cen,
                            (const float*)m.sd, (const int64_t*)m.cnt, s.cluster_poses_dev, s.cluster_stds_dev, hist, sel_state, s.floor,
                            (const double*)m.rot, frozen, aten_order);
     return MIDAS_OK;
@@ -369,11 +370,12 @@ __global__ __launch_bounds__(1024) void k_loop_anneal_small_rows(int32_t* __rest
 // a plan the host left in ctl_i (launch_anneal_select: one workgroup, no cluster arrays)
 int launch_anneal_small(midas_ctx* ctx, const LoopGrid& g, int32_t* ctl_i, double* ctl_d, const LoopMoments* m, float* centers_out,
                         float* stds_out, int32_t floor_n, const double* w, int32_t* src) {
+    const unsigned wgs = g.logmap ? 1u : 2u;  // (log-map centres are whole when they get here: no workgroup for the rotations)
     if (m && g.rows)
-        hipLaunchKernelGGL(k_loop_anneal_small_rows, dim3(2, g.by()), dim3(1024), 0, ctx->stream, ctl_i, ctl_d, (const float*)m->cen,
+        hipLaunchKernelGGL(k_loop_anneal_small_rows, dim3(wgs, g.by()), dim3(1024), 0, ctx->stream, ctl_i, ctl_d, (const float*)m->cen,
                            (const float*)m->sd, (const int64_t*)m->cnt, centers_out, stds_out, g.rows, w, src, (const double*)m->rot, g.slice);
     else if (m)
-        hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(2, g.by()), dim3(1024), 0, ctx->stream, ctl_i, ctl_d, (const float*)m->cen,
+        hipLaunchKernelGGL(k_loop_anneal_small<true>, dim3(wgs, g.by()), dim3(1024), 0, ctx->stream, ctl_i, ctl_d, (const float*)m->cen,
                            (const float*)m->sd, (const int64_t*)m->cnt, centers_out, stds_out, floor_n, w, src, (const double*)m->rot, g.slice);
     else
         hipLaunchKernelGGL(k_loop_anneal_small<false>, dim3(1, g.by()), dim3(1024), 0, ctx->stream, ctl_i, ctl_d, (const float*)nullptr,

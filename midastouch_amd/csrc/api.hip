@@ -545,6 +545,24 @@ MIDAS_EXPORT int midas_cluster_centers(midas_ctx* ctx, int64_t N, const float* p
                                   stds_dev, counts_dev);
 }
 
+MIDAS_EXPORT int midas_cluster_centers_logmap(midas_ctx* ctx, int64_t N, const float* poses_dev, const double* weights64_dev,
+                                              const float* weights32_dev, const int64_t* labels_dev, int32_t C,
+                                              const int64_t* label_values_dev, float* centers_dev, float* stds_dev,
+                                              int64_t* counts_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, N > 0 && poses_dev && labels_dev && label_values_dev && centers_dev && stds_dev && C >= 1 && C <= 65535);
+    MIDAS_REQUIRE(ctx, (weights64_dev == nullptr) != (weights32_dev == nullptr));
+    MIDAS_REQUIRE(ctx, (uintptr_t)poses_dev % 16 == 0);
+    return launch_cluster_centers(ctx, N, poses_dev, weights64_dev, weights32_dev, labels_dev, C, label_values_dev, centers_dev,
+                                  stds_dev, counts_dev, true);
+}
+
+MIDAS_EXPORT int midas_se3_log(midas_ctx* ctx, int64_t N, const float* poses_dev, double* xi_dev) {
+    MIDAS_ENTER(ctx);
+    MIDAS_REQUIRE(ctx, N > 0 && poses_dev && xi_dev && (uintptr_t)poses_dev % 16 == 0);
+    return launch_se3_log(ctx, N, poses_dev, xi_dev);
+}
+
 MIDAS_EXPORT int midas_anneal_select(midas_ctx* ctx, int64_t N, const double* weights_dev, int32_t mode, int64_t k,
                                      int32_t* src_dev) {
     MIDAS_ENTER(ctx);

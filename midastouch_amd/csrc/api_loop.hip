@@ -19,7 +19,10 @@ enum class LoopRegime { single, batch, batch_draws, batch_wide };
 static int loop_args_check(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* tree6, const midas_tree* tree3,
                            const midas_loop_args* args, int32_t phases, LoopRegime regime, int32_t B = 1, int64_t log_stride = 0,
                            const midas_object_set* objects = nullptr) {  // objects: in place of cb, the trees and args->cb_poses_dev
-    MIDAS_REQUIRE(ctx, args != nullptr && phases != 0 && (phases & ~15) == 0);
+    // the four phases; beyond them only the form of the centres, which belongs to the phase that takes them: alone, or beside other
+    // phases only, it selects nothing (one condition: a refused mask names the phases' rule it broke)
+    MIDAS_REQUIRE(ctx, args != nullptr && phases != 0 &&
+                           ((phases & ~15) == 0 || ((phases & ~15) == MIDAS_LOOP_CENTERS_LOGMAP && (phases & MIDAS_LOOP_ANNEAL))));
     const midas_loop_args& s = *args;
     const bool batch = regime != LoopRegime::single;
     MIDAS_REQUIRE(ctx, B >= 1 && B <= 65535);

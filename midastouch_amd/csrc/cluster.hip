@@ -13,6 +13,7 @@
 #include "midas_internal.hpp"
 #include "midas_math.hpp"
 #include "cluster_rot.hpp"
+#include "cluster_logmap.hpp"
 #include "loop_weights.hpp"
 
 namespace midas {
@@ -84,7 +85,10 @@ MD MomIn moments_load(int64_t nc, const float* __restrict__ poses, const double*
 // They are not simply +0.0: the sums are of 0 x (a product of quaternion components, a translation) over every lane, which is -0.0
 // where EVERY lane's factor is negative - the signs are taken once per workgroup (13 of them) - and NaN where some lane's pose
 // is not finite (then nothing is skipped).  Same bits as the sums (tests/test_gpu_knobs.py: MIDAS_MOMENTS_SKIP=0).
-template <typename LV>
+// FORM (cluster_logmap.hpp): CL_FORM_QUAT the ten products of the sign-fixed quaternion's components, CL_FORM_LOGMAP the six
+// components of the se(3) logarithm in the first six of those slots (the other four +0.0) - the skip's signs are then the six
+// components' own.  Everything else - order, extrema, translation moments - is one text.
+template <int FORM = CL_FORM_QUAT, typename LV>
 MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, double* __restrict__ part, double (*s_w)[CL_MOM],
                            bool skip = true) {
     __shared__ unsigned long long s_mem[4];
@@ -94,9 +98,20 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
     const float* P = in.P;
     const int64_t lab = in.lab;
     const double w = in.w;
-    double q[4];
-    quat_of(P, q);
-    const double tx = P[3], ty = P[7], tz = P[11];
+    constexpr int NQ = FORM == CL_FORM_LOGMAP ? 6 : 4;
+    double q[NQ];  // (log-map form: xi)
+    if constexpr (FORM == CL_FORM_LOGMAP) se3_log_f64(P, q);
+    else quat_of(P, q);
+    // A lane beyond the live count holds whatever pose lies there (the merged launch reads before it knows the count): rows never
+    // written are zero matrices, whose logarithm is NaN, and 0 x NaN would spoil every cluster's sums - such a lane counts as xi = 0,
+    // t = 0 in the log-map form (a zero matrix has a finite quaternion: the quaternion form takes the lane as it is)
+    constexpr bool dead_is_zero = FORM == CL_FORM_LOGMAP;
+    if (dead_is_zero && !live) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) q[i] = 0.0;
+    }
+    const bool zt = dead_is_zero && !live;
+    const double tx = zt ? 0.0 : P[3], ty = zt ? 0.0 : P[7], tz = zt ? 0.0 : P[11];
     unsigned long long wgmask = ~0ull;
     unsigned sgn = 0;
     if (skip && C <= 64) {
@@ -104,6 +119,10 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
         for (int c = 0; c < C; ++c) mm |= __any(live && lab == label_value(c)) ? (1ull << c) : 0ull;
         unsigned sg = 0;
         int k = 0;
+        if constexpr (FORM == CL_FORM_LOGMAP) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sg |= __all(__builtin_signbit(q[i]) ? 1 : 0) ? (1u << i) : 0u;
+        } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -112,10 +131,12 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
                 sg |= __all(__builtin_signbit(qq) ? 1 : 0) ? (1u << k) : 0u;
                 ++k;
             }
+        }
         sg |= __all(__builtin_signbit(tx) ? 1 : 0) ? (1u << 10) : 0u;
         sg |= __all(__builtin_signbit(ty) ? 1 : 0) ? (1u << 11) : 0u;
         sg |= __all(__builtin_signbit(tz) ? 1 : 0) ? (1u << 12) : 0u;
         const bool fin = __builtin_isfinite(q[0]) && __builtin_isfinite(q[1]) && __builtin_isfinite(q[2]) && __builtin_isfinite(q[3]) &&
+                         __builtin_isfinite(q[NQ - 2]) && __builtin_isfinite(q[NQ - 1]) &&  // (log-map form: xi's last two)
                          __builtin_isfinite(tx) && __builtin_isfinite(ty) && __builtin_isfinite(tz);
         sg |= __all(fin ? 1 : 0) ? (1u << 31) : 0u;
         if (lane == 0) { s_mem[wv] = mm; s_sgn[wv] = sg; }
@@ -132,8 +153,9 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
                 else if (t == M_WMIN) r = INFINITY;
                 else {
                     int bit = -1;
-                    if (t >= M_QQW && t < M_QQW + 10) bit = t - M_QQW;
-                    else if (t >= M_QQ1 && t < M_QQ1 + 10) bit = t - M_QQ1;
+                    constexpr int NS = FORM == CL_FORM_LOGMAP ? 6 : 10;  // (log-map form: the four slots behind the six are +0.0)
+                    if (t >= M_QQW && t < M_QQW + NS) bit = t - M_QQW;
+                    else if (t >= M_QQ1 && t < M_QQ1 + NS) bit = t - M_QQ1;
                     else if (t >= M_TW && t < M_TW + 3) bit = 10 + t - M_TW;
                     else if (t >= M_T1 && t < M_T1 + 3) bit = 10 + t - M_T1;
                     if (bit >= 0 && ((sgn >> bit) & 1u)) r = -0.0;
@@ -146,6 +168,10 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
         const double a = mine ? w : 0.0, b = mine ? 1.0 : 0.0;
         v[M_SW] = a; v[M_CNT] = b; v[M_WMAX] = 0.0; v[M_WMIN] = 0.0;
         int k = 0;
+        if constexpr (FORM == CL_FORM_LOGMAP) {
+#pragma unroll
+            for (int i = 0; i < 10; ++i) { v[M_XW + i] = i < 6 ? a * q[i % 6] : 0.0; v[M_X1 + i] = i < 6 ? b * q[i % 6] : 0.0; }
+        } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -154,6 +180,7 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
                 v[M_QQW + k] = a * qq; v[M_QQ1 + k] = b * qq;
                 ++k;
             }
+        }
         v[M_TW] = a * tx; v[M_TW + 1] = a * ty; v[M_TW + 2] = a * tz;
         v[M_T1] = b * tx; v[M_T1 + 1] = b * ty; v[M_T1 + 2] = b * tz;
         v[M_TTW] = a * tx * tx; v[M_TTW + 1] = a * ty * ty; v[M_TTW + 2] = a * tz * tz;
@@ -161,7 +188,8 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
         const double mx = cl_wmax(mine ? w : -INFINITY), mn = cl_wmin(mine ? w : INFINITY);
 #pragma unroll
         for (int m = 0; m < CL_MOM; ++m)
-            if (m != M_WMAX && m != M_WMIN) v[m] = cl_wsum(v[m]);
+            if (m != M_WMAX && m != M_WMIN && !(FORM == CL_FORM_LOGMAP && ((m >= M_XW + 6 && m < M_XW + 10) || (m >= M_X1 + 6 && m < M_X1 + 10))))
+                v[m] = cl_wsum(v[m]);  // (the log-map form's eight idle slots stay +0.0: 26 wave sums a cluster)
         __syncthreads();  // the previous cluster's LDS values have been read
         if (lane == 0) {
 #pragma unroll
@@ -179,14 +207,14 @@ MD void moments_accumulate(bool live, const MomIn& in, int C, LV label_value, do
     }
 }
 
-template <typename LabelT, typename LV>
+template <int FORM = CL_FORM_QUAT, typename LabelT, typename LV>
 MD void cluster_moments_body(int64_t N, const float* __restrict__ poses, const double* __restrict__ w64,
                              const float* __restrict__ w32, const LabelT* __restrict__ labels, int C, LV label_value,
                              double* __restrict__ part, double (*s_w)[CL_MOM], bool skip) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = n < N;
     const MomIn in = moments_load(live ? n : N - 1, poses, w64, w32, labels);
-    moments_accumulate(live, in, C, label_value, part, s_w, skip);
+    moments_accumulate<FORM>(live, in, C, label_value, part, s_w, skip);
 }
 
 __global__ __launch_bounds__(256) void k_cluster_moments(int64_t N, const float* __restrict__ poses, const double* __restrict__ w64,
@@ -195,13 +223,33 @@ __global__ __launch_bounds__(256) void k_cluster_moments(int64_t N, const float*
     __shared__ double s_w[4][CL_MOM];
     cluster_moments_body(N, poses, w64, w32, labels, C, [&](int c) { return label_values[c]; }, part, s_w, skip);
 }
+// the log-map form (midas_cluster_centers_logmap)
+__global__ __launch_bounds__(256) void k_cluster_moments_logmap(int64_t N, const float* __restrict__ poses, const double* __restrict__ w64,
+                                                                const float* __restrict__ w32, const int64_t* __restrict__ labels, int C,
+                                                                const int64_t* __restrict__ label_values, double* __restrict__ part,
+                                                                bool skip) {
+    __shared__ double s_w[4][CL_MOM];
+    cluster_moments_body<CL_FORM_LOGMAP>(N, poses, w64, w32, labels, C, [&](int c) { return label_values[c]; }, part, s_w, skip);
+}
+
+// N poses -> their se(3) logarithms [u, omega], (N, 6) float64 (midas_se3_log): what the log-map moments are sums of
+__global__ __launch_bounds__(256) void k_se3_log(int64_t N, const float* __restrict__ poses, double* __restrict__ xi_out) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    MomIn in;
+    moments_load_pose(n, poses, in);
+    double xi[6];
+    se3_log_f64(in.P, xi);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) xi_out[n * 6 + i] = xi[i];
+}
 
 // loop engine: labels are DBSCAN's int32 values in [-1, ncl), cluster slot c stands for label c - 1; the particle count
 // and ncl come from the control block (midas_loop_step)
-__global__ __launch_bounds__(256) void k_loop_cluster_moments(const int32_t* __restrict__ ctl_i, const float* __restrict__ poses,
-                                                              const double* __restrict__ w64, const int32_t* __restrict__ labels,
-                                                              double* __restrict__ part, bool skip, int32_t cap) {
-    __shared__ double s_w[4][CL_MOM];
+template <int FORM>
+MD void loop_cluster_moments_body(const int32_t* __restrict__ ctl_i, const float* __restrict__ poses, const double* __restrict__ w64,
+                                  const int32_t* __restrict__ labels, double* __restrict__ part, bool skip, int32_t cap,
+                                  double (*s_w)[CL_MOM]) {
     if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): `cap` particles and a launch's partials per trajectory
         const int64_t b = blockIdx.y, o = b * cap;
         ctl_i += b * LOOP_CTL_I; poses += o * 16; w64 += o; labels += o;
@@ -211,7 +259,19 @@ __global__ __launch_bounds__(256) void k_loop_cluster_moments(const int32_t* __r
     int C = ctl_i[LOOP_I_NCL] + 1;
     C = C > LOOP_MAX_CLUSTERS ? LOOP_MAX_CLUSTERS : C;
     if ((int64_t)blockIdx.x * 256 >= n) return;
-    cluster_moments_body(n, poses, w64, (const float*)nullptr, labels, C, [](int c) { return (int64_t)(c - 1); }, part, s_w, skip);
+    cluster_moments_body<FORM>(n, poses, w64, (const float*)nullptr, labels, C, [](int c) { return (int64_t)(c - 1); }, part, s_w, skip);
+}
+__global__ __launch_bounds__(256) void k_loop_cluster_moments(const int32_t* __restrict__ ctl_i, const float* __restrict__ poses,
+                                                              const double* __restrict__ w64, const int32_t* __restrict__ labels,
+                                                              double* __restrict__ part, bool skip, int32_t cap) {
+    __shared__ double s_w[4][CL_MOM];
+    loop_cluster_moments_body<CL_FORM_QUAT>(ctl_i, poses, w64, labels, part, skip, cap, s_w);
+}
+__global__ __launch_bounds__(256) void k_loop_cluster_moments_logmap(const int32_t* __restrict__ ctl_i, const float* __restrict__ poses,
+                                                                     const double* __restrict__ w64, const int32_t* __restrict__ labels,
+                                                                     double* __restrict__ part, bool skip, int32_t cap) {
+    __shared__ double s_w[4][CL_MOM];
+    loop_cluster_moments_body<CL_FORM_LOGMAP>(ctl_i, poses, w64, labels, part, skip, cap, s_w);
 }
 
 // The same with the frame's weights computed at its head (loop_weights.hpp: k_loop_weights' arithmetic, one particle a thread):
@@ -226,60 +286,22 @@ __global__ __launch_bounds__(256) void k_loop_cluster_moments(const int32_t* __r
 template <class Args>  // LoopWeightsArgs, LoopWeightsRowsArgs - rows on different objects - or LoopWeightsParamRowsArgs (loop_weights.hpp)
 __global__ __launch_bounds__(256) void k_loop_weights_moments(Args a, const int32_t* __restrict__ labels,
                                                               double* __restrict__ part, bool skip) {
-#ifdef MIDAS_ANNEAL_CLOCKS
-    const long long wck0 = wall_clock64();
-#endif
-    __shared__ double s_w[4][CL_MOM];
-    __shared__ double s_sum[LAZY_MAX_BLOCKS];
-    __shared__ double s_red[8], s_ab[8];
-    __shared__ int s_ired[8];
-    if (blockIdx.y || loop_weights_every_row(a)) {  // a batch of trajectories (midas_loop_step_batch)
-        labels += (int64_t)blockIdx.y * a.grid_n;
-        part += (size_t)blockIdx.y * gridDim.x * LOOP_MAX_CLUSTERS * CL_MOM;
-        loop_weights_batch(a, blockIdx.y);
-    }
-    const int t = threadIdx.x;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + t, ic = idx < a.grid_n ? idx : a.grid_n - 1;
-    const LoopWeightsPre pre = loop_weights_prefetch(a, blockIdx.x == 0);
-    const double e_i = a.e[ic], x_i = a.x[ic];
-    const uint8_t v_i = a.valid[ic];
-    const int32_t nn_i = a.nn_idx[ic];
-    MomIn in = moments_load(ic, a.poses_prop, (const double*)nullptr, (const float*)nullptr, labels);  // (w: below)
-    const int64_t n = a.ctl_i[LOOP_I_N];
-    int C = a.ctl_i[LOOP_I_NCL] + 1;
-    C = C > LOOP_MAX_CLUSTERS ? LOOP_MAX_CLUSTERS : C;
-    if ((int64_t)blockIdx.x * 256 >= n && blockIdx.x != 0) return;
-    WCK(24);
-    const LoopWeightsHead h = loop_weights_head(a, pre, n, s_sum, s_red, s_ired);
-    WCK(25);
-    const bool live = idx < n;
-    double w = 0.0;
-    if (live) {
-        w = loop_weight_store(a, h, idx, e_i, x_i, v_i);
-        if (h.drifted) {  // every particle back onto its codebook pose; the moments are taken of the re-projected set
-            const float4* s4 = reinterpret_cast<const float4*>(a.cb_poses + (size_t)nn_i * 16);
-            float4* d4 = reinterpret_cast<float4*>(a.poses_prop + (size_t)idx * 16);
-            const float4 r0 = s4[0], r1 = s4[1], r2 = s4[2], r3 = s4[3];
-            d4[0] = r0; d4[1] = r1; d4[2] = r2; d4[3] = r3;
-            in.P[0] = r0.x; in.P[1] = r0.y; in.P[2] = r0.z; in.P[3] = r0.w;
-            in.P[4] = r1.x; in.P[5] = r1.y; in.P[6] = r1.z; in.P[7] = r1.w;
-            in.P[8] = r2.x; in.P[9] = r2.y; in.P[10] = r2.z; in.P[11] = r2.w;
-        }
-    }
-    in.w = (double)(float)w;  // particles.weights.float() (:161)
-    WCK(26);
-    if ((int64_t)blockIdx.x * 256 < n) moments_accumulate(live, in, C, [](int c) { return (int64_t)(c - 1); }, part, s_w, skip);
-    WCK(27);
-    if (blockIdx.x == 0) loop_weights_finalise(a, h, pre, s_ab);
-    WCK(28);
-#ifdef MIDAS_ANNEAL_CLOCKS
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl_d[56 + 29] += 1.0;
-#endif
+    constexpr int FORM = CL_FORM_QUAT;
+#include "loop_weights_moments_body.hpp"
+}
+// the log-map form of the same launch (MIDAS_LOOP_CENTERS_LOGMAP): one text, the moments' form apart
+template <class Args>
+__global__ __launch_bounds__(256) void k_loop_weights_moments_logmap(Args a, const int32_t* __restrict__ labels,
+                                                                     double* __restrict__ part, bool skip) {
+    constexpr int FORM = CL_FORM_LOGMAP;
+#include "loop_weights_moments_body.hpp"
 }
 
 // one 64-thread workgroup per cluster: blocks summed in order, then the closed forms
 // rot_out (loop step): the normalised moment matrix goes there (10 doubles per cluster) and the rotation entries of the
 // centre are left to whoever solves it (cluster_rotation_write, beside the annealing); nullptr: solved here
+// FORM: the closed forms of the moments' form - cluster_close, or cluster_close_logmap (the whole centre is written: no rot_out)
+template <int FORM = CL_FORM_QUAT>
 MD void cluster_finish_body(int nblocks, size_t nbs, int c, const double* __restrict__ part, float* __restrict__ centers,
                             float* __restrict__ stds, int64_t* __restrict__ counts, double* s_m, double* __restrict__ rot_out = nullptr) {
     const int t = threadIdx.x;
@@ -393,6 +415,9 @@ MD void cluster_finish_body(int nblocks, size_t nbs, int c, const double* __rest
     }
     __syncthreads();
     if (t != 0) return;
+    if constexpr (FORM == CL_FORM_LOGMAP)
+        cluster_close_logmap(s_m, centers + (size_t)c * 16, stds + (size_t)c * 3, counts ? counts + c : nullptr);
+    else
     cluster_close(s_m, centers + (size_t)c * 16, stds + (size_t)c * 3, counts ? counts + c : nullptr,
                   rot_out ? rot_out + (size_t)c * 10 : nullptr);
 }
@@ -403,12 +428,18 @@ __global__ __launch_bounds__(64) void k_cluster_finish(int nblocks, int C, const
     __shared__ double s_m[CL_MOM];
     cluster_finish_body(nblocks, (size_t)nblocks, blockIdx.x, part, centers, stds, counts, s_m);
 }
+__global__ __launch_bounds__(64) void k_cluster_finish_logmap(int nblocks, int C, const double* __restrict__ part,
+                                                              float* __restrict__ centers, float* __restrict__ stds,
+                                                              int64_t* __restrict__ counts) {
+    __shared__ double s_m[CL_MOM];
+    cluster_finish_body<CL_FORM_LOGMAP>(nblocks, (size_t)nblocks, blockIdx.x, part, centers, stds, counts, s_m);
+}
 
 // loop engine: cluster slot c = blockIdx.x of the LOOP_MAX_CLUSTERS launched; rows of label c - 1
-__global__ __launch_bounds__(256) void k_loop_cluster_finish(const int32_t* __restrict__ ctl_i, const double* __restrict__ part,
-                                                            float* __restrict__ centers, float* __restrict__ stds,
-                                                            int64_t* __restrict__ counts, double* __restrict__ rot, int32_t nbs) {
-    __shared__ double s_m[CL_MOM];
+template <int FORM>
+MD void loop_cluster_finish_body(const int32_t* __restrict__ ctl_i, const double* __restrict__ part, float* __restrict__ centers,
+                                 float* __restrict__ stds, int64_t* __restrict__ counts, double* __restrict__ rot, int32_t nbs,
+                                 double* s_m) {
     if (blockIdx.y) {  // a batch of trajectories (midas_loop_step_batch): LOOP_MAX_CLUSTERS rows of everything per trajectory
         const size_t b = blockIdx.y;
         ctl_i += b * LOOP_CTL_I; part += b * (size_t)nbs * LOOP_MAX_CLUSTERS * CL_MOM;
@@ -419,7 +450,39 @@ __global__ __launch_bounds__(256) void k_loop_cluster_finish(const int32_t* __re
     int C = ctl_i[LOOP_I_NCL] + 1;
     C = C > LOOP_MAX_CLUSTERS ? LOOP_MAX_CLUSTERS : C;
     if ((int)blockIdx.x >= C) return;
-    cluster_finish_body((int)((n + 255) / 256), (size_t)nbs, blockIdx.x, part, centers, stds, counts, s_m, rot);
+    cluster_finish_body<FORM>((int)((n + 255) / 256), (size_t)nbs, blockIdx.x, part, centers, stds, counts, s_m, rot);
+}
+__global__ __launch_bounds__(256) void k_loop_cluster_finish(const int32_t* __restrict__ ctl_i, const double* __restrict__ part,
+                                                            float* __restrict__ centers, float* __restrict__ stds,
+                                                            int64_t* __restrict__ counts, double* __restrict__ rot, int32_t nbs) {
+    __shared__ double s_m[CL_MOM];
+    loop_cluster_finish_body<CL_FORM_QUAT>(ctl_i, part, centers, stds, counts, rot, nbs, s_m);
+}
+// The log-map form writes the whole centre (`rot` is not touched, and the annealing kernels are launched without the workgroup
+// that solves the quaternion rotation: launch_loop_decide, launch_anneal_small).  What that workgroup also did - place the
+// rotation in the COMPACT row of the cluster, the row loop_decide gives it among the labels present - is the second kernel's:
+// thread c of trajectory blockIdx.y copies slot c's nine entries; the decision writes the other seven of the row.
+__global__ __launch_bounds__(256) void k_loop_cluster_finish_logmap(const int32_t* __restrict__ ctl_i, const double* __restrict__ part,
+                                                                   float* __restrict__ centers, float* __restrict__ stds,
+                                                                   int64_t* __restrict__ counts, double* __restrict__ rot, int32_t nbs) {
+    __shared__ double s_m[CL_MOM];
+    loop_cluster_finish_body<CL_FORM_LOGMAP>(ctl_i, part, centers, stds, counts, rot, nbs, s_m);
+}
+__global__ __launch_bounds__(LOOP_MAX_CLUSTERS) void k_loop_logmap_rotations(const int32_t* __restrict__ ctl_i,
+                                                                             const float* __restrict__ centers_all,
+                                                                             const int64_t* __restrict__ counts_all,
+                                                                             float* __restrict__ centers_out) {
+    const size_t b = blockIdx.x;
+    ctl_i += b * LOOP_CTL_I; centers_all += b * LOOP_MAX_CLUSTERS * 16; counts_all += b * LOOP_MAX_CLUSTERS;
+    centers_out += b * LOOP_MAX_CLUSTERS * 16;
+    int C = ctl_i[LOOP_I_NCL] + 1;
+    C = C > LOOP_MAX_CLUSTERS ? LOOP_MAX_CLUSTERS : C;
+    const int c = threadIdx.x;
+    if (c >= C || counts_all[c] == 0) return;
+    int np = 0;
+    for (int j = 0; j < c; ++j) np += counts_all[j] != 0 ? 1 : 0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) centers_out[np * 16 + i * 4 + j] = centers_all[c * 16 + i * 4 + j];
 }
 
 // ---- fixed-N engines: the pose estimate of a frame, B trajectories at once (midas_pose_estimate) ----------------------------
@@ -629,39 +692,66 @@ static bool moments_skip() {  // MIDAS_MOMENTS_SKIP=0: every cluster summed by e
 
 // rot: LOOP_MAX_CLUSTERS x 10 doubles - the moment matrices whose eigenproblem the annealing kernel's second workgroup solves
 // (the decision only needs the translation spreads: the eigenvector runs beside the selection)
+// logmap (MIDAS_LOOP_CENTERS_LOGMAP): the log-map twins of the same launches - the finisher writes whole centres and `rot` stays
+// untouched; their rotations go to the compact rows of centers_out (the frame's cluster_poses) by one small launch
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
-                        const LoopWeightsParamRowsArgs* weights, int32_t B) {
+                        const LoopWeightsParamRowsArgs* weights, int32_t B, bool logmap, float* centers_out) {
     const unsigned by = (unsigned)(B > 1 ? B : 1);
-    if (weights && weights->rows)  // ... with their own filter parameters (midas_loop_step_batch_rows)
-        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsParamRowsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
-                           *weights, labels, part, moments_skip());
-    else if (weights && weights->cb_poses_rows)  // rows on different objects (midas_loop_step_batch_objects)
-        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsRowsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
-                           static_cast<const LoopWeightsRowsArgs&>(*weights), labels, part, moments_skip());
-    else if (weights)
-        hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsArgs>, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream,
-                           static_cast<const LoopWeightsArgs&>(*weights), labels, part, moments_skip());
-    else
-        hipLaunchKernelGGL(k_loop_cluster_moments, dim3((unsigned)ceil_div(cap, 256), by), dim3(256), 0, ctx->stream, ctl_i, poses, w64,
-                           labels, part, moments_skip(), (int32_t)cap);
-    hipLaunchKernelGGL(k_loop_cluster_finish, dim3(LOOP_MAX_CLUSTERS, by), dim3(256), 0, ctx->stream, ctl_i, (const double*)part, centers,
-                       stds, counts, rot, (int32_t)ceil_div(cap, 256));
+    const dim3 grid((unsigned)ceil_div(cap, 256), by);
+    const bool skip = moments_skip();
+    if (weights && weights->rows) {  // ... with their own filter parameters (midas_loop_step_batch_rows)
+        if (logmap) hipLaunchKernelGGL(k_loop_weights_moments_logmap<LoopWeightsParamRowsArgs>, grid, dim3(256), 0, ctx->stream, *weights, labels, part, skip);
+        else hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsParamRowsArgs>, grid, dim3(256), 0, ctx->stream, *weights, labels, part, skip);
+    } else if (weights && weights->cb_poses_rows) {  // rows on different objects (midas_loop_step_batch_objects)
+        const LoopWeightsRowsArgs& wr = static_cast<const LoopWeightsRowsArgs&>(*weights);
+        if (logmap) hipLaunchKernelGGL(k_loop_weights_moments_logmap<LoopWeightsRowsArgs>, grid, dim3(256), 0, ctx->stream, wr, labels, part, skip);
+        else hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsRowsArgs>, grid, dim3(256), 0, ctx->stream, wr, labels, part, skip);
+    } else if (weights) {
+        const LoopWeightsArgs& wp = static_cast<const LoopWeightsArgs&>(*weights);
+        if (logmap) hipLaunchKernelGGL(k_loop_weights_moments_logmap<LoopWeightsArgs>, grid, dim3(256), 0, ctx->stream, wp, labels, part, skip);
+        else hipLaunchKernelGGL(k_loop_weights_moments<LoopWeightsArgs>, grid, dim3(256), 0, ctx->stream, wp, labels, part, skip);
+    } else {
+        if (logmap) hipLaunchKernelGGL(k_loop_cluster_moments_logmap, grid, dim3(256), 0, ctx->stream, ctl_i, poses, w64, labels, part, skip, (int32_t)cap);
+        else hipLaunchKernelGGL(k_loop_cluster_moments, grid, dim3(256), 0, ctx->stream, ctl_i, poses, w64, labels, part, skip, (int32_t)cap);
+    }
+    if (logmap) {
+        hipLaunchKernelGGL(k_loop_cluster_finish_logmap, dim3(LOOP_MAX_CLUSTERS, by), dim3(256), 0, ctx->stream, ctl_i, (const double*)part,
+                           centers, stds, counts, rot, (int32_t)ceil_div(cap, 256));
+        hipLaunchKernelGGL(k_loop_logmap_rotations, dim3(by), dim3(LOOP_MAX_CLUSTERS), 0, ctx->stream, ctl_i, (const float*)centers,
+                           (const int64_t*)counts, centers_out);
+    } else {
+        hipLaunchKernelGGL(k_loop_cluster_finish, dim3(LOOP_MAX_CLUSTERS, by), dim3(256), 0, ctx->stream, ctl_i, (const double*)part, centers,
+                           stds, counts, rot, (int32_t)ceil_div(cap, 256));
+    }
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
 }
 
 int launch_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses, const double* w64, const float* w32,
                            const int64_t* labels, int32_t C, const int64_t* label_values, float* centers, float* stds,
-                           int64_t* counts) {
+                           int64_t* counts, bool logmap) {
     const int nb = (int)ceil_div(N, 256);
     void* part;
     int rc = midas_scratch(ctx, (size_t)nb * C * CL_MOM * sizeof(double), &part);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_cluster_moments, dim3((unsigned)nb), dim3(256), 0, ctx->stream, N, poses, w64, w32, labels, (int)C,
-                       label_values, (double*)part, moments_skip());
-    hipLaunchKernelGGL(k_cluster_finish, dim3((unsigned)C), dim3(64), 0, ctx->stream, nb, (int)C, (const double*)part, centers,
-                       stds, counts);
+    if (logmap) {
+        hipLaunchKernelGGL(k_cluster_moments_logmap, dim3((unsigned)nb), dim3(256), 0, ctx->stream, N, poses, w64, w32, labels, (int)C,
+                           label_values, (double*)part, moments_skip());
+        hipLaunchKernelGGL(k_cluster_finish_logmap, dim3((unsigned)C), dim3(64), 0, ctx->stream, nb, (int)C, (const double*)part, centers,
+                           stds, counts);
+    } else {
+        hipLaunchKernelGGL(k_cluster_moments, dim3((unsigned)nb), dim3(256), 0, ctx->stream, N, poses, w64, w32, labels, (int)C,
+                           label_values, (double*)part, moments_skip());
+        hipLaunchKernelGGL(k_cluster_finish, dim3((unsigned)C), dim3(64), 0, ctx->stream, nb, (int)C, (const double*)part, centers,
+                           stds, counts);
+    }
+    MIDAS_HIP_CHECK(ctx, hipGetLastError());
+    return MIDAS_OK;
+}
+
+int launch_se3_log(midas_ctx* ctx, int64_t N, const float* poses, double* xi) {
+    hipLaunchKernelGGL(k_se3_log, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, ctx->stream, N, poses, xi);
     MIDAS_HIP_CHECK(ctx, hipGetLastError());
     return MIDAS_OK;
 }

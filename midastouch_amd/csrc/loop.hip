@@ -46,7 +46,7 @@ static int loop_cluster_phase(midas_ctx* ctx, const midas_loop_args& s, const Lo
     if ((rc = midas_scratch(ctx, Bz * LOOP_MAX_CLUSTERS * sizeof(int64_t), &cnt))) return rc;
     m = LoopMoments{(float*)cen, (float*)sd, (int64_t*)cnt, (double*)rot};
     return launch_loop_cluster(ctx, g.cap, s.ctl_i_dev, s.poses_prop_dev, s.weights_dev, s.labels_dev, (double*)part, m.cen, m.sd, m.cnt, m.rot,
-                               merged, g.B);
+                               merged, g.B, g.logmap, s.cluster_poses_dev);
 }
 
 int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
@@ -55,6 +55,7 @@ int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree*
     const int64_t cap = (s.grid_n > 0 && s.grid_n < s.cap) ? s.grid_n : s.cap;
     LoopGrid g;
     g.cap = cap;
+    g.logmap = (phases & MIDAS_LOOP_CENTERS_LOGMAP) != 0;
 #ifdef MIDAS_ANNEAL_CLOCKS
     g.clocks = s.ctl_d_dev;
 #endif
@@ -126,6 +127,7 @@ static int loop_step_batch_frame(midas_ctx* ctx, const midas_codebook* cb, const
     g.cap = cap; g.B = B; g.slice = (int32_t)cap; g.log_stride = log_stride;
     g.lp_stride = (int32_t)(cap + SCAN_CHUNK);  // (the resample reads whole chunks)
     g.rows = rows;
+    g.logmap = (phases & MIDAS_LOOP_CENTERS_LOGMAP) != 0;
     int rc;
     LoopWeightsParamRowsArgs wa{};
     bool weights_merged = false;

@@ -616,7 +616,8 @@ int launch_reduce_partials(midas_ctx* ctx, int np, const double* pmax, const dou
 // cluster.hip
 int launch_cluster_centers(midas_ctx* ctx, int64_t N, const float* poses, const double* w64, const float* w32,
                            const int64_t* labels, int32_t C, const int64_t* label_values, float* centers, float* stds,
-                           int64_t* counts);
+                           int64_t* counts, bool logmap = false);  // logmap: midas_cluster_centers_logmap (cluster_logmap.hpp)
+int launch_se3_log(midas_ctx* ctx, int64_t N, const float* poses, double* xi);
 
 // the pose estimate of a fixed-N frame for B trajectories (midas_pose_estimate): weights w64 (B x N), or - nullptr - made from
 // the pipelined frame's table blocks tb (trajectory 0's, tstride doubles apart) and the valid mask
@@ -633,7 +634,9 @@ struct LoopWeightsParamRowsArgs;  // loop_weights.hpp
 int launch_loop_cluster(midas_ctx* ctx, int64_t cap, const int32_t* ctl_i, const float* poses, const double* w64,
                         const int32_t* labels, double* part, float* centers, float* stds, int64_t* counts, double* rot,
                         const LoopWeightsParamRowsArgs* weights = nullptr,  // weights: computed at the head of the moment launch (loop_weights.hip)
-                        int32_t B = 1);  // trajectories (grid.y): every array (B, ...) contiguous, the scratch ones included
+                        int32_t B = 1,  // trajectories (grid.y): every array (B, ...) contiguous, the scratch ones included
+                        bool logmap = false,           // MIDAS_LOOP_CENTERS_LOGMAP: whole centres by the finisher, their rotations
+                        float* centers_out = nullptr); //   into the compact rows of centers_out (the frame's cluster_poses)
 
 // loop.hip / dbscan.hip - the reference's whole loop body on a variable-size particle set (midas_loop_step)
 int launch_loop_step(midas_ctx* ctx, const midas_codebook* cb, const midas_tree* t6, const midas_tree* t3,
@@ -656,6 +659,7 @@ struct LoopGrid {
     int64_t log_stride = 0;    //          doubles between their log rows
     double* clocks = nullptr;  // MIDAS_ANNEAL_CLOCKS (the single call): k_loop_xe's phase clocks
     const midas_loop_row_params* rows = nullptr;  // midas_loop_step_batch_rows: B records, the phases launch the kernels that read them
+    bool logmap = false;       // MIDAS_LOOP_CENTERS_LOGMAP: the annealing kernels are launched without their rotation workgroup
     unsigned nbcap() const { return (unsigned)ceil_div(cap, SCAN_BLOCK); }
     unsigned by() const { return (unsigned)B; }
     bool batch() const { return slice != 0; }

@@ -103,7 +103,7 @@ def _log_id(seq, expt_cfg) -> str:
 def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str = "fixed", max_frames: int = None,
            cluster: bool = True, progress: bool = False, softmax: bool = True, update_freq: int = 1, floor: int = 1000,
            results_path: Optional[str] = None, draws: str = "device", seed: int = 4000, start: str = "host",
-           cluster_every: int = 50, resample: str = "weighted_random") -> dict:
+           cluster_every: int = 50, resample: str = "weighted_random", centers: str = "quat_avg") -> dict:
     """Run the filter over a sequence; returns the reference's `filter_stats` dict (filter.py:99-116).
 
     The loop body (filter.py:150-190: motionModel -> particle_rmse -> SE3_NN + get_similarity -> remove_invalid_particles
@@ -136,6 +136,9 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
     (the reference's call), or "low_var" / "low_var_batch": the systematic resampler, whose one draw a frame is a float32
     `torch.rand(1)` (:291) - with draws="host" drawn here when the resampler draws at all (NDRAW > 0), with draws="seeded" by the
     device stream, with draws="device" from Philox.
+    centers: the method `pf.get_cluster_centers(particles, ...)` is called with - "quat_avg" (filter.py:184-186), or "logmap", the
+    reference signature's default: `filter_stats["cluster_poses"]` / `["cluster_stds"]` and annealing's spread are then the log-map
+    centres' (LoopEngine(centers="logmap")).
     """
     from . import _lib
     from .engine import RESAMPLE_MODES
@@ -167,7 +170,8 @@ def filter(cfg, seq: Optional[Sequence] = None, viz=None, device=None, pace: str
         pf._mesh_tree = seq.mesh_tree
     eng = LoopEngine(codebook, None, pf.mesh_kdtree, init_particles, sig_t=pf.motion_noise["sig_t"], sig_r=pf.motion_noise["sig_r"],
                      pen_max=pf.pen_max, seed=seed, softmax=softmax, resample=resample, floor=floor, cluster=cluster,
-                     log_frames=max(traj_size + 8, 64), device=device, topk_ties="aten_cpu" if draws in ("host", "seeded") else "index")
+                     log_frames=max(traj_size + 8, 64), device=device, topk_ties="aten_cpu" if draws in ("host", "seeded") else "index",
+                     centers=centers)
     # seeded: the engine draws every frame's numbers from torch's stream on the device (LoopEngine.seed_torch_stream)
     stream = (eng.seed_torch_stream_low_var if systematic else eng.seed_torch_stream)(0) if draws == "seeded" else None
     on_device = False  # seeded: who holds torch's stream at the moment (False: the host's default generator)
@@ -424,13 +428,14 @@ def sweep_inputs(runs, plan, device):
 
 def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, max_frames: int = None, cluster: bool = True,
                  cluster_every: int = 50, softmax=True, update_freq=1, floor=1000,
-                 results_root: Optional[str] = None, draws: str = "device", resample: str = "weighted_random") -> list:
+                 results_root: Optional[str] = None, draws: str = "device", resample: str = "weighted_random",
+                 centers: str = "quat_avg") -> list:
     """The reference's experiment - `bash/run_filter.sh`: objects x logs x trials, one `filter/filter.py` process each - as ONE batch
     on the device: every (run, trial) is a row of a `BatchLoopEngine.for_objects`, a frame of all rows is one `step()`.
 
     runs: a list of `Sequence`; runs that share one `codebook` object stand on one object of the batch.  Row r * trials + k is run r,
     trial k, on the Philox streams of seed + row: it holds, frame for frame, what `filter(run_cfg, runs[r], seed=seed + row,
-    start="device", softmax=..., floor=..., update_freq=..., cluster_every=..., resample=...)` computes.  run_cfg is the run's own `Sequence.cfg`
+    start="device", softmax=..., floor=..., update_freq=..., cluster_every=..., resample=..., centers=...)` computes.  run_cfg is the run's own `Sequence.cfg`
     (None: `cfg`): a run takes its dataset's noise_t, noise_r, num_particles, noise_ratio and pen.max from it - config/expt/ycb.yaml
     and mcmaster.yaml in one sweep; the batch's capacity is the largest count, wide beyond 16 384.  softmax, floor and update_freq are
     each one value or one per run - `filter` and `filter_real`'s presets as rows of one batch.  Rows that differ in any of these go
@@ -471,7 +476,8 @@ def filter_sweep(cfg, runs, *, trials: int = 1, seed: int = 4000, device=None, m
         pfs.append(pf)
     eng = BatchLoopEngine.for_objects([(runs[r].codebook, None, pfs[r].mesh_kdtree) for r in plan["objects"]],
                                       plan["row_object"], rp["capacity"], seed=seed, cluster=cluster, cluster_every=cluster_every,
-                                      log_frames=max(T_max + 8, 64), device=device, wide=rp["wide"], resample=resample, **rp["engine"])
+                                      log_frames=max(T_max + 8, 64), device=device, wide=rp["wide"], resample=resample, centers=centers,
+                                      **rp["engine"])
     odoms, codes, gts = sweep_inputs(runs, plan, device)
     init_noise = torch.tensor([pfs[r].init_noise for r in plan["row_run"]], dtype=torch.float32, device=device)
     counts = rp["num_particles"]

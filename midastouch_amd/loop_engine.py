@@ -39,6 +39,8 @@ from .engine import RESAMPLE_MODES, advance_epoch, check_motion_draws, codebook_
 
 ALL_PHASES = _lib.LOOP_FRONT | _lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL | _lib.LOOP_RESAMPLE
 TOPK_TIES = {"index": _lib.TOPK_TIES_INDEX, "aten_cpu": _lib.TOPK_TIES_ATEN_CPU}
+# get_cluster_centers' two methods as the bit ANNEAL's calls carry (one value for the engine, chosen on the host like the resample mode)
+CENTER_FORMS = {"quat_avg": 0, "logmap": _lib.LOOP_CENTERS_LOGMAP}
 
 
 def state_table(cap: int, K: int, log_frames: int, ctl_d: int = 16):
@@ -88,7 +90,10 @@ class _LoopBase:
     (`_lead` = () or (B,)) with the `LoopArgs` that point at it, and the host's part of a frame."""
 
     def _setup(self, cb_poses, cb_embeddings, mesh_vertices, device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps,
-               cluster, cluster_every, log_frames):
+               cluster, cluster_every, log_frames, centers="quat_avg"):
+        if centers not in CENTER_FORMS:  # (before a context is asked for)
+            raise MidasError(f"centers must be one of {sorted(CENTER_FORMS)}, got {centers!r}")
+        self.centers = centers
         self.ctx, self.cb_poses, self.cb_feat, self.tree6, self.codebook, self.tree3 = codebook_index(
             cb_poses, cb_embeddings, mesh_vertices, device)
         self.device = self.ctx.device
@@ -245,6 +250,8 @@ class _LoopBase:
         """`phases` without what this frame does not run: no clustering at all, or DBSCAN on every `cluster_every`-th frame only."""
         if not self.cluster:
             return phases & ~(_lib.LOOP_DBSCAN | _lib.LOOP_ANNEAL)
+        if phases & _lib.LOOP_ANNEAL:  # the form of the centres travels with the phase that takes them
+            phases |= CENTER_FORMS[self.centers]
         if dbscan is False or (dbscan is None and self.step_count % self.cluster_every != 0):
             return phases & ~_lib.LOOP_DBSCAN
         return phases
@@ -283,9 +290,9 @@ class LoopEngine(_LoopBase):
     def __init__(self, cb_poses, cb_embeddings, mesh_vertices, num_particles: int, *, sig_t=2e-4, sig_r=0.5, pen_max=0.002,
                  seed=4000, softmax=True, resample="weighted_random", floor: int = 1000, eps: float = 1e-2, cluster: bool = True,
                  cluster_every: int = 50, log_frames: int = 4096, device=None,
-                 topk_ties: str = "index"):
+                 topk_ties: str = "index", centers: str = "quat_avg"):
         self._setup(cb_poses, cb_embeddings, mesh_vertices, device, sig_t, sig_r, pen_max, seed, softmax, resample, floor, eps,
-                    cluster, cluster_every, log_frames)
+                    cluster, cluster_every, log_frames, centers)
         self.cap = cap = int(num_particles)
         if cap < 1 or cap > (1 << 20):
             raise MidasError("LoopEngine holds 1 .. 2^20 particles")

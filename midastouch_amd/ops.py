@@ -371,8 +371,25 @@ def rmse(poses: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def cluster_centers(poses: torch.Tensor, weights: torch.Tensor, labels: torch.Tensor, label_values: torch.Tensor):
-    """K9: (centres (C,4,4) f32, stds (C,3) f32, members (C,) i64) of the clusters `label_values` (midas_cluster_centers)."""
+CLUSTER_CENTER_ENTRIES = {"quat_avg": "midas_cluster_centers", "logmap": "midas_cluster_centers_logmap"}
+
+
+def se3_log(poses: torch.Tensor) -> torch.Tensor:
+    """(N,4,4) -> (N,6) float64 tangent vectors [V^-1 t, omega] (midas_se3_log; theseus `SE3.log_map`, pose.py:105-106): what the
+    log-map cluster centres average."""
+    poses = _poses(poses)
+    out = torch.empty((poses.shape[0], 6), dtype=torch.float64, device=poses.device)
+    _ctx(poses).call("midas_se3_log", poses.shape[0], _ptr(poses), _ptr(out))
+    return out
+
+
+def cluster_centers(poses: torch.Tensor, weights: torch.Tensor, labels: torch.Tensor, label_values: torch.Tensor,
+                    method: str = "quat_avg"):
+    """K9: (centres (C,4,4) f32, stds (C,3) f32, members (C,) i64) of the clusters `label_values`: method "quat_avg"
+    (midas_cluster_centers) or "logmap" (midas_cluster_centers_logmap), get_cluster_centers' two (particle_filter.py:153-206)."""
+    entry = CLUSTER_CENTER_ENTRIES.get(method)
+    if entry is None:
+        raise MidasError(f"method must be 'quat_avg' or 'logmap', got {method!r}")
     poses = _poses(poses)
     dev = poses.device
     labels = labels.to(dev, torch.int64).contiguous()
@@ -386,7 +403,7 @@ def cluster_centers(poses: torch.Tensor, weights: torch.Tensor, labels: torch.Te
     counts = torch.empty((C,), dtype=torch.int64, device=dev)
     w64 = _ptr(weights) if weights.dtype == torch.float64 else None
     w32 = _ptr(weights) if weights.dtype == torch.float32 else None
-    _ctx(poses).call("midas_cluster_centers", poses.shape[0], _ptr(poses), w64, w32, _ptr(labels), C, _ptr(label_values),
+    _ctx(poses).call(entry, poses.shape[0], _ptr(poses), w64, w32, _ptr(labels), C, _ptr(label_values),
                      _ptr(centers), _ptr(stds), _ptr(counts))
     return centers, stds, counts
 

@@ -28,6 +28,8 @@ One JSON line per engine form with each figure's median over the repeats and [mi
                   work, so the difference to objects_mixed is the cost of the parameter table (--form=objects_rows only)
 --resample=MODE: the engines' resample mode (weighted_random by default; low_var: the systematic resampler - with --seeded its one
   float32 offset per row and frame in place of n_set float64 uniforms).
+--centers=METHOD: the form of the frames' cluster centres (quat_avg by default; logmap: the log-map centres, MIDAS_LOOP_CENTERS_LOGMAP)
+  in every loop engine form.
 --profile: frames of the batch engine only (for rocprofv3 --kernel-trace --stats; with --seeded the seeded batch, with --objects the mixed
   batch, with --form=NAME that form), no timing."""
 import json
@@ -87,6 +89,8 @@ kw = dict(floor=FLOOR, cluster_every=EVERY, device=dev)
 for a in sys.argv[1:]:
     if a.startswith("--resample="):
         kw["resample"] = a.split("=", 1)[1]
+    if a.startswith("--centers="):
+        kw["centers"] = a.split("=", 1)[1]
 SYSTEMATIC = kw.get("resample", "weighted_random") != "weighted_random"  # (a seeded systematic engine: seed_torch_stream_low_var)
 HOST_US = None  # of the latest timed() run
 
@@ -207,7 +211,7 @@ def run_single_seeded():
 
 head = {"B": B, "N0": N0, "K": K, "D": D, "floor": FLOOR, "cluster_every": EVERY, "frames": T, "repeats": R, **({"wide": True} if wide else {}),
         **({} if DBSCAN is None else {"dbscan": "batched" if DBSCAN else "serial"}), **({"objects": G} if G else {}),
-        **({"resample": kw["resample"]} if "resample" in kw else {})}
+        **({"resample": kw["resample"]} if "resample" in kw else {}), **({"centers": kw["centers"]} if "centers" in kw else {})}
 out = {}
 forms = (("batch_loop", run_batch), ("single_loop", run_single), ("pipelined_fixed", run_fixed))
 if wide:
